@@ -17,6 +17,10 @@ child, relays rank 0's JSON line and exits with the child's status.
       so that its activation buffers stay those of the 1080p plan.
 ``value`` = output MP of the whole image / max-over-ranks time, in both modes.
 
+``--dump-outputs DIR`` writes what the last timed step returned (rank 0's whole image; with --config c3 / c4 that model's output) as
+``DIR/output.npy`` in float32, a fixed seeded sample of at most 16 MB when it is larger (see ``dump_outputs``).  Weights and inputs are
+synthetic with fixed seeds, so the same arguments give the same inputs on every run.
+
 Extra objects on the JSON line:
   roofline      dominant kernel (the fused conv kernel family = every launch of the forward), MFMA-bound:
                 algorithmic FLOP (2,240,856 per output pixel) / HIP-event time of the launches
@@ -64,10 +68,16 @@ def parse():
     ap.add_argument('--dry-run', action='store_true', help='launcher / rendezvous check without a GPU: ranks meet over gloo, rank 0 prints a stub line')
     ap.add_argument('--io', default='f32', choices=['f32', 'u8'], help='tensors crossing the boundary: fp32 [N,C,H,W] in / out, or uint8 [N,H,W,C] images in / out '
                     '(the 8-bit path: /255 and clamp*255+round inside the first / last kernel; tiles cross xGMI as bytes)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step returned as DIR/<name>.npy (float32; an output larger than 64 MB '
+                    'as a fixed, seeded sample of it): the inputs are the same from run to run, so two builds can be compared output for output')
     ap.add_argument('--config', default='c2', choices=['c2', 'c3', 'c4', 'c5'],
                     help='c2 (default, BASELINE metric): N tiles of 1080p through RealESRGAN-x4plus (weak scaling); c5: one 4320x7680 input, 2x4 tiles (strong '
                     'scaling); c3: SPANPlus x4 fp16, 8x3x512x512 tiles, one GPU; c4: SwinIR-L x4 bf16 tensors, 1x3x1024x1024, one GPU')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    return args
 
 
 def launch_ranks(n: int) -> int:
@@ -363,6 +373,38 @@ class PowerSampler:
 
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 1 << 22  # elements kept of an output that does not fit: 16 MB of float32
+
+
+def dump_outputs(outdir: str, outputs: dict) -> dict:
+    """``--dump-outputs DIR``: write each output tensor as ``DIR/<name>.npy`` in float32.  An output whose float32 copy would not fit in
+    the budget is replaced by a fixed sample of ``DUMP_SAMPLE`` elements, one per equal stratum of the C-order flat index range at a
+    seeded offset inside the stratum: the same shape always gives the same positions, so two runs compare element for element.
+    Returns the note carried on the JSON line (file, shape and whether it is a sample)."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    note, used = {}, 0
+    for name, y in outputs.items():
+        flat = y.detach().reshape(-1)
+        n = flat.numel()
+        if n * 4 <= DUMP_BUDGET_BYTES - used:
+            vals, sampled = y.detach().float().cpu().numpy(), False  # whole, in its own shape
+        else:
+            k = min(n, DUMP_SAMPLE, (DUMP_BUDGET_BYTES - used) // 4)
+            lo = np.arange(k, dtype=np.int64) * n // k
+            hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+            idx = lo + np.random.Generator(np.random.PCG64(0x5EED)).integers(0, hi - lo)
+            vals = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).float().cpu().numpy()
+            sampled = True
+        path = os.path.join(outdir, name + '.npy')
+        np.save(path, vals)
+        used += vals.nbytes
+        note[name] = {'file': path, 'shape': list(y.shape), 'dtype': str(y.dtype).split('.')[-1], 'elements': int(vals.size), 'sampled': sampled}
+    return note
+
+
 SECONDARY = {
     # BASELINE.json configs[2] / configs[3]; constants: SURVEY.md 8d (algorithmic FLOP and layer-wise bytes per OUTPUT pixel)
     'c3': dict(metric='output megapixels/sec, SPANPlus x4 fp16, batch of 8 3x512x512 tiles, 1 MI355X', shape=(8, 3, 512, 512), io=torch.float16,
@@ -417,6 +459,7 @@ def secondary_result(config: str, args, steps: int, warmup: int, compact: bool =
         raise SystemExit(f'bench.py: {aborts} ring-schedule hand-offs timed out; the timed forwards are invalid')
     out_px = y.shape[0] * y.shape[2] * y.shape[3]
     kern_s = ev0.elapsed_time(ev1) / 1e3 / steps
+    dumped = dump_outputs(args.dump_outputs, {'output': y}) if (args.dump_outputs and not compact) else None
     del y
     classes = [] if args.no_kernel_roofline else kernel_classes(model, max(2, min(steps, 5)), x)
     flop, hbm = cfg['flop_px'] * out_px, cfg['bytes_px'] * out_px
@@ -433,6 +476,8 @@ def secondary_result(config: str, args, steps: int, warmup: int, compact: bool =
                          'model': f'layer-wise bytes, {cfg["bytes_px"]:,} B per output pixel (SURVEY.md 8d)'},
         'ring_aborts': aborts, 'event_ms_per_step': round(kern_s * 1e3, 3),
     }  # fmt: skip
+    if dumped is not None:
+        res['dump_outputs'] = dumped
     if classes:
         dom = classes[0]
         fm, fh = dom['tflops'] / MFMA_PEAK_TFLOPS, dom['gbs'] / HBM_PEAK_GBS
@@ -601,6 +646,7 @@ def main():
     assert total_out_px == 16 * img_h * img_w
     ms_per_step = dt / args.steps * 1e3
     value = total_out_px / 1e6 / (dt / args.steps)
+    dumped = dump_outputs(args.dump_outputs, {'output': y}) if (args.dump_outputs and rank == 0) else None  # every rank holds the whole image
     del y
 
     if rank == 0:
@@ -719,6 +765,8 @@ def main():
             'event_ms_per_step': round(ev_ms / args.steps, 3),
             'forward_ms_1080p': round(kern_s * 1e3, 3),
         }
+        if dumped is not None:
+            res['dump_outputs'] = dumped
         if sampler is not None:  # power leg: 3.5 s of back-to-back forwards, the last 2 s of samples
             sampler.begin()
             w0 = time.time()

@@ -643,6 +643,92 @@ typedef struct rsa_gated_shuffle_params {
 } rsa_gated_shuffle_params;
 int rsa_gated_shuffle_mul(const rsa_gated_shuffle_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- PLKSR ops
+ * (reference archs/plksr/plksr.py and rplksr.py; resselt_amd/csrc/plksr.hip) */
+
+/* Partial large-kernel convolution (PLKConv2d, rplksr.py:22-37, plksr.py:54-93): a dense K x K convolution, zero padding K/2, of
+ * pdim = 8*planes input channels to pdim output channels + bias.  Input: `planes` planes at in_hi / in_lo.  Output: planes
+ * [out_plane_off, out_plane_off + planes) of another buffer; no other plane is touched.  Arithmetic as rsa_conv2d: fmt RSA_PF_BF16 with
+ * products == 3 (hi + lo) or RSA_PF_F16 with products == 1 (hi only), v_mfma_f32_16x16x32_{bf16,f16}, f32 accumulate.
+ * w_packed: rsa_plk_packed_weight_bytes bytes, [plane p][K step s][cout tile ct][hi|lo][lane 64][8] where lane l of step s holds
+ * W[16 ct + (l & 15)][8 p + j][tap 4 s + (l >> 4)] (taps row-major, zero past K*K and past pdim; resselt_amd/engine/plk.py).
+ * bias: f32[16 * ceil(planes / 2)].  3 <= K <= 31 odd, planes <= 8. */
+typedef struct rsa_plk_conv_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t ksize;
+  int32_t planes;           /* pdim / 8 */
+  int32_t products;         /* 1 or 3 */
+  const void* in_hi;
+  const void* in_lo;        /* products == 3 only */
+  int64_t in_plane_stride;  /* 16-byte units */
+  int64_t in_batch_stride;
+  const void* w_packed;
+  const float* bias;
+  void* out_hi;
+  void* out_lo;             /* may be NULL */
+  int64_t out_plane_stride; /* 16-byte units */
+  int64_t out_batch_stride;
+  int32_t out_plane_off;
+  int32_t fmt;              /* enum rsa_plane_fmt of every plane operand and of w_packed */
+  int32_t reserved0;        /* must be 0 */
+  int32_t reserved1;
+} rsa_plk_conv_params;
+int64_t rsa_plk_packed_weight_bytes(int32_t ksize, int32_t planes, int32_t products);
+int rsa_plk_conv(const rsa_plk_conv_params* p, void* stream);
+
+/* nn.GroupNorm statistics over whole images (rplksr.py:94, 103): stats[n][g] = (mean, 1 / sqrt(var + eps)) of channels
+ * [g*C/groups, (g+1)*C/groups) x every pixel of an f32 map [N][C/4][H][W][4] (biased variance, as torch).  Two deterministic stages: partial
+ * (count, mean, M2) per chunk of pixels, computed around a per-group shift, into `workspace` (rsa_group_norm_workspace_bytes), then Chan's
+ * pairwise combination per (image, group).  Stays on the device: rsa_group_norm_apply reads `stats` in stream order.  groups <= 8. */
+int64_t rsa_group_norm_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t groups);
+int rsa_group_norm_stats(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t groups, float eps, float* workspace,
+                         float* stats, void* stream);
+
+/* out = (x - mean_g) * rstd_g * gamma[c] + beta[c] + skip  (PLKBlock.forward of RealPLKSR, rplksr.py:98-105) -> split planes and/or an
+ * f32 map (the next block's input and residual stream).  C a multiple of 8. */
+typedef struct rsa_group_norm_apply_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t C;
+  int32_t groups;
+  int32_t out_fmt;          /* enum rsa_plane_fmt of out_hi / out_lo */
+  const float* x_f32;       /* f32 [N][C/4][H][W][4] */
+  const float* stats;       /* [N][groups][2] from rsa_group_norm_stats */
+  const float* gamma;       /* [C] */
+  const float* beta;        /* [C] */
+  const float* skip_f32;    /* f32 map like x, or NULL */
+  void* out_hi;             /* planes [N][C/8][H][W][8], or NULL */
+  void* out_lo;             /* may be NULL */
+  int64_t out_plane_stride; /* 16-byte units */
+  int64_t out_batch_stride;
+  float* out_f32;           /* may be NULL; may not alias x_f32 / skip_f32 of other pixels (same pixel is fine) */
+  int32_t reserved0;        /* must be 0 */
+  int32_t reserved1;
+} rsa_group_norm_apply_params;
+int rsa_group_norm_apply(const rsa_group_norm_apply_params* p, void* stream);
+
+/* Element-wise attention gate (EA.forward, rplksr.py:40-49, plksr.py:247-256): out = x * sigmoid(g), g = the f32 output (bias included) of
+ * EA's 3x3 convolution of x, x read from split planes (hi + lo), out written as split planes.  A streaming kernel rather than an epilogue of
+ * rsa_conv2d: every compiled convolution schedule keeps its code unchanged.  C a multiple of 8. */
+typedef struct rsa_ea_gate_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t C;
+  const float* g_f32;       /* f32 [N][C/4][H][W][4] */
+  const void* x_hi;
+  const void* x_lo;         /* may be NULL */
+  int64_t x_plane_stride;   /* 16-byte units */
+  int64_t x_batch_stride;
+  void* out_hi;
+  void* out_lo;             /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+  int32_t fmt;              /* enum rsa_plane_fmt of x and out */
+  int32_t reserved0;        /* must be 0 */
+} rsa_ea_gate_params;
+int rsa_ea_gate(const rsa_ea_gate_params* p, void* stream);
+
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255
  *   rsa_nchw_to_image_u8   float [N][C][H][W] -> uint8 [N][H][W][C], round-half-even(clamp(v, 0, 1) * 255)  (torch: (y.clamp(0,1)*255).round())

@@ -411,6 +411,80 @@ class AimParams(C.Structure):
     ]
 
 
+class PlkConvParams(C.Structure):
+    """Mirror of ``struct rsa_plk_conv_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('H', C.c_int32),
+        ('W', C.c_int32),
+        ('ksize', C.c_int32),
+        ('planes', C.c_int32),
+        ('products', C.c_int32),
+        ('in_hi', C.c_void_p),
+        ('in_lo', C.c_void_p),
+        ('in_plane_stride', C.c_int64),
+        ('in_batch_stride', C.c_int64),
+        ('w_packed', C.c_void_p),
+        ('bias', C.c_void_p),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+        ('out_plane_off', C.c_int32),
+        ('fmt', C.c_int32),
+        ('reserved0', C.c_int32),
+        ('reserved1', C.c_int32),
+    ]
+
+
+class GroupNormApplyParams(C.Structure):
+    """Mirror of ``struct rsa_group_norm_apply_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('H', C.c_int32),
+        ('W', C.c_int32),
+        ('C', C.c_int32),
+        ('groups', C.c_int32),
+        ('out_fmt', C.c_int32),
+        ('x_f32', C.c_void_p),
+        ('stats', C.c_void_p),
+        ('gamma', C.c_void_p),
+        ('beta', C.c_void_p),
+        ('skip_f32', C.c_void_p),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+        ('out_f32', C.c_void_p),
+        ('reserved0', C.c_int32),
+        ('reserved1', C.c_int32),
+    ]
+
+
+class EaGateParams(C.Structure):
+    """Mirror of ``struct rsa_ea_gate_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('H', C.c_int32),
+        ('W', C.c_int32),
+        ('C', C.c_int32),
+        ('g_f32', C.c_void_p),
+        ('x_hi', C.c_void_p),
+        ('x_lo', C.c_void_p),
+        ('x_plane_stride', C.c_int64),
+        ('x_batch_stride', C.c_int64),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+        ('fmt', C.c_int32),
+        ('reserved0', C.c_int32),
+    ]
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -455,6 +529,12 @@ EXPORTS = (
     'rsa_gated_shuffle_mul',
     'rsa_image_u8_to_nchw',
     'rsa_nchw_to_image_u8',
+    'rsa_plk_packed_weight_bytes',
+    'rsa_plk_conv',
+    'rsa_group_norm_workspace_bytes',
+    'rsa_group_norm_stats',
+    'rsa_group_norm_apply',
+    'rsa_ea_gate',
 )
 
 
@@ -588,6 +668,18 @@ def load() -> C.CDLL:
     lib.rsa_image_u8_to_nchw.restype = C.c_int
     lib.rsa_nchw_to_image_u8.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.rsa_nchw_to_image_u8.restype = C.c_int
+    lib.rsa_plk_packed_weight_bytes.argtypes = [C.c_int32] * 3
+    lib.rsa_plk_packed_weight_bytes.restype = C.c_int64
+    lib.rsa_plk_conv.argtypes = [C.POINTER(PlkConvParams), C.c_void_p]
+    lib.rsa_plk_conv.restype = C.c_int
+    lib.rsa_group_norm_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.rsa_group_norm_workspace_bytes.restype = C.c_int64
+    lib.rsa_group_norm_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsa_group_norm_stats.restype = C.c_int
+    lib.rsa_group_norm_apply.argtypes = [C.POINTER(GroupNormApplyParams), C.c_void_p]
+    lib.rsa_group_norm_apply.restype = C.c_int
+    lib.rsa_ea_gate.argtypes = [C.POINTER(EaGateParams), C.c_void_p]
+    lib.rsa_ea_gate.restype = C.c_int
     _lib = lib
     return lib
 

@@ -108,6 +108,16 @@ def run_tile(model: Callable[[torch.Tensor], torch.Tensor], x: torch.Tensor, til
     return y[:, oy : oy + th * scale, ox : ox + tw * scale] if img else y[:, :, oy : oy + th * scale, ox : ox + tw * scale]
 
 
+def warn_global_statistics(model, n_tiles: int) -> None:
+    """Models whose class sets ``global_statistics`` (RealPLKSR: GroupNorm over the whole image) compute different statistics on every
+    tile, so a tiled result depends on the tile size; the reference has no tiling and defines the whole-image result."""
+    if n_tiles > 1 and getattr(model, 'global_statistics', False):
+        import warnings
+
+        warnings.warn(f'{type(model).__name__} normalises over the whole image: with {n_tiles} tiles every tile uses its own statistics and the '
+                      'output differs from the untiled one', RuntimeWarning, stacklevel=3)  # fmt: skip
+
+
 def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], halo: int = 32, align: int = 1, check: bool = True) -> torch.Tensor:
     """Single-device tiling of a large image: bounds the engine's activation buffers (e.g. 8K inputs).  ``x``: a float ``[N, C, H, W]``
     tensor, or a uint8 ``[N, H, W, C]`` image for models with ``supports_u8`` (the layouts ``run_tile`` / ``TileParallel`` take)."""
@@ -117,6 +127,7 @@ def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], hal
     n = x.shape[0]
     h, w = (x.shape[1], x.shape[2]) if img else (x.shape[2], x.shape[3])
     rows, cols = -(-h // tile[0]), -(-w // tile[1])
+    warn_global_statistics(model, rows * cols)
     out = None
     for t in plan_tiles(h, w, rows, cols, halo, align):
         y = run_tile(model, x, t, scale)
@@ -212,6 +223,7 @@ class TileParallel:
         h, w = (x.shape[1], x.shape[2]) if img else (x.shape[2], x.shape[3])
         s = self.scale
         tiles = self.tiles_for(h, w, world)
+        warn_global_statistics(self.model, len(tiles))
         mine = tiles[rank::world]
 
         def full_shape(c_out):

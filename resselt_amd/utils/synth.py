@@ -616,3 +616,66 @@ def drct_state_dict(in_chans=3, embed_dim=180, num_layers=2, num_heads=6, window
             _conv(sd, f'upsample.{2 * u}', 4 * 64, 64, 3, seed)
     _conv(sd, 'conv_last', in_chans, 64, 3, seed)
     return sd
+
+
+def _plksr_lk(sd, p, pdim, kernel_size, lk_type, seed):
+    if lk_type == 'PLK':
+        _conv(sd, f'{p}.lk.conv', pdim, pdim, kernel_size, seed)
+    elif lk_type == 'RectSparsePLK':
+        m, n = kernel_size, kernel_size // 3
+        for name, (kh, kw) in (('mn_conv', (m, n)), ('nm_conv', (n, m)), ('nn_conv', (n, n))):
+            fan_in = pdim * kh * kw
+            sd[f'{p}.lk.{name}.weight'] = synth_tensor(f'{p}.lk.{name}.weight', (pdim, pdim, kh, kw), fan_in, seed)
+            sd[f'{p}.lk.{name}.bias'] = synth_tensor(f'{p}.lk.{name}.bias', (pdim,), fan_in, seed)
+    elif lk_type == 'SparsePLK':  # the reference loader's fixed sub-kernels: 4 x (5 x 5) at dilations 1..4
+        for j in range(4):
+            _conv(sd, f'{p}.lk.convs.{j}', pdim, pdim, 5, seed, scale=0.5)
+    else:
+        raise ValueError(lk_type)
+
+
+def plksr_state_dict(dim=64, n_blocks=2, upscale=4, ccm_type='DCCM', kernel_size=17, split_ratio=0.25, lk_type='PLK', use_ea=True, seed=0):
+    """Keys of PLKSR (archs/plksr/plksr.py:259-318); note the reference's ``channe_mixer`` spelling."""
+    sd: OrderedDict = OrderedDict()
+    k0, k2 = {'CCM': (3, 1), 'ICCM': (1, 3), 'DCCM': (3, 3)}[ccm_type]
+    pdim = int(dim * split_ratio)
+    _conv(sd, 'feats.0', dim, 3, 3, seed)
+    for b in range(1, n_blocks + 1):
+        p = f'feats.{b}'
+        _conv(sd, f'{p}.channe_mixer.0', 2 * dim, dim, k0, seed)
+        _conv(sd, f'{p}.channe_mixer.2', dim, 2 * dim, k2, seed)
+        _plksr_lk(sd, p, pdim, kernel_size, lk_type, seed)
+        if use_ea:
+            _conv(sd, f'{p}.attn.f.0', dim, dim, 3, seed)
+        _conv(sd, f'{p}.refine', dim, dim, 1, seed)
+    _conv(sd, f'feats.{n_blocks + 1}', 3 * upscale * upscale, dim, 3, seed)
+    return sd
+
+
+def realplksr_state_dict(dim=64, n_blocks=2, upscale=4, kernel_size=17, split_ratio=0.25, use_ea=True, dysample=False, seed=0):
+    """Keys of RealPLKSR (archs/plksr/rplksr.py:108-166): GroupNorm per block, Dropout2d (no keys), PixelShuffle or DySample head."""
+    sd: OrderedDict = OrderedDict()
+    pdim = int(dim * split_ratio)
+    _conv(sd, 'feats.0', dim, 3, 3, seed)
+    for b in range(1, n_blocks + 1):
+        p = f'feats.{b}'
+        _conv(sd, f'{p}.channel_mixer.0', 2 * dim, dim, 3, seed)
+        _conv(sd, f'{p}.channel_mixer.2', dim, 2 * dim, 3, seed)
+        _conv(sd, f'{p}.lk.conv', pdim, pdim, kernel_size, seed)
+        if use_ea:
+            _conv(sd, f'{p}.attn.f.0', dim, dim, 3, seed)
+        _conv(sd, f'{p}.refine', dim, dim, 1, seed)
+        sd[f'{p}.norm.weight'] = 1.0 + synth_tensor(f'{p}.norm.weight', (dim,), 16, seed)
+        sd[f'{p}.norm.bias'] = synth_tensor(f'{p}.norm.bias', (dim,), 16, seed)
+    cin = 3 * upscale * upscale
+    _conv(sd, f'feats.{n_blocks + 2}', cin, dim, 3, seed)
+    if dysample:
+        groups = 3 if upscale % 2 else 4
+        oc = 2 * groups * upscale * upscale
+        if upscale != 1:
+            _conv(sd, 'to_img.end_conv', 3, cin, 1, seed)
+        _conv(sd, 'to_img.offset', oc, cin, 1, seed, scale=0.5)
+        _conv(sd, 'to_img.scope', oc, cin, 1, seed, bias=False)
+        h = torch.arange((-upscale + 1) / 2, (upscale - 1) / 2 + 1) / upscale
+        sd['to_img.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, groups, 1).reshape(1, -1, 1, 1)
+    return sd

@@ -25,12 +25,16 @@ import torch
 from ...engine import lib as L
 from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
-from ...engine.paramtree import build_param_tree
+from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16, Planes
-from ..swinir.arch import HEAD_PAD, regroup_proj, regroup_qkv
+from ...engine.transformer import (HEAD_PAD, LayerPacker, attn_tiles, bias_fragments_qk, layernorm, pad_heads, pixelshuffle_buffers, pixelshuffle_head,
+                                   regroup_proj, regroup_qkv, relative_position_index, shift_mask)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:879
 BN_EPS = 1e-5
+
+# names this module exported before the shared helpers moved to engine/transformer.py (attn_tiles and pad_heads are imported above)
+bias_fragments = bias_fragments_qk
 
 
 def branch_geometry(pair, idx: int):
@@ -46,67 +50,12 @@ def rpe_buffers(hs: int, ws: int):
     """``rpe_biases`` and ``relative_position_index`` buffers of one Spatial_Attention (arch.py:193-211)."""
     bh, bw = torch.arange(1 - hs, hs), torch.arange(1 - ws, ws)
     biases = torch.stack(torch.meshgrid([bh, bw], indexing='ij')).flatten(1).transpose(0, 1).contiguous().float()
-    coords = torch.stack(torch.meshgrid([torch.arange(hs), torch.arange(ws)], indexing='ij')).flatten(1)
-    rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0).contiguous()
-    rel[:, :, 0] += hs - 1
-    rel[:, :, 1] += ws - 1
-    rel[:, :, 0] *= 2 * ws - 1
-    return biases, rel.sum(-1)
+    return biases, relative_position_index(hs, ws)
 
 
 def shift_masks(H: int, W: int, split, shift):
     """The registered ``attn_mask_0/1`` buffers (arch.py:336-411); kept for state_dict parity, the kernel derives the mask itself."""
-    out = []
-    for idx in (0, 1):
-        hs, ws = branch_geometry(split, idx)
-        sh, sw = branch_geometry(shift, idx)
-        img = torch.zeros(H, W)
-        cnt = 0
-        for a in (slice(0, -hs), slice(-hs, -sh), slice(-sh, None)):
-            for b in (slice(0, -ws), slice(-ws, -sw), slice(-sw, None)):
-                img[a, b] = cnt
-                cnt += 1
-        mw = img.view(H // hs, hs, W // ws, ws).permute(0, 2, 1, 3).reshape(-1, hs * ws)
-        d = mw.unsqueeze(1) - mw.unsqueeze(2)
-        out.append(torch.where(d != 0, torch.full_like(d, -100.0), torch.zeros_like(d)))
-    return out
-
-
-def attn_tiles(ntok: int) -> int:
-    """Tiles of 32 tokens the rect-attention kernel is instantiated for."""
-    t = (ntok + 31) // 32
-    return 1 if t <= 1 else 2 if t <= 2 else 4 if t <= 4 else 8
-
-
-def bias_fragments(dense: torch.Tensor) -> torch.Tensor:
-    """[heads, N, N] (query, key) position bias -> [heads][T][T][lane 64][16] f32 in the S^T accumulator order of the kernel:
-    lane l, element r  <->  query 32*qt + (l & 31),  key 32*kt + (r & 3) + 8*(r >> 2) + 4*(l >> 5).  Padded keys get -1e30."""
-    heads, n, _ = dense.shape
-    T = attn_tiles(n)
-    full = torch.zeros((heads, 32 * T, 32 * T), dtype=torch.float32, device=dense.device)
-    full[:, :, n:] = -1e30
-    full[:, :n, :n] = dense.to(torch.float32)
-    lane = torch.arange(64, device=dense.device)
-    r = torch.arange(16, device=dense.device)
-    q_in = (lane & 31)[:, None].expand(64, 16)
-    k_in = ((r & 3) + 8 * (r >> 2))[None, :] + 4 * (lane >> 5)[:, None]
-    out = torch.empty((heads, T, T, 64, 16), dtype=torch.float32, device=dense.device)
-    for qt in range(T):
-        for kt in range(T):
-            out[:, qt, kt] = full[:, 32 * qt + q_in, 32 * kt + k_in]
-    return out.contiguous()
-
-
-def pad_heads(t: torch.Tensor, heads: int, dim: int = 0) -> torch.Tensor:
-    """Scatter a length-C axis (head-major, C = heads*hd) into the head-padded layout of length heads*32 (zeros in the pads)."""
-    c = t.shape[dim]
-    hd = c // heads
-    shape = list(t.shape)
-    t = t.to(torch.float32).reshape(shape[:dim] + [heads, hd] + shape[dim + 1 :])
-    out_shape = shape[:dim] + [heads, HEAD_PAD] + shape[dim + 1 :]
-    out = torch.zeros(out_shape, dtype=torch.float32, device=t.device)
-    out.narrow(dim + 1, 0, hd).copy_(t)
-    return out.reshape(shape[:dim] + [heads * HEAD_PAD] + shape[dim + 1 :]).contiguous()
+    return [shift_mask(H, W, branch_geometry(split, idx), branch_geometry(shift, idx)) for idx in (0, 1)]
 
 
 def pad_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
@@ -116,103 +65,82 @@ def pad_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
 
 
 def dat_param_shapes(in_chans, embed_dim, split_size, depth, num_heads, expansion_factor, qkv_bias, upscale, resi, upsampler, img_size):
-    shapes: dict = {}
+    s = ParamShapes()
     buffers: dict = {}
     C_ = embed_dim
     hidden = int(C_ * expansion_factor)
     shift_size = [split_size[0] // 2, split_size[1] // 2]
 
-    def conv(name, co, ci, k):
-        shapes[f'{name}.weight'] = (co, ci, k, k)
-        shapes[f'{name}.bias'] = (co,)
-
-    def lin(name, co, ci, bias=True):
-        shapes[f'{name}.weight'] = (co, ci)
-        if bias:
-            shapes[f'{name}.bias'] = (co,)
-
-    def ln(name, c):
-        shapes[f'{name}.weight'] = (c,)
-        shapes[f'{name}.bias'] = (c,)
-
     def bn(name, c):
-        ln(name, c)
+        s.norm(name, c)
         buffers[f'{name}.running_mean'] = torch.zeros(c)
         buffers[f'{name}.running_var'] = torch.ones(c)
         buffers[f'{name}.num_batches_tracked'] = torch.tensor(0, dtype=torch.int64)
 
     def dw(name, c):
-        shapes[f'{name}.weight'] = (c, 1, 3, 3)
-        shapes[f'{name}.bias'] = (c,)
+        s[f'{name}.weight'] = (c, 1, 3, 3)
+        s[f'{name}.bias'] = (c,)
 
     def resi_conv(name):
         if resi == '1conv':
-            conv(name, C_, C_, 3)
+            s.conv(name, C_, C_, 3)
         else:
-            conv(f'{name}.0', C_ // 4, C_, 3)
-            conv(f'{name}.2', C_ // 4, C_ // 4, 1)
-            conv(f'{name}.4', C_, C_ // 4, 3)
+            s.conv(f'{name}.0', C_ // 4, C_, 3)
+            s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
+            s.conv(f'{name}.4', C_, C_ // 4, 3)
 
     def aim(name):
         dw(f'{name}.dwconv.0', C_)
         bn(f'{name}.dwconv.1', C_)
-        conv(f'{name}.channel_interaction.1', C_ // 8, C_, 1)
+        s.conv(f'{name}.channel_interaction.1', C_ // 8, C_, 1)
         bn(f'{name}.channel_interaction.2', C_ // 8)
-        conv(f'{name}.channel_interaction.4', C_, C_ // 8, 1)
-        conv(f'{name}.spatial_interaction.0', C_ // 16, C_, 1)
+        s.conv(f'{name}.channel_interaction.4', C_, C_ // 8, 1)
+        s.conv(f'{name}.spatial_interaction.0', C_ // 16, C_, 1)
         bn(f'{name}.spatial_interaction.1', C_ // 16)
-        conv(f'{name}.spatial_interaction.3', 1, C_ // 16, 1)
+        s.conv(f'{name}.spatial_interaction.3', 1, C_ // 16, 1)
 
     pos_dim = ((C_ // 2) // 4) // 4
-    conv('conv_first', C_, in_chans, 3)
-    ln('before_RG.1', C_)
+    s.conv('conv_first', C_, in_chans, 3)
+    s.norm('before_RG.1', C_)
     masks = None
     for i, d in enumerate(depth):
         heads = num_heads[i]
         for j in range(d):
             b = f'layers.{i}.blocks.{j}'
-            ln(f'{b}.norm1', C_)
+            s.norm(f'{b}.norm1', C_)
             if j % 2 == 0:
-                lin(f'{b}.attn.qkv', 3 * C_, C_, qkv_bias)
-                lin(f'{b}.attn.proj', C_, C_)
+                s.linear(f'{b}.attn.qkv', 3 * C_, C_, qkv_bias)
+                s.linear(f'{b}.attn.proj', C_, C_)
                 for idx in (0, 1):
                     a = f'{b}.attn.attns.{idx}'
                     hs, ws = branch_geometry(split_size, idx)
                     buffers[f'{a}.rpe_biases'], buffers[f'{a}.relative_position_index'] = rpe_buffers(hs, ws)
-                    lin(f'{a}.pos.pos_proj', pos_dim, 2)
+                    s.linear(f'{a}.pos.pos_proj', pos_dim, 2)
                     for k, co in (('pos1', pos_dim), ('pos2', pos_dim), ('pos3', heads // 2)):
-                        ln(f'{a}.pos.{k}.0', pos_dim)
-                        lin(f'{a}.pos.{k}.2', co, pos_dim)
+                        s.norm(f'{a}.pos.{k}.0', pos_dim)
+                        s.linear(f'{a}.pos.{k}.2', co, pos_dim)
                 if is_shifted(i, j):
                     if masks is None:
                         masks = shift_masks(img_size, img_size, split_size, shift_size)
                     buffers[f'{b}.attn.attn_mask_0'], buffers[f'{b}.attn.attn_mask_1'] = masks
             else:
-                shapes[f'{b}.attn.temperature'] = (heads, 1, 1)
-                lin(f'{b}.attn.qkv', 3 * C_, C_, qkv_bias)
-                lin(f'{b}.attn.proj', C_, C_)
+                s[f'{b}.attn.temperature'] = (heads, 1, 1)
+                s.linear(f'{b}.attn.qkv', 3 * C_, C_, qkv_bias)
+                s.linear(f'{b}.attn.proj', C_, C_)
             aim(f'{b}.attn')
-            lin(f'{b}.ffn.fc1', hidden, C_)
-            ln(f'{b}.ffn.sg.norm', hidden // 2)
+            s.linear(f'{b}.ffn.fc1', hidden, C_)
+            s.norm(f'{b}.ffn.sg.norm', hidden // 2)
             dw(f'{b}.ffn.sg.conv', hidden // 2)
-            lin(f'{b}.ffn.fc2', C_, hidden // 2)
-            ln(f'{b}.norm2', C_)
+            s.linear(f'{b}.ffn.fc2', C_, hidden // 2)
+            s.norm(f'{b}.norm2', C_)
         resi_conv(f'layers.{i}.conv')
-    ln('norm', C_)
+    s.norm('norm', C_)
     resi_conv('conv_after_body')
     if upsampler == 'pixelshuffle':
-        conv('conv_before_upsample.0', 64, C_, 3)
-        if upscale == 3:
-            conv('upsample.0', 9 * 64, 64, 3)
-        elif upscale & (upscale - 1) == 0:
-            for u in range(int(math.log2(upscale))):
-                conv(f'upsample.{2 * u}', 4 * 64, 64, 3)
-        else:
-            raise ValueError(f'scale {upscale} is not supported. Supported scales: 2^n and 3.')
-        conv('conv_last', in_chans, 64, 3)
+        s.pixelshuffle_head(C_, 64, in_chans, upscale)
     else:
-        conv('upsample.0', upscale * upscale * in_chans, C_, 3)
-    return shapes, buffers
+        s.conv('upsample.0', upscale * upscale * in_chans, C_, 3)
+    return s, buffers
 
 
 class DAT(EngineModule):
@@ -259,29 +187,12 @@ class DAT(EngineModule):
     # ---------------------------------------------------------------- weights
     def _pack(self, device, products):
         sd = {k: v.detach().to(device) for k, v in self.state_dict().items()}
-        W: dict = {}
         C_ = self.embed_dim
+        pk = LayerPacker(sd, device, products, self.layer_policy)
+        W, conv, lin, ln = pk.W, pk.conv, pk.lin, pk.ln
 
         def f32(t):
             return t.to(torch.float32).contiguous()
-
-        mixed = products.name == 'mixed'
-
-        def policy(name):
-            return self.layer_policy(name) if mixed else (int(products), products.fmt)
-
-        def conv(name):
-            prod, fmt = policy(name)
-            W[name] = ops.ConvWeights.from_oihw(sd[f'{name}.weight'], sd.get(f'{name}.bias'), prod, device=device, fmt=fmt)
-
-        def lin(name, w=None, b=None, cin_planes=None):
-            w = sd[f'{name}.weight'] if w is None else w
-            b = sd.get(f'{name}.bias') if b is None else b
-            prod, fmt = policy(name)
-            W[name] = ops.ConvWeights.from_oihw(w[:, :, None, None], b, prod, cin_planes=cin_planes, device=device, fmt=fmt)
-
-        def ln(name):
-            W[name] = (f32(sd[f'{name}.weight']), f32(sd[f'{name}.bias']))
 
         def resi_conv(name):
             for sub in ([''] if self.resi == '1conv' else ['.0', '.2', '.4']):
@@ -335,7 +246,7 @@ class DAT(EngineModule):
                 lin(f'{b}.attn.proj', regroup_proj(sd[f'{b}.attn.proj.weight'], heads), sd[f'{b}.attn.proj.bias'], cin_planes=heads * HEAD_PAD // 8)
                 if spatial:
                     for idx in (0, 1):
-                        W[f'{b}.attn.bias{idx}'] = bias_fragments(pos_bias(f'{b}.attn.attns.{idx}'))
+                        W[f'{b}.attn.bias{idx}'] = bias_fragments_qk(pos_bias(f'{b}.attn.attns.{idx}'))
                 else:
                     W[f'{b}.attn.temperature'] = f32(sd[f'{b}.attn.temperature']).reshape(-1)
                 aim(f'{b}.attn', heads)
@@ -407,14 +318,6 @@ class DAT(EngineModule):
         Hp, Wp = H + (m - H % m) % m, Wd + (m - Wd % m) % m
         shift = [self.split_size[0] // 2, self.split_size[1] // 2]
 
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
-
-        def launch(fn_name, params):
-            fn = getattr(lib, fn_name)
-            plan.call(lambda: L.check(fn(C.byref(params), stream()), fn_name))
-            plan.count_launches(1)
-
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, with_lo)
         mean = W['mean']
 
@@ -452,17 +355,8 @@ class DAT(EngineModule):
                 wdyn[heads] = torch.zeros((n, blob), dtype=torch.bfloat16, device=dev)  # off-diagonal blocks stay zero forever
                 plan.keep.append(wdyn[heads])
 
-        def layernorm(name, x_f32, out_planes=None, out_f32=None):
-            g, b = W[name]
-            lp = L.LayerNormParams()
-            lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, C_, 1e-5
-            lp.x_f32, lp.gamma, lp.beta = x_f32.data_ptr(), g.data_ptr(), b.data_ptr()
-            if out_planes is not None:
-                lp.out_hi, lp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-                lp.out_plane_stride, lp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
-                lp.out_fmt = out_planes.fmt
-            lp.out_f32 = None if out_f32 is None else out_f32.data_ptr()
-            launch('rsa_layernorm', lp)
+        def norm(name, x_f32, out_planes=None, out_f32=None):
+            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
 
         def rect_attention(b, heads, shifted):
             for idx in (0, 1):
@@ -477,7 +371,7 @@ class DAT(EngineModule):
                 ap.bias_frag = W[f'{b}.attn.bias{idx}'].data_ptr()
                 ap.out_hi, ap.out_lo = att_pl.hi_ptr(), att_pl.lo_ptr()
                 ap.out_plane_stride, ap.out_batch_stride = att_pl.plane_stride, att_pl.batch_stride
-                launch('rsa_rect_attention', ap)
+                plan.launch('rsa_rect_attention', ap)
 
         def channel_attention(b, heads):
             hp = heads * 4
@@ -489,8 +383,7 @@ class DAT(EngineModule):
             cpar.plane_stride, cpar.batch_stride = qkv_pl.plane_stride, qkv_pl.batch_stride
             cpar.temperature = W[f'{b}.attn.temperature'].data_ptr()
             cpar.workspace, cpar.w_packed = ws_attn.data_ptr(), wdyn[heads].data_ptr()
-            launch('rsa_channel_attention_weights', cpar)
-            plan.count_launches(1)  # two kernels
+            plan.launch('rsa_channel_attention_weights', cpar, kernels=2)
             for bi in range(n):  # attn @ v: the weights differ per image
                 wts = ops.ConvWeights(wdyn[heads][bi], zero_bias, heads * HEAD_PAD, heads * HEAD_PAD, hp, 1, bprod, fmt=bfmt)
                 src = Planes(qkv_pl.hi[bi : bi + 1], None if qkv_pl.lo is None else qkv_pl.lo[bi : bi + 1])
@@ -511,7 +404,7 @@ class DAT(EngineModule):
                 dp.mul_plane_stride, dp.mul_batch_stride = mul.plane_stride, mul.batch_stride
             dp.out_hi, dp.out_lo = out.hi_ptr(), out.lo_ptr()
             dp.out_plane_stride, dp.out_batch_stride = out.plane_stride, out.batch_stride
-            launch('rsa_dwconv3x3', dp)
+            plan.launch('rsa_dwconv3x3', dp)
 
         def channel_gate(a, src, heads):
             w1, b1, w2, b2 = W[f'{a}.ci']
@@ -522,8 +415,7 @@ class DAT(EngineModule):
             gp.in_plane_stride, gp.in_batch_stride = src.plane_stride, src.batch_stride
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
-            launch('rsa_channel_gate', gp)
-            plan.count_launches(1)  # two kernels
+            plan.launch('rsa_channel_gate', gp, kernels=2)
 
         def aim_combine(a, heads, mode):
             w1, b1, w2, b2 = W[f'{a}.si']
@@ -537,12 +429,12 @@ class DAT(EngineModule):
             ap.gate, ap.w1, ap.b1, ap.w2, ap.b2 = gate.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2
             ap.out_hi, ap.out_lo = comb_pl.hi_ptr(), comb_pl.lo_ptr()
             ap.out_plane_stride, ap.out_batch_stride = comb_pl.plane_stride, comb_pl.batch_stride
-            launch('rsa_aim_combine', ap)
+            plan.launch('rsa_aim_combine', ap)
 
         def plane_stats(src, plane0, channels):
             def run():
                 L.check(lib.rsa_plane_stats_fmt(src.hi_ptr(plane0), src.lo_ptr(plane0), src.plane_stride, src.batch_stride, n, H, Wd, channels, 1e-5,
-                                                src.fmt, stats.data_ptr(), stream()), 'rsa_plane_stats')  # fmt: skip
+                                                src.fmt, stats.data_ptr(), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_plane_stats')  # fmt: skip
 
             plan.call(run)
             plan.count_launches(1)
@@ -559,7 +451,7 @@ class DAT(EngineModule):
         plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
         free = list(pool)
         cur = free.pop()
-        layernorm('before_RG.1', first, out_f32=cur)
+        norm('before_RG.1', first, out_f32=cur)
         for i, d in enumerate(self.depth):
             heads = self.num_heads[i]
             hp = heads * 4
@@ -567,7 +459,7 @@ class DAT(EngineModule):
             for j in range(d):
                 b = f'layers.{i}.blocks.{j}'
                 a = f'{b}.attn'
-                layernorm(f'{b}.norm1', cur, out_planes=a_pl)
+                norm(f'{b}.norm1', cur, out_planes=a_pl)
                 plan.conv(ops.conv_params(W[f'{a}.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
                 if j % 2 == 0:
                     rect_attention(b, heads, is_shifted(i, j))
@@ -581,7 +473,7 @@ class DAT(EngineModule):
                     aim_combine(a, heads, 1)
                 x1 = free.pop()
                 plan.conv(ops.conv_params(W[f'{a}.proj'], comb_pl, H, Wd, cin_planes=hp, res1=cur, alpha=1.0, out_f32=x1))
-                layernorm(f'{b}.norm2', x1, out_planes=a_pl)
+                norm(f'{b}.norm2', x1, out_planes=a_pl)
                 plan.conv(ops.conv_params(W[f'{b}.ffn.fc1'], a_pl, H, Wd, cin_planes=cp, act=L.ACT_GELU, out=hid_pl))
                 sgw, sgb, sgg, sgbeta = W[f'{b}.ffn.sg']
                 plane_stats(hid_pl, P1, half)
@@ -600,27 +492,15 @@ class DAT(EngineModule):
             if cur is not rg_in:
                 free.append(cur)
             cur = out
-        layernorm('norm', cur, out_planes=n_pl)
+        norm('norm', cur, out_planes=n_pl)
         resi_conv('conv_after_body', n_pl, first, out_planes=body_pl)  # + conv_first output (arch.py:981, 986)
 
         out_shape = (n, self.in_chans, H * s, Wd * s)
         out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
         final = dict(out_scale=1.0 / self.img_range, out_shift=mean)  # x / img_range + mean (arch.py:989)
         if self.upsampler == 'pixelshuffle':
-            y = plan.planes(n, 8, H, Wd, with_lo)
-            plan.conv(ops.conv_params(W['conv_before_upsample.0'], body_pl, H, Wd, cin_planes=cp, act=L.ACT_LRELU, act_param=0.01, out=y))
-            hh, ww = H, Wd
-            i = 0
-            while f'upsample.{i}' in W:
-                r = math.isqrt(W[f'upsample.{i}'].cout // 64)
-                shuffled = torch.empty((n, 64, hh * r, ww * r), dtype=torch.float32, device=dev)
-                plan.keep.append(shuffled)
-                plan.conv(ops.conv_params(W[f'upsample.{i}'], y, hh, ww, out_nchw=shuffled, pixel_shuffle=r))
-                hh, ww = hh * r, ww * r
-                ny = plan.planes(n, 8, hh, ww, with_lo)
-                plan.call(lambda src=shuffled, dst=ny: ops.nchw_to_planes(src, dst))
-                y = ny
-                i += 2
+            head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
+            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
             plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=out_buf['y'], **final))
         else:
             plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=out_buf['y'], pixel_shuffle=s, **final))

@@ -16,20 +16,22 @@ On the engine:
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
 from ...engine import lib as L
 from ...engine import ops
-from ...engine.tensors import PF_BF16, PF_F16, Planes
 from ...engine.base import EngineModule, Plan, check_fp16_range
-from ...engine.paramtree import build_param_tree
-from ..dat.arch import bias_fragments
-from ..swinir.arch import relative_position_index, shift_attn_mask
+from ...engine.paramtree import ParamShapes, build_param_tree
+from ...engine.tensors import PF_BF16, PF_F16, Planes
+from ...engine.transformer import (LayerPacker, bias_fragments_qk, layernorm, pixelshuffle_buffers, pixelshuffle_head, regroup_proj,
+                                   regroup_qkv, relative_position_index, shift_mask)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:649
+
+# names this module exported before the shared helpers moved to engine/transformer.py
+regroup_qkv_wide, regroup_proj_wide = regroup_qkv, regroup_proj
 
 
 def block_dims(embed_dim: int, gc: int, num_heads: int):
@@ -42,79 +44,35 @@ def block_dims(embed_dim: int, gc: int, num_heads: int):
     return out
 
 
-def regroup_qkv_wide(w: torch.Tensor, b: torch.Tensor | None, heads: int, pad: int) -> tuple[torch.Tensor, torch.Tensor]:
-    """[3C, C] -> [3*heads*pad, C]: row (which, head, d) <- which*C + head*hd + d, zero rows for d >= hd; q rows scaled by hd^-0.5."""
-    c3, c = w.shape
-    hd = c // heads
-    wn = torch.zeros((3, heads, pad, c), dtype=torch.float32, device=w.device)
-    bn = torch.zeros((3, heads, pad), dtype=torch.float32, device=w.device)
-    wn[:, :, :hd] = w.to(torch.float32).reshape(3, heads, hd, c)
-    if b is not None:
-        bn[:, :, :hd] = b.to(torch.float32).reshape(3, heads, hd)
-    wn[0] *= hd**-0.5
-    bn[0] *= hd**-0.5
-    return wn.reshape(3 * heads * pad, c), bn.reshape(-1)
-
-
-def regroup_proj_wide(w: torch.Tensor, heads: int, pad: int) -> torch.Tensor:
-    """[C, C] -> [C, heads*pad]: column (head, d) <- head*hd + d."""
-    c = w.shape[0]
-    hd = w.shape[1] // heads
-    wn = torch.zeros((c, heads, pad), dtype=torch.float32, device=w.device)
-    wn[:, :, :hd] = w.to(torch.float32).reshape(c, heads, hd)
-    return wn.reshape(c, heads * pad)
-
-
 def drct_param_shapes(in_chans, embed_dim, num_layers, num_heads, window, mlp_ratio, gc, upscale, resi, img_size, patch_norm, qkv_bias, upsampler):
-    shapes: dict = {}
+    s = ParamShapes()
     buffers: dict = {}
     C_ = embed_dim
 
-    def conv(name, co, ci, k):
-        shapes[f'{name}.weight'] = (co, ci, k, k)
-        shapes[f'{name}.bias'] = (co,)
-
-    def lin(name, co, ci, bias=True):
-        shapes[f'{name}.weight'] = (co, ci)
-        if bias:
-            shapes[f'{name}.bias'] = (co,)
-
-    def ln(name, c):
-        shapes[f'{name}.weight'] = (c,)
-        shapes[f'{name}.bias'] = (c,)
-
-    conv('conv_first', C_, in_chans, 3)
+    s.conv('conv_first', C_, in_chans, 3)
     if patch_norm:
-        ln('patch_embed.norm', C_)
+        s.norm('patch_embed.norm', C_)
     for i in range(num_layers):
         for j, (dim, heads, shifted, full_mlp) in enumerate(block_dims(C_, gc, num_heads[i]), start=1):
             b = f'layers.{i}.swin{j}'
             hidden = int(dim * (mlp_ratio if full_mlp else 1))
-            ln(f'{b}.norm1', dim)
-            shapes[f'{b}.attn.relative_position_bias_table'] = ((2 * window - 1) ** 2, heads)
+            s.norm(f'{b}.norm1', dim)
+            s[f'{b}.attn.relative_position_bias_table'] = ((2 * window - 1) ** 2, heads)
             buffers[f'{b}.attn.relative_position_index'] = relative_position_index(window)
             if shifted and img_size > window:
-                buffers[f'{b}.attn_mask'] = shift_attn_mask(img_size, window)
-            lin(f'{b}.attn.qkv', 3 * dim, dim, qkv_bias)
-            lin(f'{b}.attn.proj', dim, dim)
-            ln(f'{b}.norm2', dim)
-            lin(f'{b}.mlp.fc1', hidden, dim)
-            lin(f'{b}.mlp.fc2', dim, hidden)
-            conv(f'layers.{i}.adjust{j}', gc if j < 5 else C_, dim, 1)
-    ln('norm', C_)
+                buffers[f'{b}.attn_mask'] = shift_mask(img_size, img_size, (window, window), (window // 2, window // 2))
+            s.linear(f'{b}.attn.qkv', 3 * dim, dim, qkv_bias)
+            s.linear(f'{b}.attn.proj', dim, dim)
+            s.norm(f'{b}.norm2', dim)
+            s.linear(f'{b}.mlp.fc1', hidden, dim)
+            s.linear(f'{b}.mlp.fc2', dim, hidden)
+            s.conv(f'layers.{i}.adjust{j}', gc if j < 5 else C_, dim, 1)
+    s.norm('norm', C_)
     if resi == '1conv':
-        conv('conv_after_body', C_, C_, 3)
+        s.conv('conv_after_body', C_, C_, 3)
     if upsampler == 'pixelshuffle':
-        conv('conv_before_upsample.0', 64, C_, 3)
-        if upscale == 3:
-            conv('upsample.0', 9 * 64, 64, 3)
-        elif upscale & (upscale - 1) == 0:
-            for u in range(int(math.log2(upscale))):
-                conv(f'upsample.{2 * u}', 4 * 64, 64, 3)
-        else:
-            raise ValueError(f'scale {upscale} is not supported. Supported scales: 2^n and 3.')
-        conv('conv_last', in_chans, 64, 3)
-    return shapes, buffers
+        s.pixelshuffle_head(C_, 64, in_chans, upscale)
+    return s, buffers
 
 
 class DRCT(EngineModule):
@@ -169,25 +127,8 @@ class DRCT(EngineModule):
     # ---------------------------------------------------------------- weights
     def _pack(self, device, products):
         sd = {k: v.detach().to(device) for k, v in self.state_dict().items()}
-        W: dict = {}
-
-        mixed = products.name == 'mixed'
-
-        def policy(name):
-            return self.layer_policy(name) if mixed else (int(products), products.fmt)
-
-        def conv(name):
-            prod, fmt = policy(name)
-            W[name] = ops.ConvWeights.from_oihw(sd[f'{name}.weight'], sd.get(f'{name}.bias'), prod, device=device, fmt=fmt)
-
-        def lin(name, w=None, b=None, cin_planes=None):
-            w = sd[f'{name}.weight'] if w is None else w
-            b = sd.get(f'{name}.bias') if b is None else b
-            prod, fmt = policy(name)
-            W[name] = ops.ConvWeights.from_oihw(w[:, :, None, None], b, prod, cin_planes=cin_planes, device=device, fmt=fmt)
-
-        def ln(name):
-            W[name] = (sd[f'{name}.weight'].float().contiguous(), sd[f'{name}.bias'].float().contiguous())
+        pk = LayerPacker(sd, device, products, self.layer_policy)
+        W, conv, lin, ln = pk.W, pk.conv, pk.lin, pk.ln
 
         conv('conv_first')
         if self.patch_norm:
@@ -199,14 +140,14 @@ class DRCT(EngineModule):
                 pad = 32 * -(-(dim // heads) // 32)
                 ln(f'{b}.norm1')
                 ln(f'{b}.norm2')
-                wq, bq = regroup_qkv_wide(sd[f'{b}.attn.qkv.weight'], sd.get(f'{b}.attn.qkv.bias'), heads, pad)
+                wq, bq = regroup_qkv(sd[f'{b}.attn.qkv.weight'], sd.get(f'{b}.attn.qkv.bias'), heads, pad)
                 lin(f'{b}.attn.qkv', wq, bq)
-                lin(f'{b}.attn.proj', regroup_proj_wide(sd[f'{b}.attn.proj.weight'], heads, pad), sd[f'{b}.attn.proj.bias'], cin_planes=heads * pad // 8)
+                lin(f'{b}.attn.proj', regroup_proj(sd[f'{b}.attn.proj.weight'], heads, pad), sd[f'{b}.attn.proj.bias'], cin_planes=heads * pad // 8)
                 lin(f'{b}.mlp.fc1')
                 lin(f'{b}.mlp.fc2')
                 n = win * win
                 dense = sd[f'{b}.attn.relative_position_bias_table'].float()[sd[f'{b}.attn.relative_position_index'].reshape(-1).long()]
-                W[f'{b}.bias_frag'] = bias_fragments(dense.reshape(n, n, heads).permute(2, 0, 1).contiguous())
+                W[f'{b}.bias_frag'] = bias_fragments_qk(dense.reshape(n, n, heads).permute(2, 0, 1).contiguous())
                 conv(f'layers.{i}.adjust{j}')
         ln('norm')
         if self.resi == 'identity':  # nn.Identity as a 1x1 convolution (see _build_plan)
@@ -258,7 +199,6 @@ class DRCT(EngineModule):
         wide = C_ + 4 * gc
         with_lo = products == 3
         dev = plan.device
-        lib = L.load()
 
         x_all = plan.planes(nb, (c + 7) // 8, H, Wd, with_lo)
         mean = W['mean']
@@ -282,17 +222,7 @@ class DRCT(EngineModule):
         hid_pl = plan.planes(n, (int(wide * max(self.mlp_ratio, 1.0)) + 7) // 8, H, Wd, **one)
         t_pl = plan.planes(n, (wide + 7) // 8, H, Wd, **one)  # a block's output as planes (input of its adjust convolution)
         body_pl = plan.planes(n, (C_ + 7) // 8, H, Wd, with_lo)
-        y0_pl = plan.planes(n, 8, H, Wd, with_lo)
-        # the pixel-shuffle stages of the head: a plain tensor the final store writes, re-laid out as planes for the next convolution
-        stages = []
-        hh, ww, i = H, Wd, 0
-        while f'upsample.{i}' in W:
-            r = math.isqrt(W[f'upsample.{i}'].cout // 64)
-            shuffled = torch.empty((n, 64, hh * r, ww * r), dtype=torch.float32, device=dev)
-            plan.keep.append(shuffled)
-            hh, ww = hh * r, ww * r
-            stages.append((f'upsample.{i}', r, shuffled, plan.planes(n, 8, hh, ww, with_lo)))
-            i += 2
+        head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)  # shared by the images of a batch
         if self.resi == 'identity' and 'identity' not in W:
             raise RuntimeError('packed weights lack the identity layer')  # (_pack adds it)
 
@@ -300,18 +230,8 @@ class DRCT(EngineModule):
             """Channels [c0, c0 + cn) of an f32 token map as a map of their own (one image: groups are contiguous)."""
             return m[:, c0 // 4 : (c0 + cn) // 4]
 
-        def layernorm(name, x_f32, C_in, out_planes=None, out_f32=None):
-            g, b = W[name]
-            lp = L.LayerNormParams()
-            lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, C_in, 1e-5
-            lp.x_f32, lp.gamma, lp.beta = x_f32.data_ptr(), g.data_ptr(), b.data_ptr()
-            if out_planes is not None:
-                lp.out_hi, lp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-                lp.out_plane_stride, lp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
-                lp.out_fmt = out_planes.fmt
-            lp.out_f32 = None if out_f32 is None else out_f32.data_ptr()
-            plan.call(lambda: L.check(lib.rsa_layernorm(C.byref(lp), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_layernorm'))
-            plan.count_launches(1)
+        def norm(name, x_f32, C_in, out_planes=None, out_f32=None):
+            layernorm(plan, W, name, n, H, Wd, C_in, x_f32, out_planes, out_f32)
 
         def attention(name, heads, chunks, shifted):
             ap = L.RectAttnParams()
@@ -323,8 +243,7 @@ class DRCT(EngineModule):
             ap.qkv_hi, ap.qkv_lo, ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.hi_ptr(), qkv_pl.lo_ptr(), qkv_pl.plane_stride, qkv_pl.batch_stride
             ap.bias_frag = W[f'{name}.bias_frag'].data_ptr()
             ap.out_hi, ap.out_lo, ap.out_plane_stride, ap.out_batch_stride = o_pl.hi_ptr(), o_pl.lo_ptr(), o_pl.plane_stride, o_pl.batch_stride
-            plan.call(lambda: L.check(lib.rsa_rect_attention(C.byref(ap), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_rect_attention'))
-            plan.count_launches(1)
+            plan.launch('rsa_rect_attention', ap)
 
         def f32_view_conv(wts, src, **kw):
             """conv_params with f32 operands that are channel views of wider maps: checked against the view, passed by pointer."""
@@ -340,7 +259,7 @@ class DRCT(EngineModule):
             plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
             cur = cat[0]
             if self.patch_norm:
-                layernorm('patch_embed.norm', first, C_, out_f32=chan_view(cur, 0, C_))
+                norm('patch_embed.norm', first, C_, out_f32=chan_view(cur, 0, C_))
             else:
                 plan.call(lambda dst=chan_view(cur, 0, C_): dst.copy_(first))
             ci = 0
@@ -353,12 +272,12 @@ class DRCT(EngineModule):
                     cp = (dim + 7) // 8
                     hidden = int(dim * (self.mlp_ratio if full_mlp else 1))
                     xin = chan_view(cur, 0, dim)
-                    layernorm(f'{b}.norm1', xin, dim, out_planes=a_pl)
+                    norm(f'{b}.norm1', xin, dim, out_planes=a_pl)
                     plan.conv(ops.conv_params(W[f'{b}.attn.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
                     attention(b, heads, chunks, shifted and not self.unshifted)
                     x1 = chan_view(blk[0], 0, dim)
                     plan.conv(f32_view_conv(W[f'{b}.attn.proj'], o_pl, cin_planes=hp, res1=xin, alpha=1.0, out_f32=x1))
-                    layernorm(f'{b}.norm2', x1, dim, out_planes=a_pl)
+                    norm(f'{b}.norm2', x1, dim, out_planes=a_pl)
                     plan.conv(ops.conv_params(W[f'{b}.mlp.fc1'], a_pl, H, Wd, cin_planes=cp, act=L.ACT_GELU, out=hid_pl))
                     plan.conv(f32_view_conv(W[f'{b}.mlp.fc2'], hid_pl, cin_planes=(hidden + 7) // 8, res1=x1, alpha=1.0, out=t_pl))
                     # adjust_j (1x1) on the block's output: x_j = lrelu(.) stored at channel offset dim of the concatenation;
@@ -369,19 +288,12 @@ class DRCT(EngineModule):
                         plan.conv(f32_view_conv(W[f'layers.{i}.adjust{j}'], t_pl, cin_planes=cp, res1=chan_view(cur, 0, C_), alpha=0.2, out_f32=chan_view(nxt, 0, C_)))
                 ci ^= 1
             cur = cat[ci]
-            layernorm('norm', chan_view(cur, 0, C_), C_, out_planes=n_pl)
+            norm('norm', chan_view(cur, 0, C_), C_, out_planes=n_pl)
             cp0 = (C_ + 7) // 8
             # conv_after_body(forward_features(x)) + conv_first(x) (arch.py:781): a 3x3 convolution, or nn.Identity (arch.py:731-732) -- the
             # latter as a 1x1 convolution with the identity matrix, whose epilogue adds conv_first's map and writes the planes the head reads
             plan.conv(ops.conv_params(W['conv_after_body' if self.resi == '1conv' else 'identity'], n_pl, H, Wd, cin_planes=cp0, res1=first, alpha=1.0, out=body_pl))
-            plan.conv(ops.conv_params(W['conv_before_upsample.0'], body_pl, H, Wd, cin_planes=cp0, act=L.ACT_LRELU, act_param=0.01, out=y0_pl))
-            y, hh, ww = y0_pl, H, Wd
-            for name, r, shuffled, ny in stages:
-                plan.conv(ops.conv_params(W[name], y, hh, ww, out_nchw=shuffled, pixel_shuffle=r))
-                hh, ww = hh * r, ww * r
-                plan.call(lambda src=shuffled, dst=ny: ops.nchw_to_planes(src, dst))
-                plan.count_launches(1)
-                y = ny
+            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp0, H, Wd)
             placeholder = torch.empty((n,) + out_shape[1:], dtype=dtype, device=dev)  # (never written: prepare_output patches the pointer first)
             plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=placeholder, **final))
             arr = plan.flush()

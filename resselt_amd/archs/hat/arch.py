@@ -16,18 +16,18 @@ relative-position tables are gathered once, at pack time, into the kernel's accu
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
+import os
 
 import torch
 
 from ...engine import lib as L
-from ...engine import ops, swinblocks
+from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
+from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16
-from ...engine.paramtree import build_param_tree
-from ..dat.arch import attn_tiles
-from ..swinir.arch import HEAD_PAD, regroup_proj, regroup_qkv
+from ...engine.transformer import (HEAD_PAD, LayerPacker, attn_tiles, bias_fragments_qk, layernorm, mlp_block, mlp_block_fits, pixelshuffle_buffers,
+                                   pixelshuffle_head, regroup_proj, regroup_qkv, relative_position_index)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:842
 
@@ -35,100 +35,56 @@ RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:842
 def rpi_buffers(window: int, overlap_ratio: float):
     """``relative_position_index_SA`` / ``_OCA`` (arch.py:987-1034)."""
     co = torch.stack(torch.meshgrid([torch.arange(window), torch.arange(window)], indexing='ij')).flatten(1)
-    rel = (co[:, :, None] - co[:, None, :]).permute(1, 2, 0).contiguous()
-    rel[:, :, 0] += window - 1
-    rel[:, :, 1] += window - 1
-    rel[:, :, 0] *= 2 * window - 1
-    sa = rel.sum(-1)
     ext = window + int(overlap_ratio * window)
     ce = torch.stack(torch.meshgrid([torch.arange(ext), torch.arange(ext)], indexing='ij')).flatten(1)
     rel = (ce[:, None, :] - co[:, :, None]).permute(1, 2, 0).contiguous()
     rel[:, :, 0] += window - ext + 1
     rel[:, :, 1] += window - ext + 1
     rel[:, :, 0] *= window + ext - 1
-    return sa, rel.sum(-1)
-
-
-def bias_fragments_qk(dense: torch.Tensor, qt: int, kt: int) -> torch.Tensor:
-    """[heads, Nq, Nk] (query, key) position bias -> [heads][qt][kt][lane 64][16] f32 in the S^T accumulator order of rsa_rect_attention:
-    lane l, element r  <->  query 32*q + (l & 31),  key 32*k + (r & 3) + 8*(r >> 2) + 4*(l >> 5).  Padded keys get -1e30."""
-    heads, nq, nk = dense.shape
-    full = torch.zeros((heads, 32 * qt, 32 * kt), dtype=torch.float32, device=dense.device)
-    full[:, :, nk:] = -1e30
-    full[:, :nq, :nk] = dense.to(torch.float32)
-    lane = torch.arange(64, device=dense.device)
-    r = torch.arange(16, device=dense.device)
-    q_in = (lane & 31)[:, None].expand(64, 16)
-    k_in = ((r & 3) + 8 * (r >> 2))[None, :] + 4 * (lane >> 5)[:, None]
-    out = torch.empty((heads, qt, kt, 64, 16), dtype=torch.float32, device=dense.device)
-    for a in range(qt):
-        for b in range(kt):
-            out[:, a, b] = full[:, 32 * a + q_in, 32 * b + k_in]
-    return out.contiguous()
+    return relative_position_index(window), rel.sum(-1)
 
 
 def hat_param_shapes(in_chans, embed_dim, depths, num_heads, window, compress_ratio, squeeze_factor, overlap_ratio, mlp_ratio, upscale, num_feat,
                      resi, patch_norm, qkv_bias):  # fmt: skip
-    shapes: dict = {}
+    s = ParamShapes()
     C_ = embed_dim
     hidden = int(C_ * mlp_ratio)
     ext = window + int(overlap_ratio * window)
 
-    def conv(name, co, ci, k):
-        shapes[f'{name}.weight'] = (co, ci, k, k)
-        shapes[f'{name}.bias'] = (co,)
-
-    def lin(name, co, ci, bias=True):
-        shapes[f'{name}.weight'] = (co, ci)
-        if bias:
-            shapes[f'{name}.bias'] = (co,)
-
-    def ln(name):
-        shapes[f'{name}.weight'] = (C_,)
-        shapes[f'{name}.bias'] = (C_,)
-
-    conv('conv_first', C_, in_chans, 3)
+    s.conv('conv_first', C_, in_chans, 3)
     if patch_norm:
-        ln('patch_embed.norm')
+        s.norm('patch_embed.norm', C_)
     for i, depth in enumerate(depths):
         g = f'layers.{i}.residual_group'
         for j in range(depth):
             b = f'{g}.blocks.{j}'
-            ln(f'{b}.norm1')
-            shapes[f'{b}.attn.relative_position_bias_table'] = ((2 * window - 1) ** 2, num_heads[i])
-            lin(f'{b}.attn.qkv', 3 * C_, C_, qkv_bias)
-            lin(f'{b}.attn.proj', C_, C_)
-            conv(f'{b}.conv_block.cab.0', int(C_ // compress_ratio), C_, 3)
-            conv(f'{b}.conv_block.cab.2', C_, int(C_ // compress_ratio), 3)
-            conv(f'{b}.conv_block.cab.3.attention.1', int(C_ // squeeze_factor), C_, 1)
-            conv(f'{b}.conv_block.cab.3.attention.3', C_, int(C_ // squeeze_factor), 1)
-            ln(f'{b}.norm2')
-            lin(f'{b}.mlp.fc1', hidden, C_)
-            lin(f'{b}.mlp.fc2', C_, hidden)
+            s.norm(f'{b}.norm1', C_)
+            s[f'{b}.attn.relative_position_bias_table'] = ((2 * window - 1) ** 2, num_heads[i])
+            s.linear(f'{b}.attn.qkv', 3 * C_, C_, qkv_bias)
+            s.linear(f'{b}.attn.proj', C_, C_)
+            s.conv(f'{b}.conv_block.cab.0', int(C_ // compress_ratio), C_, 3)
+            s.conv(f'{b}.conv_block.cab.2', C_, int(C_ // compress_ratio), 3)
+            s.conv(f'{b}.conv_block.cab.3.attention.1', int(C_ // squeeze_factor), C_, 1)
+            s.conv(f'{b}.conv_block.cab.3.attention.3', C_, int(C_ // squeeze_factor), 1)
+            s.norm(f'{b}.norm2', C_)
+            s.linear(f'{b}.mlp.fc1', hidden, C_)
+            s.linear(f'{b}.mlp.fc2', C_, hidden)
         o = f'{g}.overlap_attn'
-        ln(f'{o}.norm1')
-        lin(f'{o}.qkv', 3 * C_, C_, qkv_bias)
-        shapes[f'{o}.relative_position_bias_table'] = ((window + ext - 1) ** 2, num_heads[i])
-        lin(f'{o}.proj', C_, C_)
-        ln(f'{o}.norm2')
-        lin(f'{o}.mlp.fc1', hidden, C_)
-        lin(f'{o}.mlp.fc2', C_, hidden)
+        s.norm(f'{o}.norm1', C_)
+        s.linear(f'{o}.qkv', 3 * C_, C_, qkv_bias)
+        s[f'{o}.relative_position_bias_table'] = ((window + ext - 1) ** 2, num_heads[i])
+        s.linear(f'{o}.proj', C_, C_)
+        s.norm(f'{o}.norm2', C_)
+        s.linear(f'{o}.mlp.fc1', hidden, C_)
+        s.linear(f'{o}.mlp.fc2', C_, hidden)
         if resi == '1conv':
-            conv(f'layers.{i}.conv', C_, C_, 3)
-    ln('norm')
+            s.conv(f'layers.{i}.conv', C_, C_, 3)
+    s.norm('norm', C_)
     if resi == '1conv':
-        conv('conv_after_body', C_, C_, 3)
-    conv('conv_before_upsample.0', num_feat, C_, 3)
-    if upscale == 3:
-        conv('upsample.0', 9 * num_feat, num_feat, 3)
-    elif upscale & (upscale - 1) == 0:
-        for u in range(int(math.log2(upscale))):
-            conv(f'upsample.{2 * u}', 4 * num_feat, num_feat, 3)
-    else:
-        raise ValueError(f'scale {upscale} is not supported. Supported scales: 2^n and 3.')
-    conv('conv_last', in_chans, num_feat, 3)
+        s.conv('conv_after_body', C_, C_, 3)
+    s.pixelshuffle_head(C_, num_feat, in_chans, upscale)
     sa, oca = rpi_buffers(window, overlap_ratio)
-    return shapes, {'relative_position_index_SA': sa, 'relative_position_index_OCA': oca}
+    return s, {'relative_position_index_SA': sa, 'relative_position_index_OCA': oca}
 
 
 class HAT(EngineModule):
@@ -150,7 +106,7 @@ class HAT(EngineModule):
             return 1, PF_F16
         return 3, PF_BF16
 
-    fused_mlp = os.environ.get('RSA_HAT_FUSED_MLP', '1') != '0'  # LayerNorm + fc1 + GELU + fc2 + shortcut as one launch where the widths allow it (engine/swinblocks.py)
+    fused_mlp = os.environ.get('RSA_HAT_FUSED_MLP', '1') != '0'  # LayerNorm + fc1 + GELU + fc2 + shortcut as one launch where the widths allow it (engine/transformer.py)
 
     def __init__(self, *, img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths=(6, 6, 6, 6), num_heads=(6, 6, 6, 6), window_size=7,
                  compress_ratio=3, squeeze_factor=30, conv_scale=0.01, overlap_ratio=0.5, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
@@ -178,30 +134,13 @@ class HAT(EngineModule):
     # ---------------------------------------------------------------- weights
     def _pack(self, device, products):
         sd = {k: v.detach().to(device) for k, v in self.state_dict().items()}
-        W: dict = {}
         C_, ws, ext = self.embed_dim, self.window_size, self.ext
         cp = (C_ + 7) // 8
+        pk = LayerPacker(sd, device, products, self.layer_policy)
+        W, conv, lin, ln = pk.W, pk.conv, pk.lin, pk.ln
 
         def f32(t):
             return t.to(torch.float32).contiguous()
-
-        mixed = products.name == 'mixed'
-
-        def policy(name):
-            return self.layer_policy(name) if mixed else (int(products), products.fmt)
-
-        def conv(name):
-            prod, fmt = policy(name)
-            W[name] = ops.ConvWeights.from_oihw(sd[f'{name}.weight'], sd.get(f'{name}.bias'), prod, device=device, fmt=fmt)
-
-        def lin(name, w=None, b=None, cin_planes=None):
-            w = sd[f'{name}.weight'] if w is None else w
-            b = sd.get(f'{name}.bias') if b is None else b
-            prod, fmt = policy(name)
-            W[name] = ops.ConvWeights.from_oihw(w[:, :, None, None], b, prod, cin_planes=cin_planes, device=device, fmt=fmt)
-
-        def ln(name):
-            W[name] = (f32(sd[f'{name}.weight']), f32(sd[f'{name}.bias']))
 
         def attention(name, heads, table_key, rpi, nq, nk, cross):
             wq, bq = regroup_qkv(sd[f'{name}.qkv.weight'], sd.get(f'{name}.qkv.bias'), heads)
@@ -301,14 +240,6 @@ class HAT(EngineModule):
         lib = L.load()
         max_heads = max(self.num_heads)
 
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
-
-        def launch(fn_name, params, kernels=1):
-            fn = getattr(lib, fn_name)
-            plan.call(lambda: L.check(fn(C.byref(params), stream()), fn_name))
-            plan.count_launches(kernels)
-
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, with_lo)
         mean = W['mean']
 
@@ -323,7 +254,7 @@ class HAT(EngineModule):
         n_pl = plan.planes(n, cp, H, Wd, with_lo) if mixed else a_pl  # the last LayerNorm -> conv_after_body (three products)
         qkv_pl = plan.planes(n, 3 * max_heads * HEAD_PAD // 8, H, Wd, **one)
         o_pl = plan.planes(n, max_heads * HEAD_PAD // 8, H, Wd, **one)
-        fuse_mlp = self.fused_mlp and swinblocks.mlp_block_fits(C_, hidden)
+        fuse_mlp = self.fused_mlp and mlp_block_fits(C_, hidden)
         hid_pl = None if fuse_mlp else plan.planes(n, (hidden + 7) // 8, H, Wd, **one)
         body_pl = plan.planes(n, cp, H, Wd, with_lo)
         cab_a = plan.planes(n, (self.compress + 7) // 8, H, Wd, **one)
@@ -332,17 +263,8 @@ class HAT(EngineModule):
         ws_gate = torch.empty((max(int(lib.rsa_channel_gate_workspace_bytes(n, H, Wd, cp)), 16) // 4,), dtype=torch.float32, device=dev)
         plan.keep += [gate, ws_gate]
 
-        def layernorm(name, x_f32, out_planes=None, out_f32=None):
-            g, b = W[name]
-            lp = L.LayerNormParams()
-            lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, C_, 1e-5
-            lp.x_f32, lp.gamma, lp.beta = x_f32.data_ptr(), g.data_ptr(), b.data_ptr()
-            if out_planes is not None:
-                lp.out_hi, lp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-                lp.out_plane_stride, lp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
-                lp.out_fmt = out_planes.fmt
-            lp.out_f32 = None if out_f32 is None else out_f32.data_ptr()
-            launch('rsa_layernorm', lp)
+        def norm(name, x_f32, out_planes=None, out_f32=None):
+            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
 
         def attention(name, heads, shift, cross):
             ap = L.RectAttnParams()
@@ -358,7 +280,7 @@ class HAT(EngineModule):
             if cross:
                 ap.kwin_h = ap.kwin_w = ext
                 ap.kpad_h = ap.kpad_w = (ext - ws) // 2
-            launch('rsa_rect_attention', ap)
+            plan.launch('rsa_rect_attention', ap)
 
         def cab_scaled_shortcut(b, shortcut, out_f32):
             """out = shortcut + CAB(LN(x)) * conv_scale, CAB = conv-GELU-conv followed by its channel attention (arch.py:37-59, 345)."""
@@ -371,20 +293,20 @@ class HAT(EngineModule):
             gp.in_plane_stride, gp.in_batch_stride = cab_b.plane_stride, cab_b.batch_stride
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
-            launch('rsa_channel_gate', gp, kernels=2)
+            plan.launch('rsa_channel_gate', gp, kernels=2)
 
             def run():
                 L.check(lib.rsa_gated_add(cab_b.hi_ptr(), cab_b.lo_ptr(), cab_b.plane_stride, cab_b.batch_stride, n, H, Wd, C_, gate.data_ptr(),
-                                          self.conv_scale, shortcut.data_ptr(), out_f32.data_ptr(), stream()), 'rsa_gated_add')  # fmt: skip
+                                          self.conv_scale, shortcut.data_ptr(), out_f32.data_ptr(), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_gated_add')  # fmt: skip
 
             plan.call(run)
             plan.count_launches(1)
 
         def mlp(b, x1, x2, out_planes=None):
             if fuse_mlp:  # one launch (csrc/swin_block.hip), nothing between leaves the chip
-                swinblocks.mlp_block(plan, W[f'{b}.norm2'], W[f'{b}.mlp.fc1'], W[f'{b}.mlp.fc2'], n, H, Wd, C_, hidden, products, x1, x2, out_planes)
+                mlp_block(plan, W[f'{b}.norm2'], W[f'{b}.mlp.fc1'], W[f'{b}.mlp.fc2'], n, H, Wd, C_, hidden, products, x1, x2, out_planes)
                 return
-            layernorm(f'{b}.norm2', x1, out_planes=a_pl)
+            norm(f'{b}.norm2', x1, out_planes=a_pl)
             plan.conv(ops.conv_params(W[f'{b}.mlp.fc1'], a_pl, H, Wd, cin_planes=cp, act=L.ACT_GELU, out=hid_pl))
             plan.conv(ops.conv_params(W[f'{b}.mlp.fc2'], hid_pl, H, Wd, cin_planes=(hidden + 7) // 8, res1=x1, alpha=1.0, out_f32=x2, out=out_planes))
 
@@ -392,7 +314,7 @@ class HAT(EngineModule):
         free = list(pool)
         if self.patch_norm:
             cur = free.pop()
-            layernorm('patch_embed.norm', first, out_f32=cur)
+            norm('patch_embed.norm', first, out_f32=cur)
         else:
             cur = first
         for i, depth in enumerate(self.depths):
@@ -407,7 +329,7 @@ class HAT(EngineModule):
 
             for j in range(depth):
                 b = f'{g}.blocks.{j}'
-                layernorm(f'{b}.norm1', cur, out_planes=a_pl)
+                norm(f'{b}.norm1', cur, out_planes=a_pl)
                 sc = free.pop()
                 cab_scaled_shortcut(b, cur, sc)
                 plan.conv(ops.conv_params(W[f'{b}.attn.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
@@ -421,7 +343,7 @@ class HAT(EngineModule):
                 free.append(x1)
                 cur = x2
             o = f'{g}.overlap_attn'
-            layernorm(f'{o}.norm1', cur, out_planes=a_pl)
+            norm(f'{o}.norm1', cur, out_planes=a_pl)
             plan.conv(ops.conv_params(W[f'{o}.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
             attention(o, heads, 0, True)
             x1 = free.pop()
@@ -438,26 +360,14 @@ class HAT(EngineModule):
                 free.append(rg_in)
             free.append(cur)
             cur = out
-        layernorm('norm', cur, out_planes=n_pl)
+        norm('norm', cur, out_planes=n_pl)
         tail = W['conv_after_body'] if self.resi == '1conv' else W['identity']
         plan.conv(ops.conv_params(tail, n_pl, H, Wd, cin_planes=cp, res1=first, alpha=1.0, out=body_pl))  # + conv_first output (arch.py:1104)
 
         out_shape = (n, self.in_chans, H * s, Wd * s)
         out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
-        y = plan.planes(n, nf // 8, H, Wd, with_lo)
-        plan.conv(ops.conv_params(W['conv_before_upsample.0'], body_pl, H, Wd, cin_planes=cp, act=L.ACT_LRELU, act_param=0.01, out=y))
-        hh, ww = H, Wd
-        i = 0
-        while f'upsample.{i}' in W:
-            r = math.isqrt(W[f'upsample.{i}'].cout // nf)
-            shuffled = torch.empty((n, nf, hh * r, ww * r), dtype=torch.float32, device=dev)
-            plan.keep.append(shuffled)
-            plan.conv(ops.conv_params(W[f'upsample.{i}'], y, hh, ww, out_nchw=shuffled, pixel_shuffle=r))
-            hh, ww = hh * r, ww * r
-            ny = plan.planes(n, nf // 8, hh, ww, with_lo)
-            plan.call(lambda src=shuffled, dst=ny: ops.nchw_to_planes(src, dst))
-            y = ny
-            i += 2
+        head = pixelshuffle_buffers(plan, W, n, H, Wd, nf, with_lo)
+        y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
         plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=out_buf['y'], out_scale=1.0 / self.img_range, out_shift=mean))
         arr = plan.flush()
         last_entry = arr[len(arr) - 1]

@@ -13,156 +13,39 @@ Weight re-layout at pack time (never per forward):
 
 from __future__ import annotations
 
-import ctypes as C
 import math
-
 import os
 
 import torch
 
 from ...engine import lib as L
-from ...engine import ops, swinblocks
+from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
-from ...engine.paramtree import build_param_tree
+from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16
+from ...engine.transformer import (HEAD_PAD, LayerPacker, bias_fragments, bias_fragments16, layernorm, mlp_block, mlp_block_fits, pixelshuffle_buffers,
+                                   pixelshuffle_head, regroup_proj, regroup_qkv, relative_position_index, shift_mask)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # resselt/archs/swinir/arch.py:788-790
-HEAD_PAD = 32  # channels each head occupies in the attention planes
-
-
-def relative_position_index(window: int) -> torch.Tensor:
-    """The registered buffer of WindowAttention (arch.py:111-122)."""
-    coords = torch.stack(torch.meshgrid([torch.arange(window), torch.arange(window)], indexing='ij')).flatten(1)
-    rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0).contiguous()
-    rel[:, :, 0] += window - 1
-    rel[:, :, 1] += window - 1
-    rel[:, :, 0] *= 2 * window - 1
-    return rel.sum(-1)
-
-
-def shift_attn_mask(img_size: int, window: int) -> torch.Tensor:
-    """The registered ``attn_mask`` buffer of shifted blocks (arch.py:268-293); kept for state_dict parity only."""
-    s = window // 2
-    img = torch.zeros(1, img_size, img_size, 1)
-    cnt = 0
-    for hs in (slice(0, -window), slice(-window, -s), slice(-s, None)):
-        for ws in (slice(0, -window), slice(-window, -s), slice(-s, None)):
-            img[:, hs, ws, :] = cnt
-            cnt += 1
-    nw = img_size // window
-    mw = img.view(1, nw, window, nw, window, 1).permute(0, 1, 3, 2, 4, 5).reshape(-1, window * window)
-    d = mw.unsqueeze(1) - mw.unsqueeze(2)
-    return torch.where(d != 0, torch.full_like(d, -100.0), torch.zeros_like(d))
-
-
-_FRAG_LUT: dict = {}
-
-
-def _fragment_lut(index: torch.Tensor, window: int, order: str) -> torch.Tensor:
-    """Row of the bias table each accumulator element reads (-1: a padded key -> -1e30; -2: a padded query -> 0), in the order of
-    `bias_fragments` ('32') or `bias_fragments16` ('16').  It depends on the window and on the index buffer only, which every layer of a
-    network shares: built once and reused while the index has the same content (the per-layer gathers were 0.2 s of a SwinIR-L cold
-    start: 54 layers x 5 indexing operations)."""
-    key = (order, window, str(index.device))
-    hit = _FRAG_LUT.get(key)
-    if hit is not None and hit[0].shape == index.shape and torch.equal(hit[0], index):
-        return hit[1]
-    n = window * window
-    dev = index.device
-    dense = torch.full((64, 64), -2, dtype=torch.long, device=dev)  # [query][key] -> table row
-    dense[:, n:] = -1
-    dense[:n, :n] = index.reshape(n, n).long()
-    lane = torch.arange(64, device=dev)
-    if order == '32':  # [qt 2][kt 2][lane 64][16]: query 32*qt + (l & 31), key 32*kt + (r & 3) + 8*(r >> 2) + 4*(l >> 5)
-        r = torch.arange(16, device=dev)
-        q_in = (lane & 31)[:, None].expand(64, 16)
-        k_in = ((r & 3) + 8 * (r >> 2))[None, :] + 4 * (lane >> 5)[:, None]
-        lut = torch.stack([torch.stack([dense[32 * qt + q_in, 32 * kt + k_in] for kt in range(2)]) for qt in range(2)])
-    else:  # [kt 4][qt 4][lane 64][4]: key 16*kt + 4*(l >> 4) + r, query 16*qt + (l & 15)
-        r = torch.arange(4, device=dev)
-        q_in = (lane & 15)[:, None].expand(64, 4)
-        k_in = 4 * (lane >> 4)[:, None] + r[None, :]
-        lut = torch.stack([torch.stack([dense[16 * qt + q_in, 16 * kt + k_in] for qt in range(4)]) for kt in range(4)])
-    _FRAG_LUT[key] = (index.clone(), lut)
-    return lut
-
-
-def _gather_fragments(table: torch.Tensor, lut: torch.Tensor, scale: float) -> torch.Tensor:
-    t = table.to(torch.float32)
-    if scale != 1.0:
-        t = t * scale
-    g = t[lut.clamp(min=0).reshape(-1)].reshape(*lut.shape, t.shape[1])  # [..., heads]
-    pad = torch.where(lut == -1, -1e30, 0.0).to(torch.float32)[..., None]
-    return torch.where((lut >= 0)[..., None], g, pad).movedim(-1, 0).contiguous()
-
-
-def bias_fragments(table: torch.Tensor, index: torch.Tensor, window: int) -> torch.Tensor:
-    """table[(2w-1)^2, heads] gathered by index[w^2, w^2] -> [heads][qt 2][kt 2][lane 64][16] f32 in the S^T accumulator order:
-    lane l, element r  <->  query 32*qt + (l & 31),  key 32*kt + (r & 3) + 8*(r >> 2) + 4*(l >> 5).  Padded keys get -1e30."""
-    return _gather_fragments(table, _fragment_lut(index, window, '32'), 1.0)
-
-
-def bias_fragments16(table: torch.Tensor, index: torch.Tensor, window: int) -> torch.Tensor:
-    """The same gather in the accumulator order of 16x16 tiles (csrc/swin_block.hip): [heads][kt 4][qt 4][lane 64][4] f32,
-    lane l, element r  <->  key 16*kt + 4*(l >> 4) + r,  query 16*qt + (l & 15).  Values are multiplied by log2(e): the kernel's
-    softmax runs in base 2 (one v_exp_f32 per logit).  Padded keys get -1e30."""
-    return _gather_fragments(table, _fragment_lut(index, window, '16'), math.log2(math.e))
-
-
-def regroup_qkv(w: torch.Tensor, b: torch.Tensor | None, heads: int, scale_q: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
-    """[3C, C] -> [3*heads*32, C]: row (which, head, d) <- which*C + head*hd + d, zero rows for d >= hd; q rows scaled by hd^-0.5."""
-    c3, c = w.shape
-    hd = c // heads
-    wn = torch.zeros((3, heads, HEAD_PAD, c), dtype=torch.float32, device=w.device)
-    bn = torch.zeros((3, heads, HEAD_PAD), dtype=torch.float32, device=w.device)
-    wn[:, :, :hd] = w.to(torch.float32).reshape(3, heads, hd, c)
-    if b is not None:
-        bn[:, :, :hd] = b.to(torch.float32).reshape(3, heads, hd)
-    if scale_q:
-        scale = hd**-0.5
-        wn[0] *= scale
-        bn[0] *= scale
-    return wn.reshape(3 * heads * HEAD_PAD, c), bn.reshape(-1)
-
-
-def regroup_proj(w: torch.Tensor, heads: int) -> torch.Tensor:
-    """[C, C] -> [C, heads*32]: column (head, d) <- head*hd + d."""
-    c = w.shape[0]
-    hd = w.shape[1] // heads
-    wn = torch.zeros((c, heads, HEAD_PAD), dtype=torch.float32, device=w.device)
-    wn[:, :, :hd] = w.to(torch.float32).reshape(c, heads, hd)
-    return wn.reshape(c, heads * HEAD_PAD)
 
 
 def swinir_param_shapes(in_ch, out_ch, embed_dim, depths, num_heads, window, mlp_ratio, upscale, upsampler, resi, img_size, patch_norm=True):
-    shapes: dict = {}
+    s = ParamShapes()
     buffers: dict = {}
     C_ = embed_dim
     hidden = int(C_ * mlp_ratio)
 
-    def conv(name, co, ci, k):
-        shapes[f'{name}.weight'] = (co, ci, k, k)
-        shapes[f'{name}.bias'] = (co,)
-
-    def lin(name, co, ci):
-        shapes[f'{name}.weight'] = (co, ci)
-        shapes[f'{name}.bias'] = (co,)
-
-    def ln(name):
-        shapes[f'{name}.weight'] = (C_,)
-        shapes[f'{name}.bias'] = (C_,)
-
     def resi_conv(name):
         if resi == '1conv':
-            conv(name, C_, C_, 3)
+            s.conv(name, C_, C_, 3)
         else:
-            conv(f'{name}.0', C_ // 4, C_, 3)
-            conv(f'{name}.2', C_ // 4, C_ // 4, 1)
-            conv(f'{name}.4', C_, C_ // 4, 3)
+            s.conv(f'{name}.0', C_ // 4, C_, 3)
+            s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
+            s.conv(f'{name}.4', C_, C_ // 4, 3)
 
-    conv('conv_first', C_, in_ch, 3)
+    s.conv('conv_first', C_, in_ch, 3)
     if patch_norm:
-        ln('patch_embed.norm')
+        s.norm('patch_embed.norm', C_)
     rp = relative_position_index(window)
     mask = None
     for i, depth in enumerate(depths):
@@ -170,44 +53,36 @@ def swinir_param_shapes(in_ch, out_ch, embed_dim, depths, num_heads, window, mlp
             b = f'layers.{i}.residual_group.blocks.{j}'
             if j % 2 == 1:
                 if mask is None:
-                    mask = shift_attn_mask(img_size, window)
+                    mask = shift_mask(img_size, img_size, (window, window), (window // 2, window // 2))
                 buffers[f'{b}.attn_mask'] = mask
-            ln(f'{b}.norm1')
-            shapes[f'{b}.attn.relative_position_bias_table'] = ((2 * window - 1) ** 2, num_heads[i])
+            s.norm(f'{b}.norm1', C_)
+            s[f'{b}.attn.relative_position_bias_table'] = ((2 * window - 1) ** 2, num_heads[i])
             buffers[f'{b}.attn.relative_position_index'] = rp
-            lin(f'{b}.attn.qkv', 3 * C_, C_)
-            lin(f'{b}.attn.proj', C_, C_)
-            ln(f'{b}.norm2')
-            lin(f'{b}.mlp.fc1', hidden, C_)
-            lin(f'{b}.mlp.fc2', C_, hidden)
+            s.linear(f'{b}.attn.qkv', 3 * C_, C_)
+            s.linear(f'{b}.attn.proj', C_, C_)
+            s.norm(f'{b}.norm2', C_)
+            s.linear(f'{b}.mlp.fc1', hidden, C_)
+            s.linear(f'{b}.mlp.fc2', C_, hidden)
         resi_conv(f'layers.{i}.conv')
-    ln('norm')
+    s.norm('norm', C_)
     resi_conv('conv_after_body')
     nf = 64
     if upsampler == 'nearest+conv':
-        conv('conv_before_upsample.0', nf, C_, 3)
-        conv('conv_up1', nf, nf, 3)
+        s.conv('conv_before_upsample.0', nf, C_, 3)
+        s.conv('conv_up1', nf, nf, 3)
         if upscale in (4, 8):
-            conv('conv_up2', nf, nf, 3)
+            s.conv('conv_up2', nf, nf, 3)
         if upscale == 8:
-            conv('conv_up3', nf, nf, 3)
-        conv('conv_hr', nf, nf, 3)
-        conv('conv_last', out_ch, nf, 3)
+            s.conv('conv_up3', nf, nf, 3)
+        s.conv('conv_hr', nf, nf, 3)
+        s.conv('conv_last', out_ch, nf, 3)
     elif upsampler == 'pixelshuffle':
-        conv('conv_before_upsample.0', nf, C_, 3)
-        if upscale == 3:
-            conv('upsample.0', 9 * nf, nf, 3)
-        elif upscale & (upscale - 1) == 0:
-            for u in range(int(math.log2(upscale))):
-                conv(f'upsample.{2 * u}', 4 * nf, nf, 3)
-        else:
-            raise ValueError(f'scale {upscale} is not supported. Supported scales: 2^n and 3.')
-        conv('conv_last', out_ch, nf, 3)
+        s.pixelshuffle_head(C_, nf, out_ch, upscale)
     elif upsampler == 'pixelshuffledirect':
-        conv('upsample.0', upscale * upscale * out_ch, C_, 3)
+        s.conv('upsample.0', upscale * upscale * out_ch, C_, 3)
     else:
-        conv('conv_last', out_ch, C_, 3)
-    return shapes, buffers
+        s.conv('conv_last', out_ch, C_, 3)
+    return s, buffers
 
 
 class SwinIR(EngineModule):
@@ -232,13 +107,13 @@ class SwinIR(EngineModule):
     @property
     def auto_precision(self) -> str:
         hidden = int(self.embed_dim * self.mlp_ratio)
-        fused = self.fused_blocks == 'whole' and swinblocks.mlp_block_fits(self.embed_dim, hidden)
+        fused = self.fused_blocks == 'whole' and mlp_block_fits(self.embed_dim, hidden)
         fused = fused and all(h <= 8 and self.embed_dim // h <= HEAD_PAD for h in self.num_heads)
         return 'mixed' if fused else 'bf16x3'
 
     @staticmethod
     def layer_policy(name: str) -> tuple[int, int]:
-        """(products, plane format of inputs and weights) of convolution ``name`` under 'mixed'."""
+        """(products, plane format of inputs and weights) of layer ``name`` (convolution or Linear) under 'mixed'."""
         if name == 'conv_first':
             return 3, PF_BF16
         if name.startswith('conv_after_body'):
@@ -277,21 +152,8 @@ class SwinIR(EngineModule):
     # ---------------------------------------------------------------- weights
     def _pack(self, device, products):
         sd = {k: v.detach().to(device) for k, v in self.state_dict().items()}
-        W: dict = {}
-
-        mixed = products.name == 'mixed'
-
-        def conv(name):
-            prod, fmt = self.layer_policy(name) if mixed else (int(products), products.fmt)
-            W[name] = ops.ConvWeights.from_oihw(sd[f'{name}.weight'], sd.get(f'{name}.bias'), prod, device=device, fmt=fmt)
-
-        def lin(name, w=None, b=None, cin_planes=None):
-            w = sd[f'{name}.weight'] if w is None else w
-            b = sd.get(f'{name}.bias') if b is None else b
-            W[name] = ops.ConvWeights.from_oihw(w[:, :, None, None], b, products, cin_planes=cin_planes, device=device)
-
-        def ln(name):
-            W[name] = (sd[f'{name}.weight'].float().contiguous(), sd[f'{name}.bias'].float().contiguous())
+        pk = LayerPacker(sd, device, products, self.layer_policy)
+        W, conv, lin, ln = pk.W, pk.conv, pk.lin, pk.ln
 
         def resi_conv(name):
             for sub in ([''] if self.resi == '1conv' else ['.0', '.2', '.4']):
@@ -302,7 +164,7 @@ class SwinIR(EngineModule):
                 # chunk-barrier kernel: 0.82 ms per 1024^2 map; the four ring launches with their generic f32-residual epilogues take longer: profiles/r04_y_*).  One image per launch list only: a
                 # slice of an f32 map is a channel view, contiguous for one image.
                 w, b = sd[f'{name}.4.weight'], sd.get(f'{name}.4.bias')
-                prod, fmt = self.layer_policy(f'{name}.4') if mixed else (int(products), products.fmt)
+                prod, fmt = pk.policy(f'{name}.4')
                 for k, c0 in enumerate(range(0, w.shape[0], 64)):
                     W[f'{name}.4.s{k}'] = ops.ConvWeights.from_oihw(w[c0 : c0 + 64], None if b is None else b[c0 : c0 + 64], prod, device=device, fmt=fmt)
 
@@ -385,7 +247,6 @@ class SwinIR(EngineModule):
         head_fmt = PF_BF16 if mixed else plan.fmt  # conv_first and the reconstruction head: bf16 planes under 'mixed'
         cp = (C_ + 7) // 8
         dev = plan.device
-        lib = L.load()
 
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, wide, head_fmt)
         mean = W['mean']
@@ -403,7 +264,7 @@ class SwinIR(EngineModule):
         max_heads = max(self.num_heads)
 
         def can_fuse(heads):
-            return self.fused_blocks and swinblocks.mlp_block_fits(C_, hidden) and heads <= 8 and C_ // heads <= HEAD_PAD
+            return self.fused_blocks and mlp_block_fits(C_, hidden) and heads <= 8 and C_ // heads <= HEAD_PAD
 
         if products.name in ('fp16', 'mixed') and not (self.fused_blocks == 'whole' and all(can_fuse(h) for h in self.num_heads)):
             raise NotImplementedError("SwinIR 'fp16' / 'mixed' need every block on the whole-block kernel (fused_blocks = 'whole', C <= 256, <= 8 heads of <= 32 "
@@ -419,18 +280,8 @@ class SwinIR(EngineModule):
         q4_a = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, wide) if self.resi == '3conv' else None
         q4_b = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, wide) if self.resi == '3conv' else None
 
-        def layernorm(name, x_f32, out_planes=None, out_f32=None):
-            g, b = W[name]
-            lp = L.LayerNormParams()
-            lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, C_, 1e-5
-            lp.x_f32, lp.gamma, lp.beta = x_f32.data_ptr(), g.data_ptr(), b.data_ptr()
-            if out_planes is not None:
-                lp.out_hi, lp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-                lp.out_plane_stride, lp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
-            lp.out_f32 = None if out_f32 is None else out_f32.data_ptr()
-            lp.out_fmt = plan.fmt
-            plan.call(lambda: L.check(lib.rsa_layernorm(C.byref(lp), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_layernorm'))
-            plan.count_launches(1)
+        def norm(name, x_f32, out_planes=None, out_f32=None):
+            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
 
         def attention(name, heads, shift):
             ap = L.WindowAttnParams()
@@ -440,8 +291,7 @@ class SwinIR(EngineModule):
             ap.bias_frag = W[f'{name}.bias_frag'].data_ptr()
             ap.out_hi, ap.out_lo = o_pl.hi_ptr(), o_pl.lo_ptr()
             ap.out_plane_stride, ap.out_batch_stride = o_pl.plane_stride, o_pl.batch_stride
-            plan.call(lambda: L.check(lib.rsa_window_attention(C.byref(ap), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_window_attention'))
-            plan.count_launches(1)
+            plan.launch('rsa_window_attention', ap)
 
         def attn_block(name, heads, shift, x_f32, out_f32):
             """norm1 -> qkv -> window attention -> proj -> + shortcut in one launch (arch.py:295-330)."""
@@ -454,8 +304,7 @@ class SwinIR(EngineModule):
             ap.bias_frag16 = W[f'{name}.bias_frag16'].data_ptr()
             ap.wproj, ap.bproj = proj.packed_for(0).data_ptr(), proj.bias.data_ptr()
             ap.out = out_f32.data_ptr()
-            plan.call(lambda: L.check(lib.rsa_swin_attn_block(C.byref(ap), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_swin_attn_block'))
-            plan.count_launches(1)
+            plan.launch('rsa_swin_attn_block', ap)
 
         def whole_block(name, heads, shift, x_f32, out_f32, out_planes=None):
             """The whole block in one launch (arch.py:295-335; csrc/swin_block_full.hip): x1 never leaves the chip."""
@@ -478,12 +327,10 @@ class SwinIR(EngineModule):
             meta = dict(kernel=f'rsa::swin_block_kernel<{int(products)},{"f16" if plan.fmt == PF_F16 else "bf16"}> (whole Swin block)', products=int(products),
                         flop=2.0 * tokens * (4 * C_ * C_ + 2 * C_ * hidden + 2 * win * win * C_),  # qkv + proj, the MLP, QK^T and PV
                         bytes=2.0 * tokens * C_ * 4 + (0 if out_planes is None else tokens * C_ * 2.0 * (2 if out_planes.lo is not None else 1)))  # fmt: skip
-            plan.call(lambda: L.check(lib.rsa_swin_block(C.byref(bp), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_swin_block'), meta)
-            plan.count_launches(1)
+            plan.launch('rsa_swin_block', bp, meta=meta)
 
-        def mlp_block(name, x_f32, out_f32, out_planes=None):
-            swinblocks.mlp_block(plan, W[f'{name}.norm2'], W[f'{name}.mlp.fc1'], W[f'{name}.mlp.fc2'], n, H, Wd, C_, hidden, products, x_f32, out_f32,
-                                 out_planes)  # fmt: skip
+        def mlp(name, x_f32, out_f32, out_planes=None):
+            mlp_block(plan, W[f'{name}.norm2'], W[f'{name}.mlp.fc1'], W[f'{name}.mlp.fc2'], n, H, Wd, C_, hidden, products, x_f32, out_f32, out_planes)
 
         def resi_conv(name, src_planes, res, out_f32=None, out_planes=None):
             """1conv / 3conv tail (arch.py:562-574) + the residual add that follows it."""
@@ -506,7 +353,7 @@ class SwinIR(EngineModule):
         free = list(pool)
         if self.patch_norm:
             cur = free.pop()
-            layernorm('patch_embed.norm', first, out_f32=cur)
+            norm('patch_embed.norm', first, out_f32=cur)
         else:
             cur = first
         for i, depth in enumerate(self.depths):
@@ -524,13 +371,13 @@ class SwinIR(EngineModule):
                 elif can_fuse(heads):
                     attn_block(b, heads, shift, cur, x1)
                     x2 = free.pop()
-                    mlp_block(b, x1, x2, body_pl if last else None)
+                    mlp(b, x1, x2, body_pl if last else None)
                 else:
-                    layernorm(f'{b}.norm1', cur, out_planes=a_pl)
+                    norm(f'{b}.norm1', cur, out_planes=a_pl)
                     plan.conv(ops.conv_params(W[f'{b}.attn.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
                     attention(b, heads, shift)
                     plan.conv(ops.conv_params(W[f'{b}.attn.proj'], o_pl, H, Wd, cin_planes=hp, res1=cur, alpha=1.0, out_f32=x1))
-                    layernorm(f'{b}.norm2', x1, out_planes=a_pl)
+                    norm(f'{b}.norm2', x1, out_planes=a_pl)
                     plan.conv(ops.conv_params(W[f'{b}.mlp.fc1'], a_pl, H, Wd, cin_planes=cp, act=L.ACT_GELU, out=hid_pl))
                     x2 = free.pop()
                     plan.conv(ops.conv_params(W[f'{b}.mlp.fc2'], hid_pl, H, Wd, cin_planes=(hidden + 7) // 8, res1=x1, alpha=1.0, out_f32=x2,
@@ -546,7 +393,7 @@ class SwinIR(EngineModule):
             if cur is not rstb_in:
                 free.append(cur)
             cur = out
-        layernorm('norm', cur, out_planes=a_pl)
+        norm('norm', cur, out_planes=a_pl)
         resi_conv('conv_after_body', a_pl, first, out_planes=head_pl)  # + conv_first output (arch.py:988)
         body_pl = head_pl  # (the head reads conv_after_body's output from here on)
         with_lo, plan_fmt = wide, plan.fmt
@@ -569,20 +416,8 @@ class SwinIR(EngineModule):
             plan.conv(ops.conv_params(W['conv_hr'], y, hh, ww, out=hr, **lre))
             plan.conv(ops.conv_params(W['conv_last'], hr, hh, ww, out_nchw=out_buf['y'], **final))
         elif self.upsampler == 'pixelshuffle':
-            y = plan.planes(n, 8, H, Wd, with_lo)
-            plan.conv(ops.conv_params(W['conv_before_upsample.0'], body_pl, H, Wd, cin_planes=cp, act=L.ACT_LRELU, act_param=0.01, out=y))
-            hh, ww = H, Wd
-            i = 0
-            while f'upsample.{i}' in W:
-                r = math.isqrt(W[f'upsample.{i}'].cout // 64)
-                shuffled = torch.empty((n, 64, hh * r, ww * r), dtype=torch.float32, device=dev)
-                plan.keep.append(shuffled)
-                plan.conv(ops.conv_params(W[f'upsample.{i}'], y, hh, ww, out_nchw=shuffled, pixel_shuffle=r))
-                hh, ww = hh * r, ww * r
-                ny = plan.planes(n, 8, hh, ww, with_lo)
-                plan.call(lambda src=shuffled, dst=ny: ops.nchw_to_planes(src, dst))
-                y = ny
-                i += 2
+            head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
+            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
             plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=out_buf['y'], **final))
         elif self.upsampler == 'pixelshuffledirect':
             plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=out_buf['y'], pixel_shuffle=s, **final))

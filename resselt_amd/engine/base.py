@@ -151,6 +151,13 @@ class Plan:
             except AttributeError:  # a callable that takes no attributes (functools.partial does; builtins do not): not priced
                 pass
 
+    def launch(self, fn_name: str, params, kernels: int = 1, meta: dict | None = None) -> None:
+        """A ``call`` step of one C-ABI entry point that takes ``(params*, stream)``; it launches ``kernels`` kernels."""
+        fn = getattr(L.load(), fn_name)
+        dev = self.device
+        self.call(lambda: L.check(fn(C.byref(params), C.c_void_p(ops.current_stream_ptr(dev))), fn_name), meta)
+        self.count_launches(kernels)
+
     def run(self) -> None:
         self.flush()
         for step in self.steps:

@@ -8,10 +8,40 @@ container node; ``build_param_tree`` nests nodes along the dotted key path.
 
 from __future__ import annotations
 
+import math
 from typing import Mapping, Sequence
 
 import torch
 from torch import nn
+
+
+class ParamShapes(dict):
+    """``dotted.name -> shape`` of a module's parameters, in registration order (the order of its state_dict)."""
+
+    def conv(self, name: str, co: int, ci: int, k: int) -> None:
+        self[f'{name}.weight'] = (co, ci, k, k)
+        self[f'{name}.bias'] = (co,)
+
+    def linear(self, name: str, co: int, ci: int, bias: bool = True) -> None:
+        self[f'{name}.weight'] = (co, ci)
+        if bias:
+            self[f'{name}.bias'] = (co,)
+
+    def norm(self, name: str, c: int) -> None:
+        self[f'{name}.weight'] = (c,)
+        self[f'{name}.bias'] = (c,)
+
+    def pixelshuffle_head(self, cin: int, nf: int, cout: int, upscale: int) -> None:
+        """conv_before_upsample -> Upsample (a conv + PixelShuffle per factor 2, or one for 3) -> conv_last."""
+        self.conv('conv_before_upsample.0', nf, cin, 3)
+        if upscale == 3:
+            self.conv('upsample.0', 9 * nf, nf, 3)
+        elif upscale & (upscale - 1) == 0:
+            for u in range(int(math.log2(upscale))):
+                self.conv(f'upsample.{2 * u}', 4 * nf, nf, 3)
+        else:
+            raise ValueError(f'scale {upscale} is not supported. Supported scales: 2^n and 3.')
+        self.conv('conv_last', cout, nf, 3)
 
 
 class ParamTree(nn.Module):

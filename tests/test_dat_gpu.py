@@ -14,10 +14,11 @@ import torch.nn.functional as F
 
 import resselt_amd
 from helpers import golden_names, load_golden, oracle_forward, synth_state_dict
-from resselt_amd.archs.dat.arch import bias_fragments, branch_geometry
+from resselt_amd.archs.dat.arch import branch_geometry
 from resselt_amd.engine import lib as L
 from resselt_amd.engine import ops, tensors
 from resselt_amd.engine.pack import pad_bias
+from resselt_amd.engine.transformer import bias_fragments_qk
 from resselt_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
@@ -187,7 +188,7 @@ def test_rect_attention_kernel(device, products, tol, split, shifted, heads, hd,
         sh, sw = branch_geometry(shift, idx)
         n_tok = hs * ws
         bias = _rand((heads // 2, n_tok, n_tok), 10 + idx, 2.0)
-        frags.append(bias_fragments(bias).to(device))
+        frags.append(bias_fragments_qk(bias).to(device))
         part = qkv[..., idx * (C_ // 2) : (idx + 1) * (C_ // 2)]
         if shifted:
             part = torch.roll(part, shifts=(-sh, -sw), dims=(1, 2))

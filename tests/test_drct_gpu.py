@@ -7,10 +7,9 @@ import pytest
 import torch
 
 import resselt_amd
-from resselt_amd.archs.dat.arch import bias_fragments
-from resselt_amd.archs.drct.arch import regroup_qkv_wide
 from resselt_amd.engine import lib as L
 from resselt_amd.engine import ops, tensors
+from resselt_amd.engine.transformer import bias_fragments_qk, regroup_qkv, relative_position_index
 from resselt_amd.utils import synth
 
 from helpers import golden_names, load_golden, oracle_forward, synth_state_dict
@@ -35,7 +34,6 @@ def test_wide_head_window_attention_kernel(device, products, tol, win, heads, hd
     pad = 32 * chunks
     qkv = _rand((B, 3 * Cdim, H, W), 1, 1.5)
     table = _rand(((2 * win - 1) ** 2, heads), 2, 1.0)
-    from resselt_amd.archs.swinir.arch import relative_position_index
 
     idx = relative_position_index(win)
     dense = table[idx.reshape(-1)].reshape(n, n, heads).permute(2, 0, 1).contiguous()
@@ -55,14 +53,14 @@ def test_wide_head_window_attention_kernel(device, products, tol, win, heads, hd
         r = torch.roll(r, shifts=(shift, shift), dims=(1, 2))
     ref = r.permute(0, 3, 1, 2)  # B C H W, channel = head*hd + d
 
-    # engine layout: [which][head][pad] channels, q pre-scaled (what regroup_qkv_wide does to the Linear weights; here on the activations)
+    # engine layout: [which][head][pad] channels, q pre-scaled (what regroup_qkv does to the Linear weights; here on the activations)
     eye = torch.eye(Cdim)
-    wq, _ = regroup_qkv_wide(torch.cat([eye, eye, eye], 0), None, heads, pad)  # [3*heads*pad, C] selector (q rows scaled)
+    wq, _ = regroup_qkv(torch.cat([eye, eye, eye], 0), None, heads, pad)  # [3*heads*pad, C] selector (q rows scaled)
     sel = wq.reshape(3, heads * pad, Cdim)
     packed = torch.cat([torch.einsum('oc,bchw->bohw', sel[i], qkv[:, i * Cdim : (i + 1) * Cdim]) for i in range(3)], 1)
     qkv_pl = tensors.nchw_to_planes(packed.to(device), with_lo=products == 3)
     o_pl = tensors.Planes.empty(B, heads * pad // 8, H, W, device, products == 3)
-    frag = bias_fragments(dense).to(device)
+    frag = bias_fragments_qk(dense).to(device)
     ap = L.RectAttnParams()
     ap.batch, ap.H, ap.W, ap.Hp, ap.Wp = B, H, W, H, W
     ap.win_h = ap.win_w = win

@@ -11,7 +11,7 @@ import torch.nn.functional as F
 
 import resselt_amd
 from helpers import golden_names, load_golden, oracle_forward, synth_state_dict
-from resselt_amd.archs.hat.arch import bias_fragments_qk
+from resselt_amd.engine.transformer import bias_fragments_qk
 from resselt_amd.engine import lib as L
 from resselt_amd.engine import ops, tensors
 from resselt_amd.utils import synth

@@ -4,10 +4,10 @@ fragment-order position-bias tables, head-padded permutations, RepConv / OmniShi
 import torch
 import torch.nn.functional as F
 
-from resselt_amd.archs.dat.arch import attn_tiles, bias_fragments, pad_heads
-from resselt_amd.archs.hat.arch import bias_fragments_qk, rpi_buffers
+from resselt_amd.archs.hat.arch import rpi_buffers
 from resselt_amd.archs.rtmosr.arch import fold_omnishift
 from resselt_amd.archs.spanpp.arch import fold_repconv, igconv_kernel
+from resselt_amd.engine.transformer import attn_tiles, bias_fragments_qk, pad_heads, relative_position_index, shift_mask
 from resselt_amd.utils import synth
 
 
@@ -17,7 +17,7 @@ def test_bias_fragment_order_matches_accumulator_layout():
     for nq, nk in ((64, 64), (96, 96), (256, 576), (16, 36)):
         dense = torch.randn((2, nq, nk), generator=g)
         qt, kt = ((nq + 31) // 32, (nk + 31) // 32) if nq != nk else (attn_tiles(nq), attn_tiles(nk))
-        frag = bias_fragments_qk(dense, qt, kt) if nq != nk else bias_fragments(dense)
+        frag = bias_fragments_qk(dense, qt, kt)
         assert tuple(frag.shape) == (2, qt, kt, 64, 16)
         for _ in range(300):
             h, a, b, lane, r = (int(torch.randint(0, n, (1,), generator=g)) for n in (2, qt, kt, 64, 16))
@@ -37,6 +37,21 @@ def test_hat_rpi_buffers_match_synth_and_shapes():
     # the reference's OCA index is shifted by (ws - ext + 1) < 0 and therefore contains NEGATIVE entries that wrap around when they index
     # the bias table (archs/hat/arch.py:1024-1031); the buffers, the oracle and the engine reproduce that verbatim
     assert int(oca.min()) < 0
+
+
+def test_window_index_and_shift_masks_match_synth():
+    """The shared relative-position index and shift-mask builders against synth's independent copies, square and rectangular windows."""
+    for window in (4, 8, 16):
+        assert torch.equal(relative_position_index(window), synth.hat_rpi(window, 0.5)[0])
+    sd = synth.dat_state_dict(split_size=(2, 4), depth=(2,), num_heads=(4,), img_size=16)
+    for idx, (hs, ws) in enumerate(((2, 4), (4, 2))):
+        assert torch.equal(relative_position_index(hs, ws), sd[f'layers.0.blocks.0.attn.attns.{idx}.relative_position_index'])
+    for H, W, split in ((16, 16, (4, 4)), (16, 24, (8, 8)), (16, 16, (2, 4)), (32, 48, (8, 16))):
+        shift = (split[0] // 2, split[1] // 2)
+        ref = synth.dat_shift_masks(H, W, split, shift)
+        for idx in (0, 1):
+            win, sh = (split, shift) if idx == 0 else (split[::-1], shift[::-1])
+            assert torch.equal(shift_mask(H, W, win, sh), ref[idx])
 
 
 def test_pad_heads_scatter():

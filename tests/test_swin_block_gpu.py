@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from resselt_amd.archs.swinir.arch import bias_fragments16, regroup_proj, regroup_qkv, relative_position_index
+from resselt_amd.engine.transformer import bias_fragments16, regroup_proj, regroup_qkv, relative_position_index
 from resselt_amd.engine import lib as L
 from resselt_amd.engine import ops, tensors
 

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import torch  # noqa: E402
 
-from resselt_amd.archs.swinir.arch import bias_fragments16, regroup_proj, regroup_qkv, relative_position_index  # noqa: E402
+from resselt_amd.engine.transformer import bias_fragments16, regroup_proj, regroup_qkv, relative_position_index  # noqa: E402
 from resselt_amd.engine import lib as L  # noqa: E402
 from resselt_amd.engine import ops, tensors  # noqa: E402
 

@@ -729,6 +729,132 @@ typedef struct rsa_ea_gate_params {
 } rsa_ea_gate_params;
 int rsa_ea_gate(const rsa_ea_gate_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- Real-CUGAN ops
+ * (reference archs/cugan/arch.py; resselt_amd/csrc/cugan.hip)
+ *
+ * The U-Nets of Real-CUGAN crop their maps (valid 3x3 convolutions, F.pad with negative pads).  The engine keeps each U-Net stage on one
+ * "grid" (a plane buffer of fixed size) and every tensor of the reference as a WINDOW of a grid: origin (y0, x0) and size (h, w) in pixels.
+ * The 3x3 convolutions run as zero-padded rsa_conv2d on the whole grid; the kernels below take windows for their operands. */
+
+/* Transposed convolution (nn.ConvTranspose2d, weights [cin][cout][k][k]; arch.py:126, 130, 181, 185, 213-214) and, through
+ * rsa_conv_s2, the stride-2 2x2 convolution (nn.Conv2d(c, c, 2, 2, 0), arch.py:124, 204-206).  Both are implicit GEMMs on
+ * v_mfma_f32_16x16x32_{bf16,f16} over phases: rsa_deconv splits the output into stride x stride phases, each a dense convolution of the
+ * input with ceil((k - r) / stride) taps per axis (r = the phase's index in o + pad); rsa_conv_s2 has one phase of 2 x 2 taps that reads
+ * the pixel pairs (2i, 2i+1) counted from the input window's origin, whatever its parity.
+ *   input   window (in_y0, in_x0, in_h, in_w) of planes with row length in_W; pixels outside the window read as zero
+ *   output  rsa_deconv: out_h = (in_h - 1) * stride - 2 pad + ksize (likewise out_w); rsa_conv_s2: out_h = in_h / 2 (floor)
+ *           written at (out_y0 + y, out_x0 + x) of a grid with row length out_W: split planes (out_hi, optional out_lo) and / or an f32 map
+ *           out_f32 [N][ceil(cout/4)][out_H][out_W][4] of the same grid; channels past cout are written as zero
+ *   epilogue v = acc + bias[c]; act (RSA_ACT_NONE or RSA_ACT_LRELU with slope act_param); + the residual window (res_hi / res_lo at
+ *           (res_y0 + y, res_x0 + x), row length res_W) when res_hi != NULL
+ *   w_packed rsa_resample_packed_weight_bytes bytes: [phase][K step][cout tile][hi|lo][lane 64][8]; see resselt_amd/engine/cugan.py.
+ * fmt RSA_PF_BF16 with products == 3 or RSA_PF_F16 with products == 1, like rsa_plk_conv.  cin_planes <= 32, cout <= 128. */
+typedef struct rsa_resample_conv_params {
+  int32_t batch;
+  int32_t ksize, stride, pad; /* rsa_deconv: (2, 2, 0), (4, 2, 3), (5, 3, 2) or any k <= 6, stride <= 3, pad < k; rsa_conv_s2: (2, 2, 0) */
+  int32_t cin_planes;
+  int32_t cout;
+  int32_t products;
+  int32_t fmt;              /* enum rsa_plane_fmt of every plane operand and of w_packed */
+  const void* in_hi;
+  const void* in_lo;        /* products == 3 only */
+  int64_t in_plane_stride;  /* 16-byte units */
+  int64_t in_batch_stride;
+  int32_t in_W;             /* row length of the input grid */
+  int32_t in_y0, in_x0, in_h, in_w;
+  int32_t act;              /* RSA_ACT_NONE or RSA_ACT_LRELU */
+  float act_param;
+  int32_t reserved0;        /* must be 0 */
+  const void* w_packed;
+  const float* bias;        /* f32[16 * ceil(cout / 16)] */
+  const void* res_hi;       /* residual planes (cout % 8 == 0 not required: channels past cout are ignored), or NULL */
+  const void* res_lo;       /* may be NULL */
+  int64_t res_plane_stride;
+  int64_t res_batch_stride;
+  int32_t res_W, res_y0, res_x0;
+  int32_t out_H, out_W, out_y0, out_x0;
+  void* out_hi;             /* may be NULL when out_f32 is given */
+  void* out_lo;             /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+  float* out_f32;           /* may be NULL */
+  int32_t reserved1;        /* must be 0 */
+} rsa_resample_conv_params;
+int64_t rsa_resample_packed_weight_bytes(int32_t ksize, int32_t stride, int32_t transposed, int32_t cin_planes, int32_t cout, int32_t products);
+int rsa_deconv(const rsa_resample_conv_params* p, void* stream);
+int rsa_conv_s2(const rsa_resample_conv_params* p, void* stream);
+
+/* Squeeze-excitation over a window (SEBlock.forward, arch.py:58-69, bias=True, reduction 8), applied IN PLACE to that window:
+ *   m[n][c] = mean of x over the window;  g = sigmoid(W2 . relu(W1 . m + b1) + b2);  x[window] *= g.
+ * The same math as rsa_channel_gate with relu = 1, but the mean covers a window of a larger map and the gate is applied.  Three kernels:
+ * per-row-chunk channel sums into `workspace` (rsa_region_se_workspace_bytes), one workgroup per image for the ordered f64 reduction and the
+ * two 1x1 convolutions (gate f32[batch][C]), and the in-place scale of the window.  Deterministic.  C = 8 * planes <= 256, hidden <= 64. */
+typedef struct rsa_region_se_params {
+  int32_t batch;
+  int32_t planes;
+  int32_t hidden;
+  int32_t fmt;              /* enum rsa_plane_fmt of x */
+  void* x_hi;
+  void* x_lo;               /* may be NULL */
+  int64_t x_plane_stride;   /* 16-byte units */
+  int64_t x_batch_stride;
+  int32_t W;                /* row length of the grid */
+  int32_t y0, x0, h, w;     /* the window */
+  int32_t reserved0;        /* must be 0 */
+  const float* w1;          /* [hidden][C] */
+  const float* b1;          /* [hidden] */
+  const float* w2;          /* [C][hidden] */
+  const float* b2;          /* [C] */
+  float* workspace;
+  float* gate;              /* [batch][C] */
+} rsa_region_se_params;
+int64_t rsa_region_se_workspace_bytes(int32_t batch, int32_t h, int32_t planes);
+int rsa_region_se(const rsa_region_se_params* p, void* stream);
+
+/* Input stage of Real-CUGAN (UpCunet*.forward, arch.py:300-306, 342-349, 386-394, 426-431): an image [N][C][h][w] of `dtype` (or RSA_U8
+ * [N][h][w][C], v = byte / 255) -> v * in_scale + in_shift (the `pro` affine x * 0.7 + 0.15, or 1 / 0) -> reflect pad (pad_top, pad_left; the
+ * padded map is unshuffle * out_H x unshuffle * out_W, every pad < h resp. w) -> pixel_unshuffle(unshuffle) -> split planes of the
+ * out_H x out_W grid (C * unshuffle^2 channels, tail channels zero). */
+typedef struct rsa_cugan_input_params {
+  const void* x;
+  int32_t dtype;
+  int32_t batch, C, h, w;
+  int32_t pad_top, pad_left;
+  int32_t unshuffle;        /* 1 or 2 */
+  float in_scale, in_shift;
+  int32_t out_H, out_W;
+  int32_t fmt;              /* enum rsa_plane_fmt of out */
+  void* out_hi;
+  void* out_lo;             /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+  int32_t reserved0;        /* must be 0 */
+} rsa_cugan_input_params;
+int rsa_cugan_input(const rsa_cugan_input_params* p, void* stream);
+
+/* Output stage of Real-CUGAN (arch.py:307-315, 350-358, 395-410, 432-442): from an f32 map [N][ceil(C r^2 / 4)][map_H][map_W][4], with r
+ * = pixel_shuffle, the output pixel (c, Y, X), Y < out_h, X < out_w, is
+ *   v = map[c r^2 + (Y % r) r + X % r][y0 + Y / r][x0 + X / r]   (the final crop and nn.PixelShuffle(r))
+ *   v += base[c][Y / base_div][X / base_div] * base_scale + base_shift   when base != NULL (F.interpolate(x00, nearest) of the input image,
+ *        of dtype `dtype`; for RSA_U8 an [N][h][w][C] image read as byte / 255)
+ *   v = (v - out_shift) / out_div                                        (the `pro` inverse; 0 and 1 otherwise)
+ * stored as `dtype` [N][C][out_h][out_w] or, for RSA_U8, [N][out_h][out_w][C] = round-half-even(clamp(v, 0, 1) * 255). */
+typedef struct rsa_cugan_output_params {
+  const float* map;
+  int32_t batch, C;
+  int32_t map_H, map_W, y0, x0;
+  int32_t pixel_shuffle;    /* 1 or 2 */
+  int32_t out_h, out_w;
+  int32_t dtype;            /* of out and of base */
+  void* out;
+  const void* base;         /* may be NULL */
+  int32_t base_h, base_w, base_div;
+  float base_scale, base_shift;
+  float out_shift, out_div;
+  int32_t reserved0;        /* must be 0 */
+} rsa_cugan_output_params;
+int rsa_cugan_output(const rsa_cugan_output_params* p, void* stream);
+
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255
  *   rsa_nchw_to_image_u8   float [N][C][H][W] -> uint8 [N][H][W][C], round-half-even(clamp(v, 0, 1) * 255)  (torch: (y.clamp(0,1)*255).round())

@@ -1,12 +1,13 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, PLKSR / RealPLKSR); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, PLKSR / RealPLKSR, Real-CUGAN); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
 from ..registry import Registry
 from .compact import CompactArch
+from .cugan import CUGANArch
 from .dat import DatArch
 from .drct import DRCTArch
 from .esrgan import ESRGANArch
@@ -19,6 +20,6 @@ from .spanpp import SpanPPArch
 from .swinir import SwinIRArch
 
 internal_registry = Registry()
-# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, Compact, PLKSR, RTMoSR, spanplus, SwinIR, SpanPP, ..., SPAN
-for _arch in (ESRGANArch, HATArch, DatArch, CompactArch, PLKSRArch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
+# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, Compact, CuGAN, PLKSR, RTMoSR, spanplus, SwinIR, SpanPP, ..., SPAN
+for _arch in (ESRGANArch, HATArch, DatArch, CompactArch, CUGANArch, PLKSRArch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
     internal_registry.add(_arch())

@@ -485,6 +485,133 @@ class EaGateParams(C.Structure):
     ]
 
 
+class ResampleConvParams(C.Structure):
+    """Mirror of ``struct rsa_resample_conv_params`` (rsa_deconv / rsa_conv_s2)."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('ksize', C.c_int32),
+        ('stride', C.c_int32),
+        ('pad', C.c_int32),
+        ('cin_planes', C.c_int32),
+        ('cout', C.c_int32),
+        ('products', C.c_int32),
+        ('fmt', C.c_int32),
+        ('in_hi', C.c_void_p),
+        ('in_lo', C.c_void_p),
+        ('in_plane_stride', C.c_int64),
+        ('in_batch_stride', C.c_int64),
+        ('in_W', C.c_int32),
+        ('in_y0', C.c_int32),
+        ('in_x0', C.c_int32),
+        ('in_h', C.c_int32),
+        ('in_w', C.c_int32),
+        ('act', C.c_int32),
+        ('act_param', C.c_float),
+        ('reserved0', C.c_int32),
+        ('w_packed', C.c_void_p),
+        ('bias', C.c_void_p),
+        ('res_hi', C.c_void_p),
+        ('res_lo', C.c_void_p),
+        ('res_plane_stride', C.c_int64),
+        ('res_batch_stride', C.c_int64),
+        ('res_W', C.c_int32),
+        ('res_y0', C.c_int32),
+        ('res_x0', C.c_int32),
+        ('out_H', C.c_int32),
+        ('out_W', C.c_int32),
+        ('out_y0', C.c_int32),
+        ('out_x0', C.c_int32),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+        ('out_f32', C.c_void_p),
+        ('reserved1', C.c_int32),
+    ]
+
+
+class RegionSEParams(C.Structure):
+    """Mirror of ``struct rsa_region_se_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('planes', C.c_int32),
+        ('hidden', C.c_int32),
+        ('fmt', C.c_int32),
+        ('x_hi', C.c_void_p),
+        ('x_lo', C.c_void_p),
+        ('x_plane_stride', C.c_int64),
+        ('x_batch_stride', C.c_int64),
+        ('W', C.c_int32),
+        ('y0', C.c_int32),
+        ('x0', C.c_int32),
+        ('h', C.c_int32),
+        ('w', C.c_int32),
+        ('reserved0', C.c_int32),
+        ('w1', C.c_void_p),
+        ('b1', C.c_void_p),
+        ('w2', C.c_void_p),
+        ('b2', C.c_void_p),
+        ('workspace', C.c_void_p),
+        ('gate', C.c_void_p),
+    ]
+
+
+class CuganInputParams(C.Structure):
+    """Mirror of ``struct rsa_cugan_input_params``."""
+
+    _fields_ = [
+        ('x', C.c_void_p),
+        ('dtype', C.c_int32),
+        ('batch', C.c_int32),
+        ('C', C.c_int32),
+        ('h', C.c_int32),
+        ('w', C.c_int32),
+        ('pad_top', C.c_int32),
+        ('pad_left', C.c_int32),
+        ('unshuffle', C.c_int32),
+        ('in_scale', C.c_float),
+        ('in_shift', C.c_float),
+        ('out_H', C.c_int32),
+        ('out_W', C.c_int32),
+        ('fmt', C.c_int32),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+        ('reserved0', C.c_int32),
+    ]
+
+
+class CuganOutputParams(C.Structure):
+    """Mirror of ``struct rsa_cugan_output_params``."""
+
+    _fields_ = [
+        ('map', C.c_void_p),
+        ('batch', C.c_int32),
+        ('C', C.c_int32),
+        ('map_H', C.c_int32),
+        ('map_W', C.c_int32),
+        ('y0', C.c_int32),
+        ('x0', C.c_int32),
+        ('pixel_shuffle', C.c_int32),
+        ('out_h', C.c_int32),
+        ('out_w', C.c_int32),
+        ('dtype', C.c_int32),
+        ('out', C.c_void_p),
+        ('base', C.c_void_p),
+        ('base_h', C.c_int32),
+        ('base_w', C.c_int32),
+        ('base_div', C.c_int32),
+        ('base_scale', C.c_float),
+        ('base_shift', C.c_float),
+        ('out_shift', C.c_float),
+        ('out_div', C.c_float),
+        ('reserved0', C.c_int32),
+    ]
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -535,6 +662,13 @@ EXPORTS = (
     'rsa_group_norm_stats',
     'rsa_group_norm_apply',
     'rsa_ea_gate',
+    'rsa_resample_packed_weight_bytes',
+    'rsa_deconv',
+    'rsa_conv_s2',
+    'rsa_region_se_workspace_bytes',
+    'rsa_region_se',
+    'rsa_cugan_input',
+    'rsa_cugan_output',
 )
 
 
@@ -680,6 +814,14 @@ def load() -> C.CDLL:
     lib.rsa_group_norm_apply.restype = C.c_int
     lib.rsa_ea_gate.argtypes = [C.POINTER(EaGateParams), C.c_void_p]
     lib.rsa_ea_gate.restype = C.c_int
+    lib.rsa_resample_packed_weight_bytes.argtypes = [C.c_int32] * 6
+    lib.rsa_resample_packed_weight_bytes.restype = C.c_int64
+    lib.rsa_region_se_workspace_bytes.argtypes = [C.c_int32] * 3
+    lib.rsa_region_se_workspace_bytes.restype = C.c_int64
+    for name, struct in (('rsa_deconv', ResampleConvParams), ('rsa_conv_s2', ResampleConvParams), ('rsa_region_se', RegionSEParams),
+                         ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams)):  # fmt: skip
+        getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
+        getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
 

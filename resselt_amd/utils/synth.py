@@ -679,3 +679,26 @@ def realplksr_state_dict(dim=64, n_blocks=2, upscale=4, kernel_size=17, split_ra
         h = torch.arange((-upscale + 1) / 2, (upscale - 1) / 2 + 1) / upscale
         sd['to_img.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, groups, 1).reshape(1, -1, 1, 1)
     return sd
+
+
+def cugan_state_dict(variant='2x', pro=False, seed=0):
+    """Keys of Real-CUGAN (archs/cugan/arch.py): UpCunet2x / 3x / 4x / 2x_fast ('2x_fast' has no `pro` form).  Transposed convolutions are
+    [cin][cout][k][k]; weights are drawn with twice the usual bound so that activations keep their scale through the U-Nets."""
+    from ..archs.cugan.arch import param_shapes
+
+    sd: OrderedDict = OrderedDict()
+    for name, shape in param_shapes(variant, 3, 3).items():
+        if name.endswith('.bias'):
+            continue
+        layer = name[: -len('.weight')]
+        transposed = layer.endswith('_up') or (layer == 'unet1.conv_bottom')
+        co, ci = (shape[1], shape[0]) if transposed else (shape[0], shape[1])
+        k = shape[2]
+        fan_in = ci * k * k // (4 if transposed and k % 2 == 0 else 9 if transposed else 1)
+        sd[name] = synth_tensor(name, shape, fan_in, seed, 2.0)
+        sd[f'{layer}.bias'] = synth_tensor(f'{layer}.bias', (co,), fan_in, seed, 0.5)
+    if pro:
+        if variant == '2x_fast':
+            raise ValueError('UpCunet2x_fast has no pro form')
+        sd['pro'] = torch.zeros(1)
+    return sd

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Secondary BASELINE.json configs (C3 SPANPlus, C4 SwinIR-L, plus SPAN) on one MI355X: one JSON line per config.
+"""Secondary BASELINE.json configs (C3 SPANPlus, C4 SwinIR-L, plus SPAN and the other built families) on one MI355X: one JSON line per config.
 
 The headline config (C2, RRDBNet-23 1080p) is bench.py; this script reports the other rows of SURVEY.md §8d with the same
 conventions (input resident in HBM, synchronised, median of `--reps` after warm-up).
@@ -58,6 +58,9 @@ def main():
         # DRCT x4 at its published size (embed 180, 6 dense groups, 6 heads, window 16, gc 32, mlp 2)
         'drct_x4_bf16_512': (synth.drct_state_dict(num_layers=6, upscale=4), (1, 3, 512, 512), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
+        # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
+        'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),
+        'cugan_x4_fp16_540p': (synth.cugan_state_dict('4x'), (1, 3, 540, 960), torch.float16, None, None),
     }  # fmt: skip
     for name, (sd, shape, dt, flop_px, bytes_px) in cases.items():
         if args.only and args.only not in name:
@@ -72,7 +75,10 @@ def main():
             x = synth.synth_input(shape, seed=0).to(dev).to(dt)
             y, t = timed(model, x, args.reps)
             out_px = y.shape[0] * y.shape[2] * y.shape[3]
-            macs = (model.macs_per_input_pixel() if hasattr(model, 'macs_per_input_pixel') else 0) * shape[0] * shape[2] * shape[3]
+            if hasattr(model, 'geometry'):  # per-pixel MACs that depend on the image size (Real-CUGAN's cropped U-Nets)
+                macs = model.macs_per_input_pixel(shape[2], shape[3]) * shape[0] * shape[2] * shape[3]
+            else:
+                macs = (model.macs_per_input_pixel() if hasattr(model, 'macs_per_input_pixel') else 0) * shape[0] * shape[2] * shape[3]
             rec = dict(config=name, precision=prec if prec == resolved else f'{prec} -> {resolved}', in_shape=list(shape), io_dtype=str(dt).split('.')[-1], ms=round(t * 1e3, 3),
                        out_mp_s=round(out_px / 1e6 / t, 2), algorithmic_tflops=round(2 * macs / t / 1e12, 2),
                        launches=model.launches_per_forward(), finite=bool(torch.isfinite(y.float()).all()))  # fmt: skip

@@ -21,6 +21,17 @@ from helpers import oracle_forward  # noqa: E402
 from resselt_amd.utils import synth  # noqa: E402
 
 
+def _cugan_accepts(sd, h, w):
+    from oracle.cugan import cugan_variant
+    from resselt_amd.archs.cugan.arch import cugan_layers
+
+    try:
+        cugan_layers(cugan_variant(sd), 3, 3, h, w)
+    except ValueError:
+        return False
+    return True
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     per_arch = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -44,6 +55,12 @@ def main():
                                                  mlp_ratio=rng.choice([2.0, 4.0]), seed=s), 9),
         'esrganbig': lambda s: (synth.rrdbnet_state_dict(nb=2, scale=4, seed=s), 1),
         'hat': lambda s: (synth.hat_state_dict(embed_dim=60, depths=(2,), num_heads=(6,), window=rng.choice([4, 8]), upscale=rng.choice([2, 4]), seed=s), 9),
+        'plksr': lambda s: ((lambda lk: synth.plksr_state_dict(dim=32, n_blocks=rng.choice([1, 2]), upscale=rng.choice([1, 2, 3, 4]), ccm_type=rng.choice(['CCM', 'ICCM', 'DCCM']),
+                                                               kernel_size=17 if lk == 'SparsePLK' else rng.choice([9, 17, 27]), lk_type=lk, use_ea=rng.random() < 0.7,
+                                                               seed=s))(rng.choice(['PLK', 'SparsePLK', 'RectSparsePLK'])), 1),
+        'realplksr': lambda s: (synth.realplksr_state_dict(dim=rng.choice([32, 64]), n_blocks=2, upscale=rng.choice([1, 2, 3, 4]), kernel_size=rng.choice([9, 17, 31]),
+                                                           use_ea=rng.random() < 0.7, dysample=rng.random() < 0.5, seed=s), 1),
+        'cugan': lambda s: ((lambda v: synth.cugan_state_dict(v, pro=v != '2x_fast' and rng.random() < 0.5, seed=s))(rng.choice(['2x', '3x', '4x', '2x_fast'])), 16),
     }  # fmt: skip
     worst = 0.0
     for arch, make in makers.items():
@@ -54,6 +71,8 @@ def main():
             h, w = rng.randint(min_hw, 45), rng.randint(min_hw, 45)
             if arch == 'esrganbig':  # many tiles per workgroup, ragged edges, a row-banded tail
                 h, w = rng.randint(300, 420), rng.randint(500, 700)
+            while arch == 'cugan' and not _cugan_accepts(sd, h, w):  # the sizes the reference refuses (the plan refuses them too)
+                h, w = rng.randint(min_hw, 90), rng.randint(min_hw, 90)
             dt = rng.choice([torch.float32, torch.float32, torch.float16, torch.bfloat16])
             cin = sd['conv_first.weight'].shape[1] if arch == 'swinir_restore' else 3
             x = synth.synth_input((n, cin, h, w), seed=s).to(dt)

@@ -29,7 +29,7 @@ def synth_state_dict(meta):
         if k in kw:
             kw[k] = tuple(kw[k])
     fn = {'esrgan': synth.rrdbnet_state_dict, 'spanplus': synth.spanplus_state_dict, 'span': synth.span_state_dict,
-          'swinir': getattr(synth, 'swinir_state_dict', None), 'compact': synth.compact_state_dict, 'dat': getattr(synth, 'dat_state_dict', None), 'spanpp': getattr(synth, 'spanpp_state_dict', None), 'hat': getattr(synth, 'hat_state_dict', None), 'rtmosr': getattr(synth, 'rtmosr_state_dict', None), 'drct': getattr(synth, 'drct_state_dict', None)}[meta['arch']]  # fmt: skip
+          'swinir': getattr(synth, 'swinir_state_dict', None), 'compact': synth.compact_state_dict, 'dat': getattr(synth, 'dat_state_dict', None), 'spanpp': getattr(synth, 'spanpp_state_dict', None), 'hat': getattr(synth, 'hat_state_dict', None), 'rtmosr': getattr(synth, 'rtmosr_state_dict', None), 'drct': getattr(synth, 'drct_state_dict', None), 'plksr': synth.plksr_state_dict, 'realplksr': synth.realplksr_state_dict, 'cugan': synth.cugan_state_dict}[meta['arch']]  # fmt: skip
     return fn(seed=meta['seed'], **kw)
 
 
@@ -74,4 +74,12 @@ def oracle_forward(meta, sd, x):
         from oracle.dat import dat_forward
 
         return dat_forward(sd, x)
+    if meta['arch'] in ('plksr', 'realplksr'):
+        from oracle.plksr import plksr_forward
+
+        return plksr_forward(sd, x)
+    if meta['arch'] == 'cugan':
+        from oracle.cugan import cugan_forward
+
+        return cugan_forward(sd, x)
     raise KeyError(meta['arch'])

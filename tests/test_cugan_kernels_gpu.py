@@ -1,6 +1,7 @@
 """The Real-CUGAN kernels (csrc/cugan.hip) one by one against torch on windows of larger grids: rsa_deconv (k2 s2 p0, k4 s2 p3, k5 s3 p2)
-and rsa_conv_s2 at even and odd origins, both with bias, LeakyReLU and a residual window, in three bf16 products and one fp16 product;
-rsa_region_se against the mean of the crop; the input and output stages (8-bit stores bit-exact)."""
+and rsa_conv_s2 at even and odd origins, both with bias, LeakyReLU and a residual window, in three bf16 products and one fp16 product, on
+windows of one workgroup and of many with ragged last tiles; rsa_region_se against the mean of the crop, with a ragged last row chunk and
+on a 540 x 960 window; the input and output stages (8-bit stores bit-exact)."""
 
 import pytest
 import torch
@@ -107,16 +108,28 @@ def test_conv_s2_parity_matters(device):
 
 
 @pytest.mark.parametrize('prec', list(PRECISIONS))
-@pytest.mark.parametrize('C', [64, 128])
-def test_region_se_matches_torch(device, C, prec):
+@pytest.mark.parametrize('k, s, pad', [(2, 2, 0), (4, 2, 3), (5, 3, 2)])
+@pytest.mark.parametrize('cout', [3, 12, 24, 64, 128])
+def test_deconv_many_workgroups_ragged_tiles(device, k, s, pad, cout, prec):
+    """A 61 x 83 input window: several workgroups per phase in both directions, ragged last tiles; couts reach every CT instantiation."""
+    _run_resample(device, True, k, s, pad, 64, cout, prec, CG.Win(2, 3, 61, 83), seed=k * 1000 + cout)
+
+
+@pytest.mark.parametrize('prec', list(PRECISIONS))
+@pytest.mark.parametrize('origin', [(2, 4), (3, 5)])
+@pytest.mark.parametrize('cout', [3, 12, 24, 64, 128])
+def test_conv_s2_many_workgroups_ragged_tiles(device, origin, cout, prec):
+    win = CG.Win(origin[0], origin[1], 61, 83)  # odd both ways: the last row and column are dropped
+    _run_resample(device, False, 2, 2, 0, 64, cout, prec, win, seed=origin[0] * 1000 + cout, residual=cout != 3)
+
+
+def _run_region_se(device, C, prec, n, gh, gw, win, seed):
     products, fmt, tol = PRECISIONS[prec]
-    n, gh, gw = 2, 37, 45
-    win = CG.Win(3, 5, 29, 33)
-    x = _rand((n, C, gh, gw), 11) + 0.3
+    x = _rand((n, C, gh, gw), seed) + 0.3
     xp, xv = _planes(x, products, fmt, device)
     hid = C // 8
-    w1, b1 = _rand((hid, C, 1, 1), 12, 0.5), _rand((hid,), 13, 0.5)
-    w2, b2 = _rand((C, hid, 1, 1), 14, 0.5), _rand((C,), 15, 0.5)
+    w1, b1 = _rand((hid, C, 1, 1), seed + 1, 0.5), _rand((hid,), seed + 2, 0.5)
+    w2, b2 = _rand((C, hid, 1, 1), seed + 3, 0.5), _rand((C,), seed + 4, 0.5)
     se = CG.SEWeights.make(w1, b1, w2, b2, device)
     ws = CG.region_se_workspace(n, win.h, xp.planes, device)
     gate = torch.empty((n, C), dtype=torch.float32, device=device)
@@ -133,6 +146,23 @@ def test_region_se_matches_torch(device, C, prec):
     mask = torch.ones_like(ref, dtype=torch.bool)
     _win(mask, win)[:] = False
     assert torch.equal(got[mask], xv[mask])  # outside the window: untouched
+
+
+@pytest.mark.parametrize('prec', list(PRECISIONS))
+@pytest.mark.parametrize('C', [64, 128])
+def test_region_se_matches_torch(device, C, prec):
+    _run_region_se(device, C, prec, 2, 37, 45, CG.Win(3, 5, 29, 33), seed=11)
+
+
+@pytest.mark.parametrize('prec', list(PRECISIONS))
+def test_region_se_ragged_last_chunk(device, prec):
+    """53 window rows: three full 16-row chunks and a ragged one of 5 rows, whose sums must reach the mean."""
+    _run_region_se(device, 128, prec, 2, 60, 41, CG.Win(4, 3, 53, 37), seed=31)
+
+
+def test_region_se_large_window(device):
+    """A 540 x 960 window (the 4x model's input frame) at C = 64: 34 chunks, a ragged last one, the gate still within 1e-6 of float64."""
+    _run_region_se(device, 64, 'bf16x3', 1, 545, 966, CG.Win(3, 5, 540, 960), seed=41)
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.bfloat16, torch.uint8])

@@ -79,6 +79,20 @@ def test_plk_conv_matches_conv2d(device, mode, k, pdim, shape):
     assert torch.all(untouched == 7.0), 'planes outside the PLK range were written'
 
 
+
+@pytest.mark.parametrize('mode', ['bf16x3', 'fp16'])
+@pytest.mark.parametrize('k', [17, 31])
+@pytest.mark.parametrize('h, w', [(5, 7), (1, 40), (40, 1)])
+def test_plk_conv_image_smaller_than_kernel(device, mode, k, h, w):
+    """H or W below K / 2: most taps of every output pixel fall in the zero padding, the halo is mostly outside the image."""
+    got, ref, pp = _run_plk(device, 2, 16, k, h, w, mode, seed=k * 10 + h)
+    tol = (1e-5 if mode == 'bf16x3' else 2e-3) * ref.abs().max().item()
+    err = (got[:, 8:24] - ref).abs().max().item()
+    print(f'plk k{k} {h}x{w} {mode}: max-abs {err:.3e} / tol {tol:.3e}')
+    assert err <= tol
+    assert torch.all(torch.cat([got[:, :8], got[:, 24:]], 1) == 7.0), 'planes outside the PLK range were written'
+
+
 def _gn_ref(x, groups, eps=plk.GN_EPS):
     n, c, h, w = x.shape
     xg = x.double().reshape(n, groups, -1)

@@ -116,3 +116,24 @@ def test_tiling_does_not_warn_for_compact():
     with warnings.catch_warnings():
         warnings.simplefilter('error')
         upscale_tiled(m, torch.rand(1, 3, 40, 40), 2, (16, 16), halo=4, check=False)
+
+
+@pytest.mark.parametrize('lk_type, k', [('PLK', 9), ('PLK', 31), ('SparsePLK', 17), ('RectSparsePLK', 9), ('RectSparsePLK', 17), ('RectSparsePLK', 27)])
+def test_model_fold_matches_unfolded_oracle(lk_type, k):
+    """The dense kernel the model packs (its own fold of the checkpoint's branches) against the oracle's UNFOLDED large-kernel layer --
+    every dilated / rectangular branch run as its own convolution -- on images larger and smaller than the kernel."""
+    from oracle.plksr import large_kernel
+
+    sd = synth.plksr_state_dict(dim=32, n_blocks=1, upscale=2, kernel_size=k, lk_type=lk_type, seed=5)
+    m = resselt_amd.load_from_state_dict(dict(sd))
+    sd64 = {key: v.to(torch.float64) for key, v in sd.items()}
+    w, b = m._lk_weights(sd64, 1)
+    kk = m.kernel_size
+    assert w.shape == (8, 8, kk, kk)
+    g = torch.Generator().manual_seed(k)
+    for hw in ((23, 29), (5, 7), (1, 12)):
+        x = torch.randn(1, 32, *hw, generator=g, dtype=torch.float64)
+        ref = large_kernel(sd64, 'feats.1.lk', x)
+        got = F.conv2d(x[:, :8], w, b, padding=kk // 2)
+        assert torch.equal(ref[:, 8:], x[:, 8:])
+        assert (got - ref[:, :8]).abs().max() <= 1e-12 * ref.abs().max(), (lk_type, k, hw)

@@ -65,10 +65,8 @@ class SRVGGNetCompact(EngineModule):
         pf, s = self.num_feat // 8, self.upscale
         x_pl = plan.planes(n, (c + 7) // 8, h, w, with_lo)
         bufs = [plan.planes(n, pf, h, w, with_lo) for _ in range(2)]
-        holder = {}
 
         def set_input(x):
-            holder['x'] = x  # the final store adds the (nearest-upsampled) input back
             ops.nchw_to_planes(x, x_pl)
 
         cur = x_pl
@@ -76,23 +74,7 @@ class SRVGGNetCompact(EngineModule):
             dst = bufs[i & 1]
             plan.conv(ops.conv_params(W[f'body.{2 * i}'], cur, h, w, act=L.ACT_PRELU, act_vec=W[f'slope.{2 * i + 1}'], out=dst))
             cur = dst
-        out_shape = (n, self.num_out_ch, h * s, w * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=plan.device)}
-        base0 = torch.empty((n, c, h, w), dtype=dtype, device=plan.device)  # placeholder pointer, patched per call
-        plan.conv(ops.conv_params(W[f'body.{self._last}'], cur, h, w, out_nchw=out_buf['y'], pixel_shuffle=s, out_base=base0))
-        arr = plan.flush()
-        last = arr[len(arr) - 1]
-
-        def prepare():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=plan.device)
-            last.out_nchw = out_buf['y'].data_ptr()
-            last.out_base = holder['x'].data_ptr()
-
-        plan.steps.insert(len(plan.steps) - 1, prepare)
-
-        def get_output():
-            holder.clear()
-            return out_buf.pop('y')
-
-        return set_input, get_output
+        y = plan.output((n, self.num_out_ch, h * s, w * s), dtype)
+        base = plan.input_ref(x_shape, dtype)  # the final store adds the (nearest-upsampled) input back
+        plan.conv(ops.conv_params(W[f'body.{self._last}'], cur, h, w, out_nchw=y, pixel_shuffle=s, out_base=base))
+        return set_input

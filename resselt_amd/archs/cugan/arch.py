@@ -312,12 +312,10 @@ class _CUGANBase(EngineModule):
             if b.f32:
                 maps[name] = plan.f32map(n, b.channels, gh, gw)
                 maps[name].zero_()
-        holder = {}
         pro = self.is_pro
         in_scale, in_shift = (PRO_SCALE, PRO_SHIFT) if pro else (1.0, 0.0)
 
         def set_input(x):
-            holder['x'] = x
             p = CG.input_params(x, x_shape, planes['x'], g.pad_top, g.pad_left, g.unshuffle, in_scale, in_shift)
             CG.run('rsa_cugan_input', p, device=dev)
 
@@ -351,27 +349,14 @@ class _CUGANBase(EngineModule):
 
         oh, ow = g.out_hw
         is_u8 = dtype == torch.uint8
-        out_shape = (n, oh, ow, self.out_ch) if is_u8 else (n, self.out_ch, oh, ow)
-        out_buf = {}
-        fmap = maps[g.out_map]
+        y = plan.output((n, oh, ow, self.out_ch) if is_u8 else (n, self.out_ch, oh, ow), dtype)
+        base = plan.input_ref((n, h0, w0, c) if is_u8 else x_shape, dtype) if g.base_div else None
         bscale, bshift = (PRO_SCALE, PRO_SHIFT) if pro else (1.0, 0.0)
         oshift, odiv = (PRO_SHIFT, PRO_SCALE) if pro else (0.0, 1.0)
-
-        def run_output():
-            y = out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-            base = holder['x'] if g.base_div else None
-            p = CG.output_params(fmap, self.out_ch, g.out_origin[0], g.out_origin[1], g.pixel_shuffle, y, (oh, ow), base=base, base_hw=(h0, w0),
-                                 base_div=max(g.base_div, 1), base_scale=bscale, base_shift=bshift, out_shift=oshift, out_div=odiv)  # fmt: skip
-            CG.run('rsa_cugan_output', p, device=dev)
-
-        plan.call(run_output)
-        plan.count_launches(1)
-
-        def get_output():
-            holder.clear()
-            return out_buf.pop('y')
-
-        return set_input, get_output
+        p = CG.output_params(maps[g.out_map], self.out_ch, g.out_origin[0], g.out_origin[1], g.pixel_shuffle, y, (oh, ow), base=base,
+                             base_hw=(h0, w0), base_div=max(g.base_div, 1), base_scale=bscale, base_shift=bshift, out_shift=oshift, out_div=odiv)  # fmt: skip
+        plan.launch('rsa_cugan_output', p)
+        return set_input
 
 
 class UpCunet2x(_CUGANBase):  # the reference's class names, recorded in the fixtures' metadata

@@ -495,26 +495,12 @@ class DAT(EngineModule):
         norm('norm', cur, out_planes=n_pl)
         resi_conv('conv_after_body', n_pl, first, out_planes=body_pl)  # + conv_first output (arch.py:981, 986)
 
-        out_shape = (n, self.in_chans, H * s, Wd * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
+        y_out = plan.output((n, self.in_chans, H * s, Wd * s), dtype)
         final = dict(out_scale=1.0 / self.img_range, out_shift=mean)  # x / img_range + mean (arch.py:989)
         if self.upsampler == 'pixelshuffle':
             head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
             y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=out_buf['y'], **final))
+            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, **final))
         else:
-            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=out_buf['y'], pixel_shuffle=s, **final))
-        arr = plan.flush()
-        last_entry = arr[len(arr) - 1]
-
-        def prepare_output():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-            last_entry.out_nchw = out_buf['y'].data_ptr()
-
-        plan.steps.insert(len(plan.steps) - 1, prepare_output)
-
-        def get_output():
-            return out_buf.pop('y')
-
-        return set_input, get_output
+            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, pixel_shuffle=s, **final))
+        return set_input

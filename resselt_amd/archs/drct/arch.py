@@ -249,10 +249,8 @@ class DRCT(EngineModule):
             """conv_params with f32 operands that are channel views of wider maps: checked against the view, passed by pointer."""
             return ops.conv_params(wts, src, H, Wd, **kw)
 
-        out_shape = (nb, self.in_chans, H * s, Wd * s)
-        out_buf: dict = {}
+        y_out = plan.output((nb, self.in_chans, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
         final = dict(out_scale=1.0 / self.img_range, out_shift=mean)  # x / img_range + mean (arch.py:790)
-        last_entries = []  # (descriptor of an image's last convolution, image index)
 
         def image(bi: int) -> None:
             x_pl = Planes(x_all.hi[bi : bi + 1], None if x_all.lo is None else x_all.lo[bi : bi + 1])
@@ -294,23 +292,9 @@ class DRCT(EngineModule):
             # latter as a 1x1 convolution with the identity matrix, whose epilogue adds conv_first's map and writes the planes the head reads
             plan.conv(ops.conv_params(W['conv_after_body' if self.resi == '1conv' else 'identity'], n_pl, H, Wd, cin_planes=cp0, res1=first, alpha=1.0, out=body_pl))
             y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp0, H, Wd)
-            placeholder = torch.empty((n,) + out_shape[1:], dtype=dtype, device=dev)  # (never written: prepare_output patches the pointer first)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=placeholder, **final))
-            arr = plan.flush()
-            last_entries.append((arr[len(arr) - 1], bi))
+            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out[bi : bi + 1], **final))
+            plan.flush()
 
         for bi in range(nb):
             image(bi)
-
-        # a fresh output tensor per call: every image's last descriptor is pointed at its slice
-        def prepare_output():
-            out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-            for e, bi in last_entries:
-                e.out_nchw = out_buf['y'][bi : bi + 1].data_ptr()
-
-        plan.steps.insert(0, prepare_output)
-
-        def get_output():
-            return out_buf.pop('y')[:, :, : h0 * s, : w0 * s]
-
-        return set_input, get_output
+        return set_input

@@ -276,15 +276,13 @@ class RRDBNet(EngineModule):
             bufs.append(plan.planes(n, pf, sub_h << lv, w << lv, with_lo))
         hr_buf = plan.planes(n, pf, sub_h * s_net, w * s_net, with_lo)
         hh, wwid = h * s_net, w * s_net
-        out_buf: dict = {}
         u8 = dtype == torch.uint8
-        out_shape = (n, hh, wwid, self.out_nc) if u8 else (n, self.out_nc, hh, wwid)
+        crop = (h_in * self.scale, w_in * self.scale) if sf else None
+        y = plan.output((n, hh, wwid, self.out_nc) if u8 else (n, self.out_nc, hh, wwid), dtype, crop)
         band_out = torch.empty(n * self.out_nc * sub_h * s_net * wwid, dtype=dtype, device=plan.device) if n_bands > 1 else None  # flat: each band views it densely
         plan.keep.append(band_out)
         from ...engine.tensors import PlaneRows
 
-        last_entries = []
-        copies = []
         for bi in range(n_bands):
             a0, a1 = bi * band_lr, min(h, (bi + 1) * band_lr)
             r0, r1 = max(0, a0 - halo_lr), min(h, a1 + halo_lr)
@@ -303,38 +301,15 @@ class RRDBNet(EngineModule):
                 tmp = band_out[: n * self.out_nc * rows * s_net * wwid]
                 tmp = tmp.view(n, rows * s_net, wwid, self.out_nc) if u8 else tmp.view(n, self.out_nc, rows * s_net, wwid)
                 plan.conv(ops.conv_params(W[f'model.{k + 2}'], hr, rows * s_net, wwid, out_nchw=tmp))
-                arr = plan.flush()
                 lo, hi_ = (a0 - r0) * s_net, (a1 - r0) * s_net
 
                 def copy_band(tmp=tmp, lo=lo, hi_=hi_, y0=a0 * s_net, y1=a1 * s_net):
                     if u8:
-                        out_buf['y'][:, y0:y1] = tmp[:, lo:hi_]
+                        plan.current_output()[:, y0:y1] = tmp[:, lo:hi_]
                     else:
-                        out_buf['y'][:, :, y0:y1] = tmp[:, :, lo:hi_]
+                        plan.current_output()[:, :, y0:y1] = tmp[:, :, lo:hi_]
 
                 plan.call(copy_band)
             else:
-                placeholder = torch.empty(out_shape, dtype=dtype, device=plan.device)
-                out_buf['y'] = placeholder
-                plan.conv(ops.conv_params(W[f'model.{k + 2}'], hr, hh, wwid, out_nchw=placeholder))
-                arr = plan.flush()
-                last_entries.append(arr[len(arr) - 1])
-
-        # a fresh output tensor per call (single band: patch the last descriptor's pointer; bands: the copies fill it)
-        def prepare_output():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=plan.device)
-            for e in last_entries:
-                e.out_nchw = out_buf['y'].data_ptr()
-
-        plan.steps.insert(0, prepare_output)
-        if n_bands > 1:
-            out_buf.pop('y', None)
-
-        def get_output():
-            y = out_buf.pop('y')
-            if sf:
-                y = y[:, : h_in * self.scale, : w_in * self.scale] if u8 else y[:, :, : h_in * self.scale, : w_in * self.scale]
-            return y
-
-        return set_input, get_output
+                plan.conv(ops.conv_params(W[f'model.{k + 2}'], hr, hh, wwid, out_nchw=y))
+        return set_input

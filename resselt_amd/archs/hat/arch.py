@@ -364,22 +364,8 @@ class HAT(EngineModule):
         tail = W['conv_after_body'] if self.resi == '1conv' else W['identity']
         plan.conv(ops.conv_params(tail, n_pl, H, Wd, cin_planes=cp, res1=first, alpha=1.0, out=body_pl))  # + conv_first output (arch.py:1104)
 
-        out_shape = (n, self.in_chans, H * s, Wd * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
+        y_out = plan.output((n, self.in_chans, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
         head = pixelshuffle_buffers(plan, W, n, H, Wd, nf, with_lo)
         y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-        plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=out_buf['y'], out_scale=1.0 / self.img_range, out_shift=mean))
-        arr = plan.flush()
-        last_entry = arr[len(arr) - 1]
-
-        def prepare_output():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-            last_entry.out_nchw = out_buf['y'].data_ptr()
-
-        plan.steps.insert(len(plan.steps) - 1, prepare_output)
-
-        def get_output():
-            return out_buf.pop('y')[:, :, : h0 * s, : w0 * s]
-
-        return set_input, get_output
+        plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, out_scale=1.0 / self.img_range, out_shift=mean))
+        return set_input

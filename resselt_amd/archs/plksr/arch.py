@@ -17,16 +17,14 @@ convolution), so the DySample input exists as split planes; offset/scope and the
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
+from ...engine import dysample as dys
 from ...engine import lib as L
 from ...engine import ops, plk
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import Planes
-from ..spanplus.arch import dysample_init_pos
 
 _CCM_K = {'CCM': (3, 1), 'ICCM': (1, 3), 'DCCM': (3, 3)}  # kernel sizes of channel_mixer.0 / .2
 _SPARSE = ((5, 1), (5, 2), (5, 3), (5, 4))  # the reference loader's fixed SparsePLK sub-kernels (archs/plksr/__init__.py: sparse_kernels / dilations)
@@ -102,21 +100,12 @@ class _PLKBase(EngineModule):
 
     def _pack_dysample(self, W, sd, device, products):
         s, cin = self.upscale, self.in_ch * self.upscale**2
-        G, out_ch = self.dys_groups, self.in_ch
-        w = torch.cat([sd['to_img.offset.weight'], sd['to_img.scope.weight']], 0)
-        b = torch.cat([sd['to_img.offset.bias'], torch.zeros_like(sd['to_img.offset.bias'])], 0)
-        W['offscope'] = ops.ConvWeights.from_oihw(w, b, products, device=device)
         if s != 1:
-            end_w, end_b = sd['to_img.end_conv.weight'].reshape(out_ch, cin), sd['to_img.end_conv.bias']
+            end_w, end_b = sd['to_img.end_conv.weight'].reshape(self.in_ch, cin), sd['to_img.end_conv.bias']
         else:  # no end convolution (end_convolution = s != 1): the sampled channels are the output
             end_w, end_b = torch.eye(cin, device=device), torch.zeros(cin, device=device)
-        # the 1x1 end conv per channel group before the (linear) sampling: z[4g + o] = sum over the channels c of group g of W_end[o][c] x[c]
-        cpg = cin // G
-        wz = torch.zeros((4 * G, cin), dtype=torch.float32, device=device)
-        for g in range(G):
-            wz[4 * g : 4 * g + out_ch, g * cpg : (g + 1) * cpg] = end_w[:, g * cpg : (g + 1) * cpg]
-        W['zproj'] = ops.ConvWeights.from_oihw(wz[:, :, None, None], None, products, device=device)
-        W['dys'] = dict(init_pos=sd['to_img.init_pos'].reshape(-1).contiguous(), end_b=end_b.contiguous())
+        dys.pack(W, sd['to_img.offset.weight'], sd['to_img.offset.bias'], sd['to_img.scope.weight'], end_w, end_b, sd['to_img.init_pos'],
+                      self.dys_groups, s, products=products, device=device)  # fmt: skip
 
     def macs_per_input_pixel(self) -> int:
         d, p, s = self.dim, self.pdim, self.upscale
@@ -148,10 +137,8 @@ class _PLKBase(EngineModule):
             plan.keep += [stats, ws]
         fin = X[nb % 2]
         img = Planes(fin.hi[:, pf : pf + 1], None if fin.lo is None else fin.lo[:, pf : pf + 1])
-        holder = {}
 
         def set_input(x):
-            holder['x'] = x
             ops.nchw_to_planes(x, img)
 
         plan.conv(ops.conv_params(W['feats.0'], fin, h, w, in_plane0=pf, out=X[0], out_f32=Xf[0]))
@@ -164,14 +151,10 @@ class _PLKBase(EngineModule):
             if pdim < dim:
                 plan.conv(ops.conv_params(W[f'{p}.mix2b'], T, h, w, out=M, out_plane_off=pp))
             blob, lk_bias = W[f'{p}.lk']
-            lp = plk.plk_params(blob, lk_bias, self.kernel_size, products, Sb, M, 0)
-            plan.call(lambda lp=lp: plk.plk_conv(lp, stream()), meta=None)
-            plan.count_launches(1)
+            plan.launch('rsa_plk_conv', plk.plk_params(blob, lk_bias, self.kernel_size, products, Sb, M, 0))
             if self.use_ea:
                 plan.conv(ops.conv_params(W[f'{p}.ea'], M, h, w, out_f32=G))
-                ep = plk.ea_gate_params(G, M, M, dim)
-                plan.call(lambda ep=ep: plk.ea_gate(ep, stream()))
-                plan.count_launches(1)
+                plan.launch('rsa_ea_gate', plk.ea_gate_params(G, M, M, dim))
             if self._norm:
                 plan.conv(ops.conv_params(W[f'{p}.refine'], M, h, w, out_f32=R))
                 gamma, beta = W[f'{p}.norm']
@@ -186,54 +169,14 @@ class _PLKBase(EngineModule):
             else:
                 plan.conv(ops.conv_params(W[f'{p}.refine'], M, h, w, res1=Xf[xi], out=X[xo], out_f32=Xf[xo]))
 
-        out_shape = (n, self.in_ch, h * s, w * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
-        if not getattr(self, 'dysample', False):
-            base0 = torch.empty((n, c, h, w), dtype=dtype, device=dev)  # placeholder pointer, patched per call
-            plan.conv(ops.conv_params(W['last'], fin, h, w, out_nchw=out_buf['y'], pixel_shuffle=s, out_base=base0))
-            arr = plan.flush()
-            last = arr[len(arr) - 1]
-
-            def prepare():
-                if 'y' not in out_buf:
-                    out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-                last.out_nchw = out_buf['y'].data_ptr()
-                last.out_base = holder['x'].data_ptr()
-
-            plan.steps.insert(len(plan.steps) - 1, prepare)
-        else:
-            cin = self.in_ch * s * s
-            Gs = self.dys_groups
-            Y = plan.planes(n, (cin + 7) // 8, h, w, with_lo)
+        y = plan.output((n, self.in_ch, h * s, w * s), dtype)
+        if getattr(self, 'dysample', False):
+            Y = plan.planes(n, (self.in_ch * s * s + 7) // 8, h, w, with_lo)
             plan.conv(ops.conv_params(W['last'], fin, h, w, out=Y))
-            oc = 2 * Gs * s * s
-            offscope = plan.f32map(n, 2 * oc, h, w)
-            z = plan.f32map(n, 4 * Gs, h, w)
-            plan.conv(ops.conv_params(W['offscope'], Y, h, w, out_f32=offscope))
-            plan.conv(ops.conv_params(W['zproj'], Y, h, w, out_f32=z))
-            plan.flush()
-            d = W['dys']
-            dp = L.DySampleParams()
-            dp.batch, dp.H, dp.W, dp.C, dp.groups, dp.scale, dp.out_ch = n, h, w, 4 * Gs, Gs, s, self.in_ch
-            dp.x_f32, dp.offscope = z.data_ptr(), offscope.data_ptr()
-            dp.init_pos, dp.end_w, dp.end_b = d['init_pos'].data_ptr(), None, d['end_b'].data_ptr()
-            dp.out_dtype = ops.rsa_dtype(dtype)
-            lib = L.load()
-
-            def run_dysample():
-                if 'y' not in out_buf:
-                    out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-                dp.out_nchw = out_buf['y'].data_ptr()
-                L.check(lib.rsa_dysample(C.byref(dp), C.c_void_p(stream())), 'rsa_dysample')
-
-            plan.call(run_dysample)
-            plan.count_launches(1)
-
-        def get_output():
-            holder.clear()
-            return out_buf.pop('y')
-
-        return set_input, get_output
+            dys.emit(plan, W, Y, y)
+        else:
+            plan.conv(ops.conv_params(W['last'], fin, h, w, out_nchw=y, pixel_shuffle=s, out_base=plan.input_ref(x_shape, dtype)))
+        return set_input
 
 
 class plksr(_PLKBase):  # noqa: N801  (the reference's class name, recorded in the fixtures' metadata)
@@ -349,7 +292,7 @@ class realplksr(_PLKBase):  # noqa: N801
             shapes['to_img.offset.weight'] = (oc, cin, 1, 1)
             shapes['to_img.offset.bias'] = (oc,)
             shapes['to_img.scope.weight'] = (oc, cin, 1, 1)
-            buffers['to_img.init_pos'] = dysample_init_pos(s, self.dys_groups)
+            buffers['to_img.init_pos'] = dys.dysample_init_pos(s, self.dys_groups)
         build_param_tree(self, shapes, buffers)
 
     def _last_index(self) -> int:

@@ -144,10 +144,8 @@ class RTMoSR(EngineModule):
             plan.count_launches(1)
 
         x_pl = plan.planes(n, (3 * u * u + 7) // 8, H, Wd, with_lo)
-        holder = {}
 
         def set_input(x):
-            holder['x'] = x  # the final store adds the nearest-upsampled input back (arch.py:387)
             ops.nchw_to_planes(x, x_pl, unshuffle=u)  # check_img_size's reflect padding and the PixelUnshuffle front end, fused
 
         cur = plan.f32map(n, dim, H, Wd)
@@ -212,23 +210,7 @@ class RTMoSR(EngineModule):
         if self.n_blocks == 0:
             raise NotImplementedError('RTMoSR without blocks')
 
-        out_shape = (n, 3, H * s_int, Wd * s_int)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
-        base0 = torch.empty((n, 3, h0, w0), dtype=dtype, device=dev)  # placeholder pointer, patched per call
-        plan.conv(ops.conv_params(W['to_img.0'], feat_pl, H, Wd, out_nchw=out_buf['y'], pixel_shuffle=s_int, out_base=base0, out_base_div=out_scale))
-        arr = plan.flush()
-        last_entry = arr[len(arr) - 1]
-
-        def prepare():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-            last_entry.out_nchw = out_buf['y'].data_ptr()
-            last_entry.out_base = holder['x'].data_ptr()
-
-        plan.steps.insert(len(plan.steps) - 1, prepare)
-
-        def get_output():
-            holder.clear()
-            return out_buf.pop('y')[:, :, : h0 * out_scale, : w0 * out_scale]
-
-        return set_input, get_output
+        y = plan.output((n, 3, H * s_int, Wd * s_int), dtype, crop=(h0 * out_scale, w0 * out_scale))
+        base = plan.input_ref(x_shape, dtype)  # the final store adds the nearest-upsampled input back (arch.py:387)
+        plan.conv(ops.conv_params(W['to_img.0'], feat_pl, H, Wd, out_nchw=y, pixel_shuffle=s_int, out_base=base, out_base_div=out_scale))
+        return set_input

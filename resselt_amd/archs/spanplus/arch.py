@@ -2,23 +2,17 @@
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
+from ...engine import dysample as dys
+from ...engine.dysample import dysample_init_pos
 from ...engine import lib as L
 from ...engine import ops
 from ...engine.base import EngineModule, Plan
 from ...engine.paramtree import build_param_tree
-from ...engine.spanblocks import SPAN_MIXED, SpabChain, conv3xc_shapes, pack_span_family, spab_shapes
+from ...engine.spanblocks import SPAN_MIXED, SpabChain, conv3xc_shapes, first_input, pack_span_family, spab_shapes
 
 _GROUPS = 4  # DySample groups, fixed by the reference (utilities/dysample.py:17)
-
-
-def dysample_init_pos(scale: int, groups: int = _GROUPS) -> torch.Tensor:
-    """The reference's registered buffer (utilities/dysample.py:43-45): sub-pixel centre offsets per group."""
-    h = torch.arange((-scale + 1) / 2, (scale - 1) / 2 + 1) / scale
-    return torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, groups, 1).reshape(1, -1, 1, 1)
 
 
 class SpanPlus(EngineModule):
@@ -70,7 +64,7 @@ class SpanPlus(EngineModule):
             shapes['upsampler.offset.weight'] = (oc, fc, 1, 1)
             shapes['upsampler.offset.bias'] = (oc,)
             shapes['upsampler.scope.weight'] = (oc, fc, 1, 1)
-            buffers['upsampler.init_pos'] = dysample_init_pos(upscale)
+            buffers['upsampler.init_pos'] = dysample_init_pos(upscale, _GROUPS)
         build_param_tree(self, shapes, buffers)
 
     # ---------------------------------------------------------------- weights
@@ -92,25 +86,10 @@ class SpanPlus(EngineModule):
         W = pack_span_family(self, device, products, self._conv3xc_names(), plain)
         if self.upsampler_kind == 'dys':
             sd = {k: v.detach().to(device=device, dtype=torch.float32) for k, v in self.state_dict().items()}
-            # offset (with bias) and scope (no bias) 1x1 convs as ONE k1 convolution: channels [0,oc) | [oc,2oc)
-            w = torch.cat([sd['upsampler.offset.weight'], sd['upsampler.scope.weight']], 0)
-            b = torch.cat([sd['upsampler.offset.bias'], torch.zeros_like(sd['upsampler.offset.bias'])], 0)
             head = dict(products=3, fmt=1) if products.name == 'mixed' else dict(products=products)  # the head reads hi + lo planes (spanblocks.SPAN_MIXED)
-            W['upsampler.offscope'] = ops.ConvWeights.from_oihw(w, b, device=device, **head)
-            end_w = sd['upsampler.end_conv.weight'].reshape(self.out_ch, self.fc)
-            if self.out_ch <= 4:
-                # bilinear sampling is linear: the 1x1 end conv is applied per channel group BEFORE the sampling, at low resolution
-                # (rsa_dysample's pre-projected mode): z[4g + o] = sum over the channels c of group g of W_end[o][c] * x[c]
-                cpg = self.fc // _GROUPS
-                wz = torch.zeros((4 * _GROUPS, self.fc), dtype=torch.float32, device=device)
-                for g in range(_GROUPS):
-                    wz[4 * g : 4 * g + self.out_ch, g * cpg : (g + 1) * cpg] = end_w[:, g * cpg : (g + 1) * cpg]
-                W['upsampler.zproj'] = ops.ConvWeights.from_oihw(wz[:, :, None, None], None, device=device, **head)
-            W['dys'] = dict(
-                init_pos=sd['upsampler.init_pos'].reshape(-1).contiguous(),
-                end_w=sd['upsampler.end_conv.weight'].reshape(self.out_ch, self.fc).contiguous(),
-                end_b=sd['upsampler.end_conv.bias'].contiguous(),
-            )
+            dys.pack(W, sd['upsampler.offset.weight'], sd['upsampler.offset.bias'], sd['upsampler.scope.weight'],
+                          sd['upsampler.end_conv.weight'].reshape(self.out_ch, self.fc), sd['upsampler.end_conv.bias'], sd['upsampler.init_pos'],
+                          _GROUPS, self.upscale, device=device, **head)  # fmt: skip
         return W
 
     def macs_per_input_pixel(self) -> int:
@@ -131,18 +110,9 @@ class SpanPlus(EngineModule):
         fc, pf, s = self.fc, self.fc // 8, self.upscale
         with_lo = products == 3
         wide = with_lo or products.name == 'mixed'  # buffers read by a three-product layer (conv_cat, the head) keep hi + lo
-        # The first convolution (3 -> fc) takes the ring schedule when its input has a whole half chunk of 16 channels: a second, all-zero plane
-        # (zeroed once, here) beside the image's plane, weights padded to match (`_pack`).  The chunk-barrier kernel ran it at 0.36 ms per
-        # 2 Mpx (one fill in flight per CU); fp16 three-product form only (the ring's half mode in three products exists for fp16 planes).
-        ring_first = W['feats.0'].cin_planes == 2
-        x_pl = plan.planes(n, 2 if ring_first else (c + 7) // 8, h, w, wide)
-        if ring_first:
-            x_pl.hi.zero_()
-            if x_pl.lo is not None:
-                x_pl.lo.zero_()
+        x_pl = first_input(plan, W, 'feats.0', n, c, h, w, wide)
         chain = SpabChain(plan, W, n, h, w, fc, L.ACT_MISH, with_lo, cat_lo=wide)
-        preproj = self.upsampler_kind == 'dys' and 'upsampler.zproj' in W
-        need_f32_feat = self.upsampler_kind == 'dys' and not preproj
+        need_f32_feat = self.upsampler_kind == 'dys' and dys.needs_f32_input(W)
 
         def set_input(x):
             ops.nchw_to_planes(x, x_pl)
@@ -169,48 +139,10 @@ class SpanPlus(EngineModule):
                 else:
                     chain.run(names, cat, xf[bi & 1], feat, 0, feat_f32)
 
-        out_shape = (n, self.out_ch, h * s, w * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=plan.device)}
-        if self.upsampler_kind in ('ps', 'conv'):
-            key = 'upsampler.0' if self.upsampler_kind == 'ps' else 'upsampler'
-            plan.conv(ops.conv_params(W[key], feat, h, w, out_nchw=out_buf['y'], pixel_shuffle=s))
-            arr = plan.flush()
-            last = arr[len(arr) - 1]
-
-            def prepare_output():
-                if 'y' not in out_buf:
-                    out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=plan.device)
-                last.out_nchw = out_buf['y'].data_ptr()
-
-            plan.steps.insert(len(plan.steps) - 1, prepare_output)
+        y = plan.output((n, self.out_ch, h * s, w * s), dtype)
+        if self.upsampler_kind == 'dys':
+            dys.emit(plan, W, feat, y, feat_f32)
         else:
-            oc = 2 * _GROUPS * s * s
-            offscope = plan.f32map(n, 2 * oc, h, w)
-            plan.conv(ops.conv_params(W['upsampler.offscope'], feat, h, w, out_f32=offscope))
-            plan.flush()
-            d = W['dys']
-            dp = L.DySampleParams()
-            if preproj:
-                z = plan.f32map(n, 4 * _GROUPS, h, w)
-                plan.conv(ops.conv_params(W['upsampler.zproj'], feat, h, w, out_f32=z))
-                plan.flush()
-            dp.batch, dp.H, dp.W, dp.C, dp.groups, dp.scale, dp.out_ch = n, h, w, (4 * _GROUPS if preproj else fc), _GROUPS, s, self.out_ch
-            dp.x_f32, dp.offscope = (z if preproj else feat_f32).data_ptr(), offscope.data_ptr()
-            dp.init_pos, dp.end_w, dp.end_b = d['init_pos'].data_ptr(), (None if preproj else d['end_w'].data_ptr()), d['end_b'].data_ptr()
-            dp.out_dtype = ops.rsa_dtype(dtype)
-            lib = L.load()
-            dev = plan.device
-
-            def run_dysample():
-                if 'y' not in out_buf:
-                    out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-                dp.out_nchw = out_buf['y'].data_ptr()
-                L.check(lib.rsa_dysample(C.byref(dp), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_dysample')
-
-            plan.call(run_dysample)
-            plan.count_launches(1)
-
-        def get_output():
-            return out_buf.pop('y')
-
-        return set_input, get_output
+            key = 'upsampler.0' if self.upsampler_kind == 'ps' else 'upsampler'
+            plan.conv(ops.conv_params(W[key], feat, h, w, out_nchw=y, pixel_shuffle=s))
+        return set_input

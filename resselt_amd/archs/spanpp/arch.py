@@ -19,7 +19,7 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan
 from ...engine.paramtree import build_param_tree
 from ...engine.base import check_fp16_range
-from ...engine.spanblocks import SPAN_FIRST, SPAN_MIXED, SpabChain, conv3xc_shapes, fold_conv3xc, span_layer_policy
+from ...engine.spanblocks import SPAN_FIRST, SPAN_MIXED, SpabChain, conv3xc_shapes, first_input, fold_conv3xc, span_layer_policy
 
 
 def repconv_shapes(shapes: dict, name: str, cout: int, cin: int) -> None:
@@ -160,12 +160,7 @@ class SpanPP(EngineModule):
         fc, pf, s = self.fc, self.fc // 8, self._scale
         with_lo = products == 3
         wide = with_lo or products.name == 'mixed'  # buffers read by a three-product layer (conv_cat, the head) keep hi + lo
-        ring_first = W['conv0'].cin_planes == 2  # a second, all-zero input plane: the first convolution takes the ring schedule (see SpanPlus)
-        x_pl = plan.planes(n, 2 if ring_first else (c + 7) // 8, h, w, wide)
-        if ring_first:
-            x_pl.hi.zero_()
-            if x_pl.lo is not None:
-                x_pl.lo.zero_()
+        x_pl = first_input(plan, W, 'conv0', n, c, h, w, wide)
         chain = SpabChain(plan, W, n, h, w, fc, L.ACT_SILU, with_lo, cat_lo=wide)
 
         def set_input(x):
@@ -177,20 +172,6 @@ class SpanPP(EngineModule):
         plan.conv(ops.conv_params(W['conv0'], x_pl, h, w, out=cat, out_plane_off=0, out_f32=xf))
         names = dict(first='block_1', middle=[f'block_{i}' for i in range(2, 6)], end='block_6', conv_2='conv_2', conv_cat='conv_cat')
         chain.run(names, cat, xf, feat, 0, None)
-        out_shape = (n, 3, h * s, w * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=plan.device)}
-        plan.conv(ops.conv_params(W[f'up{s}'], feat, h, w, out_nchw=out_buf['y'], pixel_shuffle=s))
-        arr = plan.flush()
-        last = arr[len(arr) - 1]
-
-        def prepare_output():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=plan.device)
-            last.out_nchw = out_buf['y'].data_ptr()
-
-        plan.steps.insert(len(plan.steps) - 1, prepare_output)
-
-        def get_output():
-            return out_buf.pop('y')
-
-        return set_input, get_output
+        y = plan.output((n, 3, h * s, w * s), dtype)
+        plan.conv(ops.conv_params(W[f'up{s}'], feat, h, w, out_nchw=y, pixel_shuffle=s))
+        return set_input

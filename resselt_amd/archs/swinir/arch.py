@@ -251,11 +251,8 @@ class SwinIR(EngineModule):
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, wide, head_fmt)
         mean = W['mean']
 
-        holder = {}
-
         def set_input(x):
             # check_image_size (reflect pad to the window multiple) and (x - mean) * img_range, fused (arch.py:964-967)
-            holder['x'] = x
             ops.nchw_to_planes(x, x_pl, mean, self.img_range)
 
         first = plan.f32map(n, C_, H, Wd)
@@ -399,8 +396,7 @@ class SwinIR(EngineModule):
         with_lo, plan_fmt = wide, plan.fmt
         plan.fmt = head_fmt  # buffers of the head
 
-        out_shape = (n, self.out_chans, H * s, Wd * s)
-        out_buf = {'y': torch.empty(out_shape, dtype=dtype, device=dev)}
+        y_out = plan.output((n, self.out_chans, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
         final = dict(out_scale=1.0 / self.img_range, out_shift=mean)  # x / img_range + mean (arch.py:1013)
         lre = dict(act=L.ACT_LRELU, act_param=0.2)
         if self.upsampler == 'nearest+conv':
@@ -414,34 +410,17 @@ class SwinIR(EngineModule):
                 y = ny
             hr = plan.planes(n, 8, hh, ww, with_lo)
             plan.conv(ops.conv_params(W['conv_hr'], y, hh, ww, out=hr, **lre))
-            plan.conv(ops.conv_params(W['conv_last'], hr, hh, ww, out_nchw=out_buf['y'], **final))
+            plan.conv(ops.conv_params(W['conv_last'], hr, hh, ww, out_nchw=y_out, **final))
         elif self.upsampler == 'pixelshuffle':
             head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
             y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=out_buf['y'], **final))
+            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, **final))
         elif self.upsampler == 'pixelshuffledirect':
-            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=out_buf['y'], pixel_shuffle=s, **final))
+            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, pixel_shuffle=s, **final))
         else:
             # denoising / JPEG artefact heads (arch.py:1007-1010): (x_norm + conv_last(res)) / img_range + mean == x + conv_last(res) / img_range,
             # so the final store scales the convolution and adds the caller's own (unpadded) input as the base image
-            base0 = torch.empty((n, self.in_chans, h0, w0), dtype=dtype, device=dev)  # placeholder pointer, patched per call
-            plan.conv(ops.conv_params(W['conv_last'], body_pl, H, Wd, cin_planes=cp, out_nchw=out_buf['y'], out_scale=1.0 / self.img_range,
-                                      out_base=base0, out_base_div=1))  # fmt: skip
+            plan.conv(ops.conv_params(W['conv_last'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, out_scale=1.0 / self.img_range,
+                                      out_base=plan.input_ref(x_shape, dtype), out_base_div=1))  # fmt: skip
         plan.fmt = plan_fmt
-        arr = plan.flush()
-        last_entry = arr[len(arr) - 1]
-
-        def prepare_output():
-            if 'y' not in out_buf:
-                out_buf['y'] = torch.empty(out_shape, dtype=dtype, device=dev)
-            last_entry.out_nchw = out_buf['y'].data_ptr()
-            if self.upsampler == '':
-                last_entry.out_base = holder['x'].data_ptr()
-
-        plan.steps.insert(len(plan.steps) - 1, prepare_output)
-
-        def get_output():
-            holder.clear()
-            return out_buf.pop('y')[:, :, : h0 * s, : w0 * s]
-
-        return set_input, get_output
+        return set_input

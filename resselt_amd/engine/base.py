@@ -99,6 +99,13 @@ class Plan:
         # switches it off for A/B runs).  Measured on RRDBNet-23 at 1080p: 101.0 -> 97.8 ms per frame (profiles/r03_c_*).
         self.serpentine = True
         self._n_conv = 0
+        # the forward's output and the caller's input (``output`` / ``input_ref``): the tensor currently held, the address of the placeholder the
+        # descriptors were built against, and the (struct, field, byte offset) of every pointer field into it
+        self._y = self._x = None
+        self._out_spec = None
+        self._y0 = self._x0 = (0, 0)
+        self._out_binds: list = []
+        self._in_binds: list = []
 
     # ---- buffers ----
     def planes(self, n, planes, h, w, with_lo=True, fmt: int | None = None, lo_planes: int | None = None) -> Planes:
@@ -110,6 +117,60 @@ class Plan:
         t = empty_f32map(n, channels, h, w, self.device)
         self.keep.append(t)
         return t
+
+    # ---- the forward's output and the caller's input ----
+    def output(self, shape, dtype, crop=None) -> torch.Tensor:
+        """A placeholder of the forward's output, for ``conv_params(out_nchw=...)`` and the like (slices included); it is also the first forward's
+        output.  Every descriptor field that points into it is re-pointed, at the same byte offset, to a fresh tensor by one host step at the
+        start of ``steps`` whenever no output is held.  ``crop``: the (rows, columns) ``take_output`` keeps (dims 2-3; dims 1-2 of uint8 NHWC)."""
+        self._y = torch.empty(shape, dtype=dtype, device=self.device)
+        self._y0 = (self._y.data_ptr(), self._y.numel() * self._y.element_size())
+        self._out_spec = (tuple(shape), dtype, crop)
+        self.steps.insert(0, self._prepare_output)
+        return self._y
+
+    def input_ref(self, shape, dtype) -> torch.Tensor:
+        """A placeholder of the caller's input, for ``out_base``-style reads of it; ``feed`` re-points every field into it.  Held until the first
+        ``feed``, so that no buffer allocated during the build can take its address."""
+        self._x = torch.empty(shape, dtype=dtype, device=self.device)
+        self._x0 = (self._x.data_ptr(), self._x.numel() * self._x.element_size())
+        return self._x
+
+    def _bind(self, struct) -> None:
+        """Record the pointer fields of a descriptor that point into the output or input placeholder (build time)."""
+        for name, typ in struct._fields_:
+            if typ is C.c_void_p:
+                ptr = getattr(struct, name) or 0
+                for (base, size), binds in ((self._y0, self._out_binds), (self._x0, self._in_binds)):
+                    if base <= ptr < base + size:
+                        binds.append((struct, name, ptr - base))
+
+    def _prepare_output(self) -> None:
+        if self._y is None:
+            shape, dtype, _ = self._out_spec
+            self._y = torch.empty(shape, dtype=dtype, device=self.device)
+            base = self._y.data_ptr()
+            for struct, name, off in self._out_binds:
+                setattr(struct, name, base + off)
+
+    def current_output(self) -> torch.Tensor:
+        """The output tensor of the running forward (for host steps that write it directly)."""
+        return self._y
+
+    def feed(self, x: torch.Tensor) -> None:
+        """Point every descriptor field that reads the caller's input at ``x``, and hold ``x`` until ``take_output``."""
+        base = x.data_ptr()
+        for struct, name, off in self._in_binds:
+            setattr(struct, name, base + off)
+        self._x = x
+
+    def take_output(self) -> torch.Tensor:
+        """The forward's output, cropped; the plan lets go of it and of the input."""
+        y, self._y, self._x = self._y, None, None
+        crop = self._out_spec[2]
+        if crop is not None:
+            y = y[:, : crop[0], : crop[1]] if y.dtype == torch.uint8 else y[:, :, : crop[0], : crop[1]]
+        return y
 
     # ---- launch list ----
     def conv(self, params: L.ConvParams) -> L.ConvParams:
@@ -126,6 +187,8 @@ class Plan:
         if not self._pending:
             return None
         arr = (L.ConvParams * len(self._pending))(*self._pending)
+        for p in arr:
+            self._bind(p)
         self._n_launches = getattr(self, '_n_launches', 0) + len(self._pending)
         self._pending = []
         self.conv_arrays.append(arr)
@@ -153,9 +216,9 @@ class Plan:
 
     def launch(self, fn_name: str, params, kernels: int = 1, meta: dict | None = None) -> None:
         """A ``call`` step of one C-ABI entry point that takes ``(params*, stream)``; it launches ``kernels`` kernels."""
-        fn = getattr(L.load(), fn_name)
+        self._bind(params)
         dev = self.device
-        self.call(lambda: L.check(fn(C.byref(params), C.c_void_p(ops.current_stream_ptr(dev))), fn_name), meta)
+        self.call(lambda: L.launch(fn_name, params, ops.current_stream_ptr(dev)), meta)
         self.count_launches(kernels)
 
     def run(self) -> None:
@@ -185,6 +248,9 @@ class Plan:
         self.conv_cin.clear()
         self._pending = []
         self._pending_cin = []
+        self._y = self._x = None
+        self._out_binds.clear()
+        self._in_binds.clear()
 
     def buffer_bytes(self) -> int:
         total = 0
@@ -230,7 +296,7 @@ class EngineModule(nn.Module):
     def _drop_plan(self, key) -> None:
         entry = self._plans.pop(key)
         entry[0].release()
-        entry[1:] = [None, None, None]  # input setter / output getter / graph: closures over the plan's buffers
+        entry[1:] = [None, None]  # input setter / graph: closures over the plan's buffers
 
     def invalidate(self) -> None:
         """Drop the packed weights and every plan.  Called automatically by load_state_dict / .to() / .half() and when a parameter's
@@ -297,7 +363,8 @@ class EngineModule(nn.Module):
         raise NotImplementedError
 
     def _build_plan(self, plan: Plan, packed, x_shape, dtype, products: int):
-        """Return (input_setter, output_getter)."""
+        """Fill ``plan`` (its output through ``plan.output``) and return the input setter: ``set_input(x)`` converts the caller's tensor into
+        the plan's buffers."""
         raise NotImplementedError
 
     def _weights(self, device):
@@ -370,20 +437,22 @@ class EngineModule(nn.Module):
         new_plan = entry is None
         if entry is None:
             plan = Plan(x.device, self.products.fmt)
-            set_input, get_output = self._build_plan(plan, packed, shape, x.dtype, self.products)
+            set_input = self._build_plan(plan, packed, shape, x.dtype, self.products)
             plan.flush()
-            entry = [plan, set_input, get_output, None]
+            entry = [plan, set_input, None]
         self._plans[key] = entry  # most recently used last
         # least-recently-used plans go first when the cache holds too many plans or too many bytes (never the one about to run)
         while len(self._plans) > 1 and (len(self._plans) > self._max_plans or sum(e[0].buffer_bytes() for e in self._plans.values()) > self.max_plan_bytes):
             self._drop_plan(next(iter(self._plans)))
-        plan, set_input, get_output, graph = entry
+        plan, set_input, graph = entry
         name = type(self).__name__
         guard = self._fp16_guard()  # the resolved policy has fp16 layers: scan for non-finite values behind every forward
         auto = self.precision == 'auto'
         with torch.cuda.device(x.device):
             if not self.use_graph:
-                set_input(x.contiguous())
+                x = x.contiguous()
+                plan.feed(x)
+                set_input(x)
                 stale = None
                 try:
                     plan.run()
@@ -396,7 +465,7 @@ class EngineModule(nn.Module):
                         L.check_status(name)
                     except L.Fp16RangeError as e:
                         stale = e  # an EARLIER forward's range check (this one's kernels are still in flight)
-                y = get_output()
+                y = plan.take_output()
                 if stale is not None:
                     if not auto:
                         raise stale
@@ -413,12 +482,13 @@ class EngineModule(nn.Module):
                 return y
             if graph is None:
                 static_x = x.contiguous().clone()
+                plan.feed(static_x)
                 set_input(static_x)  # one eager pass first: lazy initialisation and allocator warm-up must not happen under capture
                 try:
                     plan.run()
                 finally:
                     L.check_status(name)
-                y0 = get_output()
+                y0 = plan.take_output()
                 if guard:
                     self._range_probe(plan, y0)
                 torch.cuda.synchronize(x.device)
@@ -431,12 +501,13 @@ class EngineModule(nn.Module):
                 del y0
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):  # every C-ABI launch of the plan asks for the CURRENT stream, i.e. the capture stream
+                    plan.feed(static_x)
                     set_input(static_x)
                     plan.run()
-                    static_y = get_output()
+                    static_y = plan.take_output()
                     if guard:
                         self._range_probe(plan, static_y)
-                graph = entry[3] = (g, static_x, static_y)
+                graph = entry[2] = (g, static_x, static_y)
             g, static_x, static_y = graph
             static_x.copy_(x)
             g.replay()

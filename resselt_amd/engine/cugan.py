@@ -5,7 +5,6 @@ A ``Win`` is a window of a grid (origin + size in pixels): include/resselt_amd.h
 
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import torch
@@ -180,8 +179,7 @@ def resample_flop_bytes(p: L.ResampleConvParams, transposed: bool) -> tuple[int,
 
 
 def run_resample(p: L.ResampleConvParams, transposed: bool, stream: int) -> None:
-    fn = 'rsa_deconv' if transposed else 'rsa_conv_s2'
-    L.check(getattr(L.load(), fn)(C.byref(p), C.c_void_p(stream)), fn)
+    L.launch('rsa_deconv' if transposed else 'rsa_conv_s2', p, stream)
 
 
 # ---------------------------------------------------------------------------------------------------------------- region SE
@@ -262,9 +260,7 @@ def output_params(fmap: torch.Tensor, channels: int, y0: int, x0: int, r: int, o
 
 def run(fn: str, p, stream: int | None = None, device=None) -> None:
     """Launch one ``(params*, stream)`` entry point on ``stream`` (default: the current stream of ``device``)."""
-    if stream is None:
-        stream = current_stream_ptr(device)
-    L.check(getattr(L.load(), fn)(C.byref(p), C.c_void_p(stream)), fn)
+    L.launch(fn, p, current_stream_ptr(device) if stream is None else stream)
 
 
 __all__ = ['Win', 'PF_BF16', 'PF_F16', 'phase_taps', 'deconv_out', 'pack_resample_weights', 'ResampleWeights', 'resample_params', 'SEWeights',

@@ -841,6 +841,11 @@ def check(rc: int, what: str) -> None:
         raise cls(f'{what} failed (status {rc}): {msg.decode() if msg else "?"}')
 
 
+def launch(name: str, params, stream: int) -> None:
+    """Call the C-ABI entry point ``name`` that takes ``(params*, stream)`` and raise if it fails."""
+    check(getattr(load(), name)(C.byref(params), C.c_void_p(stream)), name)
+
+
 def check_finite(t, stream: int) -> None:
     """Scan a plain float tensor (or the hi / lo storage of a split-plane buffer) for non-finite values (``rsa_check_finite``; asynchronous:
     ``check_status`` raises ``Fp16RangeError`` once the launch has completed)."""

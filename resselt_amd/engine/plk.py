@@ -99,7 +99,7 @@ def _planes_of(blob: torch.Tensor, k: int, products: int) -> int:
 
 
 def plk_conv(p: L.PlkConvParams, stream: int) -> None:
-    L.check(L.load().rsa_plk_conv(C.byref(p), C.c_void_p(stream)), 'rsa_plk_conv')
+    L.launch('rsa_plk_conv', p, stream)
 
 
 # ------------------------------------------------------------------------------------------------------------------ GroupNorm
@@ -131,7 +131,7 @@ def group_norm_apply_params(x_f32: torch.Tensor, C_: int, groups: int, stats: to
 
 
 def group_norm_apply(p: L.GroupNormApplyParams, stream: int) -> None:
-    L.check(L.load().rsa_group_norm_apply(C.byref(p), C.c_void_p(stream)), 'rsa_group_norm_apply')
+    L.launch('rsa_group_norm_apply', p, stream)
 
 
 # ------------------------------------------------------------------------------------------------------------------ EA gate
@@ -149,4 +149,4 @@ def ea_gate_params(g_f32: torch.Tensor, x: Planes, out: Planes, C_: int) -> L.Ea
 
 
 def ea_gate(p: L.EaGateParams, stream: int) -> None:
-    L.check(L.load().rsa_ea_gate(C.byref(p), C.c_void_p(stream)), 'rsa_ea_gate')
+    L.launch('rsa_ea_gate', p, stream)

@@ -134,6 +134,19 @@ def span_layer_policy(name: str, conv3xc: bool) -> tuple[int, int]:
     return (1, PF_F16) if conv3xc and name not in SPAN_FIRST else (3, PF_F16)
 
 
+def first_input(plan: Plan, W: dict, name: str, n: int, c: int, h: int, w: int, with_lo: bool) -> Planes:
+    """Input planes of the first convolution ``name``.  Where the packing padded that layer to a whole 16-channel half chunk (``pack_span_family``),
+    they carry a second, all-zero plane beside the image's, zeroed once here: the layer then takes the ring schedule.  The chunk-barrier kernel
+    ran it at 0.36 ms per 2 Mpx (one fill in flight per CU)."""
+    ring_first = W[name].cin_planes == 2
+    x_pl = plan.planes(n, 2 if ring_first else (c + 7) // 8, h, w, with_lo)
+    if ring_first:
+        x_pl.hi.zero_()
+        if x_pl.lo is not None:
+            x_pl.lo.zero_()
+    return x_pl
+
+
 def pack_span_family(module, device, products: int, conv3xc_names: list[str], plain_names: list[str]) -> dict:
     # The re-parameterisation is weight preprocessing on ~100 KB of tensors: it runs on the HOST in f64 (no vendor GEMM / reduction kernel is
     # launched from inside the package); ConvWeights.from_oihw uploads the folded f32 kernel and packs it with rsa_pack_weights.
@@ -144,7 +157,7 @@ def pack_span_family(module, device, products: int, conv3xc_names: list[str], pl
         w, b = fold_conv3xc(sd, name)
         prod, fmt = span_layer_policy(name, True) if mixed else (int(products), getattr(products, 'fmt', None))
         # the first convolution (3 input channels) is packed over a whole 16-channel half chunk: its input planes carry a second, all-zero plane
-        # so that the layer takes the ring schedule (archs/spanplus/arch.py::_build_plan) -- only where the ring takes the padded layer at all:
+        # so that the layer takes the ring schedule (``first_input``) -- only where the ring takes the padded layer at all:
         # three products and three cout tiles (33..48 features); elsewhere the extra plane would only be extra work for the chunk-barrier kernel
         ring_first = name in SPAN_FIRST and w.shape[1] <= 8 and int(prod) == 3 and (w.shape[0] + 15) // 16 == 3
         W[name] = ops.ConvWeights.from_oihw(w, b, prod, device=device, fmt=fmt, cin_planes=2 if ring_first else None)

@@ -89,6 +89,21 @@ def test_spanplus_x4_fp16_batch_vs_oracle(device, ups):
     assert (m(x.to(device)).cpu() - ref).abs().max().item() <= 5e-3 * max(1.0, ref.abs().max().item())
 
 
+def test_spanplus_dysample_end_conv_after_sampling_vs_oracle(device):
+    """More than 4 output channels: the DySample head samples the f32 features and applies its end convolution after the sampling."""
+    sd = synth.spanplus_state_dict(num_out_ch=8, upscale=2, upsampler='dys', seed=11)
+    x = synth.synth_input((2, 3, 20, 24), seed=11)
+    with torch.no_grad():
+        ref = oracle_forward(dict(arch='spanplus'), sd, x)
+    m = resselt_amd.load_from_state_dict(dict(sd)).to(device)
+    for precision in ('auto', 'bf16x3'):
+        m.precision = precision
+        y = m(x.to(device))
+        assert y.shape == ref.shape == (2, 8, 40, 48)
+        err = (y.cpu() - ref).abs().max().item()
+        assert err <= _tol(ref), f'{precision}: max-abs {err:.3e}'
+
+
 def test_span_eval_and_train_mode_agree(device):
     """The reference folds Conv3XC only in eval mode (SPANPlus) / always (SPAN); both paths give the same function."""
     sd = synth.spanplus_state_dict(upscale=2, upsampler='ps', seed=5)

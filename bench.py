@@ -21,12 +21,17 @@ child, relays rank 0's JSON line and exits with the child's status.
 ``DIR/output.npy`` in float32, a fixed seeded sample of at most 16 MB when it is larger (see ``dump_outputs``).  Weights and inputs are
 synthetic with fixed seeds, so the same arguments give the same inputs on every run.
 
-Extra objects on the JSON line:
-  roofline      dominant kernel (the fused conv kernel family = every launch of the forward), MFMA-bound:
-                algorithmic FLOP (2,240,856 per output pixel) / HIP-event time of the launches
+A plain run does only what its headline needs: set up, warm up, time the steps, dump the outputs if asked, print the line (the headline
+fields, ``config``, ``ring_aborts`` and ``event_ms_per_step``).  ``--full`` adds, after the timed steps and on rank 0, the legs below;
+``--no-kernel-roofline``, ``--no-power``, ``--no-secondary`` and ``--no-cpu-baseline`` leave single legs out of a ``--full`` run.
+  roofline      dominant kernel of one HxW frame, its per-kernel classes replayed launch by launch (``roofline_kernels``), the frame's
+                algorithmic FLOP (2,240,856 per output pixel) / HIP-event time of a forward (``roofline_frame``)
   roofline_hbm  the same time priced against the layer-wise HBM model of SURVEY.md §8d (7,790 B / output px)
+  power         socket power and clock over 3.5 s of back-to-back forwards (one GPU)
+  secondary     compact C3 / C4 legs with parity against the CPU oracle on a crop (one GPU, the default C2 workload)
   cpu_baseline  the CPU oracle (oracle/rrdbnet.py, a restatement of the reference forward; the reference
                 cannot travel to the GPU box) timed on the host cores on a bounded 256x256 crop
+With ``--config c3 | c4``, ``--full`` adds that model's per-kernel roofline and its CPU baseline.
 """
 
 from __future__ import annotations
@@ -59,12 +64,15 @@ def parse():
     ap.add_argument('--blocks', type=int, default=23)
     ap.add_argument('--precision', default='auto', choices=['auto', 'mixed', 'bf16x3', 'bf16'],
                     help="auto = the engine's default policy (RRDBNet: residual dense blocks in one fp16 product, head / tail in three bf16 products)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure the kernel-only frame time, per-kernel rooflines, socket power, the compact c3 / c4 legs '
+                    'and the CPU baseline (a plain run prints the headline alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--cpu-crop', type=int, default=256)
     ap.add_argument('--halo', type=int, default=32)
-    ap.add_argument('--no-power', action='store_true', help='skip the socket-power leg (rocm-smi sampled by a child process started before the GPU is touched)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the compact c3 / c4 legs that the default one-GPU run appends under "secondary"')
-    ap.add_argument('--no-kernel-roofline', action='store_true', help='skip the per-kernel replays (profiling runs: keeps the launch mix that of plain forwards)')
+    ap.add_argument('--no-power', action='store_true', help='--full: skip the socket-power leg (rocm-smi sampled by a child process started before the GPU is touched)')
+    ap.add_argument('--no-secondary', action='store_true', help='--full: skip the compact c3 / c4 legs that the one-GPU run appends under "secondary"')
+    ap.add_argument('--no-kernel-roofline', action='store_true', help='--full: skip the per-kernel replays (profiling runs: keeps the launch mix that of plain forwards)')
     ap.add_argument('--dry-run', action='store_true', help='launcher / rendezvous check without a GPU: ranks meet over gloo, rank 0 prints a stub line')
     ap.add_argument('--io', default='f32', choices=['f32', 'u8'], help='tensors crossing the boundary: fp32 [N,C,H,W] in / out, or uint8 [N,H,W,C] images in / out '
                     '(the 8-bit path: /255 and clamp*255+round inside the first / last kernel; tiles cross xGMI as bytes)')
@@ -424,9 +432,10 @@ def secondary(args):
 
 
 def secondary_result(config: str, args, steps: int, warmup: int, compact: bool = False) -> dict:
-    """BASELINE configs[2] (c3) and configs[3] (c4) on ONE GPU, same JSON schema as the headline: roofline of the dominant kernel measured
-    live (the plan replayed launch by launch between HIP events), the layer-wise HBM fraction, and the CPU oracle beside it.
-    ``compact``: the object the DEFAULT run carries under ``secondary`` (value, ms_per_step, dtype, dominant-kernel roofline, and the
+    """BASELINE configs[2] (c3) and configs[3] (c4) on ONE GPU, same JSON schema as the headline: the layer-wise MFMA and HBM fractions
+    of the timed forwards and, with ``--full``, the roofline of the dominant kernel measured live (the plan replayed launch by launch
+    between HIP events) and the CPU oracle beside it.
+    ``compact``: the object a ``--full`` C2 run carries under ``secondary`` (value, ms_per_step, dtype, dominant-kernel roofline, and the
     max-abs difference against the CPU oracle on a crop of the same synthetic input)."""
     import resselt_amd
     from resselt_amd.engine import lib as L
@@ -461,7 +470,7 @@ def secondary_result(config: str, args, steps: int, warmup: int, compact: bool =
     kern_s = ev0.elapsed_time(ev1) / 1e3 / steps
     dumped = dump_outputs(args.dump_outputs, {'output': y}) if (args.dump_outputs and not compact) else None
     del y
-    classes = [] if args.no_kernel_roofline else kernel_classes(model, max(2, min(steps, 5)), x)
+    classes = kernel_classes(model, max(2, min(steps, 5)), x) if (args.full and not args.no_kernel_roofline) else []
     flop, hbm = cfg['flop_px'] * out_px, cfg['bytes_px'] * out_px
     res = {
         'metric': cfg['metric'], 'value': round(out_px / 1e6 / dt, 3), 'unit': 'output megapixels/s', 'n_gpus': 1, 'steps': steps, 'warmup': warmup,
@@ -516,7 +525,7 @@ def secondary_result(config: str, args, steps: int, warmup: int, compact: bool =
                          'sample': f'{"x".join(map(str, cshape))} crop of the synthetic input, oracle ({fwd.__module__}) fp32 on the CPU'}  # fmt: skip
         model._invalidate()
         return out
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cshape = (2, 3, 512, 512) if config == 'c3' else (1, 3, 128, 128)
         xc = synth.synth_input(cshape, seed=0)
         default_threads = torch.get_num_threads()
@@ -531,6 +540,113 @@ def secondary_result(config: str, args, steps: int, warmup: int, compact: bool =
         torch.set_num_threads(default_threads)
         res['cpu_baseline'] = {'value': round(yc.shape[0] * yc.shape[2] * yc.shape[3] / 1e6 / best, 4), 'unit': 'output megapixels/s', 'cores': 8, 'kind': 'port',
                                'sample': f'oracle ({fwd.__module__}) fp32 on a {"x".join(map(str, cshape))} sample of the workload, best of 2, {best:.2f} s, torch {torch.__version__} CPU'}  # fmt: skip
+    return res
+
+
+def full_legs(args, model, sd, xt, world: int, sampler) -> dict:
+    """``--full``, rank 0, after the timed steps: the objects the line carries beside the headline -- kernel-only time of one HxW frame
+    ``xt`` and the rooflines priced from it, the power leg, the compact C3 / C4 legs and the CPU baseline."""
+    H, W = args.height, args.width
+    # kernel-only time of the conv launches of one forward of ONE HxW frame, from HIP events on the launch stream
+    k0 = torch.cuda.Event(enable_timing=True)
+    k1 = torch.cuda.Event(enable_timing=True)
+    model(xt)
+    torch.cuda.synchronize()
+    k0.record()
+    for _ in range(args.steps):
+        model(xt)
+    k1.record()
+    torch.cuda.synchronize()
+    kern_s = k0.elapsed_time(k1) / 1e3 / args.steps
+    out_px = 16 * H * W
+    n_launch = model.launches_per_forward()
+    macs = model.macs_per_input_pixel()
+    if args.blocks == 23:
+        assert 2 * macs == FLOP_PER_OUT_PX * 16, macs  # cross-check with SURVEY.md 8d
+    flop = 2 * macs * H * W
+    achieved_tf = flop / kern_s / 1e12
+    achieved_gbs = HBM_B_PER_OUT_PX * out_px / kern_s / 1e9
+    layout_bytes = model.conv_bytes_per_forward()  # same layer-wise model, priced in this engine's split-plane/f32-map layouts
+    prec = model.resolved_precision()
+    if args.no_kernel_roofline:
+        classes = [{'kernel': 'all conv launches of one forward (per-kernel replays skipped)', 'launches': n_launch, 'avg_us': round(kern_s / n_launch * 1e6, 2),
+                    'ms_per_forward': round(kern_s * 1e3, 3), 'flop_per_launch': round(flop / n_launch), 'tflops': round(achieved_tf, 2)}]  # fmt: skip
+    else:
+        classes = kernel_classes(model, max(2, min(args.steps, 5)), xt)
+    priced = [c for c in classes if c['launches']]
+    dom = max(priced, key=lambda c: c['ms_per_forward'])
+    issued_tf = sum(c['tflops'] * c.get('products', 1) * c['ms_per_forward'] for c in priced) / max(1e-9, sum(c['ms_per_forward'] for c in priced))
+    traffic = measured_traffic(dom['kernel']) if (prec == 'mixed' and (H, W, args.blocks) == (1080, 1920, 23)) else {'bytes': None, 'note': 'PMC traffic is only collected for the default workload'}
+    # which roof the dominant kernel is nearer to: its algorithmic FLOP rate over the dense MFMA peak, or its algorithmic bytes (every
+    # operand once, in the layouts it reads and writes) per second over the HBM peak
+    dom_mfma, dom_hbm = dom['tflops'] / MFMA_PEAK_TFLOPS, dom.get('gbs', 0.0) / HBM_PEAK_GBS
+    dom_bound = 'hbm' if dom_hbm > dom_mfma else 'mfma'
+    res = {
+        # the DOMINANT kernel (largest share of the frame), timed live per launch with HIP events on the launch stream
+        'roofline': {
+            'bound': dom_bound,
+            'kernel': dom['kernel'],
+            'achieved': dom['gbs'] if dom_bound == 'hbm' else dom['tflops'],
+            'peak': HBM_PEAK_GBS if dom_bound == 'hbm' else MFMA_PEAK_TFLOPS,
+            'unit': 'GB/s' if dom_bound == 'hbm' else 'TFLOP/s',
+            'frac': round(max(dom_hbm, dom_mfma), 4),
+            'frac_mfma': round(dom_mfma, 4),
+            'frac_hbm': round(dom_hbm, 4),
+            'bytes_per_launch': dom.get('bytes_per_launch'),
+            'fused_bytes_per_launch': dom.get('fused_bytes_per_launch'),  # a fused launch: what it must move at least (common input once)
+            'traffic': traffic['bytes'],
+            'traffic_note': traffic['note'],
+            'avg_launch_us': dom['avg_us'],
+            'launches_per_forward': dom['launches'],
+            'flop_per_launch': dom['flop_per_launch'],
+            'mfma_issued_frac': round(dom['tflops'] * dom.get('products', 1) / MFMA_PEAK_TFLOPS, 4),
+            'share_of_frame': round(dom['ms_per_forward'] / (kern_s * 1e3), 3),
+        },
+        'roofline_kernels': classes,  # every kernel class of the forward, same definitions
+        'roofline_frame': {
+            'bound': 'mfma',
+            'achieved': round(achieved_tf, 2),
+            'peak': MFMA_PEAK_TFLOPS,
+            'unit': 'TFLOP/s',
+            'frac': round(achieved_tf / MFMA_PEAK_TFLOPS, 4),
+            'mfma_issued_frac': round(issued_tf / MFMA_PEAK_TFLOPS, 4),
+            'note': f'all {n_launch} launches of one forward: 2,240,856 algorithmic FLOP per output pixel / event time of the forward',
+        },
+        'roofline_hbm': {
+            'bound': 'hbm',
+            'achieved': round(achieved_gbs, 1),
+            'peak': HBM_PEAK_GBS,
+            'unit': 'GB/s',
+            'frac': round(achieved_gbs / HBM_PEAK_GBS, 4),
+            'model': 'layer-wise bf16 bytes, 7,790 B per output pixel (SURVEY.md 8d)',
+            'layout_bytes_per_launch': None if not layout_bytes else round(layout_bytes / n_launch),
+            'layout_achieved': None if not layout_bytes else round(layout_bytes / kern_s / 1e9, 1),
+            'layout_note': 'the same every-operand-once model priced in the engine layouts (split planes hi+lo = 4 B/channel where a layer reads or writes both halves, 2 B/channel for hi-only fp16 planes)',
+        },
+        'forward_ms_1080p': round(kern_s * 1e3, 3),
+    }
+    if sampler is not None:  # power leg: 3.5 s of back-to-back forwards, the last 2 s of samples
+        sampler.begin()
+        w0 = time.time()
+        while time.time() - w0 < 3.5:
+            model(xt)
+            torch.cuda.synchronize()
+        w1 = time.time()
+        res['power'] = sampler.stop(w1 - 2.0, w1)
+    res['roofline_kernels_note'] = ('the launch list of one forward replayed in order, one launch at a time, a HIP event between consecutive launches: '
+                                    f'sum of ms_per_forward = {sum(c["ms_per_forward"] for c in classes):.3f} ms (the replayed frame; forward_ms_1080p is the same list in one host call)')
+    if world == 1 and args.config == 'c2' and not args.no_secondary and (H, W, args.blocks) == (1080, 1920, 23):
+        # BASELINE configs[2] and [3] in the same process, after the headline (its buffers are released first): compact objects
+        model._invalidate()
+        torch.cuda.empty_cache()
+        res['secondary'] = {}
+        for name in ('c3', 'c4'):
+            t_sec = time.perf_counter()
+            res['secondary'][name] = secondary_result(name, args, steps=max(3, min(args.steps, 10)), warmup=3, compact=True)
+            res['secondary'][name]['leg_seconds'] = round(time.perf_counter() - t_sec, 1)
+            torch.cuda.empty_cache()
+    if world == 1 and not args.no_cpu_baseline:
+        res['cpu_baseline'] = cpu_baseline(sd, args.cpu_crop)
     return res
 
 
@@ -554,7 +670,7 @@ def main():
     # The power sampler is a child process started before the first GPU call.  Under a profiler the GPU is already initialised by the
     # preloaded tool library when this line runs, and a process that has touched the GPU must not start programs: no power leg then.
     profiled = any(k.startswith(('ROCPROF', 'ROCP_', 'ROCTRACER', 'RPD_')) for k in os.environ) or 'rocprof' in os.environ.get('LD_PRELOAD', '')
-    sampler = PowerSampler() if (world == 1 and not args.no_power and not profiled) else None
+    sampler = PowerSampler() if (args.full and world == 1 and not args.no_power and not profiled) else None
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs a GPU: the engine has no CPU path')
     # RSA_DIST_BACKEND=gloo rehearses the N > 1 code path with several ranks on ONE GPU (RCCL refuses two ranks per device)
@@ -650,27 +766,6 @@ def main():
     del y
 
     if rank == 0:
-        # kernel-only time of the conv launches of one forward of ONE HxW frame, from HIP events on the launch stream
-        k0 = torch.cuda.Event(enable_timing=True)
-        k1 = torch.cuda.Event(enable_timing=True)
-        xt = (x[:, :H, :W] if args.io == 'u8' else x[:, :, :H, :W]).contiguous()
-        model(xt)
-        torch.cuda.synchronize()
-        k0.record()
-        for _ in range(args.steps):
-            model(xt)
-        k1.record()
-        torch.cuda.synchronize()
-        kern_s = k0.elapsed_time(k1) / 1e3 / args.steps
-        out_px = 16 * H * W
-        n_launch = model.launches_per_forward()
-        macs = model.macs_per_input_pixel()
-        if args.blocks == 23:
-            assert 2 * macs == FLOP_PER_OUT_PX * 16, macs  # cross-check with SURVEY.md 8d
-        flop = 2 * macs * H * W
-        achieved_tf = flop / kern_s / 1e12
-        achieved_gbs = HBM_B_PER_OUT_PX * out_px / kern_s / 1e9
-        layout_bytes = model.conv_bytes_per_forward()  # same layer-wise model, priced in this engine's split-plane/f32-map layouts
         prec = model.resolved_precision()
         prec_note = {
             'mixed': 'residual-dense-block convolutions (92 % of the MACs) in ONE fp16 product on hi planes, conv_first / upsampling / HR / last '
@@ -678,19 +773,6 @@ def main():
             'bf16x3': 'bf16 MFMA operands split hi+lo (3 products), f32 accumulate',
             'bf16': 'plain bf16 MFMA operands, f32 accumulate',
         }[prec]  # fmt: skip
-        if args.no_kernel_roofline:
-            classes = [{'kernel': 'all conv launches of one forward (per-kernel replays skipped)', 'launches': n_launch, 'avg_us': round(kern_s / n_launch * 1e6, 2),
-                        'ms_per_forward': round(kern_s * 1e3, 3), 'flop_per_launch': round(flop / n_launch), 'tflops': round(achieved_tf, 2)}]  # fmt: skip
-        else:
-            classes = kernel_classes(model, max(2, min(args.steps, 5)), xt)
-        priced = [c for c in classes if c['launches']]
-        dom = max(priced, key=lambda c: c['ms_per_forward'])
-        issued_tf = sum(c['tflops'] * c.get('products', 1) * c['ms_per_forward'] for c in priced) / max(1e-9, sum(c['ms_per_forward'] for c in priced))
-        traffic = measured_traffic(dom['kernel']) if (prec == 'mixed' and (H, W, args.blocks) == (1080, 1920, 23)) else {'bytes': None, 'note': 'PMC traffic is only collected for the default workload'}
-        # which roof the dominant kernel is nearer to: its algorithmic FLOP rate over the dense MFMA peak, or its algorithmic bytes (every
-        # operand once, in the layouts it reads and writes) per second over the HBM peak
-        dom_mfma, dom_hbm = dom['tflops'] / MFMA_PEAK_TFLOPS, dom.get('gbs', 0.0) / HBM_PEAK_GBS
-        dom_bound = 'hbm' if dom_hbm > dom_mfma else 'mfma'
         tile_note = {
             'c2': (f'{rows}x{cols} full-width row bands of {H}x{W} (+{args.halo} rows of input halo), one per GPU; one asynchronous RCCL all-gather of '
                    + ('uint8 HWC output bands straight into the result image' if args.io == 'u8' else 'fp32 output tiles')) if world > 1 else 'single tile',
@@ -718,77 +800,16 @@ def main():
                 'precision_policy': prec_note,
                 'io': 'uint8 [N,H,W,C] images in and out' if args.io == 'u8' else 'fp32 [N,C,H,W] tensors in and out',
                 'tile_parallel': tile_note,
-                'launches_per_step': n_launch,
-            },
-            # the DOMINANT kernel (largest share of the frame), timed live per launch with HIP events on the launch stream
-            'roofline': {
-                'bound': dom_bound,
-                'kernel': dom['kernel'],
-                'achieved': dom['gbs'] if dom_bound == 'hbm' else dom['tflops'],
-                'peak': HBM_PEAK_GBS if dom_bound == 'hbm' else MFMA_PEAK_TFLOPS,
-                'unit': 'GB/s' if dom_bound == 'hbm' else 'TFLOP/s',
-                'frac': round(max(dom_hbm, dom_mfma), 4),
-                'frac_mfma': round(dom_mfma, 4),
-                'frac_hbm': round(dom_hbm, 4),
-                'bytes_per_launch': dom.get('bytes_per_launch'),
-                'fused_bytes_per_launch': dom.get('fused_bytes_per_launch'),  # a fused launch: what it must move at least (common input once)
-                'traffic': traffic['bytes'],
-                'traffic_note': traffic['note'],
-                'avg_launch_us': dom['avg_us'],
-                'launches_per_forward': dom['launches'],
-                'flop_per_launch': dom['flop_per_launch'],
-                'mfma_issued_frac': round(dom['tflops'] * dom.get('products', 1) / MFMA_PEAK_TFLOPS, 4),
-                'share_of_frame': round(dom['ms_per_forward'] / (kern_s * 1e3), 3),
-            },
-            'roofline_kernels': classes,  # every kernel class of the forward, same definitions
-            'roofline_frame': {
-                'bound': 'mfma',
-                'achieved': round(achieved_tf, 2),
-                'peak': MFMA_PEAK_TFLOPS,
-                'unit': 'TFLOP/s',
-                'frac': round(achieved_tf / MFMA_PEAK_TFLOPS, 4),
-                'mfma_issued_frac': round(issued_tf / MFMA_PEAK_TFLOPS, 4),
-                'note': f'all {n_launch} launches of one forward: 2,240,856 algorithmic FLOP per output pixel / event time of the forward',
-            },
-            'roofline_hbm': {
-                'bound': 'hbm',
-                'achieved': round(achieved_gbs, 1),
-                'peak': HBM_PEAK_GBS,
-                'unit': 'GB/s',
-                'frac': round(achieved_gbs / HBM_PEAK_GBS, 4),
-                'model': 'layer-wise bf16 bytes, 7,790 B per output pixel (SURVEY.md 8d)',
-                'layout_bytes_per_launch': None if not layout_bytes else round(layout_bytes / n_launch),
-                'layout_achieved': None if not layout_bytes else round(layout_bytes / kern_s / 1e9, 1),
-                'layout_note': 'the same every-operand-once model priced in the engine layouts (split planes hi+lo = 4 B/channel where a layer reads or writes both halves, 2 B/channel for hi-only fp16 planes)',
+                'launches_per_step': model.launches_per_forward(),
             },
             'ring_aborts': aborts,
             'event_ms_per_step': round(ev_ms / args.steps, 3),
-            'forward_ms_1080p': round(kern_s * 1e3, 3),
         }
         if dumped is not None:
             res['dump_outputs'] = dumped
-        if sampler is not None:  # power leg: 3.5 s of back-to-back forwards, the last 2 s of samples
-            sampler.begin()
-            w0 = time.time()
-            while time.time() - w0 < 3.5:
-                model(xt)
-                torch.cuda.synchronize()
-            w1 = time.time()
-            res['power'] = sampler.stop(w1 - 2.0, w1)
-        res['roofline_kernels_note'] = ('the launch list of one forward replayed in order, one launch at a time, a HIP event between consecutive launches: '
-                                        f'sum of ms_per_forward = {sum(c["ms_per_forward"] for c in classes):.3f} ms (the replayed frame; forward_ms_1080p is the same list in one host call)')
-        if world == 1 and args.config == 'c2' and not args.no_secondary and (H, W, args.blocks) == (1080, 1920, 23):
-            # BASELINE configs[2] and [3] in the same process, after the headline (its buffers are released first): compact objects
-            model._invalidate()
-            torch.cuda.empty_cache()
-            res['secondary'] = {}
-            for name in ('c3', 'c4'):
-                t_sec = time.perf_counter()
-                res['secondary'][name] = secondary_result(name, args, steps=max(3, min(args.steps, 10)), warmup=3, compact=True)
-                res['secondary'][name]['leg_seconds'] = round(time.perf_counter() - t_sec, 1)
-                torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
-            res['cpu_baseline'] = cpu_baseline(sd, args.cpu_crop)
+        if args.full:
+            xt = (x[:, :H, :W] if args.io == 'u8' else x[:, :, :H, :W]).contiguous()
+            res.update(full_legs(args, model, sd, xt, world, sampler))
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

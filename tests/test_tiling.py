@@ -339,3 +339,26 @@ def test_bench_power_sampler_matches_samples_by_wall_clock(tmp_path, monkeypatch
     none = bench.PowerSampler()
     assert none.proc is None and none.stop(0.0, time.time()) is None
     assert sys.executable
+
+
+def test_bench_plain_run_starts_no_power_sampler(monkeypatch):
+    """A plain `bench.py` run does only what its headline needs, so the power-sampler child (a `--full` leg) is not started; `--full`
+    starts it before the GPU is touched.  The GPU is hidden here: both runs stop at the GPU check, right after that decision."""
+    import importlib.util
+    import sys
+
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    started = []
+    monkeypatch.setattr(bench, 'PowerSampler', lambda: started.append(True))
+    monkeypatch.setattr(bench.torch.cuda, 'is_available', lambda: False)
+    for k in list(os.environ):
+        if k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK') or k.startswith(('ROCPROF', 'ROCP_', 'ROCTRACER', 'RPD_')):
+            monkeypatch.delenv(k)
+    for flags, want in (([], []), (['--full'], [True])):
+        started.clear()
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '1', *flags])
+        with pytest.raises(SystemExit, match='needs a GPU'):
+            bench.main()
+        assert started == want, flags

@@ -1,6 +1,6 @@
 #!/bin/bash
 # runs on the GPU box: samples socket power / clocks (rocm-smi) while a command runs in the background -> gpurun_out/$1
-# usage: tools/power_trace.sh OUT.txt python3 bench.py --steps 40 --warmup 2 --no-cpu-baseline --no-kernel-roofline
+# usage: tools/power_trace.sh OUT.txt python3 bench.py --full --steps 40 --warmup 2 --no-cpu-baseline --no-kernel-roofline
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/${1:-power_trace.txt}; shift
 {

@@ -26,7 +26,7 @@ def agg(db):
 def main():
     o1, n1, d1 = agg(sys.argv[1])
     o2, _, d2 = agg(sys.argv[2])
-    lines = ['# rocprofv3 --pmc, two separate passes over `python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline` (3 forwards), FINAL build, MI355X',
+    lines = ['# rocprofv3 --pmc, two separate passes over `python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline` (3 forwards), FINAL build, MI355X',
              '# per kernel family, summed over its launches.  clock = GRBM_GUI_ACTIVE / 8 XCDs / duration (pass 2);',
              '# MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / (duration * clock) (pass 1)']  # fmt: skip
     for fam in sorted(o1):

@@ -855,6 +855,63 @@ typedef struct rsa_cugan_output_params {
 } rsa_cugan_output_params;
 int rsa_cugan_output(const rsa_cugan_output_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- MoSR ops
+ * (reference archs/mosr/arch.py and archs/mosrv2/arch.py; resselt_amd/csrc/mosr.hip) */
+
+/* The middle step of the MoSR / MoSRv2 gated block (mosr/arch.py:99-105, mosrv2/arch.py:174-210, 272-278):
+ *   out = mish(g) * cat(x[0 : i_planes), seg_0(x), seg_1(x), ...)
+ * on split planes.  Output plane p multiplies plane p of g with plane p of the concatenation; the concatenation's planes are read from x in
+ * the same order (passthrough planes first, then each segment's planes), so out, g and x each have i_planes + sum(seg[s].planes) planes.
+ * A segment is a depthwise convolution of its own planes, zero padding (kh/2, kw/2) as nn.Conv2d(..., groups=C): 1 x 1 = identity (no
+ * weights; weight / bias ignored), k x k for k in {3, 5, 7, 9, 11}, and the bands 1 x k and k x 1 for the same k.  Any other shape:
+ * RSA_E_UNSUPPORTED.  weight f32 [planes*8][kh*kw] (row-major taps), bias f32 [planes*8].  fmt: enum rsa_plane_fmt of every plane operand. */
+typedef struct rsa_gated_dwconv_segment {
+  int32_t planes;            /* 8 channels each, >= 1 */
+  int32_t kh, kw;
+  int32_t reserved0;         /* must be 0 */
+  const float* weight;
+  const float* bias;
+} rsa_gated_dwconv_segment;
+
+typedef struct rsa_gated_dwconv_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t fmt;
+  int32_t i_planes;          /* passthrough planes, >= 0 */
+  int32_t n_segments;        /* 0..4 */
+  rsa_gated_dwconv_segment seg[4];
+  const void* g_hi;
+  const void* g_lo;          /* may be NULL */
+  int64_t g_plane_stride;    /* 16-byte units */
+  int64_t g_batch_stride;
+  const void* x_hi;
+  const void* x_lo;          /* may be NULL */
+  int64_t x_plane_stride;
+  int64_t x_batch_stride;
+  void* out_hi;
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_gated_dwconv_params;
+int rsa_gated_dwconv(const rsa_gated_dwconv_params* p, void* stream);
+
+/* The image shortcut of MoSRv2 (mosrv2/arch.py:297, 328-337):  out[n][c][Y][X] += bilinear(xp, scale)[n][c][Y][X]  (align_corners=False)
+ * for Y < out_h, X < out_w, where xp is the input x [N][C][h][w] reflect-padded at the bottom / right to pad_h x pad_w (pad_h < 2h,
+ * pad_w < 2w; the pad is applied on the fly) and bilinear samples xp at ((Y + 0.5) / scale - 0.5, (X + 0.5) / scale - 0.5), clamped to
+ * [0, pad - 1].  out is [N][C][out_H][out_W] with out_h <= out_H, out_w <= out_W; x and out share `dtype` (RSA_F32 / RSA_F16 / RSA_BF16). */
+typedef struct rsa_bilinear_add_params {
+  int32_t batch, C;
+  int32_t h, w;              /* input */
+  int32_t pad_h, pad_w;      /* reflect-padded input size */
+  int32_t scale;             /* 1..8 */
+  int32_t dtype;
+  int32_t out_H, out_W;      /* output tensor */
+  int32_t out_h, out_w;      /* region written */
+  const void* x;
+  void* out;
+} rsa_bilinear_add_params;
+int rsa_bilinear_add(const rsa_bilinear_add_params* p, void* stream);
+
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255
  *   rsa_nchw_to_image_u8   float [N][C][H][W] -> uint8 [N][H][W][C], round-half-even(clamp(v, 0, 1) * 255)  (torch: (y.clamp(0,1)*255).round())

@@ -612,6 +612,66 @@ class CuganOutputParams(C.Structure):
     ]
 
 
+class GatedDwConvSegment(C.Structure):
+    """Mirror of ``struct rsa_gated_dwconv_segment``."""
+
+    _fields_ = [
+        ('planes', C.c_int32),
+        ('kh', C.c_int32),
+        ('kw', C.c_int32),
+        ('reserved0', C.c_int32),
+        ('weight', C.c_void_p),
+        ('bias', C.c_void_p),
+    ]
+
+
+class GatedDwConvParams(C.Structure):
+    """Mirror of ``struct rsa_gated_dwconv_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('H', C.c_int32),
+        ('W', C.c_int32),
+        ('fmt', C.c_int32),
+        ('i_planes', C.c_int32),
+        ('n_segments', C.c_int32),
+        ('seg', GatedDwConvSegment * 4),
+        ('g_hi', C.c_void_p),
+        ('g_lo', C.c_void_p),
+        ('g_plane_stride', C.c_int64),
+        ('g_batch_stride', C.c_int64),
+        ('x_hi', C.c_void_p),
+        ('x_lo', C.c_void_p),
+        ('x_plane_stride', C.c_int64),
+        ('x_batch_stride', C.c_int64),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+    ]
+
+
+class BilinearAddParams(C.Structure):
+    """Mirror of ``struct rsa_bilinear_add_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('C', C.c_int32),
+        ('h', C.c_int32),
+        ('w', C.c_int32),
+        ('pad_h', C.c_int32),
+        ('pad_w', C.c_int32),
+        ('scale', C.c_int32),
+        ('dtype', C.c_int32),
+        ('out_H', C.c_int32),
+        ('out_W', C.c_int32),
+        ('out_h', C.c_int32),
+        ('out_w', C.c_int32),
+        ('x', C.c_void_p),
+        ('out', C.c_void_p),
+    ]
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -669,6 +729,8 @@ EXPORTS = (
     'rsa_region_se',
     'rsa_cugan_input',
     'rsa_cugan_output',
+    'rsa_gated_dwconv',
+    'rsa_bilinear_add',
 )
 
 
@@ -819,7 +881,8 @@ def load() -> C.CDLL:
     lib.rsa_region_se_workspace_bytes.argtypes = [C.c_int32] * 3
     lib.rsa_region_se_workspace_bytes.restype = C.c_int64
     for name, struct in (('rsa_deconv', ResampleConvParams), ('rsa_conv_s2', ResampleConvParams), ('rsa_region_se', RegionSEParams),
-                         ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams)):  # fmt: skip
+                         ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams), ('rsa_gated_dwconv', GatedDwConvParams),
+                         ('rsa_bilinear_add', BilinearAddParams)):  # fmt: skip
         getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
         getattr(lib, name).restype = C.c_int
     _lib = lib

@@ -702,3 +702,119 @@ def cugan_state_dict(variant='2x', pro=False, seed=0):
             raise ValueError('UpCunet2x_fast has no pro form')
         sd['pro'] = torch.zeros(1)
     return sd
+
+
+def _dwconv(sd, name, c, kh, kw, seed):
+    sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (c, 1, kh, kw), kh * kw, seed)
+    sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), kh * kw, seed)
+
+
+def _mosr_trunk(sd, first: int, n_block: int, dim: int, seed) -> None:
+    """The three convolutions after the gated blocks (mosr/arch.py:126, mosrv2/arch.py:307-313)."""
+    t = first + n_block
+    _conv(sd, f'gblocks.{t}', 2 * dim, dim, 3, seed)
+    _conv(sd, f'gblocks.{t + 2}', dim, 2 * dim, 3, seed)
+    _conv(sd, f'gblocks.{t + 4}', dim, dim, 1, seed)
+
+
+def mosr_state_dict(in_ch=3, out_ch=3, upscale=4, n_block=24, dim=64, upsampler='ps', kernel_size=7, expansion_ratio=1.5, conv_ratio=1.0, seed=0):
+    """Keys of the reference MoSR module (archs/mosr/arch.py:108-156): 'ps', 'dys' or 'gps' head."""
+    sd: OrderedDict = OrderedDict()
+    if upsampler == 'ps':
+        out_ch = in_ch
+    hidden = int(expansion_ratio * dim)
+    cc = int(conv_ratio * dim)
+    _conv(sd, 'gblocks.0', dim, in_ch, 3, seed)
+    for i in range(1, n_block + 1):
+        b = f'gblocks.{i}'
+        sd[f'{b}.norm.weight'] = 1.0 + synth_tensor(f'{b}.norm.weight', (dim,), 16, seed)
+        sd[f'{b}.norm.bias'] = synth_tensor(f'{b}.norm.bias', (dim,), 16, seed)
+        _conv(sd, f'{b}.fc1', 2 * hidden, dim, 3, seed)
+        _dwconv(sd, f'{b}.conv', cc, kernel_size, kernel_size, seed)
+        _conv(sd, f'{b}.fc2', dim, hidden, 3, seed)
+    _mosr_trunk(sd, 1, n_block, dim, seed)
+    _conv(sd, 'shortcut.block.0', dim, in_ch, 3, seed)
+    _conv(sd, 'shortcut.block.2', dim, dim, 3, seed)
+    _conv(sd, 'shortcut.conv11', dim, in_ch, 1, seed)
+    if upsampler == 'ps':
+        _conv(sd, 'upsampler.0', out_ch * upscale * upscale, dim, 3, seed)
+    elif upsampler == 'dys':
+        oc = 8 * upscale * upscale
+        _conv(sd, 'upsampler.end_conv', out_ch, dim, 1, seed)
+        _conv(sd, 'upsampler.offset', oc, dim, 1, seed, scale=0.5)
+        _conv(sd, 'upsampler.scope', oc, dim, 1, seed, bias=False)
+        h = torch.arange((-upscale + 1) / 2, (upscale - 1) / 2 + 1) / upscale
+        sd['upsampler.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+    elif upsampler == 'gps':
+        _conv(sd, 'upsampler.in_to_k', upscale * upscale * out_ch * 8, dim, 3, seed)
+    else:
+        raise ValueError(f'unknown MoSR upsampler {upsampler!r}')
+    return sd
+
+
+MOSRV2_SAMPLE_MODS = ('conv', 'pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample')
+
+
+def mosrv2_state_dict(in_ch=3, scale=4, n_block=24, dim=64, upsampler='pixelshuffledirect', expansion_ratio=1.5, mid_dim=32, unshuffle_mod=True,
+                      rms_norm=False, seed=0):  # fmt: skip
+    """Keys of the reference MoSRv2 module (archs/mosrv2/arch.py:281-337), ``to_img.MetaUpsample`` included."""
+    sd: OrderedDict = OrderedDict()
+    s_int = scale
+    if unshuffle_mod and scale < 3:
+        u = 4 // scale
+        _conv(sd, 'gblocks.1', dim, in_ch * u * u, 3, seed)
+        first, s_int = 2, 4
+    else:
+        _conv(sd, 'gblocks.0', dim, in_ch, 3, seed)
+        first = 1
+    hidden = int(expansion_ratio * dim)
+    gc = int(dim * 0.125)
+    for i in range(first, first + n_block):
+        b = f'gblocks.{i}'
+        if rms_norm:
+            sd[f'{b}.norm.scale'] = 1.0 + synth_tensor(f'{b}.norm.scale', (dim, 1, 1), 16, seed)
+            sd[f'{b}.norm.offset'] = synth_tensor(f'{b}.norm.offset', (dim, 1, 1), 16, seed)
+        else:
+            sd[f'{b}.norm.weight'] = 1.0 + synth_tensor(f'{b}.norm.weight', (dim,), 16, seed)
+            sd[f'{b}.norm.bias'] = synth_tensor(f'{b}.norm.bias', (dim,), 16, seed)
+        _conv(sd, f'{b}.fc1', 2 * hidden, dim, 3, seed)
+        _dwconv(sd, f'{b}.conv.dwconv_hw', gc, 3, 3, seed)
+        _dwconv(sd, f'{b}.conv.dwconv_w', gc, 1, 11, seed)
+        _dwconv(sd, f'{b}.conv.dwconv_h', gc, 11, 1, seed)
+        _conv(sd, f'{b}.fc2', dim, hidden, 3, seed)
+        sd[f'{b}.gamma'] = 1.0 + synth_tensor(f'{b}.gamma', (1, dim, 1, 1), 16, seed)
+    _mosr_trunk(sd, first, n_block, dim, seed)
+    up, s = upsampler, s_int
+    if s == 1 or up == 'conv':
+        _conv(sd, 'to_img.0', in_ch, dim, 3, seed)
+    elif up == 'pixelshuffledirect':
+        _conv(sd, 'to_img.0', in_ch * s * s, dim, 3, seed)
+    elif up == 'pixelshuffle':
+        _conv(sd, 'to_img.0', mid_dim, dim, 3, seed)
+        i = 2
+        for r in [2] * (s.bit_length() - 1) if s & (s - 1) == 0 else [3]:
+            _conv(sd, f'to_img.{i}', r * r * mid_dim, mid_dim, 3, seed)
+            i += 2
+        _conv(sd, f'to_img.{i}', in_ch, mid_dim, 3, seed)
+    elif up == 'nearest+conv':
+        i = 0
+        for _ in range(s.bit_length() - 1 if s & (s - 1) == 0 else 1):
+            _conv(sd, f'to_img.{i}', dim, dim, 3, seed)
+            i += 3
+        _conv(sd, f'to_img.{i}', dim, dim, 3, seed)
+        _conv(sd, f'to_img.{i + 2}', in_ch, dim, 3, seed)
+    elif up == 'dysample':
+        i, dys_dim = 0, dim
+        if mid_dim != dim:
+            _conv(sd, 'to_img.0', mid_dim, dim, 3, seed)
+            i, dys_dim = 2, mid_dim
+        oc = 8 * s * s
+        _conv(sd, f'to_img.{i}.end_conv', in_ch, dys_dim, 1, seed)
+        _conv(sd, f'to_img.{i}.offset', oc, dys_dim, 1, seed, scale=0.5)
+        _conv(sd, f'to_img.{i}.scope', oc, dys_dim, 1, seed, bias=False)
+        h = torch.arange((-s + 1) / 2, (s - 1) / 2 + 1) / s
+        sd[f'to_img.{i}.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+    else:
+        raise ValueError(f'unknown MoSRv2 upsampler {up!r}')
+    sd['to_img.MetaUpsample'] = torch.tensor([2, MOSRV2_SAMPLE_MODS.index(up), s, dim, in_ch, mid_dim, 4], dtype=torch.uint8)
+    return sd

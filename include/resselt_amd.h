@@ -912,6 +912,75 @@ typedef struct rsa_bilinear_add_params {
 } rsa_bilinear_add_params;
 int rsa_bilinear_add(const rsa_bilinear_add_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- RGT ops
+ * (reference archs/rgt/arch.py, RG_SA :500-544 and Block :608-619; resselt_amd/csrc/rgt.hip) */
+
+/* Cross-attention of every token of a full-resolution map against a small per-image key / value set (RG_SA :534-542):
+ *   out[n][head][i] = softmax_j( q[n][head][i] . k[n][head][j] ) v[n][head][j]     over ALL j < nkeys, no mask, no bias
+ * The scale is folded into the q weights by the host.  Maps use the head-padded layout: head h owns planes [4h, 4h+4) (32 channels) of
+ * q, k, v and out; channels past dim_qk (q, k) and dim_v (v) must be zero.  Key / value token j is unit j of its planes (a row-major
+ * h' x w' map).  products 3: bf16 hi+lo, three products per contraction; products 1: hi only, fmt = RSA_PF_BF16 or RSA_PF_F16 (the
+ * one-product fp16 form, v_mfma_f32_32x32x16_f16, probabilities rounded to fp16).  q, k, v and out share the format. */
+#define RSA_RG_MAX_KEYS 3969 /* 63 x 63: the eval recursion count of RG_SA keeps H / 4^t and W / 4^t below 64 */
+typedef struct rsa_rg_attn_params {
+  int32_t batch;
+  int32_t H, W;              /* query / output map */
+  int32_t heads;
+  int32_t nkeys;             /* 1..RSA_RG_MAX_KEYS tokens per image */
+  int32_t dim_qk, dim_v;     /* per-head widths, 1..32 (RSA_E_UNSUPPORTED otherwise) */
+  int32_t products;          /* 1 or 3 */
+  int32_t fmt;               /* enum rsa_plane_fmt */
+  int32_t reserved0;         /* must be 0 */
+  const void* q_hi;
+  const void* q_lo;          /* NULL allowed with products == 1 (also k_lo, v_lo) */
+  int64_t q_plane_stride;    /* 16-byte units, >= H*W */
+  int64_t q_batch_stride;
+  const void* k_hi;
+  const void* k_lo;
+  int64_t k_plane_stride;    /* >= nkeys */
+  int64_t k_batch_stride;
+  const void* v_hi;
+  const void* v_lo;
+  int64_t v_plane_stride;    /* >= nkeys */
+  int64_t v_batch_stride;
+  void* out_hi;
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;  /* >= H*W */
+  int64_t out_batch_stride;
+} rsa_rg_attn_params;
+int rsa_rg_attention(const rsa_rg_attn_params* p, void* stream);
+
+/* RG_SA's recursion (:512-523): the depthwise 4x4 stride-4 convolution `reduction1` (weights and bias) applied `times` times, each step
+ * with its own bias as in the reference, in one launch.  The output is (H >> 2t) x (W >> 2t): every step floors, so rows / columns past
+ * 4^t * (H >> 2t) are never read.  weight f32 [planes*8][16] (row-major taps), bias f32 [planes*8].  Input and output planes share fmt;
+ * lo pointers may be NULL.  RSA_E_ARG when the map reduces to nothing. */
+typedef struct rsa_rg_reduce_params {
+  int32_t batch;
+  int32_t H, W;              /* input map */
+  int32_t planes;            /* 8 channels each */
+  int32_t times;             /* 1..6 */
+  int32_t fmt;               /* enum rsa_plane_fmt */
+  const void* in_hi;
+  const void* in_lo;
+  int64_t in_plane_stride;
+  int64_t in_batch_stride;
+  const float* weight;
+  const float* bias;
+  void* out_hi;
+  void* out_lo;
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_rg_reduce_params;
+int rsa_rg_reduce(const rsa_rg_reduce_params* p, void* stream);
+
+/* GELU(LayerNorm(x)) over the C channels of an f32 NCHW4c map into split planes (RG_SA's norm_act, :494).  Same descriptor as
+ * rsa_layernorm; out_hi is required, out_f32 must be NULL.  One thread per pixel: meant for the pooled map of RG_SA. */
+int rsa_layernorm_gelu(const rsa_layernorm_params* p, void* stream);
+
+/* out += gamma[c] * res over f32 NCHW4c maps [N][ceil(C/4)][H][W][4] (the HAI term of RGT's Block, :619).  gamma f32[round_up(C, 4)],
+ * zero-padded; all pointers 16-byte aligned. */
+int rsa_scale_add(const float* res, const float* gamma, float* out, int32_t batch, int32_t H, int32_t W, int32_t C, void* stream);
+
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255
  *   rsa_nchw_to_image_u8   float [N][C][H][W] -> uint8 [N][H][W][C], round-half-even(clamp(v, 0, 1) * 255)  (torch: (y.clamp(0,1)*255).round())

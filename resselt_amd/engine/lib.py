@@ -672,6 +672,62 @@ class BilinearAddParams(C.Structure):
     ]
 
 
+class RgAttnParams(C.Structure):
+    """Mirror of ``struct rsa_rg_attn_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('H', C.c_int32),
+        ('W', C.c_int32),
+        ('heads', C.c_int32),
+        ('nkeys', C.c_int32),
+        ('dim_qk', C.c_int32),
+        ('dim_v', C.c_int32),
+        ('products', C.c_int32),
+        ('fmt', C.c_int32),
+        ('reserved0', C.c_int32),
+        ('q_hi', C.c_void_p),
+        ('q_lo', C.c_void_p),
+        ('q_plane_stride', C.c_int64),
+        ('q_batch_stride', C.c_int64),
+        ('k_hi', C.c_void_p),
+        ('k_lo', C.c_void_p),
+        ('k_plane_stride', C.c_int64),
+        ('k_batch_stride', C.c_int64),
+        ('v_hi', C.c_void_p),
+        ('v_lo', C.c_void_p),
+        ('v_plane_stride', C.c_int64),
+        ('v_batch_stride', C.c_int64),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+    ]
+
+
+class RgReduceParams(C.Structure):
+    """Mirror of ``struct rsa_rg_reduce_params``."""
+
+    _fields_ = [
+        ('batch', C.c_int32),
+        ('H', C.c_int32),
+        ('W', C.c_int32),
+        ('planes', C.c_int32),
+        ('times', C.c_int32),
+        ('fmt', C.c_int32),
+        ('in_hi', C.c_void_p),
+        ('in_lo', C.c_void_p),
+        ('in_plane_stride', C.c_int64),
+        ('in_batch_stride', C.c_int64),
+        ('weight', C.c_void_p),
+        ('bias', C.c_void_p),
+        ('out_hi', C.c_void_p),
+        ('out_lo', C.c_void_p),
+        ('out_plane_stride', C.c_int64),
+        ('out_batch_stride', C.c_int64),
+    ]
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -731,6 +787,10 @@ EXPORTS = (
     'rsa_cugan_output',
     'rsa_gated_dwconv',
     'rsa_bilinear_add',
+    'rsa_rg_attention',
+    'rsa_rg_reduce',
+    'rsa_layernorm_gelu',
+    'rsa_scale_add',
 )
 
 
@@ -882,9 +942,12 @@ def load() -> C.CDLL:
     lib.rsa_region_se_workspace_bytes.restype = C.c_int64
     for name, struct in (('rsa_deconv', ResampleConvParams), ('rsa_conv_s2', ResampleConvParams), ('rsa_region_se', RegionSEParams),
                          ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams), ('rsa_gated_dwconv', GatedDwConvParams),
-                         ('rsa_bilinear_add', BilinearAddParams)):  # fmt: skip
+                         ('rsa_bilinear_add', BilinearAddParams), ('rsa_rg_attention', RgAttnParams), ('rsa_rg_reduce', RgReduceParams),
+                         ('rsa_layernorm_gelu', LayerNormParams)):  # fmt: skip
         getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
         getattr(lib, name).restype = C.c_int
+    lib.rsa_scale_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.rsa_scale_add.restype = C.c_int
     _lib = lib
     return lib
 

@@ -818,3 +818,102 @@ def mosrv2_state_dict(in_ch=3, scale=4, n_block=24, dim=64, upsampler='pixelshuf
         raise ValueError(f'unknown MoSRv2 upsampler {up!r}')
     sd['to_img.MetaUpsample'] = torch.tensor([2, MOSRV2_SAMPLE_MODS.index(up), s, dim, in_ch, mid_dim, 4], dtype=torch.uint8)
     return sd
+
+
+def rgt_state_dict(in_chans=3, embed_dim=48, split_size=(2, 4), depth=(2,), num_heads=(4,), mlp_ratio=2.0, qkv_bias=True, upscale=2, resi='1conv',
+                   c_ratio=0.5, img_size=64, seed=0):  # fmt: skip
+    """Keys (parameters AND buffers) of the reference RGT module (archs/rgt/arch.py:630-838).
+
+    Every term is made visible: the HAI ``gamma`` is of order 0.1-1 (not the 1e-4 init), LayerNorm affines and the position-bias MLPs are
+    non-trivial, and ``reduction1`` is about 1/16 per tap so that t repeats of it neither vanish nor blow up.
+    """
+    sd: OrderedDict = OrderedDict()
+    C = embed_dim
+    hidden = int(C * mlp_ratio)
+    cr = int(C * c_ratio)
+    split_size = list(split_size)
+    shift_size = [split_size[0] // 2, split_size[1] // 2]
+
+    def lin(name, cout, cin, bias=True):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (cout, cin), cin, seed)
+        if bias:
+            sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (cout,), cin, seed)
+
+    def ln(name, c):
+        sd[f'{name}.weight'] = 1.0 + synth_tensor(f'{name}.weight', (c,), 16, seed)
+        sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), 16, seed)
+
+    def dw(name, c, k=3, scale=1.0):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (c, 1, k, k), k * k, seed, scale)
+        sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), k * k, seed, scale)
+
+    def resi_conv(name):
+        if resi == '1conv':
+            _conv(sd, name, C, C, 3, seed)
+        else:
+            _conv(sd, f'{name}.0', C // 4, C, 3, seed)
+            _conv(sd, f'{name}.2', C // 4, C // 4, 1, seed)
+            _conv(sd, f'{name}.4', C, C // 4, 3, seed)
+
+    def window_branch(name, idx, heads):
+        hs, ws = dat_geometry(split_size, idx)
+        bh, bw = torch.arange(1 - hs, hs), torch.arange(1 - ws, ws)
+        sd[f'{name}.rpe_biases'] = torch.stack(torch.meshgrid([bh, bw], indexing='ij')).flatten(1).transpose(0, 1).contiguous().float()
+        coords = torch.stack(torch.meshgrid([torch.arange(hs), torch.arange(ws)], indexing='ij')).flatten(1)
+        rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0).contiguous()
+        rel[:, :, 0] += hs - 1
+        rel[:, :, 1] += ws - 1
+        rel[:, :, 0] *= 2 * ws - 1
+        sd[f'{name}.relative_position_index'] = rel.sum(-1)
+        pos_dim = ((C // 2) // 4) // 4  # WindowAttention(dim // 2) -> DynamicPosBias(dim // 4) -> pos_dim = dim // 4 (arch.py:103, 164)
+        lin(f'{name}.pos.pos_proj', pos_dim, 2)
+        for k, cout in (('pos1', pos_dim), ('pos2', pos_dim), ('pos3', heads)):
+            sd[f'{name}.pos.{k}.0.weight'] = 1.0 + synth_tensor(f'{name}.pos.{k}.0.weight', (pos_dim,), 16, seed)
+            sd[f'{name}.pos.{k}.0.bias'] = synth_tensor(f'{name}.pos.{k}.0.bias', (pos_dim,), 16, seed)
+            lin(f'{name}.pos.{k}.2', cout, pos_dim)
+
+    _conv(sd, 'conv_first', C, in_chans, 3, seed)
+    ln('before_RG.1', C)
+    for i, d in enumerate(depth):
+        heads = num_heads[i]
+        for j in range(d):
+            b = f'layers.{i}.blocks.{j}'
+            ln(f'{b}.norm1', C)
+            if j % 2 == 0:  # L_SA
+                lin(f'{b}.attn.qkv', 3 * C, C, qkv_bias)
+                lin(f'{b}.attn.proj', C, C)
+                for idx in (0, 1):
+                    window_branch(f'{b}.attn.attns.{idx}', idx, heads // 2)
+                if dat_shifted(i, j):
+                    m0, m1 = dat_shift_masks(img_size, img_size, split_size, shift_size)
+                    sd[f'{b}.attn.attn_mask_0'] = m0
+                    sd[f'{b}.attn.attn_mask_1'] = m1
+                dw(f'{b}.attn.get_v', C)
+            else:  # RG_SA
+                sd[f'{b}.attn.reduction1.weight'] = (1.0 + 8.0 * synth_tensor(f'{b}.attn.reduction1.weight', (C, 1, 4, 4), 16, seed)) / 16.0
+                sd[f'{b}.attn.reduction1.bias'] = synth_tensor(f'{b}.attn.reduction1.bias', (C,), 16, seed, 0.5)
+                dw(f'{b}.attn.dwconv', C)
+                _conv(sd, f'{b}.attn.conv', cr, C, 1, seed)
+                ln(f'{b}.attn.norm_act.0', cr)
+                lin(f'{b}.attn.q', cr, C, qkv_bias)
+                lin(f'{b}.attn.k', cr, cr, qkv_bias)
+                lin(f'{b}.attn.v', C, cr, qkv_bias)
+                dw(f'{b}.attn.cpe', C)
+                lin(f'{b}.attn.proj', C, C)
+            lin(f'{b}.mlp.fc1', hidden, C)
+            ln(f'{b}.mlp.sg.norm', hidden // 2)
+            dw(f'{b}.mlp.sg.conv', hidden // 2)
+            lin(f'{b}.mlp.fc2', C, hidden // 2)
+            ln(f'{b}.norm2', C)
+            sd[f'{b}.gamma'] = 0.55 + synth_tensor(f'{b}.gamma', (C,), 1, seed, 0.45)
+        resi_conv(f'layers.{i}.conv')
+    ln('norm', C)
+    resi_conv('conv_after_body')
+    _conv(sd, 'conv_before_upsample.0', 64, C, 3, seed)
+    if upscale == 3:
+        _conv(sd, 'upsample.0', 9 * 64, 64, 3, seed)
+    else:
+        for u in range({1: 0, 2: 1, 4: 2, 8: 3}[upscale]):
+            _conv(sd, f'upsample.{2 * u}', 4 * 64, 64, 3, seed)
+    _conv(sd, 'conv_last', in_chans, 64, 3, seed)
+    return sd

@@ -57,6 +57,13 @@ def main():
             (1, 3, 512, 512), torch.bfloat16, None, None),
         # DRCT x4 at its published size (embed 180, 6 dense groups, 6 heads, window 16, gc 32, mlp 2)
         'drct_x4_bf16_512': (synth.drct_state_dict(num_layers=6, upscale=4), (1, 3, 512, 512), torch.bfloat16, None, None),
+        # RGT / RGT-S x4 from the paper (embed 180, 8 / 6 groups x 6 blocks, 6 heads, mlp 2, split 8x32, c_ratio 0.5); 512^2 = 1,024 pooled keys
+        'rgt_x4_bf16_512': (
+            synth.rgt_state_dict(embed_dim=180, depth=(6,) * 8, num_heads=(6,) * 8, split_size=(8, 32), mlp_ratio=2.0, upscale=4, c_ratio=0.5),
+            (1, 3, 512, 512), torch.bfloat16, None, None),
+        'rgt_s_x4_bf16_512': (
+            synth.rgt_state_dict(embed_dim=180, depth=(6,) * 6, num_heads=(6,) * 6, split_size=(8, 32), mlp_ratio=2.0, upscale=4, c_ratio=0.5),
+            (1, 3, 512, 512), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
         # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
         'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),

@@ -745,7 +745,7 @@ int rsa_ea_gate(const rsa_ea_gate_params* p, void* stream);
  *   output  rsa_deconv: out_h = (in_h - 1) * stride - 2 pad + ksize (likewise out_w); rsa_conv_s2: out_h = in_h / 2 (floor)
  *           written at (out_y0 + y, out_x0 + x) of a grid with row length out_W: split planes (out_hi, optional out_lo) and / or an f32 map
  *           out_f32 [N][ceil(cout/4)][out_H][out_W][4] of the same grid; channels past cout are written as zero
- *   epilogue v = acc + bias[c]; act (RSA_ACT_NONE or RSA_ACT_LRELU with slope act_param); + the residual window (res_hi / res_lo at
+ *   epilogue v = acc + bias[c]; act (RSA_ACT_NONE, RSA_ACT_LRELU with slope act_param, or for rsa_deconv RSA_ACT_GELU); + the residual window (res_hi / res_lo at
  *           (res_y0 + y, res_x0 + x), row length res_W) when res_hi != NULL
  *   w_packed rsa_resample_packed_weight_bytes bytes: [phase][K step][cout tile][hi|lo][lane 64][8]; see resselt_amd/engine/cugan.py.
  * fmt RSA_PF_BF16 with products == 3 or RSA_PF_F16 with products == 1, like rsa_plk_conv.  cin_planes <= 32, cout <= 128. */
@@ -762,7 +762,7 @@ typedef struct rsa_resample_conv_params {
   int64_t in_batch_stride;
   int32_t in_W;             /* row length of the input grid */
   int32_t in_y0, in_x0, in_h, in_w;
-  int32_t act;              /* RSA_ACT_NONE or RSA_ACT_LRELU */
+  int32_t act;              /* RSA_ACT_NONE or RSA_ACT_LRELU; rsa_deconv also RSA_ACT_GELU (erf GELU, FDAT's x4 transpose+conv head) */
   float act_param;
   int32_t reserved0;        /* must be 0 */
   const void* w_packed;
@@ -980,6 +980,117 @@ int rsa_layernorm_gelu(const rsa_layernorm_params* p, void* stream);
 /* out += gamma[c] * res over f32 NCHW4c maps [N][ceil(C/4)][H][W][4] (the HAI term of RGT's Block, :619).  gamma f32[round_up(C, 4)],
  * zero-padded; all pointers 16-byte aligned. */
 int rsa_scale_add(const float* res, const float* gamma, float* out, int32_t batch, int32_t H, int32_t W, int32_t C, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------- FDAT ops
+ * (reference archs/fdat/arch.py, SimplifiedAIM :521-548, SimplifiedDATBlock :574-607, LDA_AQU :135-279, PA :282-288; csrc/fdat.hip) */
+
+/* The AIM interaction of an FDAT block, the residual add and norm2, in one pass over the C-wide stream:
+ *   mode 0 (spatial block):  f = a * cm[n][ch] + c                       (channel_modulates_spatial, cm = the channel gate of c)
+ *   mode 1 (channel block):  f = a + c * sigmoid(sum_ch w[ch] * a[ch])   (spatial_modulates_channel)
+ *   x_out = x + f  (f32 NCHW4c; x_out may equal x);  out = LayerNorm(x + f) with gamma, beta, eps (centred form) as split planes.
+ * a (the attention's proj output) and c (GELU(dwconv(n1))) are split planes [N][ceil(C/8)][H][W][8] of format fmt; lo pointers may be
+ * NULL.  out_hi NULL: only x_out is written.  x NULL (out_hi NULL too): x_out = f, the interaction alone -- the unfused path's first
+ * pass, followed by rsa_scale_add (x += f) and rsa_layernorm.  Tail channels of out are written as zero.
+ * C 1..256.  A pixel's channels belong to one workgroup (mode 1's dot product needs all of them before the gate). */
+typedef struct rsa_fdat_interact_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t C;                 /* 1..256 */
+  int32_t mode;              /* 0 or 1 */
+  int32_t fmt;               /* enum rsa_plane_fmt of a, c and out */
+  const void* a_hi;
+  const void* a_lo;
+  int64_t a_plane_stride;    /* 16-byte units, >= H*W */
+  int64_t a_batch_stride;
+  const void* c_hi;
+  const void* c_lo;
+  int64_t c_plane_stride;
+  int64_t c_batch_stride;
+  const float* cm;           /* mode 0: [batch][8 * ceil(C/8)] (the layout of rsa_channel_gate's gate) */
+  const float* w;            /* mode 1: [C] */
+  const float* x;            /* f32 NCHW4c [N][ceil(C/4)][H][W][4]; NULL: x_out = f */
+  float* x_out;              /* may equal x */
+  const float* gamma;        /* [C], with out_hi */
+  const float* beta;
+  float eps;
+  int32_t reserved0;         /* must be 0 */
+  void* out_hi;              /* may be NULL */
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_fdat_interact_params;
+int rsa_fdat_interact(const rsa_fdat_interact_params* p, void* stream);
+
+/* PA of FDAT's pa_up head followed by its LeakyReLU:  out = lrelu(x * sigmoid(logit), slope), unit by unit over `planes` planes.
+ * logit is the 1x1 convolution PA.conv (bias included) written as planes.  x, logit and out share strides and the plane format; lo
+ * pointers may be NULL; out may equal x. */
+int rsa_pa_gate(const void* x_hi, const void* x_lo, const void* logit_hi, const void* logit_lo, int64_t plane_stride, int64_t batch_stride,
+                int32_t batch, int32_t H, int32_t W, int32_t planes, float slope, int32_t fmt, void* out_hi, void* out_lo, void* stream);
+
+/* LDA_AQU (reference :135-279) at the output resolution Hout x Wout, in two kernels around one rsa_conv2d:
+ *   rsa_lda_offsets    per output pixel: q_hr = bilinear(q, align_corners=True) of the H x W map q (`hidden` channels), its depthwise
+ *                      3x3 (zero padding at Hout x Wout, no bias; weight [gc][9] shared by the groups), LayerNorm over each group's gc =
+ *                      hidden / groups channels (gamma, beta [gc], eps) and SiLU, as split planes of `hidden` channels
+ *   (rsa_conv2d)       the offset convolution gc -> 2 * 9 per group as one 3x3 launch with block-diagonal weights, into an f32 map
+ *   rsa_lda_attention  per output pixel and group g: nine sample points (i, j) + tanh(o) * range + base (channel order (kh kw d), d = 0
+ *                      = y), mapped to the H x W maps as the reference does: y_lr = (i + dy) * (H - 1) / (Hout - 1), likewise x; bilinear
+ *                      gathers with zeros outside of group g's channels of k (+ rpb[tap][ch]) and of v; scores scale * q_hr . k summed over
+ *                      ALL groups (one head), a softmax over the nine taps, and out[g * C/groups + c] = sum_tap p_tap * v_g,tap[c].
+ * groups must be 2; hidden 2..64 and even; C (v and out channels) a multiple of 16 up to 256; Hout, Wout >= 2. */
+typedef struct rsa_lda_offsets_params {
+  int32_t batch;
+  int32_t H, W;              /* q map */
+  int32_t Hout, Wout;
+  int32_t hidden;
+  int32_t groups;            /* 2 */
+  int32_t fmt;               /* enum rsa_plane_fmt of q and out */
+  const void* q_hi;
+  const void* q_lo;          /* may be NULL */
+  int64_t q_plane_stride;
+  int64_t q_batch_stride;
+  const float* dw_weight;    /* [hidden / groups][9] */
+  const float* gamma;        /* [hidden / groups] */
+  const float* beta;
+  float eps;
+  int32_t reserved0;         /* must be 0 */
+  void* out_hi;              /* Hout x Wout planes of `hidden` channels */
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_lda_offsets_params;
+int rsa_lda_offsets(const rsa_lda_offsets_params* p, void* stream);
+
+typedef struct rsa_lda_attn_params {
+  int32_t batch;
+  int32_t H, W;              /* q, k, v maps */
+  int32_t Hout, Wout;
+  int32_t hidden;            /* q / k channels */
+  int32_t C;                 /* v / out channels */
+  int32_t groups;            /* 2 */
+  int32_t fmt;               /* enum rsa_plane_fmt of q, k, v and out */
+  float range;               /* offset range factor (11) */
+  float scale;               /* hidden ** -0.5 */
+  int32_t reserved0;         /* must be 0 */
+  const void* q_hi;
+  const void* q_lo;
+  int64_t q_plane_stride;
+  int64_t q_batch_stride;
+  const void* k_hi;
+  const void* k_lo;
+  int64_t k_plane_stride;
+  int64_t k_batch_stride;
+  const void* v_hi;
+  const void* v_lo;
+  int64_t v_plane_stride;
+  int64_t v_batch_stride;
+  const float* offset;       /* f32 NCHW4c [N][ceil(18 * groups / 4)][Hout][Wout][4]: group g = channels [18 g, 18 g + 18) */
+  const float* rpb;          /* [9][hidden] relative_position_bias_table */
+  void* out_hi;              /* Hout x Wout planes of C channels */
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_lda_attn_params;
+int rsa_lda_attention(const rsa_lda_attn_params* p, void* stream);
 
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255

@@ -16,7 +16,6 @@ the optional mid_dim conv + LeakyReLU 0.01).  ``self.short`` -- bilinear upsampl
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 
@@ -26,38 +25,8 @@ from ...engine import ops, plk
 from ...engine.base import Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16
+from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes, pack_head  # noqa: F401  (SAMPLE_MODS, head_layers: re-exported)
 from ..mosr.arch import _check_dims, _conv_weights, _GatedBase
-
-SAMPLE_MODS = ('conv', 'pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample')
-
-
-def head_layers(upsample: str, scale: int, in_dim: int, out_dim: int, mid_dim: int):
-    """UniUpsample's layers with parameters: [(index, cout, cin, k)], and the DySample sub-module's index (or None)."""
-    if scale == 1 or upsample == 'conv':
-        return [(0, out_dim, in_dim, 3)], None
-    if upsample == 'pixelshuffledirect':
-        return [(0, out_dim * scale * scale, in_dim, 3)], None
-    pow2 = scale & (scale - 1) == 0
-    if upsample in ('pixelshuffle', 'nearest+conv') and not pow2 and scale != 3:
-        raise ValueError(f'scale {scale} is not supported. Supported scales: 2^n and 3.')
-    if upsample == 'pixelshuffle':
-        layers, i = [(0, mid_dim, in_dim, 3)], 2
-        for r in [2] * int(math.log2(scale)) if pow2 else [3]:
-            layers.append((i, r * r * mid_dim, mid_dim, 3))
-            i += 2
-        return layers + [(i, out_dim, mid_dim, 3)], None
-    if upsample == 'nearest+conv':
-        layers, i = [], 0
-        for _ in range(int(math.log2(scale)) if pow2 else 1):
-            layers.append((i, in_dim, in_dim, 3))
-            i += 3
-        return layers + [(i, in_dim, in_dim, 3), (i + 2, out_dim, in_dim, 3)], None
-    if upsample == 'dysample':
-        if mid_dim != in_dim:
-            return [(0, mid_dim, in_dim, 3)], 2
-        return [], 0
-    raise ValueError(f'An invalid Upsample was selected. Please choose one of {SAMPLE_MODS}')
-
 
 class MoSRv2(_GatedBase):
     def __init__(self, in_ch: int = 3, scale: int = 4, n_block: int = 24, dim: int = 64, upsampler: str = 'pixelshuffledirect', expansion_ratio: float = 1.5,
@@ -100,22 +69,9 @@ class MoSRv2(_GatedBase):
         for k, (co, ci, ks) in ((t, (2 * dim, dim, 3)), (t + 2, (dim, 2 * dim, 3)), (t + 4, (dim, dim, 1))):
             shapes[f'gblocks.{k}.weight'] = (co, ci, ks, ks)
             shapes[f'gblocks.{k}.bias'] = (co,)
-        for i, co, ci, k in self.layers:
-            shapes[f'to_img.{i}.weight'] = (co, ci, k, k)
-            shapes[f'to_img.{i}.bias'] = (co,)
         meta = torch.tensor([2, SAMPLE_MODS.index(upsampler), self.s_int, dim, in_ch, mid_dim, 4], dtype=torch.uint8)
         buffers = {'to_img.MetaUpsample': meta}
-        if self.dys_index is not None:
-            d, s = f'to_img.{self.dys_index}', self.s_int
-            dys_dim = mid_dim if self.dys_index else dim
-            if dys_dim <= 4 or dys_dim % 4:
-                raise ValueError('Incorrect in_channels and groups values.')
-            shapes[f'{d}.end_conv.weight'] = (in_ch, dys_dim, 1, 1)
-            shapes[f'{d}.end_conv.bias'] = (in_ch,)
-            shapes[f'{d}.offset.weight'] = (8 * s * s, dys_dim, 1, 1)
-            shapes[f'{d}.offset.bias'] = (8 * s * s,)
-            shapes[f'{d}.scope.weight'] = (8 * s * s, dys_dim, 1, 1)
-            buffers[f'{d}.init_pos'] = dys.dysample_init_pos(s, 4)
+        head_shapes(shapes, buffers, 'to_img', self.layers, self.dys_index, self.s_int, dim, in_ch, mid_dim)
         build_param_tree(self, shapes, buffers)
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -146,16 +102,7 @@ class MoSRv2(_GatedBase):
         last = self._trunk_tail(W, sd, self.first, products, device)
         W['tail2'] = cw(sd[f'gblocks.{last}.weight'], sd[f'gblocks.{last}.bias'])
         W['zeros'] = torch.zeros(dim, dtype=torch.float32, device=device)
-        for j, (i, co, ci, k) in enumerate(self.layers):
-            w, b = sd[f'to_img.{i}.weight'], sd[f'to_img.{i}.bias']
-            if self.head == 'nearest+conv' and self.s_int == 3 and j == 0:
-                # conv -> Upsample(3): every output channel 9 times, stored through depth-to-space (channel 9c + k -> sub-pixel k of c)
-                w, b = w.repeat_interleave(9, 0), b.repeat_interleave(9, 0)
-            W[f'head{j}'] = cw(w, b)
-        if self.dys_index is not None:
-            d = f'to_img.{self.dys_index}'
-            dys.pack(W, sd[f'{d}.offset.weight'], sd[f'{d}.offset.bias'], sd[f'{d}.scope.weight'], sd[f'{d}.end_conv.weight'].reshape(self.in_ch, -1),
-                     sd[f'{d}.end_conv.bias'], sd[f'{d}.init_pos'], 4, self.s_int, products=products, device=device)  # fmt: skip
+        pack_head(W, sd, 'to_img', self.head, self.s_int, self.layers, self.dys_index, self.in_ch, products, device)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -217,59 +164,5 @@ class MoSRv2(_GatedBase):
         plan.launch('rsa_bilinear_add', bp)
         return set_input
 
-    def _emit_head(self, plan: Plan, W, fe, fe32, y, n, H, Wd, with_lo):  # noqa: C901
-        up, s, layers = self.head, self.s_int, self.layers
-        if s == 1 or up in ('conv', 'pixelshuffledirect'):
-            plan.conv(ops.conv_params(W['head0'], fe, H, Wd, out_nchw=y, pixel_shuffle=1 if up == 'conv' or s == 1 else s))
-            return
-        if up == 'dysample':
-            x, x32 = fe, fe32
-            if self.dys_index == 2:
-                mid = self.mid_dim
-                x = plan.planes(n, mid // 8, H, Wd, with_lo)
-                x32 = plan.f32map(n, mid, H, Wd) if dys.needs_f32_input(W) else None
-                plan.conv(ops.conv_params(W['head0'], fe, H, Wd, act=L.ACT_LRELU, act_param=0.01, out=x, out_f32=x32))
-            dys.emit(plan, W, x, y, x32)
-            return
-        if up == 'pixelshuffle':
-            mid = self.mid_dim
-            t = plan.planes(n, mid // 8, H, Wd, with_lo)
-            plan.conv(ops.conv_params(W['head0'], fe, H, Wd, act=L.ACT_LRELU, act_param=0.01, out=t))
-            hh, ww = H, Wd
-            for j in range(1, len(layers) - 1):
-                r = math.isqrt(layers[j][1] // mid)
-                shuffled = torch.empty((n, mid, hh * r, ww * r), dtype=torch.float32, device=plan.device)
-                plan.keep.append(shuffled)
-                plan.conv(ops.conv_params(W[f'head{j}'], t, hh, ww, out_nchw=shuffled, pixel_shuffle=r))
-                hh, ww = hh * r, ww * r
-                t = plan.planes(n, mid // 8, hh, ww, with_lo)
-                plan.call(lambda src=shuffled, dst=t: ops.nchw_to_planes(src, dst))
-                plan.count_launches(1)
-            plan.conv(ops.conv_params(W[f'head{len(layers) - 1}'], t, hh, ww, out_nchw=y))
-            return
-        # nearest+conv: conv -> Upsample -> LeakyReLU(0.2) per stage (the activation commutes with the nearest upsampling)
-        dim, pd = self.dim, self.dim // 8
-        t, hh, ww = fe, H, Wd
-        stages = len(layers) - 2
-        if s == 3:
-            shuffled = torch.empty((n, dim, 3 * H, 3 * Wd), dtype=torch.float32, device=plan.device)
-            plan.keep.append(shuffled)
-            plan.conv(ops.conv_params(W['head0'], fe, H, Wd, act=L.ACT_LRELU, act_param=0.2, out_nchw=shuffled, pixel_shuffle=3))
-            hh, ww = 3 * H, 3 * Wd
-            t = plan.planes(n, pd, hh, ww, with_lo)
-            plan.call(lambda src=shuffled, dst=t: ops.nchw_to_planes(src, dst))
-            plan.count_launches(1)
-            upsampled = False
-        else:
-            upsampled = False
-            for j in range(stages):
-                o = plan.planes(n, pd, hh * 2 if upsampled else hh, ww * 2 if upsampled else ww, with_lo)
-                if upsampled:
-                    hh, ww = hh * 2, ww * 2
-                plan.conv(ops.conv_params(W[f'head{j}'], t, hh, ww, upsample2x=upsampled, act=L.ACT_LRELU, act_param=0.2, out=o))
-                t, upsampled = o, True
-        if upsampled:
-            hh, ww = hh * 2, ww * 2
-        o = plan.planes(n, pd, hh, ww, with_lo)
-        plan.conv(ops.conv_params(W[f'head{stages}'], t, hh, ww, upsample2x=upsampled, act=L.ACT_LRELU, act_param=0.2, out=o))
-        plan.conv(ops.conv_params(W[f'head{stages + 1}'], o, hh, ww, out_nchw=y))
+    def _emit_head(self, plan: Plan, W, fe, fe32, y, n, H, Wd, with_lo):
+        emit_head(plan, W, self.head, self.s_int, self.layers, self.dim, self.mid_dim, self.dys_index, fe, fe32, y, n, H, Wd, with_lo)

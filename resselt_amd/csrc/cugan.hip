@@ -29,7 +29,7 @@ struct rs_rows {
   static constexpr int value = CT >= 8 ? 2 : 4;  // 8 cout tiles: 64 accumulator VGPRs per row in three products
 };
 
-template <int FMT, int PROD, int CT, bool TRANS>
+template <int FMT, int PROD, int CT, bool TRANS, bool GELU = false>
 __global__ __launch_bounds__(256) void resample_conv_kernel(const rsa_resample_conv_params p, int smax) {
   constexpr int ROWS = rs_rows<CT>::value;
   constexpr int HL = PROD == 3 ? 2 : 1;
@@ -114,7 +114,10 @@ __global__ __launch_bounds__(256) void resample_conv_kernel(const rsa_resample_c
       const int oy = TRANS ? s * (qy0 + r) + ry - p.pad : qy0 + r;
       if (oy < 0 || oy >= out_h) continue;
       f32x4 v = acc[r][c] + b;
-      if (p.act == RSA_ACT_LRELU) {
+      if constexpr (GELU) {  // a separate instantiation: the LeakyReLU / linear kernels keep their code
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = gelu_fast(v[j]);
+      } else if (p.act == RSA_ACT_LRELU) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * p.act_param;
       }
@@ -146,7 +149,7 @@ static int rs_smax(int ksize, int stride, bool trans, int cin_planes) {
   return (t * t * cin_planes + 3) / 4;
 }
 
-template <int FMT, int PROD, bool TRANS>
+template <int FMT, int PROD, bool TRANS, bool GELU = false>
 static int rs_launch(const rsa_resample_conv_params& p, hipStream_t stream) {
   const int s = p.stride, K = p.ksize;
   const int out_h = TRANS ? (p.in_h - 1) * s - 2 * p.pad + K : p.in_h / 2;
@@ -158,7 +161,7 @@ static int rs_launch(const rsa_resample_conv_params& p, hipStream_t stream) {
   {                                                                                                                     \
     constexpr int rows = rs_rows<CT_>::value;                                                                           \
     const dim3 grid((qw + 15) / 16 * nphase, (qh + 4 * rows - 1) / (4 * rows), p.batch);                                \
-    resample_conv_kernel<FMT, PROD, CT_, TRANS><<<grid, 256, 0, stream>>>(p, smax);                                     \
+    resample_conv_kernel<FMT, PROD, CT_, TRANS, GELU><<<grid, 256, 0, stream>>>(p, smax);                               \
   }
   if (ct <= 1)
     RS_GO(1)
@@ -194,7 +197,8 @@ static int rs_validate(const rsa_resample_conv_params* p, bool trans, const char
   if (p->out_hi && p->out_plane_stride < (int64_t)p->out_H * p->out_W) return set_error(RSA_E_ARG, "resample conv: bad output plane stride");
   if (p->res_hi && (p->res_y0 < 0 || p->res_x0 < 0 || p->res_x0 + out_w > p->res_W || p->res_plane_stride < (int64_t)(p->res_y0 + out_h) * p->res_W))
     return set_error(RSA_E_ARG, "resample conv: the residual window leaves its planes");
-  if (p->act != RSA_ACT_NONE && p->act != RSA_ACT_LRELU) return set_error(RSA_E_UNSUPPORTED, "resample conv: act must be none or LeakyReLU");
+  if (p->act != RSA_ACT_NONE && p->act != RSA_ACT_LRELU && !(trans && p->act == RSA_ACT_GELU))
+    return set_error(RSA_E_UNSUPPORTED, "resample conv: act must be none or LeakyReLU (rsa_deconv: or GELU)");
   if (!p->in_hi || !p->w_packed || !p->bias || (!p->out_hi && !p->out_f32) || (p->products == 3 && !p->in_lo) || (p->res_lo && !p->res_hi) ||
       (p->out_lo && !p->out_hi))
     return set_error(RSA_E_ARG, "resample conv: null operand");
@@ -394,6 +398,8 @@ extern "C" int rsa_deconv(const rsa_resample_conv_params* p, void* stream) {
   const int e = rs_validate(p, true, "deconv");
   if (e) return e;
   hipStream_t s = (hipStream_t)stream;
+  if (p->act == RSA_ACT_GELU)
+    return p->fmt == RSA_PF_BF16 ? rs_launch<RSA_PF_BF16, 3, true, true>(*p, s) : rs_launch<RSA_PF_F16, 1, true, true>(*p, s);
   return p->fmt == RSA_PF_BF16 ? rs_launch<RSA_PF_BF16, 3, true>(*p, s) : rs_launch<RSA_PF_F16, 1, true>(*p, s);
 }
 

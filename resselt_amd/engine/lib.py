@@ -728,6 +728,49 @@ class RgReduceParams(C.Structure):
     ]
 
 
+def _plane_fields(prefix: str) -> list:
+    return [(f'{prefix}_hi', C.c_void_p), (f'{prefix}_lo', C.c_void_p), (f'{prefix}_plane_stride', C.c_int64), (f'{prefix}_batch_stride', C.c_int64)]
+
+
+class FdatInteractParams(C.Structure):
+    """Mirror of ``struct rsa_fdat_interact_params``."""
+
+    _fields_ = (
+        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('mode', C.c_int32), ('fmt', C.c_int32)]
+        + _plane_fields('a')
+        + _plane_fields('c')
+        + [('cm', C.c_void_p), ('w', C.c_void_p), ('x', C.c_void_p), ('x_out', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p)]
+        + [('eps', C.c_float), ('reserved0', C.c_int32)]
+        + _plane_fields('out')
+    )
+
+
+class LdaOffsetsParams(C.Structure):
+    """Mirror of ``struct rsa_lda_offsets_params``."""
+
+    _fields_ = (
+        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Hout', C.c_int32), ('Wout', C.c_int32), ('hidden', C.c_int32)]
+        + [('groups', C.c_int32), ('fmt', C.c_int32)]
+        + _plane_fields('q')
+        + [('dw_weight', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('eps', C.c_float), ('reserved0', C.c_int32)]
+        + _plane_fields('out')
+    )
+
+
+class LdaAttnParams(C.Structure):
+    """Mirror of ``struct rsa_lda_attn_params``."""
+
+    _fields_ = (
+        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Hout', C.c_int32), ('Wout', C.c_int32), ('hidden', C.c_int32)]
+        + [('C', C.c_int32), ('groups', C.c_int32), ('fmt', C.c_int32), ('range', C.c_float), ('scale', C.c_float), ('reserved0', C.c_int32)]
+        + _plane_fields('q')
+        + _plane_fields('k')
+        + _plane_fields('v')
+        + [('offset', C.c_void_p), ('rpb', C.c_void_p)]
+        + _plane_fields('out')
+    )
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -791,6 +834,10 @@ EXPORTS = (
     'rsa_rg_reduce',
     'rsa_layernorm_gelu',
     'rsa_scale_add',
+    'rsa_fdat_interact',
+    'rsa_pa_gate',
+    'rsa_lda_offsets',
+    'rsa_lda_attention',
 )
 
 
@@ -943,11 +990,14 @@ def load() -> C.CDLL:
     for name, struct in (('rsa_deconv', ResampleConvParams), ('rsa_conv_s2', ResampleConvParams), ('rsa_region_se', RegionSEParams),
                          ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams), ('rsa_gated_dwconv', GatedDwConvParams),
                          ('rsa_bilinear_add', BilinearAddParams), ('rsa_rg_attention', RgAttnParams), ('rsa_rg_reduce', RgReduceParams),
-                         ('rsa_layernorm_gelu', LayerNormParams)):  # fmt: skip
+                         ('rsa_layernorm_gelu', LayerNormParams), ('rsa_fdat_interact', FdatInteractParams), ('rsa_lda_offsets', LdaOffsetsParams),
+                         ('rsa_lda_attention', LdaAttnParams)):  # fmt: skip
         getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
         getattr(lib, name).restype = C.c_int
     lib.rsa_scale_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.rsa_scale_add.restype = C.c_int
+    lib.rsa_pa_gate.argtypes = [C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsa_pa_gate.restype = C.c_int
     _lib = lib
     return lib
 

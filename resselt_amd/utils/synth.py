@@ -917,3 +917,123 @@ def rgt_state_dict(in_chans=3, embed_dim=48, split_size=(2, 4), depth=(2,), num_
             _conv(sd, f'upsample.{2 * u}', 4 * 64, 64, 3, seed)
     _conv(sd, 'conv_last', in_chans, 64, 3, seed)
     return sd
+
+
+FDAT_SAMPLE_MODS = ('conv', 'pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample', 'transpose+conv', 'lda', 'pa_up')
+
+
+def fdat_state_dict(num_in_ch=3, num_out_ch=3, scale=4, embed_dim=48, num_groups=1, depth_per_group=1, num_heads=4, window_size=4,
+                    ffn_expansion_ratio=2.0, aim_reduction_ratio=8, mid_dim=32, upsampler_type='transpose+conv', unshuffle_mod=False, seed=0):  # fmt: skip
+    """Keys of the reference FDAT module (archs/fdat/arch.py:632-735), ``upsampler.MetaUpsample`` included (LDA's ``base_offset`` is not
+    persistent).  The window bias, the channel-attention temperature, the AIM gates and the LDA offsets are of visible size; the LDA offset
+    convolution is scaled so that tanh(o) * 11 spans a few pixels without saturating."""
+    sd: OrderedDict = OrderedDict()
+    C = embed_dim
+    hidden = int(C * ffn_expansion_ratio)
+    red = C // aim_reduction_ratio
+    s = scale
+    if unshuffle_mod and scale < 3:
+        u = 4 // scale
+        _conv(sd, 'conv_first.1', C, num_in_ch * u * u, 3, seed)
+        s = 4
+    else:
+        _conv(sd, 'conv_first', C, num_in_ch, 3, seed)
+
+    def t(name, shape, fan_in, scale_=1.0):
+        sd[name] = synth_tensor(name, shape, fan_in, seed, scale_)
+
+    for g in range(num_groups):
+        for j in range(2 * depth_per_group):
+            b = f'groups.{g}.blocks.{j}'
+            for nrm in ('n1', 'n2'):
+                sd[f'{b}.{nrm}.weight'] = 1.0 + synth_tensor(f'{b}.{nrm}.weight', (C,), 16, seed)
+                t(f'{b}.{nrm}.bias', (C,), 16)
+            if j % 2 == 0:
+                t(f'{b}.attn.bias', (num_heads, window_size**2, window_size**2), 4)
+            else:
+                sd[f'{b}.attn.temp'] = 1.0 + synth_tensor(f'{b}.attn.temp', (num_heads, 1, 1), 4, seed)
+            t(f'{b}.attn.qkv.weight', (3 * C, C), C)
+            t(f'{b}.attn.proj.weight', (C, C), C)
+            t(f'{b}.attn.proj.bias', (C,), C)
+            t(f'{b}.conv.0.weight', (C, 1, 3, 3), 9)
+            t(f'{b}.inter.sg.0.weight', (1, C, 1, 1), C)
+            t(f'{b}.inter.cg.1.weight', (red, C, 1, 1), C, 2.0)
+            t(f'{b}.inter.cg.3.weight', (C, red, 1, 1), red, 2.0)
+            t(f'{b}.ffn.fc1.weight', (hidden, C), C)
+            t(f'{b}.ffn.fc2.weight', (C, hidden), hidden)
+            t(f'{b}.ffn.smix.weight', (hidden, 1, 3, 3), 9)
+        t(f'groups.{g}.conv.weight', (C, C, 3, 3), 9 * C)
+    t('conv_after.weight', (C, C, 3, 3), 9 * C)
+    up, out, mid = upsampler_type, num_out_ch, mid_dim
+    sd['upsampler.MetaUpsample'] = torch.tensor([3, FDAT_SAMPLE_MODS.index(up), s, C, out, mid, 4], dtype=torch.uint8)
+    pow2 = s & (s - 1) == 0
+    if s == 1 or up == 'conv':
+        _conv(sd, 'upsampler.0', out, C, 3, seed)
+    elif up == 'pixelshuffledirect':
+        _conv(sd, 'upsampler.0', out * s * s, C, 3, seed)
+    elif up == 'pixelshuffle':
+        _conv(sd, 'upsampler.0', mid, C, 3, seed)
+        i = 2
+        for r in [2] * (s.bit_length() - 1) if pow2 else [3]:
+            _conv(sd, f'upsampler.{i}', r * r * mid, mid, 3, seed)
+            i += 2
+        _conv(sd, f'upsampler.{i}', out, mid, 3, seed)
+    elif up == 'nearest+conv':
+        i = 0
+        for _ in range(s.bit_length() - 1 if pow2 else 1):
+            _conv(sd, f'upsampler.{i}', C, C, 3, seed)
+            i += 3
+        _conv(sd, f'upsampler.{i}', C, C, 3, seed)
+        _conv(sd, f'upsampler.{i + 2}', out, C, 3, seed)
+    elif up == 'dysample':
+        i, dys_dim = 0, C
+        if mid != C:
+            _conv(sd, 'upsampler.0', mid, C, 3, seed)
+            i, dys_dim = 2, mid
+        oc = 8 * s * s
+        _conv(sd, f'upsampler.{i}.end_conv', out, dys_dim, 1, seed)
+        _conv(sd, f'upsampler.{i}.offset', oc, dys_dim, 1, seed, scale=0.5)
+        _conv(sd, f'upsampler.{i}.scope', oc, dys_dim, 1, seed, bias=False)
+        h = torch.arange((-s + 1) / 2, (s - 1) / 2 + 1) / s
+        sd[f'upsampler.{i}.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+    elif up == 'transpose+conv':
+        def deconv(name, cin, cout, k):
+            t(f'{name}.weight', (cin, cout, k, k), cin * k * k // 4)
+            t(f'{name}.bias', (cout,), cin)
+
+        if s == 2:
+            deconv('upsampler.0', C, out, 4)
+        elif s == 3:
+            deconv('upsampler.0', C, out, 3)
+        else:
+            deconv('upsampler.0', C, C, 4)
+            deconv('upsampler.2', C, out, 4)
+        _conv(sd, f'upsampler.{1 if s < 4 else 3}', out, out, 3, seed)
+    elif up == 'lda':
+        i = 0
+        if mid != C:
+            _conv(sd, 'upsampler.0', mid, C, 3, seed)
+            i = 2
+        u = f'upsampler.{i}'
+        hid, gc = mid // 4, mid // 8
+        t(f'{u}.relative_position_bias_table', (1, 1, 1, 9, hid), 4, 0.5)
+        t(f'{u}.proj_q.weight', (hid, mid, 1, 1), mid, 2.0)
+        t(f'{u}.proj_k.weight', (hid, mid, 1, 1), mid, 2.0)
+        t(f'{u}.conv_offset.0.weight', (gc, 1, 3, 3), 9)
+        sd[f'{u}.conv_offset.1.weight'] = 1.0 + synth_tensor(f'{u}.conv_offset.1.weight', (gc,), 16, seed)
+        t(f'{u}.conv_offset.1.bias', (gc,), 16)
+        _conv(sd, f'{u}.conv_offset.3', 18, gc, 3, seed, scale=0.3)
+        sd[f'{u}.layer_norm.weight'] = 1.0 + synth_tensor(f'{u}.layer_norm.weight', (mid,), 16, seed)
+        t(f'{u}.layer_norm.bias', (mid,), 16)
+        _conv(sd, f'upsampler.{i + 1}', out, mid, 3, seed)
+    elif up == 'pa_up':
+        i, cin = 0, C
+        for _ in range(s.bit_length() - 1 if pow2 else 1):
+            _conv(sd, f'upsampler.{i + 1}', mid, cin, 3, seed)
+            _conv(sd, f'upsampler.{i + 2}.conv.0', mid, mid, 1, seed)
+            _conv(sd, f'upsampler.{i + 4}', mid, mid, 3, seed)
+            i, cin = i + 6, mid
+        _conv(sd, f'upsampler.{i}', out, mid, 3, seed)
+    else:
+        raise ValueError(f'unknown FDAT upsampler {up!r}')
+    return sd

@@ -64,6 +64,12 @@ def main():
         'rgt_s_x4_bf16_512': (
             synth.rgt_state_dict(embed_dim=180, depth=(6,) * 6, num_heads=(6,) * 6, split_size=(8, 32), mlp_ratio=2.0, upscale=4, c_ratio=0.5),
             (1, 3, 512, 512), torch.bfloat16, None, None),
+        # FDAT x4 with the reference constructor's defaults (embed 120, 4 groups x 3 x [spatial, channel], 4 heads, window 8, ffn 2, AIM 8,
+        # transpose+conv), and the same trunk with the lda head (mid 64), whose two kernels run at the 2048^2 output resolution
+        'fdat_x4_bf16_512': (synth.fdat_state_dict(embed_dim=120, num_groups=4, depth_per_group=3, num_heads=4, window_size=8, mid_dim=64, scale=4),
+                             (1, 3, 512, 512), torch.bfloat16, None, None),
+        'fdat_x4_lda_bf16_512': (synth.fdat_state_dict(embed_dim=120, num_groups=4, depth_per_group=3, num_heads=4, window_size=8, mid_dim=64, scale=4,
+                                                       upsampler_type='lda'), (1, 3, 512, 512), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
         # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
         'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),

@@ -562,7 +562,9 @@ typedef struct rsa_channel_gate_params {
   float* workspace;
   float* gate;               /* [batch][C] */
   int32_t relu;              /* 0 = GELU hidden, sigmoid gate (DAT); 1 = ReLU, sigmoid (the RCAN-style channel attention of HAT's CAB,
-                                archs/hat/arch.py:28-35); 2 = ReLU, Hardsigmoid (RTMoSR's CSELayer, archs/rtmosr/arch.py:7-22) */
+                                archs/hat/arch.py:28-35); 2 = ReLU, Hardsigmoid (RTMoSR's CSELayer, archs/rtmosr/arch.py:7-22);
+                                3 = SiLU, sigmoid (OmniSR's MBConv squeeze-excitation, archs/omni/arch.py:446-461).  Any other value is
+                                RSA_E_ARG (before OmniSR, every non-zero value ran as mode 1) */
   int32_t fmt;               /* enum rsa_plane_fmt of every plane operand of this call (0 = bf16, the default of a zeroed descriptor; round 4: fp16 planes) */
 } rsa_channel_gate_params;
 int64_t rsa_channel_gate_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t planes);
@@ -1091,6 +1093,111 @@ typedef struct rsa_lda_attn_params {
   int64_t out_batch_stride;
 } rsa_lda_attn_params;
 int rsa_lda_attention(const rsa_lda_attn_params* p, void* stream);
+
+/* ---- OmniSR (csrc/omnisr.hip; reference resselt/archs/omni/arch.py) ----
+ * Heads sit on whole 8-channel planes: head h of a width-d head owns planes [h*hp, h*hp + hp), hp = ceil(d / 8), its channels >= d are zero.
+ * The qkv planes hold q at planes [0, heads*hp), k at [heads*hp, 2*heads*hp) and v at [2*heads*hp, 3*heads*hp).  H and W are the padded
+ * map, multiples of ws.  Token sets:
+ *   block (grid = 0): window (wy, wx) holds pixels (wy*ws + r, wx*ws + c), r, c < ws                          (:824, :521-596)
+ *   grid  (grid = 1): rsa_omni_window_attention: window (wy, wx) holds pixels (r*H/ws + wy, c*W/ws + wx)       (:842)
+ *                     rsa_omni_channel_attention: residue class (r0, c0) holds pixels (i*ws + r0, j*ws + c0)   (:742-799)
+ * rsa_omni_window_attention: out = softmax(q k^T + B[rel(i, j)][h]) v per window and head (q pre-scaled by the host); bias_table is
+ *   nn.Embedding((2ws-1)^2, heads).weight or NULL; ws in 2..8, head_dim <= 32, heads <= 8.
+ * rsa_omni_channel_attention: per token set and head, A = softmax_row(T[h] * q^ k^T) over the d channels with q^, k^ the L2-normalised
+ *   (eps 1e-12) channel rows over the set, out = A v.  Window mode with ws^2 <= 64: one launch, everything in LDS, no workspace (may
+ *   be NULL).  Otherwise three kernels, no atomics: partial Gram matrices and squared norms per 64-token chunk into `workspace`, one
+ *   ordered finish per (image, set, head), then the apply pass.  ws >= 1, head_dim <= 32, heads <= 8. */
+typedef struct rsa_omni_attn_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t ws;
+  int32_t heads;
+  int32_t head_dim;
+  int32_t grid;              /* 0 = block token sets, 1 = grid token sets (see above) */
+  int32_t fmt;               /* enum rsa_plane_fmt of the qkv and out planes */
+  const void* qkv_hi;
+  const void* qkv_lo;        /* may be NULL */
+  int64_t qkv_plane_stride;
+  int64_t qkv_batch_stride;
+  const float* bias_table;   /* window attention: optional [(2ws-1)^2][heads]; channel attention: must be NULL */
+  const float* temperature;  /* channel attention: [heads]; window attention: must be NULL */
+  float* workspace;          /* channel attention: rsa_omni_channel_attn_workspace_bytes() (0 in the one-launch window mode); window attention: must be NULL */
+  void* out_hi;              /* heads*hp planes */
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_omni_attn_params;
+int rsa_omni_window_attention(const rsa_omni_attn_params* p, void* stream);
+int64_t rsa_omni_channel_attn_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t ws, int32_t heads, int32_t head_dim, int32_t grid);
+int rsa_omni_channel_attention(const rsa_omni_attn_params* p, void* stream);
+
+/* Gated_Conv_FeedForward's middle (:436-439): out = GELU(dw3x3(x1)) * dw3x3(x2), zero padding 1, no bias, exact (erf) GELU.  x1 is planes
+ * [0, planes) and x2 planes [planes, 2*planes) of the input; weight [2*planes*8][9] in the same channel order. */
+typedef struct rsa_gelu_gate_dwconv_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t planes;            /* output planes */
+  int32_t fmt;               /* enum rsa_plane_fmt of every plane operand */
+  int32_t reserved0;         /* must be 0 */
+  const void* in_hi;
+  const void* in_lo;         /* may be NULL */
+  int64_t in_plane_stride;
+  int64_t in_batch_stride;
+  const float* weight;
+  void* out_hi;
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_gelu_gate_dwconv_params;
+int rsa_gelu_gate_dwconv(const rsa_gelu_gate_dwconv_params* p, void* stream);
+
+/* MBConv's squeeze-excitation applied (:460): out[b][c][p] = in[b][c][p] * gate[b][c] with gate [batch][8*planes] from rsa_channel_gate
+ * (relu = 3); in place allowed (out = in). */
+int rsa_omni_gate_scale(const void* in_hi, const void* in_lo, int64_t plane_stride, int64_t batch_stride, int32_t batch, int32_t H, int32_t W,
+                        int32_t planes, const float* gate, int32_t fmt, void* out_hi, void* out_lo, void* stream);
+
+/* ESA (:18-46) on f32 NCHW4c maps [N][ceil(C/4)][H][W][4]:
+ *   rsa_esa_conv3x3   3x3 convolution with bias, stride 1 or 2, zero padding 0 or 1 (conv2: stride 2 pad 0; conv3: stride 1 pad 1);
+ *                     Hout = (H + 2 pad - 3) / stride + 1; cin, cout <= 64
+ *   rsa_esa_maxpool   max_pool2d(7, stride 3): Hout = (H - 7) / 3 + 1 (H, W >= 7)
+ *   rsa_esa_apply     out = x * sigmoid(W4 (bilinear(c3) + Wf c1 + bf) + b4), bilinear with align_corners = False from Hc x Wc to H x W;
+ *                     out (f32 map, may be x) and optionally split planes of out; f <= 32, C <= 128 */
+typedef struct rsa_esa_conv_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t Hout, Wout;
+  int32_t cin, cout;
+  int32_t stride, pad;
+  int32_t reserved0;         /* must be 0 */
+  const float* in;
+  const float* weight;       /* [cout][cin][3][3] */
+  const float* bias;         /* [cout] */
+  float* out;
+} rsa_esa_conv_params;
+int rsa_esa_conv3x3(const rsa_esa_conv_params* p, void* stream);
+int rsa_esa_maxpool(const float* in, int32_t batch, int32_t C, int32_t H, int32_t W, float* out, void* stream);
+
+typedef struct rsa_esa_apply_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t C;                 /* channels of x */
+  int32_t f;                 /* ESA channels */
+  int32_t Hc, Wc;            /* c3 map */
+  int32_t fmt;               /* enum rsa_plane_fmt of out_hi / out_lo */
+  const float* x;            /* f32 map, C channels */
+  const float* c1;           /* f32 map, f channels, H x W (conv1's output) */
+  const float* c3;           /* f32 map, f channels, Hc x Wc */
+  const float* wf;           /* [f][f] conv_f */
+  const float* bf;           /* [f] */
+  const float* w4;           /* [C][f] conv4 */
+  const float* b4;           /* [C] */
+  float* out;                /* f32 map, C channels (may equal x) */
+  void* out_hi;              /* optional split planes of out */
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_esa_apply_params;
+int rsa_esa_apply(const rsa_esa_apply_params* p, void* stream);
 
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255

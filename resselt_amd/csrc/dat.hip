@@ -932,7 +932,7 @@ __global__ __launch_bounds__(256) void channel_gate_kernel(const rsa_channel_gat
     const int k = threadIdx.x;
     float s = p.b1[k];
     for (int c = 0; c < C; ++c) s += p.w1[(int64_t)k * C + c] * s_mean[c];
-    s_hid[k] = p.relu ? fmaxf(s, 0.f) : gelu_erf(s);
+    s_hid[k] = p.relu == 3 ? s * sigmoidf(s) : p.relu ? fmaxf(s, 0.f) : gelu_erf(s);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {
@@ -1179,6 +1179,7 @@ extern "C" int rsa_channel_gate(const rsa_channel_gate_params* p, void* stream) 
   if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "channel_gate: fmt must be an rsa_plane_fmt");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->planes < 1 || p->planes > 64 || p->hidden < 1 || p->hidden > 128)
     return set_error(RSA_E_ARG, "channel_gate: bad geometry (planes <= 64, hidden <= 128)");
+  if (p->relu < 0 || p->relu > 3) return set_error(RSA_E_ARG, "channel_gate: relu must be 0..3");
   if (!p->in_hi || !p->w1 || !p->b1 || !p->w2 || !p->b2 || !p->workspace || !p->gate) return set_error(RSA_E_ARG, "channel_gate: null pointer");
   if (misaligned(p->in_hi) || misaligned(p->in_lo)) return set_error(RSA_E_ALIGN, "channel_gate: maps must be 16-byte aligned");
   const int64_t chunks = ((int64_t)p->H * p->W + CG_PIX - 1) / CG_PIX;

@@ -771,6 +771,50 @@ class LdaAttnParams(C.Structure):
     )
 
 
+class OmniAttnParams(C.Structure):
+    """Mirror of ``struct rsa_omni_attn_params``."""
+
+    _fields_ = (
+        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('ws', C.c_int32), ('heads', C.c_int32), ('head_dim', C.c_int32)]
+        + [('grid', C.c_int32), ('fmt', C.c_int32)]
+        + _plane_fields('qkv')
+        + [('bias_table', C.c_void_p), ('temperature', C.c_void_p), ('workspace', C.c_void_p)]
+        + _plane_fields('out')
+    )
+
+
+class GeluGateDwConvParams(C.Structure):
+    """Mirror of ``struct rsa_gelu_gate_dwconv_params``."""
+
+    _fields_ = (
+        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('planes', C.c_int32), ('fmt', C.c_int32), ('reserved0', C.c_int32)]
+        + _plane_fields('in')
+        + [('weight', C.c_void_p)]
+        + _plane_fields('out')
+    )
+
+
+class EsaConvParams(C.Structure):
+    """Mirror of ``struct rsa_esa_conv_params``."""
+
+    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'Hout', 'Wout', 'cin', 'cout', 'stride', 'pad', 'reserved0')] + [
+        ('in_', C.c_void_p),
+        ('weight', C.c_void_p),
+        ('bias', C.c_void_p),
+        ('out', C.c_void_p),
+    ]
+
+
+class EsaApplyParams(C.Structure):
+    """Mirror of ``struct rsa_esa_apply_params``."""
+
+    _fields_ = (
+        [(k, C.c_int32) for k in ('batch', 'H', 'W', 'C', 'f', 'Hc', 'Wc', 'fmt')]
+        + [(k, C.c_void_p) for k in ('x', 'c1', 'c3', 'wf', 'bf', 'w4', 'b4', 'out')]
+        + _plane_fields('out')
+    )
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -838,6 +882,14 @@ EXPORTS = (
     'rsa_pa_gate',
     'rsa_lda_offsets',
     'rsa_lda_attention',
+    'rsa_omni_window_attention',
+    'rsa_omni_channel_attn_workspace_bytes',
+    'rsa_omni_channel_attention',
+    'rsa_gelu_gate_dwconv',
+    'rsa_omni_gate_scale',
+    'rsa_esa_conv3x3',
+    'rsa_esa_maxpool',
+    'rsa_esa_apply',
 )
 
 
@@ -991,13 +1043,21 @@ def load() -> C.CDLL:
                          ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams), ('rsa_gated_dwconv', GatedDwConvParams),
                          ('rsa_bilinear_add', BilinearAddParams), ('rsa_rg_attention', RgAttnParams), ('rsa_rg_reduce', RgReduceParams),
                          ('rsa_layernorm_gelu', LayerNormParams), ('rsa_fdat_interact', FdatInteractParams), ('rsa_lda_offsets', LdaOffsetsParams),
-                         ('rsa_lda_attention', LdaAttnParams)):  # fmt: skip
+                         ('rsa_lda_attention', LdaAttnParams), ('rsa_omni_window_attention', OmniAttnParams),
+                         ('rsa_omni_channel_attention', OmniAttnParams), ('rsa_gelu_gate_dwconv', GeluGateDwConvParams),
+                         ('rsa_esa_conv3x3', EsaConvParams), ('rsa_esa_apply', EsaApplyParams)):  # fmt: skip
         getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
         getattr(lib, name).restype = C.c_int
     lib.rsa_scale_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.rsa_scale_add.restype = C.c_int
     lib.rsa_pa_gate.argtypes = [C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rsa_pa_gate.restype = C.c_int
+    lib.rsa_omni_channel_attn_workspace_bytes.argtypes = [C.c_int32] * 7
+    lib.rsa_omni_channel_attn_workspace_bytes.restype = C.c_int64
+    lib.rsa_omni_gate_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+    lib.rsa_omni_gate_scale.restype = C.c_int
+    lib.rsa_esa_maxpool.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
+    lib.rsa_esa_maxpool.restype = C.c_int
     _lib = lib
     return lib
 

@@ -1037,3 +1037,28 @@ def fdat_state_dict(num_in_ch=3, num_out_ch=3, scale=4, embed_dim=48, num_groups
     else:
         raise ValueError(f'unknown FDAT upsampler {up!r}')
     return sd
+
+
+def omnisr_state_dict(num_in_ch=3, num_feat=64, res_num=1, block_num=1, pe=True, window_size=8, up_scale=4, bias=True, seed=0):
+    """Keys of the reference OmniSR module (archs/omni/arch.py:907-974).  LayerNorm weights sit around 1, the channel-attention temperatures
+    around 1 and the relative-position bias tables are of visible size."""
+    from ..archs.omnisr.arch import omnisr_param_shapes
+
+    sd: OrderedDict = OrderedDict()
+    shapes = omnisr_param_shapes(num_in_ch, num_in_ch, num_feat, res_num, block_num, window_size, pe, up_scale, bias)
+    for name, shape in shapes.items():
+        if name.endswith('norm.weight'):
+            sd[name] = 1.0 + synth_tensor(name, shape, 16, seed)
+        elif name.endswith('norm.bias'):
+            sd[name] = synth_tensor(name, shape, 16, seed)
+        elif name.endswith('temperature'):
+            sd[name] = 1.0 + synth_tensor(name, shape, 1, seed, 0.5)
+        elif name.endswith('rel_pos_bias.weight'):
+            sd[name] = synth_tensor(name, shape, 1, seed)
+        elif name.endswith('.weight'):
+            fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+            sd[name] = synth_tensor(name, shape, fan_in, seed)
+        else:  # a bias: the fan-in of its weight
+            w = shapes[name[: -len('bias')] + 'weight']
+            sd[name] = synth_tensor(name, shape, int(np.prod(w[1:])), seed)
+    return sd

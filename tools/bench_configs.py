@@ -70,6 +70,9 @@ def main():
                              (1, 3, 512, 512), torch.bfloat16, None, None),
         'fdat_x4_lda_bf16_512': (synth.fdat_state_dict(embed_dim=120, num_groups=4, depth_per_group=3, num_heads=4, window_size=8, mid_dim=64, scale=4,
                                                        upsampler_type='lda'), (1, 3, 512, 512), torch.bfloat16, None, None),
+        # OmniSR x4 with the common checkpoint shape (num_feat 64, res_num 5, block_num 1, window 8, pe)
+        'omnisr_x4_bf16_512': (synth.omnisr_state_dict(num_feat=64, res_num=5, block_num=1, pe=True, window_size=8, up_scale=4),
+                               (1, 3, 512, 512), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
         # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
         'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),

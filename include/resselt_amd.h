@@ -1199,6 +1199,127 @@ typedef struct rsa_esa_apply_params {
 } rsa_esa_apply_params;
 int rsa_esa_apply(const rsa_esa_apply_params* p, void* stream);
 
+/* ---- ATD (csrc/atd.hip; reference resselt/archs/atd/arch.py) ----
+ * Tokens are the pixels of the padded H x W map, token index = y*W + x.  The similarity path (wq, wk, L2 normalisation, logits, softmax,
+ * argmax) is f32 whatever `products` says.  Nothing here uses atomics whose order could change a result: every reduction has a fixed order.
+ *
+ * rsa_atd_dict      per image, from the dictionary td [batch][m][C] (f32): kn[batch][m][16] = normalize(wk td + bk) (eps 1e-12, columns >= rc
+ *                   zero) and V^T = (wv td + bv)^T as bf16 hi / lo [batch][32*ceil(C/32)][128] (rows >= C and columns >= m zero).    (:236-241)
+ * rsa_atd_ca        per pixel: q = normalize(wq xn + bq); sim = softmax_m(q . kn * scale[m]); id = first maximum of sim; out = sim V
+ *                   (v_mfma_f32_32x32x16_bf16, three products or one) as an f32 NCHW4c map.  scale[m] = 1 + clamp(s, 0, 1) ln m.   (:234-249)
+ * rsa_atd_sort      stable counting sort of ids [batch][n] (values < m <= 128): perm[b][pos] = token, inv[b][token] = pos, tokens of one
+ *                   category in ascending token index.  Three kernels; workspace of rsa_atd_sort_workspace_bytes().                 (:304-307)
+ * rsa_atd_attention softmax(scale * q k^T (+ bias) (+ mask)) v over token groups of at most 256 tokens, flash-style on
+ *                   v_mfma_f32_32x32x16_bf16.  The qkv planes hold q at planes [0, heads*hp), k at [heads*hp, 2*heads*hp), v behind them;
+ *                   head h owns planes [h*hp, h*hp + hp), hp = ceil(head_dim / 8), channels >= head_dim zero.
+ *                     mode 0 (window, :446-472): group = a ws x ws window of the map rolled by -shift; bias_table [heads][(2ws-1)^2];
+ *                       the shift mask (-100 across the regions of :1057-1082) is derived from the geometry.  H, W multiples of ws.
+ *                     mode 1 (category, :297-331): group g = sorted positions [g*gs, g*gs + gs) through perm; positions >= n of the last
+ *                       group are the flipped tail of the sorted sequence (keys only).  gs = min(n, category_size) <= 256.
+ *                   The output of a token lands on that token's pixel in both modes.
+ * rsa_atd_dwconv    out = x + GELU(dw5x5(x) + bias) on split planes (ConvFFN's middle, :81-85); weight f32 [planes*8][25].
+ * rsa_atd_refine    td <- sigmoid(sigma) td + (1 - sigmoid(sigma)) softmax_n(InstanceNorm(sim^T)) x  (:483-487): column statistics in f64
+ *                   partial sums, a softmax over all pixels and the weighted sum of x (f32 NCHW4c map), four kernels, fixed reduction
+ *                   trees; workspace of rsa_atd_refine_workspace_bytes(). */
+typedef struct rsa_atd_dict_params {
+  int32_t batch;
+  int32_t C;                 /* 1..256 */
+  int32_t m;                 /* dictionary tokens, 1..128 */
+  int32_t rc;                /* reduced width, 1..16 */
+  const float* td;           /* [batch][m][C] */
+  const float* wk;           /* [rc][C] */
+  const float* bk;           /* [rc] or NULL */
+  const float* wv;           /* [C][C] */
+  const float* bv;           /* [C] or NULL */
+  float* kn;                 /* [batch][m][16] */
+  void* vt_hi;               /* bf16 [batch][32*ceil(C/32)][128] */
+  void* vt_lo;               /* same shape */
+} rsa_atd_dict_params;
+int rsa_atd_dict(const rsa_atd_dict_params* p, void* stream);
+
+typedef struct rsa_atd_ca_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t C;                 /* 1..256 */
+  int32_t m;                 /* 1..128 */
+  int32_t rc;                /* 1..16 */
+  int32_t products;          /* 3 or 1: bf16 products of sim V */
+  int32_t reserved0;         /* must be 0 */
+  const float* xn;           /* f32 NCHW4c map of norm1(x) */
+  const float* wq;           /* [rc][C] */
+  const float* bq;           /* [rc] or NULL */
+  const float* kn;           /* rsa_atd_dict */
+  const float* scale;        /* [m] */
+  const void* vt_hi;
+  const void* vt_lo;
+  float* sim;                /* [batch][H*W][m] or NULL */
+  int32_t* ids;              /* [batch][H*W] or NULL */
+  float* out;                /* f32 NCHW4c map */
+} rsa_atd_ca_params;
+int rsa_atd_ca(const rsa_atd_ca_params* p, void* stream);
+
+int64_t rsa_atd_sort_workspace_bytes(int32_t batch, int64_t n);
+int rsa_atd_sort(const int32_t* ids, int32_t batch, int64_t n, int32_t m, int32_t* perm, int32_t* inv, void* workspace, void* stream);
+
+typedef struct rsa_atd_attn_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t heads;
+  int32_t head_dim;          /* 1..64 */
+  int32_t mode;              /* 0 = window, 1 = category */
+  int32_t ws;                /* window mode: 2..16 */
+  int32_t shift;             /* window mode: 0 <= shift < ws */
+  int32_t gs;                /* category mode: group size, 1..256 */
+  int32_t products;          /* 3 or 1 */
+  float scale;               /* multiplies q k^T */
+  int32_t reserved0;         /* must be 0 */
+  const void* qkv_hi;
+  const void* qkv_lo;        /* products == 3 */
+  int64_t qkv_plane_stride;
+  int64_t qkv_batch_stride;
+  const float* bias_table;   /* window mode: [heads][(2ws-1)^2] or NULL */
+  const int32_t* perm;       /* category mode: [batch][H*W], values < H*W */
+  void* out_hi;              /* heads*hp planes */
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_atd_attn_params;
+int rsa_atd_attention(const rsa_atd_attn_params* p, void* stream);
+
+typedef struct rsa_atd_dwconv_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t planes;
+  const void* in_hi;
+  const void* in_lo;         /* may be NULL */
+  int64_t in_plane_stride;
+  int64_t in_batch_stride;
+  const float* weight;       /* [planes*8][25] */
+  const float* bias;         /* [planes*8] */
+  void* out_hi;
+  void* out_lo;              /* may be NULL */
+  int64_t out_plane_stride;
+  int64_t out_batch_stride;
+} rsa_atd_dwconv_params;
+int rsa_atd_dwconv(const rsa_atd_dwconv_params* p, void* stream);
+
+typedef struct rsa_atd_refine_params {
+  int32_t batch;
+  int32_t H, W;
+  int32_t C;                 /* 1..256 */
+  int32_t m;                 /* 1..128 */
+  float eps;                 /* InstanceNorm1d eps */
+  const float* sim;          /* [batch][H*W][m] */
+  const float* x;            /* f32 NCHW4c map (the layer's output) */
+  const float* gamma;        /* norm3.weight [m] */
+  const float* beta;         /* norm3.bias [m] */
+  const float* sigma;        /* [m], before the sigmoid */
+  float* td;                 /* [batch][m][C], updated in place */
+  void* workspace;
+} rsa_atd_refine_params;
+int64_t rsa_atd_refine_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t C, int32_t m);
+int rsa_atd_refine(const rsa_atd_refine_params* p, void* stream);
+
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255
  *   rsa_nchw_to_image_u8   float [N][C][H][W] -> uint8 [N][H][W][C], round-half-even(clamp(v, 0, 1) * 255)  (torch: (y.clamp(0,1)*255).round())

@@ -815,6 +815,46 @@ class EsaApplyParams(C.Structure):
     )
 
 
+class AtdDictParams(C.Structure):
+    """Mirror of ``struct rsa_atd_dict_params``."""
+
+    _fields_ = [(k, C.c_int32) for k in ('batch', 'C', 'm', 'rc')] + [(k, C.c_void_p) for k in ('td', 'wk', 'bk', 'wv', 'bv', 'kn', 'vt_hi', 'vt_lo')]
+
+
+class AtdCaParams(C.Structure):
+    """Mirror of ``struct rsa_atd_ca_params``."""
+
+    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'C', 'm', 'rc', 'products', 'reserved0')] + [
+        (k, C.c_void_p) for k in ('xn', 'wq', 'bq', 'kn', 'scale', 'vt_hi', 'vt_lo', 'sim', 'ids', 'out')
+    ]
+
+
+class AtdAttnParams(C.Structure):
+    """Mirror of ``struct rsa_atd_attn_params``."""
+
+    _fields_ = (
+        [(k, C.c_int32) for k in ('batch', 'H', 'W', 'heads', 'head_dim', 'mode', 'ws', 'shift', 'gs', 'products')]
+        + [('scale', C.c_float), ('reserved0', C.c_int32)]
+        + _plane_fields('qkv')
+        + [('bias_table', C.c_void_p), ('perm', C.c_void_p)]
+        + _plane_fields('out')
+    )
+
+
+class AtdDwConvParams(C.Structure):
+    """Mirror of ``struct rsa_atd_dwconv_params``."""
+
+    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'planes')] + _plane_fields('in') + [('weight', C.c_void_p), ('bias', C.c_void_p)] + _plane_fields('out')
+
+
+class AtdRefineParams(C.Structure):
+    """Mirror of ``struct rsa_atd_refine_params``."""
+
+    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'C', 'm')] + [('eps', C.c_float)] + [
+        (k, C.c_void_p) for k in ('sim', 'x', 'gamma', 'beta', 'sigma', 'td', 'workspace')
+    ]
+
+
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
     'rsa_version',
@@ -890,6 +930,14 @@ EXPORTS = (
     'rsa_esa_conv3x3',
     'rsa_esa_maxpool',
     'rsa_esa_apply',
+    'rsa_atd_dict',
+    'rsa_atd_ca',
+    'rsa_atd_sort_workspace_bytes',
+    'rsa_atd_sort',
+    'rsa_atd_attention',
+    'rsa_atd_dwconv',
+    'rsa_atd_refine_workspace_bytes',
+    'rsa_atd_refine',
 )
 
 
@@ -1056,6 +1104,16 @@ def load() -> C.CDLL:
     lib.rsa_omni_channel_attn_workspace_bytes.restype = C.c_int64
     lib.rsa_omni_gate_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
     lib.rsa_omni_gate_scale.restype = C.c_int
+    for name, struct in (('rsa_atd_dict', AtdDictParams), ('rsa_atd_ca', AtdCaParams), ('rsa_atd_attention', AtdAttnParams),
+                         ('rsa_atd_dwconv', AtdDwConvParams), ('rsa_atd_refine', AtdRefineParams)):  # fmt: skip
+        getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
+        getattr(lib, name).restype = C.c_int
+    lib.rsa_atd_sort_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
+    lib.rsa_atd_sort_workspace_bytes.restype = C.c_int64
+    lib.rsa_atd_sort.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsa_atd_sort.restype = C.c_int
+    lib.rsa_atd_refine_workspace_bytes.argtypes = [C.c_int32] * 5
+    lib.rsa_atd_refine_workspace_bytes.restype = C.c_int64
     lib.rsa_esa_maxpool.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
     lib.rsa_esa_maxpool.restype = C.c_int
     _lib = lib

@@ -1062,3 +1062,40 @@ def omnisr_state_dict(num_in_ch=3, num_feat=64, res_num=1, block_num=1, pe=True,
             w = shapes[name[: -len('bias')] + 'weight']
             sd[name] = synth_tensor(name, shape, int(np.prod(w[1:])), seed)
     return sd
+
+
+def atd_state_dict(in_chans=3, embed_dim=48, depths=(2, 2), num_heads=(4, 4), window_size=8, num_tokens=64, reducted_dim=8, convffn_kernel_size=5,
+                   mlp_ratio=2.0, qkv_bias=True, patch_norm=True, upscale=2, upsampler='pixelshuffledirect', resi_connection='1conv', norm=True,
+                   seed=0):  # fmt: skip
+    """Keys of the reference ATD module (archs/atd/arch.py:829-1010).  The dictionary, wq and wk are of visible size, so the similarity maps
+    are far from uniform (cosine logits span about +-(1 + ln m / 2)); LayerNorm / InstanceNorm weights sit around 1; outputs stay of order 1."""
+    from ..archs.atd.arch import atd_param_shapes
+
+    sd: OrderedDict = OrderedDict()
+    shapes, buffers = atd_param_shapes(in_chans, embed_dim, list(depths), list(num_heads), window_size, num_tokens, reducted_dim, convffn_kernel_size,
+                                       mlp_ratio, qkv_bias, patch_norm, upscale, upsampler, resi_connection, norm)  # fmt: skip
+    for name, value in buffers.items():
+        sd[name] = value.clone()
+    for name, shape in shapes.items():
+        leaf = name.rsplit('.', 1)[-1]
+        if leaf == 'td':
+            sd[name] = synth_tensor(name, shape, 1, seed)
+        elif leaf == 'sigma':
+            sd[name] = synth_tensor(name, shape, 1, seed)
+        elif name.endswith('attn_atd.scale'):
+            sd[name] = 0.5 + synth_tensor(name, shape, 1, seed, 0.7)  # some entries leave [0, 1]: the clamp is exercised
+        elif leaf == 'logit_scale':
+            sd[name] = float(np.log(10.0)) + synth_tensor(name, shape, 1, seed, 0.5)
+        elif leaf == 'relative_position_bias_table':
+            sd[name] = synth_tensor(name, shape, 1, seed)
+        elif '.norm' in name and leaf == 'weight' or name in ('norm.weight', 'patch_embed.norm.weight'):
+            sd[name] = 1.0 + synth_tensor(name, shape, 16, seed)
+        elif '.norm' in name and leaf == 'bias' or name in ('norm.bias', 'patch_embed.norm.bias'):
+            sd[name] = synth_tensor(name, shape, 16, seed)
+        elif '.wq.' in name or '.wk.' in name:
+            sd[name] = synth_tensor(name, shape, int(np.prod(shapes[name[: -len(leaf)] + 'weight'][1:])), seed, 2.0)
+        elif leaf == 'weight':
+            sd[name] = synth_tensor(name, shape, int(np.prod(shape[1:])) if len(shape) > 1 else 1, seed)
+        else:  # a bias: the fan-in of its weight
+            sd[name] = synth_tensor(name, shape, int(np.prod(shapes[name[: -len('bias')] + 'weight'][1:])), seed)
+    return sd

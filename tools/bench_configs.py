@@ -73,6 +73,13 @@ def main():
         # OmniSR x4 with the common checkpoint shape (num_feat 64, res_num 5, block_num 1, window 8, pe)
         'omnisr_x4_bf16_512': (synth.omnisr_state_dict(num_feat=64, res_num=5, block_num=1, pe=True, window_size=8, up_scale=4),
                                (1, 3, 512, 512), torch.bfloat16, None, None),
+        # ATD-light x4 (embed 48, 4 blocks x 6 layers, 4 heads, window 16, 64 tokens, category_size 128) and ATD x4 at its released width
+        # (embed 210, 6 blocks x 6 layers, 6 heads, window 16, 128 tokens of width 10, category_size 256), both at 256^2: the f32 sim map is
+        # n * m * 4 bytes per image (16.8 MB / 33.5 MB here)
+        'atd_light_x4_bf16_256': (synth.atd_state_dict(embed_dim=48, depths=(6,) * 4, num_heads=(4,) * 4, window_size=16, num_tokens=64, reducted_dim=8,
+                                                       mlp_ratio=1.0, upscale=4, upsampler='pixelshuffledirect'), (1, 3, 256, 256), torch.bfloat16, None, None),
+        'atd_x4_bf16_256': (synth.atd_state_dict(embed_dim=210, depths=(6,) * 6, num_heads=(6,) * 6, window_size=16, num_tokens=128, reducted_dim=10,
+                                                 mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle'), (1, 3, 256, 256), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
         # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
         'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),

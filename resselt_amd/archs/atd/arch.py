@@ -27,7 +27,8 @@ from ...engine import lib as L
 from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import ParamShapes, build_param_tree
-from ...engine.transformer import LayerPacker, layernorm, pixelshuffle_buffers, pixelshuffle_head, regroup_proj, regroup_qkv, relative_position_index
+from ...engine.transformer import (LayerPacker, ResidualTail, head_macs, head_shapes, layernorm_on, pack_head, reconstruction_head, regroup_proj, regroup_qkv,
+                                   relative_position_index, tail_layers, tail_macs, tail_shapes)
 from ..dat.arch import pad_rows
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:894
@@ -47,14 +48,6 @@ def atd_param_shapes(in_chans, embed_dim, depths, num_heads, window, num_tokens,
     hidden = int(C_ * mlp_ratio)
     if not norm:
         buffers['no_norm'] = torch.zeros(1)
-
-    def resi_conv(name):
-        if resi == '1conv':
-            s.conv(name, C_, C_, 3)
-        else:
-            s.conv(f'{name}.0', C_ // 4, C_, 3)
-            s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
-            s.conv(f'{name}.4', C_, C_ // 4, 3)
 
     s.conv('conv_first', C_, in_chans, 3)
     if patch_norm:
@@ -85,22 +78,10 @@ def atd_param_shapes(in_chans, embed_dim, depths, num_heads, window, num_tokens,
             s[f'{b}.convffn.dwconv.depthwise_conv.0.weight'] = (hidden, 1, ksize, ksize)
             s[f'{b}.convffn.dwconv.depthwise_conv.0.bias'] = (hidden,)
             s.linear(f'{b}.convffn.fc2', C_, hidden)
-        resi_conv(f'layers.{i}.conv')
+        tail_shapes(s, f'layers.{i}.conv', C_, resi)
     s.norm('norm', C_)
-    resi_conv('conv_after_body')
-    nf = 64
-    if upsampler == 'pixelshuffle':
-        s.pixelshuffle_head(C_, nf, in_chans, upscale)
-    elif upsampler == 'pixelshuffledirect':
-        s.conv('upsample.0', upscale * upscale * in_chans, C_, 3)
-    elif upsampler == 'nearest+conv':
-        s.conv('conv_before_upsample.0', nf, C_, 3)
-        s.conv('conv_up1', nf, nf, 3)
-        s.conv('conv_up2', nf, nf, 3)
-        s.conv('conv_hr', nf, nf, 3)
-        s.conv('conv_last', in_chans, nf, 3)
-    else:
-        s.conv('conv_last', in_chans, C_, 3)
+    tail_shapes(s, 'conv_after_body', C_, resi)
+    head_shapes(s, upsampler, C_, 64, in_chans, upscale)  # ('nearest+conv' is x4 only: ATD.__init__)
     return s, buffers
 
 
@@ -190,8 +171,8 @@ class ATD(EngineModule):
         W, conv, lin, ln = pk.W, pk.conv, pk.lin, pk.ln
 
         def resi_conv(name):
-            for sub in [''] if self.resi == '1conv' else ['.0', '.2', '.4']:
-                conv(name + sub)
+            for layer in tail_layers(name, self.resi):
+                conv(layer)
 
         conv('conv_first')
         if self.patch_norm:
@@ -213,9 +194,7 @@ class ATD(EngineModule):
             resi_conv(f'layers.{i}.conv')
         ln('norm')
         resi_conv('conv_after_body')
-        for name in ('conv_before_upsample.0', 'conv_up1', 'conv_up2', 'conv_hr', 'conv_last', 'upsample.0', 'upsample.2', 'upsample.4'):
-            if f'{name}.weight' in sd:
-                conv(name)
+        pack_head(pk)
         check_fp16_range(v for v in W.values() if isinstance(v, ops.ConvWeights))
         W['mean'] = torch.tensor(RGB_MEAN if self.in_chans == 3 else [0.0] * self.in_chans, dtype=torch.float32, device=device)
         return W
@@ -224,28 +203,11 @@ class ATD(EngineModule):
         """Algorithmic MACs per (padded) input pixel: convolutions, Linear layers, the three attentions and the refinement."""
         C_, hid, m, rc, w = self.embed_dim, self.hidden, self.num_tokens, self.reducted_dim, self.window_size
         macs = 9 * self.in_chans * C_
-        resi = 9 * C_ * C_ if self.resi == '1conv' else (9 * C_ * (C_ // 4) * 2 + (C_ // 4) ** 2)
+        resi = tail_macs(C_, self.resi)
         for d in self.depths:
             layer = 3 * C_ * C_ + 2 * C_ * C_ + rc * C_ + m * rc + m * C_ + 2 * w * w * C_ + 2 * self.category_size * C_ + 2 * C_ * hid + 25 * hid
             macs += d * layer + (d - 1) * m * C_ + resi
-        macs += resi
-        s = self.upscale
-        if self.upsampler == 'pixelshuffle':
-            macs += 9 * C_ * 64
-            res = 1
-            if s == 3:
-                macs += 9 * 64 * 576
-                res = 9
-            else:
-                for _ in range(int(math.log2(s))):
-                    macs += 9 * 64 * 256 * res
-                    res *= 4
-            macs += 9 * 64 * self.in_chans * res
-        elif self.upsampler == 'nearest+conv':
-            macs += 9 * C_ * 64 + 9 * 64 * 64 * (4 + 16 + 16) + 9 * 64 * self.in_chans * 16
-        else:
-            macs += 9 * C_ * s * s * self.in_chans
-        return macs
+        return macs + resi + head_macs(self.upsampler, C_, 64, self.in_chans, self.upscale)
 
     # ---------------------------------------------------------------- plan
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):
@@ -303,8 +265,7 @@ class ATD(EngineModule):
         hid_pl = plan.planes(n, P1, H, Wd, with_lo)
         hid2_pl = plan.planes(n, P1, H, Wd, with_lo)
         body_pl = plan.planes(n, cp, H, Wd, with_lo)
-        q4_a = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if self.resi == '3conv' else None
-        q4_b = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if self.resi == '3conv' else None
+        resi_conv = ResidualTail(plan, W, self.resi, n, H, Wd, C_, with_lo)
         td_buf = f32buf(n, m, C_)
         kn = f32buf(n, m, 16)
         vt_hi = torch.empty((n, Cp32, 128), dtype=torch.bfloat16, device=dev)
@@ -316,8 +277,7 @@ class ATD(EngineModule):
         refine_ws = torch.empty(max(int(lib.rsa_atd_refine_workspace_bytes(n, H, Wd, C_, m)), 16), dtype=torch.uint8, device=dev)
         plan.keep += [sort_ws, refine_ws]
 
-        def norm(name, x_f32, out_planes=None, out_f32=None):
-            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
+        norm = layernorm_on(plan, W, n, H, Wd, C_)
 
         def dictionary(t):
             dp = L.AtdDictParams()
@@ -355,12 +315,10 @@ class ATD(EngineModule):
             ap = L.AtdAttnParams()
             ap.batch, ap.H, ap.W, ap.heads, ap.head_dim, ap.mode = n, H, Wd, heads, C_ // heads, mode
             ap.ws, ap.shift, ap.gs, ap.products, ap.scale = win, shift, gs, prod, scale
-            ap.qkv_hi, ap.qkv_lo = qkv_pl.hi_ptr(), qkv_pl.lo_ptr()
-            ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.plane_stride, qkv_pl.batch_stride
+            qkv_pl.bind(ap, 'qkv')
             ap.bias_table = None if bias_table is None else bias_table.data_ptr()
             ap.perm = perm.data_ptr() if mode == 1 else None
-            ap.out_hi, ap.out_lo = cat_pl.hi_ptr(plane0), cat_pl.lo_ptr(plane0)
-            ap.out_plane_stride, ap.out_batch_stride = cat_pl.plane_stride, cat_pl.batch_stride
+            cat_pl.bind(ap, 'out', plane0)
             tokens = n * ntok
             G = win * win if mode == 0 else gs
             meta = dict(kernel=f'rsa::atd_attention_kernel ({"window" if mode == 0 else "category"})', products=prod, flop=4.0 * tokens * G * C_,
@@ -370,9 +328,9 @@ class ATD(EngineModule):
         def dwconv(t):
             dp = L.AtdDwConvParams()
             dp.batch, dp.H, dp.W, dp.planes = n, H, Wd, P1
-            dp.in_hi, dp.in_lo, dp.in_plane_stride, dp.in_batch_stride = hid_pl.hi_ptr(), hid_pl.lo_ptr(), hid_pl.plane_stride, hid_pl.batch_stride
+            hid_pl.bind(dp, 'in')
             dp.weight, dp.bias = t['dw'][0].data_ptr(), t['dw'][1].data_ptr()
-            dp.out_hi, dp.out_lo, dp.out_plane_stride, dp.out_batch_stride = hid2_pl.hi_ptr(), hid2_pl.lo_ptr(), hid2_pl.plane_stride, hid2_pl.batch_stride
+            hid2_pl.bind(dp, 'out')
             plan.launch('rsa_atd_dwconv', dp)
 
         def refine(t, x_f32):
@@ -381,15 +339,6 @@ class ATD(EngineModule):
             rp.sim, rp.x, rp.gamma, rp.beta, rp.sigma = sim.data_ptr(), x_f32.data_ptr(), t['norm3'][0].data_ptr(), t['norm3'][1].data_ptr(), t['sigma'].data_ptr()
             rp.td, rp.workspace = td_buf.data_ptr(), refine_ws.data_ptr()
             plan.launch('rsa_atd_refine', rp, kernels=4)
-
-        def resi_conv(name, src_planes, res, out_f32=None, out_planes=None):
-            if self.resi == '1conv':
-                plan.conv(ops.conv_params(W[name], src_planes, H, Wd, cin_planes=cp, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
-            else:
-                lre = dict(act=L.ACT_LRELU, act_param=0.2)
-                plan.conv(ops.conv_params(W[f'{name}.0'], src_planes, H, Wd, cin_planes=cp, out=q4_a, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.2'], q4_a, H, Wd, out=q4_b, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.4'], q4_b, H, Wd, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
 
         plan.call(lambda: model.atd_recorded.clear())
         plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
@@ -445,28 +394,6 @@ class ATD(EngineModule):
         resi_conv('conv_after_body', a_pl, first, out_planes=body_pl)  # + conv_first output
 
         y_out = plan.output((n, self.in_chans, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
-        final = dict(out_scale=1.0 / in_scale, out_shift=sub_mean)  # x / img_range + mean (arch.py:1131-1132)
-        lre = dict(act=L.ACT_LRELU, act_param=0.2)
-        if self.upsampler == 'pixelshuffle':
-            head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
-            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, **final))
-        elif self.upsampler == 'pixelshuffledirect':
-            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, pixel_shuffle=s, **final))
-        elif self.upsampler == 'nearest+conv':
-            y = plan.planes(n, 8, H, Wd, with_lo)
-            plan.conv(ops.conv_params(W['conv_before_upsample.0'], body_pl, H, Wd, cin_planes=cp, act=L.ACT_LRELU, act_param=0.01, out=y))
-            hh, ww = H, Wd
-            for u in (1, 2):
-                hh, ww = hh * 2, ww * 2
-                ny = plan.planes(n, 8, hh, ww, with_lo)
-                plan.conv(ops.conv_params(W[f'conv_up{u}'], y, hh, ww, upsample2x=True, out=ny, **lre))
-                y = ny
-            hr = plan.planes(n, 8, hh, ww, with_lo)
-            plan.conv(ops.conv_params(W['conv_hr'], y, hh, ww, out=hr, **lre))
-            plan.conv(ops.conv_params(W['conv_last'], hr, hh, ww, out_nchw=y_out, **final))
-        else:
-            # (x_norm + conv_last(res)) / img_range + mean == x + conv_last(res) / img_range: the caller's input is the base image
-            plan.conv(ops.conv_params(W['conv_last'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, out_scale=1.0 / in_scale,
-                                      out_base=plan.input_ref(x_shape, dtype), out_base_div=1))  # fmt: skip
+        # the last store: x / img_range + mean (arch.py:1131-1132)
+        reconstruction_head(plan, W, self.upsampler, body_pl, cp, n, H, Wd, s, with_lo, y_out, 1.0 / in_scale, sub_mean, (x_shape, dtype))
         return set_input

@@ -17,9 +17,6 @@ in training mode, where DropPath is random and BatchNorm uses batch statistics; 
 
 from __future__ import annotations
 
-import ctypes as C
-import math
-
 import torch
 
 from ...engine import lib as L
@@ -27,19 +24,15 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16, Planes
-from ...engine.transformer import (HEAD_PAD, LayerPacker, attn_tiles, bias_fragments_qk, layernorm, pad_heads, pixelshuffle_buffers, pixelshuffle_head,
-                                   regroup_proj, regroup_qkv, relative_position_index, shift_mask)
+from ...engine.transformer import (HEAD_PAD, LayerPacker, ResidualTail, attn_tiles, bias_fragments_qk, branch_geometry, dwconv3x3, head_macs, head_shapes,
+                                   layernorm_on, pack_head, pad_heads, plane_stats, reconstruction_head, rect_attention, regroup_proj, regroup_qkv,
+                                   relative_position_index, shift_mask, tail_layers, tail_macs, tail_shapes)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:879
 BN_EPS = 1e-5
 
-# names this module exported before the shared helpers moved to engine/transformer.py (attn_tiles and pad_heads are imported above)
+# names this module exported before the shared helpers moved to engine/transformer.py (attn_tiles, branch_geometry and pad_heads are imported above)
 bias_fragments = bias_fragments_qk
-
-
-def branch_geometry(pair, idx: int):
-    """(h, w) of a per-branch quantity: branch 1 swaps the rectangle (arch.py:186-191)."""
-    return (pair[0], pair[1]) if idx == 0 else (pair[1], pair[0])
 
 
 def is_shifted(rg_idx: int, b_idx: int) -> bool:  # arch.py:312, 453
@@ -80,14 +73,6 @@ def dat_param_shapes(in_chans, embed_dim, split_size, depth, num_heads, expansio
     def dw(name, c):
         s[f'{name}.weight'] = (c, 1, 3, 3)
         s[f'{name}.bias'] = (c,)
-
-    def resi_conv(name):
-        if resi == '1conv':
-            s.conv(name, C_, C_, 3)
-        else:
-            s.conv(f'{name}.0', C_ // 4, C_, 3)
-            s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
-            s.conv(f'{name}.4', C_, C_ // 4, 3)
 
     def aim(name):
         dw(f'{name}.dwconv.0', C_)
@@ -133,13 +118,10 @@ def dat_param_shapes(in_chans, embed_dim, split_size, depth, num_heads, expansio
             dw(f'{b}.ffn.sg.conv', hidden // 2)
             s.linear(f'{b}.ffn.fc2', C_, hidden // 2)
             s.norm(f'{b}.norm2', C_)
-        resi_conv(f'layers.{i}.conv')
+        tail_shapes(s, f'layers.{i}.conv', C_, resi)
     s.norm('norm', C_)
-    resi_conv('conv_after_body')
-    if upsampler == 'pixelshuffle':
-        s.pixelshuffle_head(C_, 64, in_chans, upscale)
-    else:
-        s.conv('upsample.0', upscale * upscale * in_chans, C_, 3)
+    tail_shapes(s, 'conv_after_body', C_, resi)
+    head_shapes(s, upsampler, C_, 64, in_chans, upscale)
     return s, buffers
 
 
@@ -195,8 +177,8 @@ class DAT(EngineModule):
             return t.to(torch.float32).contiguous()
 
         def resi_conv(name):
-            for sub in ([''] if self.resi == '1conv' else ['.0', '.2', '.4']):
-                conv(name + sub)
+            for layer in tail_layers(name, self.resi):
+                conv(layer)
 
         def bn_fold(name):
             """(scale, shift) of an eval-mode BatchNorm: y = x * scale + shift."""
@@ -263,9 +245,7 @@ class DAT(EngineModule):
             resi_conv(f'layers.{i}.conv')
         ln('norm')
         resi_conv('conv_after_body')
-        for name in ('conv_before_upsample.0', 'conv_last', 'upsample.0', 'upsample.2', 'upsample.4'):
-            if f'{name}.weight' in sd:
-                conv(name)
+        pack_head(pk)
         check_fp16_range(W.values())
         W['mean'] = torch.tensor(RGB_MEAN if self.in_chans == 3 else [0.0] * self.in_chans, dtype=torch.float32, device=device)
         return W
@@ -275,7 +255,7 @@ class DAT(EngineModule):
         C_, hid = self.embed_dim, self.hidden
         ntok = self.split_size[0] * self.split_size[1]
         macs = 9 * self.in_chans * C_
-        resi = 9 * C_ * C_ if self.resi == '1conv' else (9 * C_ * (C_ // 4) * 2 + (C_ // 4) ** 2)
+        resi = tail_macs(C_, self.resi)
         for i, d in enumerate(self.depth):
             hd = C_ // self.num_heads[i]
             for j in range(d):
@@ -283,22 +263,7 @@ class DAT(EngineModule):
                 macs += 2 * ntok * C_ if j % 2 == 0 else 2 * hd * C_  # QK^T + PV, or Gram + attn @ v
                 macs += C_ * hid + 9 * (hid // 2) + (hid // 2) * C_  # SGFN
             macs += resi
-        macs += resi
-        s = self.upscale
-        if self.upsampler == 'pixelshuffle':
-            macs += 9 * C_ * 64
-            res = 1
-            if s == 3:
-                macs += 9 * 64 * 576
-                res = 9
-            else:
-                for _ in range(int(math.log2(s))):
-                    macs += 9 * 64 * 256 * res
-                    res *= 4
-            macs += 9 * 64 * self.in_chans * res
-        else:
-            macs += 9 * C_ * s * s * self.in_chans
-        return macs
+        return macs + resi + head_macs(self.upsampler, C_, 64, self.in_chans, self.upscale)
 
     # ---------------------------------------------------------------- plan
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):
@@ -314,9 +279,6 @@ class DAT(EngineModule):
         lib = L.load()
         max_heads = max(self.num_heads)
         hp_max = max_heads * HEAD_PAD // 8
-        m = max(self.split_size)
-        Hp, Wp = H + (m - H % m) % m, Wd + (m - Wd % m) % m
-        shift = [self.split_size[0] // 2, self.split_size[1] // 2]
 
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, with_lo)
         mean = W['mean']
@@ -339,8 +301,7 @@ class DAT(EngineModule):
         hid_pl = plan.planes(n, 2 * P1, H, Wd, **body_kw)
         gate_pl = plan.planes(n, P1, H, Wd, **body_kw)
         body_pl = plan.planes(n, cp, H, Wd, with_lo)
-        q4_a = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if self.resi == '3conv' else None
-        q4_b = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if self.resi == '3conv' else None
+        resi_conv = ResidualTail(plan, W, self.resi, n, H, Wd, C_, with_lo)
         stats = torch.empty((n, H * Wd, 2), dtype=torch.float32, device=dev)
         gate = torch.empty((n, max_heads * HEAD_PAD), dtype=torch.float32, device=dev)
         ws_gate = torch.empty((max(int(lib.rsa_channel_gate_workspace_bytes(n, H, Wd, hp_max)), 16) // 4,), dtype=torch.float32, device=dev)
@@ -355,23 +316,7 @@ class DAT(EngineModule):
                 wdyn[heads] = torch.zeros((n, blob), dtype=torch.bfloat16, device=dev)  # off-diagonal blocks stay zero forever
                 plan.keep.append(wdyn[heads])
 
-        def norm(name, x_f32, out_planes=None, out_f32=None):
-            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
-
-        def rect_attention(b, heads, shifted):
-            for idx in (0, 1):
-                ap = L.RectAttnParams()
-                ap.batch, ap.H, ap.W, ap.Hp, ap.Wp = n, H, Wd, Hp, Wp
-                ap.win_h, ap.win_w = branch_geometry(self.split_size, idx)
-                ap.shift_h, ap.shift_w = branch_geometry(shift, idx) if shifted else (0, 0)
-                ap.heads, ap.head0, ap.heads_total, ap.products = heads // 2, idx * (heads // 2), heads, bprod
-                ap.fmt = bfmt
-                ap.qkv_hi, ap.qkv_lo = qkv_pl.hi_ptr(), qkv_pl.lo_ptr()
-                ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.plane_stride, qkv_pl.batch_stride
-                ap.bias_frag = W[f'{b}.attn.bias{idx}'].data_ptr()
-                ap.out_hi, ap.out_lo = att_pl.hi_ptr(), att_pl.lo_ptr()
-                ap.out_plane_stride, ap.out_batch_stride = att_pl.plane_stride, att_pl.batch_stride
-                plan.launch('rsa_rect_attention', ap)
+        norm = layernorm_on(plan, W, n, H, Wd, C_)
 
         def channel_attention(b, heads):
             hp = heads * 4
@@ -390,29 +335,12 @@ class DAT(EngineModule):
                 dst = Planes(att_pl.hi[bi : bi + 1], None if att_pl.lo is None else att_pl.lo[bi : bi + 1])
                 plan.conv(ops.conv_params(wts, src, H, Wd, in_plane0=2 * hp, cin_planes=hp, out=dst))
 
-        def dwconv(weights, src, src_plane0, planes, out, act=L.ACT_NONE, stats_t=None, gamma=None, beta=None, mul=None, mul_plane0=0):
-            dp = L.DwConvParams()
-            dp.batch, dp.H, dp.W, dp.planes, dp.act = n, H, Wd, planes, act
-            dp.fmt = src.fmt  # (source, multiplier and output planes of a call share their format)
-            dp.in_hi, dp.in_lo = src.hi_ptr(src_plane0), src.lo_ptr(src_plane0)
-            dp.in_plane_stride, dp.in_batch_stride = src.plane_stride, src.batch_stride
-            dp.weight, dp.bias = weights[0].data_ptr(), weights[1].data_ptr()
-            if stats_t is not None:
-                dp.stats, dp.gamma, dp.beta = stats_t.data_ptr(), gamma.data_ptr(), beta.data_ptr()
-            if mul is not None:
-                dp.mul_hi, dp.mul_lo = mul.hi_ptr(mul_plane0), mul.lo_ptr(mul_plane0)
-                dp.mul_plane_stride, dp.mul_batch_stride = mul.plane_stride, mul.batch_stride
-            dp.out_hi, dp.out_lo = out.hi_ptr(), out.lo_ptr()
-            dp.out_plane_stride, dp.out_batch_stride = out.plane_stride, out.batch_stride
-            plan.launch('rsa_dwconv3x3', dp)
-
         def channel_gate(a, src, heads):
             w1, b1, w2, b2 = W[f'{a}.ci']
             gp = L.ChannelGateParams()
             gp.batch, gp.H, gp.W, gp.planes, gp.hidden = n, H, Wd, heads * 4, w1.shape[0]
             gp.fmt = src.fmt
-            gp.in_hi, gp.in_lo = src.hi_ptr(), src.lo_ptr()
-            gp.in_plane_stride, gp.in_batch_stride = src.plane_stride, src.batch_stride
+            src.bind(gp, 'in')
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
             plan.launch('rsa_channel_gate', gp, kernels=2)
@@ -422,31 +350,11 @@ class DAT(EngineModule):
             ap = L.AimParams()
             ap.batch, ap.H, ap.W, ap.planes, ap.hidden, ap.mode = n, H, Wd, heads * 4, w1.shape[0], mode
             ap.fmt = att_pl.fmt
-            ap.att_hi, ap.att_lo = att_pl.hi_ptr(), att_pl.lo_ptr()
-            ap.att_plane_stride, ap.att_batch_stride = att_pl.plane_stride, att_pl.batch_stride
-            ap.conv_hi, ap.conv_lo = conv_pl.hi_ptr(), conv_pl.lo_ptr()
-            ap.conv_plane_stride, ap.conv_batch_stride = conv_pl.plane_stride, conv_pl.batch_stride
+            att_pl.bind(ap, 'att')
+            conv_pl.bind(ap, 'conv')
             ap.gate, ap.w1, ap.b1, ap.w2, ap.b2 = gate.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2
-            ap.out_hi, ap.out_lo = comb_pl.hi_ptr(), comb_pl.lo_ptr()
-            ap.out_plane_stride, ap.out_batch_stride = comb_pl.plane_stride, comb_pl.batch_stride
+            comb_pl.bind(ap, 'out')
             plan.launch('rsa_aim_combine', ap)
-
-        def plane_stats(src, plane0, channels):
-            def run():
-                L.check(lib.rsa_plane_stats_fmt(src.hi_ptr(plane0), src.lo_ptr(plane0), src.plane_stride, src.batch_stride, n, H, Wd, channels, 1e-5,
-                                                src.fmt, stats.data_ptr(), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_plane_stats')  # fmt: skip
-
-            plan.call(run)
-            plan.count_launches(1)
-
-        def resi_conv(name, src_planes, res, out_f32=None, out_planes=None):
-            if self.resi == '1conv':
-                plan.conv(ops.conv_params(W[name], src_planes, H, Wd, cin_planes=cp, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
-            else:
-                lre = dict(act=L.ACT_LRELU, act_param=0.2)
-                plan.conv(ops.conv_params(W[f'{name}.0'], src_planes, H, Wd, cin_planes=cp, out=q4_a, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.2'], q4_a, H, Wd, out=q4_b, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.4'], q4_b, H, Wd, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
 
         plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
         free = list(pool)
@@ -462,13 +370,13 @@ class DAT(EngineModule):
                 norm(f'{b}.norm1', cur, out_planes=a_pl)
                 plan.conv(ops.conv_params(W[f'{a}.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
                 if j % 2 == 0:
-                    rect_attention(b, heads, is_shifted(i, j))
-                    dwconv(W[f'{a}.dw'], qkv_pl, 2 * hp, hp, conv_pl, act=L.ACT_GELU)
+                    rect_attention(plan, qkv_pl, att_pl, [W[f'{a}.bias{idx}'] for idx in (0, 1)], n, H, Wd, self.split_size, heads, is_shifted(i, j), bprod, bfmt)
+                    dwconv3x3(plan, W[f'{a}.dw'], qkv_pl, 2 * hp, hp, conv_pl, act=L.ACT_GELU)
                     channel_gate(a, conv_pl, heads)
                     aim_combine(a, heads, 0)
                 else:
                     channel_attention(b, heads)
-                    dwconv(W[f'{a}.dw'], qkv_pl, 2 * hp, hp, conv_pl, act=L.ACT_GELU)
+                    dwconv3x3(plan, W[f'{a}.dw'], qkv_pl, 2 * hp, hp, conv_pl, act=L.ACT_GELU)
                     channel_gate(a, att_pl, heads)
                     aim_combine(a, heads, 1)
                 x1 = free.pop()
@@ -476,8 +384,8 @@ class DAT(EngineModule):
                 norm(f'{b}.norm2', x1, out_planes=a_pl)
                 plan.conv(ops.conv_params(W[f'{b}.ffn.fc1'], a_pl, H, Wd, cin_planes=cp, act=L.ACT_GELU, out=hid_pl))
                 sgw, sgb, sgg, sgbeta = W[f'{b}.ffn.sg']
-                plane_stats(hid_pl, P1, half)
-                dwconv((sgw, sgb), hid_pl, P1, P1, gate_pl, stats_t=stats, gamma=sgg, beta=sgbeta, mul=hid_pl, mul_plane0=0)
+                plane_stats(plan, hid_pl, P1, half, stats)
+                dwconv3x3(plan, (sgw, sgb), hid_pl, P1, P1, gate_pl, stats=stats, gamma=sgg, beta=sgbeta, mul=hid_pl)
                 x2 = free.pop()
                 last = j == d - 1
                 plan.conv(ops.conv_params(W[f'{b}.ffn.fc2'], gate_pl, H, Wd, cin_planes=P1, res1=x1, alpha=1.0, out_f32=x2,
@@ -496,11 +404,6 @@ class DAT(EngineModule):
         resi_conv('conv_after_body', n_pl, first, out_planes=body_pl)  # + conv_first output (arch.py:981, 986)
 
         y_out = plan.output((n, self.in_chans, H * s, Wd * s), dtype)
-        final = dict(out_scale=1.0 / self.img_range, out_shift=mean)  # x / img_range + mean (arch.py:989)
-        if self.upsampler == 'pixelshuffle':
-            head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
-            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, **final))
-        else:
-            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, pixel_shuffle=s, **final))
+        # the last store: x / img_range + mean (arch.py:989)
+        reconstruction_head(plan, W, self.upsampler, body_pl, cp, n, H, Wd, s, with_lo, y_out, 1.0 / self.img_range, mean, (x_shape, dtype))
         return set_input

@@ -16,8 +16,6 @@ On the engine:
 
 from __future__ import annotations
 
-import math
-
 import torch
 
 from ...engine import lib as L
@@ -25,8 +23,8 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16, Planes
-from ...engine.transformer import (LayerPacker, bias_fragments_qk, layernorm, pixelshuffle_buffers, pixelshuffle_head, regroup_proj,
-                                   regroup_qkv, relative_position_index, shift_mask)
+from ...engine.transformer import (LayerPacker, bias_fragments_qk, layernorm, pack_head, pixelshuffle_buffers, pixelshuffle_head, pixelshuffle_macs,
+                                   regroup_proj, regroup_qkv, relative_position_index, shift_mask)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:649
 
@@ -153,9 +151,9 @@ class DRCT(EngineModule):
         if self.resi == 'identity':  # nn.Identity as a 1x1 convolution (see _build_plan)
             eye = torch.eye(self.embed_dim, dtype=torch.float32, device=device)[:, :, None, None]
             W['identity'] = ops.ConvWeights.from_oihw(eye, torch.zeros(self.embed_dim, dtype=torch.float32, device=device), int(products), device=device, fmt=products.fmt)
-        for name in ('conv_after_body', 'conv_before_upsample.0', 'upsample.0', 'upsample.2', 'upsample.4', 'conv_last'):
-            if f'{name}.weight' in sd:
-                conv(name)
+        if self.resi == '1conv':
+            conv('conv_after_body')
+        pack_head(pk)
         check_fp16_range(W.values())
         W['mean'] = torch.tensor(RGB_MEAN if self.in_chans == 3 else [0.0] * self.in_chans, dtype=torch.float32, device=device)
         return W
@@ -171,16 +169,7 @@ class DRCT(EngineModule):
                 total += 4 * dim * dim + 2 * n_tok * dim + 2 * dim * hidden + dim * (gc if j < 5 else C_)
         if self.resi == '1conv':
             total += 9 * C_ * C_
-        total += 9 * C_ * 64
-        res = 1
-        if self.upscale == 3:
-            total += 9 * 64 * 9 * 64
-            res = 9
-        else:
-            for _ in range(int(math.log2(self.upscale))):
-                total += 9 * 64 * 4 * 64 * res
-                res *= 4
-        return total + 9 * 64 * self.in_chans * res
+        return total + pixelshuffle_macs(C_, 64, self.in_chans, self.upscale)
 
     # ---------------------------------------------------------------- plan
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):
@@ -240,9 +229,9 @@ class DRCT(EngineModule):
             ap.shift_h = ap.shift_w = win // 2 if shifted else 0
             ap.heads, ap.head0, ap.heads_total, ap.products, ap.head_chunks = heads, 0, heads, (1 if mixed else int(products)), chunks
             ap.fmt = qkv_pl.fmt
-            ap.qkv_hi, ap.qkv_lo, ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.hi_ptr(), qkv_pl.lo_ptr(), qkv_pl.plane_stride, qkv_pl.batch_stride
+            qkv_pl.bind(ap, 'qkv')
             ap.bias_frag = W[f'{name}.bias_frag'].data_ptr()
-            ap.out_hi, ap.out_lo, ap.out_plane_stride, ap.out_batch_stride = o_pl.hi_ptr(), o_pl.lo_ptr(), o_pl.plane_stride, o_pl.batch_stride
+            o_pl.bind(ap, 'out')
             plan.launch('rsa_rect_attention', ap)
 
         def f32_view_conv(wts, src, **kw):
@@ -291,8 +280,7 @@ class DRCT(EngineModule):
             # conv_after_body(forward_features(x)) + conv_first(x) (arch.py:781): a 3x3 convolution, or nn.Identity (arch.py:731-732) -- the
             # latter as a 1x1 convolution with the identity matrix, whose epilogue adds conv_first's map and writes the planes the head reads
             plan.conv(ops.conv_params(W['conv_after_body' if self.resi == '1conv' else 'identity'], n_pl, H, Wd, cin_planes=cp0, res1=first, alpha=1.0, out=body_pl))
-            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp0, H, Wd)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out[bi : bi + 1], **final))
+            pixelshuffle_head(plan, W, head, body_pl, cp0, H, Wd, y_out[bi : bi + 1], **final)
             plan.flush()
 
         for bi in range(nb):

@@ -356,9 +356,9 @@ class FDAT(EngineModule):
         def dwconv(weights, src, planes, out, act):
             dp = L.DwConvParams()
             dp.batch, dp.H, dp.W, dp.planes, dp.act, dp.fmt = n, H, Wd, planes, act, src.fmt
-            dp.in_hi, dp.in_lo, dp.in_plane_stride, dp.in_batch_stride = src.hi_ptr(), src.lo_ptr(), src.plane_stride, src.batch_stride
+            src.bind(dp, 'in')
             dp.weight, dp.bias = weights[0].data_ptr(), weights[1].data_ptr()
-            dp.out_hi, dp.out_lo, dp.out_plane_stride, dp.out_batch_stride = out.hi_ptr(), out.lo_ptr(), out.plane_stride, out.batch_stride
+            out.bind(dp, 'out')
             plan.launch('rsa_dwconv3x3', dp)
 
         def spatial_attention(b):
@@ -366,9 +366,9 @@ class FDAT(EngineModule):
             ap.batch, ap.H, ap.W, ap.Hp, ap.Wp = n, H, Wd, Hw, Ww
             ap.win_h, ap.win_w, ap.shift_h, ap.shift_w = ws, ws, 0, 0
             ap.heads, ap.head0, ap.heads_total, ap.products, ap.fmt = heads, 0, heads, prod, fmt
-            ap.qkv_hi, ap.qkv_lo, ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.hi_ptr(), qkv_pl.lo_ptr(), qkv_pl.plane_stride, qkv_pl.batch_stride
+            qkv_pl.bind(ap, 'qkv')
             ap.bias_frag = W[f'{b}.attn.bias'].data_ptr()
-            ap.out_hi, ap.out_lo, ap.out_plane_stride, ap.out_batch_stride = att_pl.hi_ptr(), att_pl.lo_ptr(), att_pl.plane_stride, att_pl.batch_stride
+            att_pl.bind(ap, 'out')
             plan.launch('rsa_rect_attention', ap)
 
         def channel_attention(b):
@@ -390,7 +390,7 @@ class FDAT(EngineModule):
             w1, b1, w2, b2 = W[f'{b}.inter.cg']
             gp = L.ChannelGateParams()
             gp.batch, gp.H, gp.W, gp.planes, gp.hidden, gp.relu, gp.fmt = n, H, Wd, cp, self.aim_hidden, 0, fmt
-            gp.in_hi, gp.in_lo, gp.in_plane_stride, gp.in_batch_stride = cb_pl.hi_ptr(), cb_pl.lo_ptr(), cb_pl.plane_stride, cb_pl.batch_stride
+            cb_pl.bind(gp, 'in')
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
             plan.launch('rsa_channel_gate', gp, kernels=2)
@@ -398,8 +398,8 @@ class FDAT(EngineModule):
         def interact(b, mode, x, x_out):
             ip = L.FdatInteractParams()
             ip.batch, ip.H, ip.W, ip.C, ip.mode, ip.fmt = n, H, Wd, C_, mode, fmt
-            ip.a_hi, ip.a_lo, ip.a_plane_stride, ip.a_batch_stride = prj_pl.hi_ptr(), prj_pl.lo_ptr(), prj_pl.plane_stride, prj_pl.batch_stride
-            ip.c_hi, ip.c_lo, ip.c_plane_stride, ip.c_batch_stride = cb_pl.hi_ptr(), cb_pl.lo_ptr(), cb_pl.plane_stride, cb_pl.batch_stride
+            prj_pl.bind(ip, 'a')
+            cb_pl.bind(ip, 'c')
             if mode == 0:
                 ip.cm = gate.data_ptr()
             else:
@@ -408,7 +408,7 @@ class FDAT(EngineModule):
             if self.fused_interact:
                 ip.x, ip.x_out = x.data_ptr(), x_out.data_ptr()
                 ip.gamma, ip.beta, ip.eps = g2.data_ptr(), b2.data_ptr(), 1e-5
-                ip.out_hi, ip.out_lo, ip.out_plane_stride, ip.out_batch_stride = a_pl.hi_ptr(), a_pl.lo_ptr(), a_pl.plane_stride, a_pl.batch_stride
+                a_pl.bind(ip, 'out')
                 plan.launch('rsa_fdat_interact', ip)
                 return
             # three passes over the stream, as DAT's separate launches: the interaction alone into an f32 map, the residual add, norm2
@@ -553,7 +553,8 @@ class FDAT(EngineModule):
         lp = L.LayerNormParams()
         lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, mid, LDA_EPS
         lp.x_f32, lp.gamma, lp.beta = xl32.data_ptr(), g.data_ptr(), be.data_ptr()
-        lp.out_hi, lp.out_lo, lp.out_plane_stride, lp.out_batch_stride, lp.out_fmt = nrm.hi_ptr(), nrm.lo_ptr(), nrm.plane_stride, nrm.batch_stride, nrm.fmt
+        nrm.bind(lp, 'out')
+        lp.out_fmt = nrm.fmt
         plan.launch('rsa_layernorm', lp)
         qk = plan.planes(n, 2 * hp, H, Wd, with_lo)
         plan.conv(ops.conv_params(W[f'{u}.qk'], nrm, H, Wd, out=qk))
@@ -561,9 +562,9 @@ class FDAT(EngineModule):
         dw, lg, lb = W[f'{u}.dw']
         op = L.LdaOffsetsParams()
         op.batch, op.H, op.W, op.Hout, op.Wout, op.hidden, op.groups, op.fmt = n, H, Wd, Ho, Wo, hid, 2, qk.fmt
-        op.q_hi, op.q_lo, op.q_plane_stride, op.q_batch_stride = qk.hi_ptr(), qk.lo_ptr(), qk.plane_stride, qk.batch_stride
+        qk.bind(op, 'q')
         op.dw_weight, op.gamma, op.beta, op.eps = dw.data_ptr(), lg.data_ptr(), lb.data_ptr(), LDA_EPS
-        op.out_hi, op.out_lo, op.out_plane_stride, op.out_batch_stride = offp.hi_ptr(), offp.lo_ptr(), offp.plane_stride, offp.batch_stride
+        offp.bind(op, 'out')
         plan.launch('rsa_lda_offsets', op)
         off32 = plan.f32map(n, 36, Ho, Wo)
         plan.conv(ops.conv_params(W[f'{u}.off'], offp, Ho, Wo, out_f32=off32))
@@ -571,10 +572,10 @@ class FDAT(EngineModule):
         ap = L.LdaAttnParams()
         ap.batch, ap.H, ap.W, ap.Hout, ap.Wout, ap.hidden, ap.C, ap.groups, ap.fmt = n, H, Wd, Ho, Wo, hid, mid, 2, qk.fmt
         ap.range, ap.scale = LDA_RANGE, hid**-0.5
-        ap.q_hi, ap.q_lo, ap.q_plane_stride, ap.q_batch_stride = qk.hi_ptr(), qk.lo_ptr(), qk.plane_stride, qk.batch_stride
-        ap.k_hi, ap.k_lo, ap.k_plane_stride, ap.k_batch_stride = qk.hi_ptr(hp), qk.lo_ptr(hp), qk.plane_stride, qk.batch_stride
-        ap.v_hi, ap.v_lo, ap.v_plane_stride, ap.v_batch_stride = xl.hi_ptr(), xl.lo_ptr(), xl.plane_stride, xl.batch_stride
+        qk.bind(ap, 'q')
+        qk.bind(ap, 'k', hp)
+        xl.bind(ap, 'v')
         ap.offset, ap.rpb = off32.data_ptr(), W[f'{u}.rpb'].data_ptr()
-        ap.out_hi, ap.out_lo, ap.out_plane_stride, ap.out_batch_stride = att.hi_ptr(), att.lo_ptr(), att.plane_stride, att.batch_stride
+        att.bind(ap, 'out')
         plan.launch('rsa_lda_attention', ap)
         plan.conv(ops.conv_params(W[f'upsampler.{layers[-1][1]}'], att, Ho, Wo, out_nchw=y))

@@ -16,7 +16,6 @@ relative-position tables are gathered once, at pack time, into the kernel's accu
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 
 import torch
@@ -26,8 +25,8 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16
-from ...engine.transformer import (HEAD_PAD, LayerPacker, attn_tiles, bias_fragments_qk, layernorm, mlp_block, mlp_block_fits, pixelshuffle_buffers,
-                                   pixelshuffle_head, regroup_proj, regroup_qkv, relative_position_index)
+from ...engine.transformer import (HEAD_PAD, LayerPacker, attn_tiles, bias_fragments_qk, layernorm_on, mlp_block, mlp_block_fits, pack_head,
+                                   pixelshuffle_macs, reconstruction_head, regroup_proj, regroup_qkv, relative_position_index)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:842
 
@@ -194,9 +193,7 @@ class HAT(EngineModule):
             conv('conv_after_body')
         else:  # 'identity': the residual adds still run as (exact) identity k1 launches
             W['identity'] = ops.ConvWeights.from_oihw(torch.eye(C_, device=device)[:, :, None, None], None, int(products), device=device, fmt=products.fmt)
-        for name in ('conv_before_upsample.0', 'conv_last', 'upsample.0', 'upsample.2', 'upsample.4'):
-            if f'{name}.weight' in sd:
-                conv(name)
+        pack_head(pk)
         check_fp16_range(W.values())
         W['mean'] = torch.tensor(RGB_MEAN if self.in_chans == 3 else [0.0] * self.in_chans, dtype=torch.float32, device=device)
         return W
@@ -211,17 +208,7 @@ class HAT(EngineModule):
             macs += 4 * C_ * C_ + 2 * ext * ext * C_ + 2 * C_ * hidden
             macs += 9 * C_ * C_ if self.resi == '1conv' else 0
         macs += 9 * C_ * C_ if self.resi == '1conv' else 0
-        nf, s = self.num_feat, self.upscale
-        macs += 9 * C_ * nf
-        res = 1
-        if s == 3:
-            macs += 9 * nf * 9 * nf
-            res = 9
-        else:
-            for _ in range(int(math.log2(s))):
-                macs += 9 * nf * 4 * nf * res
-                res *= 4
-        return macs + 9 * nf * self.in_chans * res
+        return macs + pixelshuffle_macs(C_, self.num_feat, self.in_chans, self.upscale)
 
     # ---------------------------------------------------------------- plan
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):
@@ -263,8 +250,7 @@ class HAT(EngineModule):
         ws_gate = torch.empty((max(int(lib.rsa_channel_gate_workspace_bytes(n, H, Wd, cp)), 16) // 4,), dtype=torch.float32, device=dev)
         plan.keep += [gate, ws_gate]
 
-        def norm(name, x_f32, out_planes=None, out_f32=None):
-            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
+        norm = layernorm_on(plan, W, n, H, Wd, C_)
 
         def attention(name, heads, shift, cross):
             ap = L.RectAttnParams()
@@ -272,11 +258,9 @@ class HAT(EngineModule):
             ap.win_h, ap.win_w, ap.shift_h, ap.shift_w = ws, ws, shift, shift
             ap.heads, ap.head0, ap.heads_total, ap.products = heads, 0, heads, (1 if mixed else int(products))
             ap.fmt = qkv_pl.fmt
-            ap.qkv_hi, ap.qkv_lo = qkv_pl.hi_ptr(), qkv_pl.lo_ptr()
-            ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.plane_stride, qkv_pl.batch_stride
+            qkv_pl.bind(ap, 'qkv')
             ap.bias_frag = W[f'{name}.bias_frag'].data_ptr()
-            ap.out_hi, ap.out_lo = o_pl.hi_ptr(), o_pl.lo_ptr()
-            ap.out_plane_stride, ap.out_batch_stride = o_pl.plane_stride, o_pl.batch_stride
+            o_pl.bind(ap, 'out')
             if cross:
                 ap.kwin_h = ap.kwin_w = ext
                 ap.kpad_h = ap.kpad_w = (ext - ws) // 2
@@ -289,8 +273,7 @@ class HAT(EngineModule):
             w1, b1, w2, b2 = W[f'{b}.ca']
             gp = L.ChannelGateParams()
             gp.batch, gp.H, gp.W, gp.planes, gp.hidden, gp.relu = n, H, Wd, cp, w1.shape[0], 1
-            gp.in_hi, gp.in_lo = cab_b.hi_ptr(), cab_b.lo_ptr()
-            gp.in_plane_stride, gp.in_batch_stride = cab_b.plane_stride, cab_b.batch_stride
+            cab_b.bind(gp, 'in')
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
             plan.launch('rsa_channel_gate', gp, kernels=2)
@@ -365,7 +348,5 @@ class HAT(EngineModule):
         plan.conv(ops.conv_params(tail, n_pl, H, Wd, cin_planes=cp, res1=first, alpha=1.0, out=body_pl))  # + conv_first output (arch.py:1104)
 
         y_out = plan.output((n, self.in_chans, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
-        head = pixelshuffle_buffers(plan, W, n, H, Wd, nf, with_lo)
-        y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-        plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, out_scale=1.0 / self.img_range, out_shift=mean))
+        reconstruction_head(plan, W, 'pixelshuffle', body_pl, cp, n, H, Wd, s, with_lo, y_out, 1.0 / self.img_range, mean, None, nf=nf)
         return set_input

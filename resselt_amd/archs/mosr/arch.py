@@ -168,8 +168,8 @@ class _GatedBase(EngineModule):
             lp = L.LayerNormParams()
             lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, dim, LN_EPS
             lp.x_f32, lp.gamma, lp.beta = cur.data_ptr(), sc.data_ptr(), off.data_ptr()
-            lp.out_hi, lp.out_lo = N_pl.hi_ptr(), N_pl.lo_ptr()
-            lp.out_plane_stride, lp.out_batch_stride, lp.out_fmt = N_pl.plane_stride, N_pl.batch_stride, N_pl.fmt
+            N_pl.bind(lp, 'out')
+            lp.out_fmt = N_pl.fmt
             plan.launch('rsa_layernorm', lp)
         plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
         hp = blk['planes']
@@ -178,12 +178,9 @@ class _GatedBase(EngineModule):
         for s, (pl, kh, kw, wt, bt) in enumerate(blk['segs']):
             gp.seg[s].planes, gp.seg[s].kh, gp.seg[s].kw = pl, kh, kw
             gp.seg[s].weight, gp.seg[s].bias = wt.data_ptr(), bt.data_ptr()
-        gp.g_hi, gp.g_lo = F_pl.hi_ptr(0), F_pl.lo_ptr(0)
-        gp.x_hi, gp.x_lo = F_pl.hi_ptr(hp), F_pl.lo_ptr(hp)
-        gp.g_plane_stride = gp.x_plane_stride = F_pl.plane_stride
-        gp.g_batch_stride = gp.x_batch_stride = F_pl.batch_stride
-        gp.out_hi, gp.out_lo = M_pl.hi_ptr(), M_pl.lo_ptr()
-        gp.out_plane_stride, gp.out_batch_stride = M_pl.plane_stride, M_pl.batch_stride
+        F_pl.bind(gp, 'g')
+        F_pl.bind(gp, 'x', hp)
+        M_pl.bind(gp, 'out')
         # byte model: g and cat(i, c) read once, the product written once (the halo re-reads stay on chip)
         unit = 16 * (2 if F_pl.lo is not None else 1)
         plan.launch('rsa_gated_dwconv', gp, meta=dict(kernel='rsa_gated_dwconv', flop=0, bytes=n * H * Wd * unit * 3 * hp))

@@ -251,22 +251,23 @@ class OmniSR(EngineModule):
             lp = L.LayerNormParams()
             lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, c, eps
             lp.x_f32, lp.gamma, lp.beta = x.data_ptr(), g_.data_ptr(), b_.data_ptr()
-            lp.out_hi, lp.out_lo, lp.out_plane_stride, lp.out_batch_stride, lp.out_fmt = a_pl.hi_ptr(), a_pl.lo_ptr(), a_pl.plane_stride, a_pl.batch_stride, fmt
+            a_pl.bind(lp, 'out')
+            lp.out_fmt = fmt
             plan.launch('rsa_layernorm', lp)
 
         def dwconv(weights, src, planes, out, act):
             dp = L.DwConvParams()
             dp.batch, dp.H, dp.W, dp.planes, dp.act, dp.fmt = n, H, Wd, planes, act, fmt
-            dp.in_hi, dp.in_lo, dp.in_plane_stride, dp.in_batch_stride = src.hi_ptr(), src.lo_ptr(), src.plane_stride, src.batch_stride
+            src.bind(dp, 'in')
             dp.weight, dp.bias = weights[0].data_ptr(), weights[1].data_ptr()
-            dp.out_hi, dp.out_lo, dp.out_plane_stride, dp.out_batch_stride = out.hi_ptr(), out.lo_ptr(), out.plane_stride, out.batch_stride
+            out.bind(dp, 'out')
             plan.launch('rsa_dwconv3x3', dp)
 
         def attn_params(src, grid):
             p = L.OmniAttnParams()
             p.batch, p.H, p.W, p.ws, p.heads, p.head_dim, p.grid, p.fmt = n, H, Wd, ws, HEADS, self.hd, grid, fmt
-            p.qkv_hi, p.qkv_lo, p.qkv_plane_stride, p.qkv_batch_stride = src.hi_ptr(), src.lo_ptr(), src.plane_stride, src.batch_stride
-            p.out_hi, p.out_lo, p.out_plane_stride, p.out_batch_stride = att_pl.hi_ptr(), att_pl.lo_ptr(), att_pl.plane_stride, att_pl.batch_stride
+            src.bind(p, 'qkv')
+            att_pl.bind(p, 'out')
             return p
 
         def mbconv(b, x, out):
@@ -275,7 +276,7 @@ class OmniSR(EngineModule):
             w1, b1, w2, b2 = W[f'{b}.0.fn.4']
             gp = L.ChannelGateParams()
             gp.batch, gp.H, gp.W, gp.planes, gp.hidden, gp.relu, gp.fmt = n, H, Wd, cp, self.se_hidden, 3, fmt
-            gp.in_hi, gp.in_lo, gp.in_plane_stride, gp.in_batch_stride = h_pl.hi_ptr(), h_pl.lo_ptr(), h_pl.plane_stride, h_pl.batch_stride
+            h_pl.bind(gp, 'in')
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
             plan.launch('rsa_channel_gate', gp, kernels=2)
@@ -311,9 +312,9 @@ class OmniSR(EngineModule):
             plan.conv(ops.conv_params(W[f'{b}.{i}.fn.project_in'], a_pl, H, Wd, out=ffn_pl))
             gp = L.GeluGateDwConvParams()
             gp.batch, gp.H, gp.W, gp.planes, gp.fmt = n, H, Wd, cp, fmt
-            gp.in_hi, gp.in_lo, gp.in_plane_stride, gp.in_batch_stride = ffn_pl.hi_ptr(), ffn_pl.lo_ptr(), ffn_pl.plane_stride, ffn_pl.batch_stride
+            ffn_pl.bind(gp, 'in')
             gp.weight = W[f'{b}.{i}.fn.dwconv'].data_ptr()
-            gp.out_hi, gp.out_lo, gp.out_plane_stride, gp.out_batch_stride = mid_pl.hi_ptr(), mid_pl.lo_ptr(), mid_pl.plane_stride, mid_pl.batch_stride
+            mid_pl.bind(gp, 'out')
             plan.launch('rsa_gelu_gate_dwconv', gp)
             plan.conv(ops.conv_params(W[f'{b}.{i}.fn.project_out'], mid_pl, H, Wd, res1=x, alpha=1.0, out_f32=out, out=planes_out))
 
@@ -339,7 +340,7 @@ class OmniSR(EngineModule):
             apar.batch, apar.H, apar.W, apar.C, apar.f, apar.Hc, apar.Wc, apar.fmt = n, H, Wd, c, f, Hc, Wc, fmt
             apar.x, apar.c1, apar.c3, apar.out = x.data_ptr(), c1f.data_ptr(), c3f.data_ptr(), x.data_ptr()
             apar.wf, apar.bf, apar.w4, apar.b4 = wf.data_ptr(), bf.data_ptr(), w4.data_ptr(), b4.data_ptr()
-            apar.out_hi, apar.out_lo, apar.out_plane_stride, apar.out_batch_stride = s_pl.hi_ptr(), s_pl.lo_ptr(), s_pl.plane_stride, s_pl.batch_stride
+            s_pl.bind(apar, 'out')
             plan.launch('rsa_esa_apply', apar)
 
         plan.conv(ops.conv_params(W['input'], x_pl, H, Wd, out_f32=first, out=s_pl))

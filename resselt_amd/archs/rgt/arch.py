@@ -26,9 +26,10 @@ from ...engine import lib as L
 from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import ParamShapes, build_param_tree
-from ...engine.transformer import (HEAD_PAD, LayerPacker, bias_fragments_qk, layernorm, pad_heads, pixelshuffle_buffers, pixelshuffle_head,
-                                   regroup_proj, regroup_qkv)
-from ..dat.arch import branch_geometry, is_shifted, pad_rows, rpe_buffers, shift_masks
+from ...engine.transformer import (HEAD_PAD, LayerPacker, ResidualTail, bias_fragments_qk, branch_geometry, dwconv3x3, head_shapes, layernorm_on, pack_head,
+                                   pad_heads, pixelshuffle_macs, plane_stats, reconstruction_head, rect_attention, regroup_proj, regroup_qkv, tail_layers,
+                                   tail_macs, tail_shapes)
+from ..dat.arch import is_shifted, pad_rows, rpe_buffers, shift_masks
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # arch.py:656
 RG_MAX_KEYS = 63 * 63  # RSA_RG_MAX_KEYS
@@ -57,14 +58,6 @@ def rgt_param_shapes(in_chans, embed_dim, split_size, depth, num_heads, mlp_rati
     def dw(name, c, k=3):
         s[f'{name}.weight'] = (c, 1, k, k)
         s[f'{name}.bias'] = (c,)
-
-    def resi_conv(name):
-        if resi == '1conv':
-            s.conv(name, C_, C_, 3)
-        else:
-            s.conv(f'{name}.0', C_ // 4, C_, 3)
-            s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
-            s.conv(f'{name}.4', C_, C_ // 4, 3)
 
     s.conv('conv_first', C_, in_chans, 3)
     s.norm('before_RG.1', C_)
@@ -106,10 +99,10 @@ def rgt_param_shapes(in_chans, embed_dim, split_size, depth, num_heads, mlp_rati
             s.linear(f'{b}.mlp.fc2', C_, hidden // 2)
             s.norm(f'{b}.norm2', C_)
             s[f'{b}.gamma'] = (C_,)
-        resi_conv(f'layers.{i}.conv')
+        tail_shapes(s, f'layers.{i}.conv', C_, resi)
     s.norm('norm', C_)
-    resi_conv('conv_after_body')
-    s.pixelshuffle_head(C_, 64, in_chans, upscale)
+    tail_shapes(s, 'conv_after_body', C_, resi)
+    head_shapes(s, 'pixelshuffle', C_, 64, in_chans, upscale)
     return s, buffers
 
 
@@ -160,8 +153,8 @@ class RGT(EngineModule):
             return t.to(torch.float32).contiguous()
 
         def resi_conv(name):
-            for sub in [''] if self.resi == '1conv' else ['.0', '.2', '.4']:
-                conv(name + sub)
+            for layer in tail_layers(name, self.resi):
+                conv(layer)
 
         def pos_bias(a):
             """DynamicPosBias (residual=False, arch.py:94-118) on rpe_biases, gathered to [heads, N, N] (arch.py:218-224)."""
@@ -222,9 +215,7 @@ class RGT(EngineModule):
             resi_conv(f'layers.{i}.conv')
         ln('norm')
         resi_conv('conv_after_body')
-        for name in ('conv_before_upsample.0', 'conv_last', 'upsample.0', 'upsample.2', 'upsample.4'):
-            if f'{name}.weight' in sd:
-                conv(name)
+        pack_head(pk)
         check_fp16_range(W.values())
         W['mean'] = torch.tensor(RGB_MEAN if self.in_chans == 3 else [0.0] * self.in_chans, dtype=torch.float32, device=device)
         return W
@@ -260,7 +251,7 @@ class RGT(EngineModule):
         C_, hid, cr = self.embed_dim, self.hidden, self.cr
         ntok = self.split_size[0] * self.split_size[1]
         macs = 9 * self.in_chans * C_
-        resi = 9 * C_ * C_ if self.resi == '1conv' else (9 * C_ * (C_ // 4) * 2 + (C_ // 4) ** 2)
+        resi = tail_macs(C_, self.resi)
         for d in self.depth:
             for j in range(d):
                 if j % 2 == 0:
@@ -270,17 +261,7 @@ class RGT(EngineModule):
                     macs += C_ * cr + C_ * C_ + 1024 * heads * (cr + C_) + C_ // 16 + (9 * C_ + C_ * cr + cr * cr + cr * C_ + 9 * C_) // 256
                 macs += C_ * hid + 9 * (hid // 2) + (hid // 2) * C_
             macs += resi
-        macs += resi + 9 * C_ * 64
-        s = self.upscale
-        res = 1
-        if s == 3:
-            macs += 9 * 64 * 576
-            res = 9
-        else:
-            for _ in range(int(math.log2(s))):
-                macs += 9 * 64 * 256 * res
-                res *= 4
-        return macs + 9 * 64 * self.in_chans * res
+        return macs + resi + pixelshuffle_macs(C_, 64, self.in_chans, self.upscale)
 
     # ---------------------------------------------------------------- plan
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):
@@ -304,9 +285,6 @@ class RGT(EngineModule):
         lib = L.load()
         max_heads = max(self.num_heads)
         hp_max = max_heads * HEAD_PAD // 8
-        m = max(self.split_size)
-        Hp, Wp = H + (m - H % m) % m, Wd + (m - Wd % m) % m
-        shift = [self.split_size[0] // 2, self.split_size[1] // 2]
         stream = lambda: C.c_void_p(ops.current_stream_ptr(dev))  # noqa: E731
 
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, with_lo)
@@ -323,8 +301,7 @@ class RGT(EngineModule):
         hid_pl = plan.planes(n, 2 * P1, H, Wd, with_lo)
         gate_pl = plan.planes(n, P1, H, Wd, with_lo)
         body_pl = plan.planes(n, cp, H, Wd, with_lo)
-        q4_a = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if self.resi == '3conv' else None
-        q4_b = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if self.resi == '3conv' else None
+        resi_conv = ResidualTail(plan, W, self.resi, n, H, Wd, C_, with_lo)
         stats = torch.empty((n, H * Wd, 2), dtype=torch.float32, device=dev)
         plan.keep.append(stats)
         if has_rg:
@@ -335,76 +312,36 @@ class RGT(EngineModule):
             kv_pl = plan.planes(n, 2 * hp_max, hs, ws, with_lo)
             v_pl = plan.planes(n, hp_max, hs, ws, with_lo)
 
-        def norm(name, x_f32, out_planes=None, out_f32=None):
-            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
-
-        def rect_attention(a, heads, shifted):
-            for idx in (0, 1):
-                ap = L.RectAttnParams()
-                ap.batch, ap.H, ap.W, ap.Hp, ap.Wp = n, H, Wd, Hp, Wp
-                ap.win_h, ap.win_w = branch_geometry(self.split_size, idx)
-                ap.shift_h, ap.shift_w = branch_geometry(shift, idx) if shifted else (0, 0)
-                ap.heads, ap.head0, ap.heads_total, ap.products = heads // 2, idx * (heads // 2), heads, prod
-                ap.fmt = fmt
-                ap.qkv_hi, ap.qkv_lo = qkv_pl.hi_ptr(), qkv_pl.lo_ptr()
-                ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.plane_stride, qkv_pl.batch_stride
-                ap.bias_frag = W[f'{a}.bias{idx}'].data_ptr()
-                ap.out_hi, ap.out_lo = cat_pl.hi_ptr(), cat_pl.lo_ptr()
-                ap.out_plane_stride, ap.out_batch_stride = cat_pl.plane_stride, cat_pl.batch_stride
-                plan.launch('rsa_rect_attention', ap)
-
-        def dwconv(weights, src, src_plane0, planes, out, out_plane0, h, w, stats_t=None, gamma=None, beta=None, mul=None):
-            dp = L.DwConvParams()
-            dp.batch, dp.H, dp.W, dp.planes, dp.act = n, h, w, planes, L.ACT_NONE
-            dp.fmt = src.fmt
-            dp.in_hi, dp.in_lo = src.hi_ptr(src_plane0), src.lo_ptr(src_plane0)
-            dp.in_plane_stride, dp.in_batch_stride = src.plane_stride, src.batch_stride
-            dp.weight, dp.bias = weights[0].data_ptr(), weights[1].data_ptr()
-            if stats_t is not None:
-                dp.stats, dp.gamma, dp.beta = stats_t.data_ptr(), gamma.data_ptr(), beta.data_ptr()
-            if mul is not None:
-                dp.mul_hi, dp.mul_lo = mul.hi_ptr(), mul.lo_ptr()
-                dp.mul_plane_stride, dp.mul_batch_stride = mul.plane_stride, mul.batch_stride
-            dp.out_hi, dp.out_lo = out.hi_ptr(out_plane0), out.lo_ptr(out_plane0)
-            dp.out_plane_stride, dp.out_batch_stride = out.plane_stride, out.batch_stride
-            plan.launch('rsa_dwconv3x3', dp)
+        norm = layernorm_on(plan, W, n, H, Wd, C_)
 
         def rg_attention(a, heads):
             hp = heads * 4
             rp = L.RgReduceParams()  # reduction1 x t on the norm1 output
             rp.batch, rp.H, rp.W, rp.planes, rp.times, rp.fmt = n, H, Wd, cp, t, fmt
-            rp.in_hi, rp.in_lo, rp.in_plane_stride, rp.in_batch_stride = a_pl.hi_ptr(), a_pl.lo_ptr(), a_pl.plane_stride, a_pl.batch_stride
+            a_pl.bind(rp, 'in')
             rp.weight, rp.bias = W[f'{a}.reduction1'][0].data_ptr(), W[f'{a}.reduction1'][1].data_ptr()
-            rp.out_hi, rp.out_lo, rp.out_plane_stride, rp.out_batch_stride = red_pl.hi_ptr(), red_pl.lo_ptr(), red_pl.plane_stride, red_pl.batch_stride
+            red_pl.bind(rp, 'out')
             plan.launch('rsa_rg_reduce', rp)
-            dwconv(W[f'{a}.dwconv'], red_pl, 0, cp, dws_pl, 0, hs, ws)
+            dwconv3x3(plan, W[f'{a}.dwconv'], red_pl, 0, cp, dws_pl)
             plan.conv(ops.conv_params(W[f'{a}.conv'], dws_pl, hs, ws, cin_planes=cp, out_f32=cv_f32))
             g, be = W[f'{a}.norm_act.0']
             lp = L.LayerNormParams()
             lp.batch, lp.H, lp.W, lp.C, lp.eps = n, hs, ws, cr, 1e-5
             lp.x_f32, lp.gamma, lp.beta = cv_f32.data_ptr(), g.data_ptr(), be.data_ptr()
-            lp.out_hi, lp.out_lo, lp.out_plane_stride, lp.out_batch_stride = nrm_pl.hi_ptr(), nrm_pl.lo_ptr(), nrm_pl.plane_stride, nrm_pl.batch_stride
+            nrm_pl.bind(lp, 'out')
             lp.out_fmt = fmt
             plan.launch('rsa_layernorm_gelu', lp)
             plan.conv(ops.conv_params(W[f'{a}.kv'], nrm_pl, hs, ws, cin_planes=crp, out=kv_pl))
-            dwconv(W[f'{a}.cpe'], kv_pl, hp, hp, v_pl, 0, hs, ws)  # v + cpe(v)
+            dwconv3x3(plan, W[f'{a}.cpe'], kv_pl, hp, hp, v_pl)  # v + cpe(v)
             plan.conv(ops.conv_params(W[f'{a}.q'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
             ap = L.RgAttnParams()
             ap.batch, ap.H, ap.W, ap.heads, ap.nkeys = n, H, Wd, heads, hs * ws
             ap.dim_qk, ap.dim_v, ap.products, ap.fmt = cr // heads, C_ // heads, prod, fmt
-            ap.q_hi, ap.q_lo, ap.q_plane_stride, ap.q_batch_stride = qkv_pl.hi_ptr(), qkv_pl.lo_ptr(), qkv_pl.plane_stride, qkv_pl.batch_stride
-            ap.k_hi, ap.k_lo, ap.k_plane_stride, ap.k_batch_stride = kv_pl.hi_ptr(), kv_pl.lo_ptr(), kv_pl.plane_stride, kv_pl.batch_stride
-            ap.v_hi, ap.v_lo, ap.v_plane_stride, ap.v_batch_stride = v_pl.hi_ptr(), v_pl.lo_ptr(), v_pl.plane_stride, v_pl.batch_stride
-            ap.out_hi, ap.out_lo, ap.out_plane_stride, ap.out_batch_stride = cat_pl.hi_ptr(), cat_pl.lo_ptr(), cat_pl.plane_stride, cat_pl.batch_stride
+            qkv_pl.bind(ap, 'q')
+            kv_pl.bind(ap, 'k')
+            v_pl.bind(ap, 'v')
+            cat_pl.bind(ap, 'out')
             plan.launch('rsa_rg_attention', ap)
-
-        def plane_stats(src, plane0, channels):
-            def run():
-                L.check(lib.rsa_plane_stats_fmt(src.hi_ptr(plane0), src.lo_ptr(plane0), src.plane_stride, src.batch_stride, n, H, Wd, channels, 1e-5,
-                                                src.fmt, stats.data_ptr(), stream()), 'rsa_plane_stats')  # fmt: skip
-
-            plan.call(run)
-            plan.count_launches(1)
 
         def scale_add(res, gamma, out):
             def run():
@@ -412,15 +349,6 @@ class RGT(EngineModule):
 
             plan.call(run)
             plan.count_launches(1)
-
-        def resi_conv(name, src_planes, res, out_f32=None, out_planes=None):
-            if self.resi == '1conv':
-                plan.conv(ops.conv_params(W[name], src_planes, H, Wd, cin_planes=cp, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
-            else:
-                lre = dict(act=L.ACT_LRELU, act_param=0.2)
-                plan.conv(ops.conv_params(W[f'{name}.0'], src_planes, H, Wd, cin_planes=cp, out=q4_a, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.2'], q4_a, H, Wd, out=q4_b, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.4'], q4_b, H, Wd, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
 
         plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
         free = list(pool)
@@ -437,8 +365,8 @@ class RGT(EngineModule):
                 x1 = free.pop()
                 if j % 2 == 0:
                     plan.conv(ops.conv_params(W[f'{a}.qkv'], a_pl, H, Wd, cin_planes=cp, out=qkv_pl))
-                    rect_attention(a, heads, is_shifted(i, j))
-                    dwconv(W[f'{a}.get_v'], qkv_pl, 2 * hp, hp, cat_pl, hp, H, Wd)
+                    rect_attention(plan, qkv_pl, cat_pl, [W[f'{a}.bias{idx}'] for idx in (0, 1)], n, H, Wd, self.split_size, heads, is_shifted(i, j), prod, fmt)
+                    dwconv3x3(plan, W[f'{a}.get_v'], qkv_pl, 2 * hp, hp, cat_pl, hp)
                     plan.conv(ops.conv_params(W[f'{a}.proj'], cat_pl, H, Wd, cin_planes=2 * hp, res1=cur, alpha=1.0, out_f32=x1))
                 else:
                     rg_attention(a, heads)
@@ -447,8 +375,8 @@ class RGT(EngineModule):
                 scale_add(cur, W[f'{b}.gamma'], x1)  # HAI: x1 + mlp(norm2(x1)) + gamma * res, once norm2 has read x1
                 plan.conv(ops.conv_params(W[f'{b}.mlp.fc1'], a_pl, H, Wd, cin_planes=cp, act=L.ACT_GELU, out=hid_pl))
                 sgw, sgb, sgg, sgbeta = W[f'{b}.mlp.sg']
-                plane_stats(hid_pl, P1, half)
-                dwconv((sgw, sgb), hid_pl, P1, P1, gate_pl, 0, H, Wd, stats_t=stats, gamma=sgg, beta=sgbeta, mul=hid_pl)
+                plane_stats(plan, hid_pl, P1, half, stats)
+                dwconv3x3(plan, (sgw, sgb), hid_pl, P1, P1, gate_pl, stats=stats, gamma=sgg, beta=sgbeta, mul=hid_pl)
                 x2 = free.pop()
                 last = j == d - 1
                 plan.conv(ops.conv_params(W[f'{b}.mlp.fc2'], gate_pl, H, Wd, cin_planes=P1, res1=x1, alpha=1.0, out_f32=x2,
@@ -467,7 +395,5 @@ class RGT(EngineModule):
         resi_conv('conv_after_body', a_pl, first, out_planes=body_pl)  # + conv_first output (arch.py:832)
 
         y_out = plan.output((n, self.in_chans, H * s, Wd * s), dtype)
-        head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
-        y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-        plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, out_scale=1.0 / self.img_range, out_shift=mean))  # x / img_range + mean
+        reconstruction_head(plan, W, 'pixelshuffle', body_pl, cp, n, H, Wd, s, with_lo, y_out, 1.0 / self.img_range, mean, None)  # x / img_range + mean
         return set_input

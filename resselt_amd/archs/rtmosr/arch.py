@@ -184,24 +184,24 @@ class RTMoSR(EngineModule):
             ow, ob = W[f'{b}.omni']
             dp = L.DwConvParams()
             dp.batch, dp.H, dp.W, dp.planes, dp.act = n, H // 2, Wd // 2, 4 * pd, L.ACT_NONE
-            dp.in_hi, dp.in_lo, dp.in_plane_stride, dp.in_batch_stride = c_pl.hi_ptr(), c_pl.lo_ptr(), c_pl.plane_stride, c_pl.batch_stride
+            c_pl.bind(dp, 'in')
             dp.weight, dp.bias = ow.data_ptr(), ob.data_ptr()
-            dp.out_hi, dp.out_lo, dp.out_plane_stride, dp.out_batch_stride = o_pl.hi_ptr(), o_pl.lo_ptr(), o_pl.plane_stride, o_pl.batch_stride
+            o_pl.bind(dp, 'out')
             plan.launch('rsa_dwconv5x5', dp)
             if self.se:
                 w1, b1, w2, b2 = W[f'{b}.se']
                 gp = L.ChannelGateParams()
                 gp.batch, gp.H, gp.W, gp.planes, gp.hidden, gp.relu = n, H // 2, Wd // 2, 4 * pd, w1.shape[0], 2
-                gp.in_hi, gp.in_lo, gp.in_plane_stride, gp.in_batch_stride = o_pl.hi_ptr(), o_pl.lo_ptr(), o_pl.plane_stride, o_pl.batch_stride
+                o_pl.bind(gp, 'in')
                 gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
                 gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
                 plan.launch('rsa_channel_gate', gp, kernels=2)
             sp = L.GatedShuffleParams()
             sp.batch, sp.H, sp.W, sp.g_planes, sp.i_planes = n, H, Wd, ph, gi
-            sp.f_hi, sp.f_lo, sp.f_plane_stride, sp.f_batch_stride = f_pl.hi_ptr(), f_pl.lo_ptr(), f_pl.plane_stride, f_pl.batch_stride
-            sp.c_hi, sp.c_lo, sp.c_plane_stride, sp.c_batch_stride = o_pl.hi_ptr(), o_pl.lo_ptr(), o_pl.plane_stride, o_pl.batch_stride
+            f_pl.bind(sp, 'f')
+            o_pl.bind(sp, 'c')
             sp.gate, sp.gate_stride = (gate.data_ptr() if self.se else None), 4 * dim
-            sp.out_hi, sp.out_lo, sp.out_plane_stride, sp.out_batch_stride = m_pl.hi_ptr(), m_pl.lo_ptr(), m_pl.plane_stride, m_pl.batch_stride
+            m_pl.bind(sp, 'out')
             plan.launch('rsa_gated_shuffle_mul', sp)
             last = i == self.n_blocks - 1
             # mish(fc2(.)) + shortcut: activation, then the residual, both in the conv epilogue

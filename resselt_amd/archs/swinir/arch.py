@@ -13,7 +13,6 @@ Weight re-layout at pack time (never per forward):
 
 from __future__ import annotations
 
-import math
 import os
 
 import torch
@@ -23,8 +22,9 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, PF_F16
-from ...engine.transformer import (HEAD_PAD, LayerPacker, bias_fragments, bias_fragments16, layernorm, mlp_block, mlp_block_fits, pixelshuffle_buffers,
-                                   pixelshuffle_head, regroup_proj, regroup_qkv, relative_position_index, shift_mask)
+from ...engine.transformer import (HEAD_PAD, LayerPacker, ResidualTail, bias_fragments, bias_fragments16, head_macs, head_shapes, layernorm_on, mlp_block,
+                                   mlp_block_fits, pack_head, reconstruction_head, regroup_proj, regroup_qkv, relative_position_index, shift_mask,
+                                   tail_layers, tail_macs, tail_shapes)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # resselt/archs/swinir/arch.py:788-790
 
@@ -34,14 +34,6 @@ def swinir_param_shapes(in_ch, out_ch, embed_dim, depths, num_heads, window, mlp
     buffers: dict = {}
     C_ = embed_dim
     hidden = int(C_ * mlp_ratio)
-
-    def resi_conv(name):
-        if resi == '1conv':
-            s.conv(name, C_, C_, 3)
-        else:
-            s.conv(f'{name}.0', C_ // 4, C_, 3)
-            s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
-            s.conv(f'{name}.4', C_, C_ // 4, 3)
 
     s.conv('conv_first', C_, in_ch, 3)
     if patch_norm:
@@ -63,25 +55,10 @@ def swinir_param_shapes(in_ch, out_ch, embed_dim, depths, num_heads, window, mlp
             s.norm(f'{b}.norm2', C_)
             s.linear(f'{b}.mlp.fc1', hidden, C_)
             s.linear(f'{b}.mlp.fc2', C_, hidden)
-        resi_conv(f'layers.{i}.conv')
+        tail_shapes(s, f'layers.{i}.conv', C_, resi)
     s.norm('norm', C_)
-    resi_conv('conv_after_body')
-    nf = 64
-    if upsampler == 'nearest+conv':
-        s.conv('conv_before_upsample.0', nf, C_, 3)
-        s.conv('conv_up1', nf, nf, 3)
-        if upscale in (4, 8):
-            s.conv('conv_up2', nf, nf, 3)
-        if upscale == 8:
-            s.conv('conv_up3', nf, nf, 3)
-        s.conv('conv_hr', nf, nf, 3)
-        s.conv('conv_last', out_ch, nf, 3)
-    elif upsampler == 'pixelshuffle':
-        s.pixelshuffle_head(C_, nf, out_ch, upscale)
-    elif upsampler == 'pixelshuffledirect':
-        s.conv('upsample.0', upscale * upscale * out_ch, C_, 3)
-    else:
-        s.conv('conv_last', out_ch, C_, 3)
+    tail_shapes(s, 'conv_after_body', C_, resi)
+    head_shapes(s, upsampler, C_, 64, out_ch, upscale)
     return s, buffers
 
 
@@ -156,8 +133,8 @@ class SwinIR(EngineModule):
         W, conv, lin, ln = pk.W, pk.conv, pk.lin, pk.ln
 
         def resi_conv(name):
-            for sub in ([''] if self.resi == '1conv' else ['.0', '.2', '.4']):
-                conv(name + sub)
+            for layer in tail_layers(name, self.resi):
+                conv(layer)
             if self.resi == '3conv' and self.tail_slices:
                 # Round 4: the last convolution of a 3conv tail (C/4 -> C, e.g. 60 -> 240) as output-channel SLICES of at most 64 channels: each
                 # slice has whole 32-channel input chunks and 33..64 output channels, i.e. it takes the ring schedule (the whole layer ran the
@@ -189,10 +166,7 @@ class SwinIR(EngineModule):
             resi_conv(f'layers.{i}.conv')
         ln('norm')
         resi_conv('conv_after_body')
-        for name in ('conv_before_upsample.0', 'conv_up1', 'conv_up2', 'conv_up3', 'conv_hr', 'conv_last', 'upsample.0', 'upsample.2',
-                     'upsample.4'):  # fmt: skip
-            if f'{name}.weight' in sd:
-                conv(name)
+        pack_head(pk)
         mean = torch.tensor(RGB_MEAN if self.in_chans == 3 else [0.0] * self.in_chans, dtype=torch.float32, device=device)
         W['mean'] = mean
         check_fp16_range(W.values())
@@ -205,30 +179,8 @@ class SwinIR(EngineModule):
         nblocks = sum(self.depths)
         macs = 9 * self.in_chans * C_
         macs += nblocks * (3 * C_ * C_ + C_ * C_ + 2 * C_ * hidden + 2 * w * w * C_)
-        resi = 9 * C_ * C_ if self.resi == '1conv' else (9 * C_ * (C_ // 4) * 2 + (C_ // 4) ** 2)
-        macs += (len(self.depths) + 1) * resi
-        s = self.upscale
-        if self.upsampler == 'nearest+conv':
-            macs += 9 * C_ * 64
-            res = 1
-            for _ in range(int(math.log2(s))):
-                res *= 4
-                macs += 9 * 64 * 64 * res
-            macs += (9 * 64 * 64 + 9 * 64 * self.out_chans) * res
-        elif self.upsampler == 'pixelshuffle':
-            macs += 9 * C_ * 64
-            res = 1
-            if s == 3:
-                macs += 9 * 64 * 576
-                res = 9
-            else:
-                for _ in range(int(math.log2(s))):
-                    macs += 9 * 64 * 256 * res
-                    res *= 4
-            macs += 9 * 64 * self.out_chans * res
-        else:
-            macs += 9 * C_ * s * s * self.out_chans
-        return macs
+        macs += (len(self.depths) + 1) * tail_macs(C_, self.resi)
+        return macs + head_macs(self.upsampler, C_, 64, self.out_chans, self.upscale)
 
     # ---------------------------------------------------------------- plan
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):
@@ -274,20 +226,15 @@ class SwinIR(EngineModule):
             hid_pl = plan.planes(n, (hidden + 7) // 8, H, Wd, with_lo)
         body_pl = plan.planes(n, cp, H, Wd, with_lo)  # the last block of a residual group -> that group's convolution
         head_pl = plan.planes(n, cp, H, Wd, wide, head_fmt) if mixed else body_pl  # conv_after_body -> the reconstruction head
-        q4_a = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, wide) if self.resi == '3conv' else None
-        q4_b = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, wide) if self.resi == '3conv' else None
-
-        def norm(name, x_f32, out_planes=None, out_f32=None):
-            layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
+        tail = ResidualTail(plan, W, self.resi, n, H, Wd, C_, wide)
+        norm = layernorm_on(plan, W, n, H, Wd, C_)
 
         def attention(name, heads, shift):
             ap = L.WindowAttnParams()
             ap.batch, ap.H, ap.W, ap.heads, ap.window, ap.shift, ap.products = n, H, Wd, heads, win, shift, products
-            ap.qkv_hi, ap.qkv_lo = qkv_pl.hi_ptr(), qkv_pl.lo_ptr()
-            ap.qkv_plane_stride, ap.qkv_batch_stride = qkv_pl.plane_stride, qkv_pl.batch_stride
+            qkv_pl.bind(ap, 'qkv')
             ap.bias_frag = W[f'{name}.bias_frag'].data_ptr()
-            ap.out_hi, ap.out_lo = o_pl.hi_ptr(), o_pl.lo_ptr()
-            ap.out_plane_stride, ap.out_batch_stride = o_pl.plane_stride, o_pl.batch_stride
+            o_pl.bind(ap, 'out')
             plan.launch('rsa_window_attention', ap)
 
         def attn_block(name, heads, shift, x_f32, out_f32):
@@ -318,8 +265,7 @@ class SwinIR(EngineModule):
             bp.out = out_f32.data_ptr()
             bp.fmt = plan.fmt
             if out_planes is not None:
-                bp.out_hi, bp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-                bp.out_plane_stride, bp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
+                out_planes.bind(bp, 'out')
             tokens = n * H * Wd
             meta = dict(kernel=f'rsa::swin_block_kernel<{int(products)},{"f16" if plan.fmt == PF_F16 else "bf16"}> (whole Swin block)', products=int(products),
                         flop=2.0 * tokens * (4 * C_ * C_ + 2 * C_ * hidden + 2 * win * win * C_),  # qkv + proj, the MLP, QK^T and PV
@@ -331,20 +277,15 @@ class SwinIR(EngineModule):
 
         def resi_conv(name, src_planes, res, out_f32=None, out_planes=None):
             """1conv / 3conv tail (arch.py:562-574) + the residual add that follows it."""
-            if self.resi == '1conv':
-                plan.conv(ops.conv_params(W[name], src_planes, H, Wd, cin_planes=cp, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
+            if n == 1 and f'{name}.4.s0' in W and C_ % 8 == 0:  # (`tail_slices`: the last convolution in <= 64-channel slices)
+                q4 = tail.squeeze(name, src_planes)
+                for k, c0 in enumerate(range(0, C_, 64)):
+                    cw = min(64, C_ - c0)
+                    plan.conv(ops.conv_params(W[f'{name}.4.s{k}'], q4, H, Wd, res1=res[:, c0 // 4 : (c0 + cw) // 4], alpha=1.0,
+                                              out_f32=None if out_f32 is None else out_f32[:, c0 // 4 : (c0 + cw) // 4],
+                                              out=out_planes, out_plane_off=c0 // 8))  # fmt: skip
             else:
-                lre = dict(act=L.ACT_LRELU, act_param=0.2)
-                plan.conv(ops.conv_params(W[f'{name}.0'], src_planes, H, Wd, cin_planes=cp, out=q4_a, **lre))
-                plan.conv(ops.conv_params(W[f'{name}.2'], q4_a, H, Wd, out=q4_b, **lre))
-                if n == 1 and f'{name}.4.s0' in W and C_ % 8 == 0:
-                    for k, c0 in enumerate(range(0, C_, 64)):
-                        cw = min(64, C_ - c0)
-                        plan.conv(ops.conv_params(W[f'{name}.4.s{k}'], q4_b, H, Wd, res1=res[:, c0 // 4 : (c0 + cw) // 4], alpha=1.0,
-                                                  out_f32=None if out_f32 is None else out_f32[:, c0 // 4 : (c0 + cw) // 4],
-                                                  out=out_planes, out_plane_off=c0 // 8))  # fmt: skip
-                else:
-                    plan.conv(ops.conv_params(W[f'{name}.4'], q4_b, H, Wd, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes))
+                tail(name, src_planes, res, out_f32, out_planes)
 
         plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
         free = list(pool)
@@ -397,30 +338,7 @@ class SwinIR(EngineModule):
         plan.fmt = head_fmt  # buffers of the head
 
         y_out = plan.output((n, self.out_chans, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
-        final = dict(out_scale=1.0 / self.img_range, out_shift=mean)  # x / img_range + mean (arch.py:1013)
-        lre = dict(act=L.ACT_LRELU, act_param=0.2)
-        if self.upsampler == 'nearest+conv':
-            y = plan.planes(n, 8, H, Wd, with_lo)
-            plan.conv(ops.conv_params(W['conv_before_upsample.0'], body_pl, H, Wd, cin_planes=cp, act=L.ACT_LRELU, act_param=0.01, out=y))
-            hh, ww = H, Wd
-            for u in range(1, int(math.log2(s)) + 1):
-                hh, ww = hh * 2, ww * 2
-                ny = plan.planes(n, 8, hh, ww, with_lo)
-                plan.conv(ops.conv_params(W[f'conv_up{u}'], y, hh, ww, upsample2x=True, out=ny, **lre))
-                y = ny
-            hr = plan.planes(n, 8, hh, ww, with_lo)
-            plan.conv(ops.conv_params(W['conv_hr'], y, hh, ww, out=hr, **lre))
-            plan.conv(ops.conv_params(W['conv_last'], hr, hh, ww, out_nchw=y_out, **final))
-        elif self.upsampler == 'pixelshuffle':
-            head = pixelshuffle_buffers(plan, W, n, H, Wd, 64, with_lo)
-            y, hh, ww = pixelshuffle_head(plan, W, head, body_pl, cp, H, Wd)
-            plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, **final))
-        elif self.upsampler == 'pixelshuffledirect':
-            plan.conv(ops.conv_params(W['upsample.0'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, pixel_shuffle=s, **final))
-        else:
-            # denoising / JPEG artefact heads (arch.py:1007-1010): (x_norm + conv_last(res)) / img_range + mean == x + conv_last(res) / img_range,
-            # so the final store scales the convolution and adds the caller's own (unpadded) input as the base image
-            plan.conv(ops.conv_params(W['conv_last'], body_pl, H, Wd, cin_planes=cp, out_nchw=y_out, out_scale=1.0 / self.img_range,
-                                      out_base=plan.input_ref(x_shape, dtype), out_base_div=1))  # fmt: skip
+        # the last store: x / img_range + mean (arch.py:1013); the denoising / JPEG artefact heads add the caller's own input (arch.py:1007-1010)
+        reconstruction_head(plan, W, self.upsampler, body_pl, cp, n, H, Wd, s, with_lo, y_out, 1.0 / self.img_range, mean, (x_shape, dtype))
         plan.fmt = plan_fmt
         return set_input

@@ -206,8 +206,7 @@ def region_se_params(se: SEWeights, x: Planes, win: Win, workspace: torch.Tensor
         raise ValueError('region_se: workspace / gate too small')
     p = L.RegionSEParams()
     p.batch, p.planes, p.hidden, p.fmt = x.n, x.planes, hidden, x.fmt
-    p.x_hi, p.x_lo = x.hi_ptr(), x.lo_ptr()
-    p.x_plane_stride, p.x_batch_stride = x.plane_stride, x.batch_stride
+    x.bind(p, 'x')
     p.W, p.y0, p.x0, p.h, p.w = x.w, win.y0, win.x0, win.h, win.w
     p.w1, p.b1, p.w2, p.b2 = se.w1.data_ptr(), se.b1.data_ptr(), se.w2.data_ptr(), se.b2.data_ptr()
     p.workspace, p.gate = workspace.data_ptr(), gate.data_ptr()

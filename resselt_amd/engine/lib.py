@@ -24,724 +24,253 @@ PF_BF16, PF_F16 = range(2)
 E_INTERNAL = -4
 
 
+def _i32(*names: str) -> list:
+    return [(k, C.c_int32) for k in names]
+
+
+def _i64(*names: str) -> list:
+    return [(k, C.c_int64) for k in names]
+
+
+def _f32(*names: str) -> list:
+    return [(k, C.c_float) for k in names]
+
+
+def _ptr(*names: str) -> list:
+    return [(k, C.c_void_p) for k in names]
+
+
+def _plane_fields(prefix: str) -> list:
+    """A split-plane operand: what ``Planes.bind(params, prefix)`` fills."""
+    return _ptr(f'{prefix}_hi', f'{prefix}_lo') + _i64(f'{prefix}_plane_stride', f'{prefix}_batch_stride')
+
+
+# Mirrors of the descriptors in include/resselt_amd.h: field order and types are the ABI (tests/test_pack_and_capi.py compares every one of
+# them with the header).
 class ConvParams(C.Structure):
     """Mirror of ``struct rsa_conv_params`` (include/resselt_amd.h); field order is the ABI."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('ksize', C.c_int32),
-        ('upsample2x', C.c_int32),
-        ('cin_planes', C.c_int32),
-        ('cout', C.c_int32),
-        ('products', C.c_int32),
-        ('in_hi', C.c_void_p),
-        ('in_lo', C.c_void_p),
-        ('in_plane_stride', C.c_int64),
-        ('in_batch_stride', C.c_int64),
-        ('w_packed', C.c_void_p),
-        ('bias', C.c_void_p),
-        ('act', C.c_int32),
-        ('act_param', C.c_float),
-        ('alpha', C.c_float),
-        ('res1', C.c_void_p),
-        ('beta', C.c_float),
-        ('res2', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_off', C.c_int32),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('out_f32', C.c_void_p),
-        ('out_nchw', C.c_void_p),
-        ('out_dtype', C.c_int32),
-        ('pixel_shuffle', C.c_int32),
-        ('out_scale', C.c_float),
-        ('out_shift', C.c_void_p),
-        ('act_vec', C.c_void_p),
-        ('out_base', C.c_void_p),
-        ('out_base_div', C.c_int32),
-        ('out_base_h', C.c_int32),
-        ('out_base_w', C.c_int32),
-        ('w_layout', C.c_int32),
-        ('res1_hi', C.c_void_p),
-        ('res1_lo', C.c_void_p),
-        ('res2_hi', C.c_void_p),
-        ('res2_lo', C.c_void_p),
-        ('res_plane_stride', C.c_int64),
-        ('res_batch_stride', C.c_int64),
-        ('in_fmt', C.c_int32),
-        ('out_fmt', C.c_int32),
-        ('res_fmt', C.c_int32),
-        ('tile_order', C.c_int32),
-        ('lo8_flags', C.c_int32),
-        ('reserved_lo8', C.c_int32),
-        ('lo8_batch_stride', C.c_int64),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'ksize', 'upsample2x', 'cin_planes', 'cout', 'products') + _plane_fields('in') + _ptr('w_packed', 'bias')
+        + _i32('act') + _f32('act_param', 'alpha') + _ptr('res1') + _f32('beta') + _ptr('res2', 'out_hi', 'out_lo') + _i32('out_plane_off')
+        + _i64('out_plane_stride', 'out_batch_stride') + _ptr('out_f32', 'out_nchw') + _i32('out_dtype', 'pixel_shuffle')
+        + _f32('out_scale') + _ptr('out_shift', 'act_vec', 'out_base') + _i32('out_base_div', 'out_base_h', 'out_base_w', 'w_layout')
+        + _ptr('res1_hi', 'res1_lo', 'res2_hi', 'res2_lo') + _i64('res_plane_stride', 'res_batch_stride')
+        + _i32('in_fmt', 'out_fmt', 'res_fmt', 'tile_order', 'lo8_flags', 'reserved_lo8') + _i64('lo8_batch_stride')
+    )
 
 
 class DySampleParams(C.Structure):
     """Mirror of ``struct rsa_dysample_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('groups', C.c_int32),
-        ('scale', C.c_int32),
-        ('out_ch', C.c_int32),
-        ('x_f32', C.c_void_p),
-        ('offscope', C.c_void_p),
-        ('init_pos', C.c_void_p),
-        ('end_w', C.c_void_p),
-        ('end_b', C.c_void_p),
-        ('out_nchw', C.c_void_p),
-        ('out_dtype', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C', 'groups', 'scale', 'out_ch') + _ptr('x_f32', 'offscope', 'init_pos', 'end_w', 'end_b', 'out_nchw')
+        + _i32('out_dtype')
+    )
 
 
 class LayerNormParams(C.Structure):
     """Mirror of ``struct rsa_layernorm_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('eps', C.c_float),
-        ('x_f32', C.c_void_p),
-        ('gamma', C.c_void_p),
-        ('beta', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('out_f32', C.c_void_p),
-        ('out_fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C') + _f32('eps') + _ptr('x_f32', 'gamma', 'beta') + _plane_fields('out') + _ptr('out_f32')
+        + _i32('out_fmt', 'reserved0')
+    )
 
 
 class SwinAttnBlockParams(C.Structure):
     """Mirror of ``struct rsa_swin_attn_block_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('heads', C.c_int32),
-        ('window', C.c_int32),
-        ('shift', C.c_int32),
-        ('products', C.c_int32),
-        ('eps', C.c_float),
-        ('x', C.c_void_p),
-        ('gamma', C.c_void_p),
-        ('beta', C.c_void_p),
-        ('wqkv', C.c_void_p),
-        ('bqkv', C.c_void_p),
-        ('bias_frag16', C.c_void_p),
-        ('wproj', C.c_void_p),
-        ('bproj', C.c_void_p),
-        ('out', C.c_void_p),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C', 'heads', 'window', 'shift', 'products') + _f32('eps')
+        + _ptr('x', 'gamma', 'beta', 'wqkv', 'bqkv', 'bias_frag16', 'wproj', 'bproj', 'out')
+    )
 
 
 class SwinMlpBlockParams(C.Structure):
     """Mirror of ``struct rsa_swin_mlp_block_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('hidden', C.c_int32),
-        ('products', C.c_int32),
-        ('eps', C.c_float),
-        ('x', C.c_void_p),
-        ('gamma', C.c_void_p),
-        ('beta', C.c_void_p),
-        ('w1', C.c_void_p),
-        ('b1', C.c_void_p),
-        ('w2', C.c_void_p),
-        ('b2', C.c_void_p),
-        ('out', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C', 'hidden', 'products') + _f32('eps') + _ptr('x', 'gamma', 'beta', 'w1', 'b1', 'w2', 'b2', 'out')
+        + _plane_fields('out') + _i32('fmt', 'reserved0')
+    )
 
 
 class SwinBlockParams(C.Structure):
     """Mirror of ``struct rsa_swin_block_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('heads', C.c_int32),
-        ('window', C.c_int32),
-        ('shift', C.c_int32),
-        ('hidden', C.c_int32),
-        ('products', C.c_int32),
-        ('eps', C.c_float),
-        ('x', C.c_void_p),
-        ('gamma1', C.c_void_p),
-        ('beta1', C.c_void_p),
-        ('wqkv', C.c_void_p),
-        ('bqkv', C.c_void_p),
-        ('bias_frag16', C.c_void_p),
-        ('wproj', C.c_void_p),
-        ('bproj', C.c_void_p),
-        ('gamma2', C.c_void_p),
-        ('beta2', C.c_void_p),
-        ('w1', C.c_void_p),
-        ('b1', C.c_void_p),
-        ('w2', C.c_void_p),
-        ('b2', C.c_void_p),
-        ('out', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C', 'heads', 'window', 'shift', 'hidden', 'products') + _f32('eps')
+        + _ptr('x', 'gamma1', 'beta1', 'wqkv', 'bqkv', 'bias_frag16', 'wproj', 'bproj', 'gamma2', 'beta2', 'w1', 'b1', 'w2', 'b2')
+        + _ptr('out') + _plane_fields('out') + _i32('fmt', 'reserved0')
+    )
 
 
 class WindowAttnParams(C.Structure):
     """Mirror of ``struct rsa_window_attn_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('heads', C.c_int32),
-        ('window', C.c_int32),
-        ('shift', C.c_int32),
-        ('products', C.c_int32),
-        ('qkv_hi', C.c_void_p),
-        ('qkv_lo', C.c_void_p),
-        ('qkv_plane_stride', C.c_int64),
-        ('qkv_batch_stride', C.c_int64),
-        ('bias_frag', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-    ]
+    _fields_ = _i32('batch', 'H', 'W', 'heads', 'window', 'shift', 'products') + _plane_fields('qkv') + _ptr('bias_frag') + _plane_fields('out')
 
 
 class RectAttnParams(C.Structure):
     """Mirror of ``struct rsa_rect_attn_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('Hp', C.c_int32),
-        ('Wp', C.c_int32),
-        ('win_h', C.c_int32),
-        ('win_w', C.c_int32),
-        ('shift_h', C.c_int32),
-        ('shift_w', C.c_int32),
-        ('heads', C.c_int32),
-        ('head0', C.c_int32),
-        ('heads_total', C.c_int32),
-        ('products', C.c_int32),
-        ('qkv_hi', C.c_void_p),
-        ('qkv_lo', C.c_void_p),
-        ('qkv_plane_stride', C.c_int64),
-        ('qkv_batch_stride', C.c_int64),
-        ('bias_frag', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('kwin_h', C.c_int32),
-        ('kwin_w', C.c_int32),
-        ('kpad_h', C.c_int32),
-        ('kpad_w', C.c_int32),
-        ('head_chunks', C.c_int32),
-        ('fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'Hp', 'Wp', 'win_h', 'win_w', 'shift_h', 'shift_w', 'heads', 'head0', 'heads_total', 'products')
+        + _plane_fields('qkv') + _ptr('bias_frag') + _plane_fields('out')
+        + _i32('kwin_h', 'kwin_w', 'kpad_h', 'kpad_w', 'head_chunks', 'fmt', 'reserved0')
+    )
 
 
 class ChannelAttnParams(C.Structure):
     """Mirror of ``struct rsa_channel_attn_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('heads', C.c_int32),
-        ('head_dim', C.c_int32),
-        ('products', C.c_int32),
-        ('q_hi', C.c_void_p),
-        ('q_lo', C.c_void_p),
-        ('k_hi', C.c_void_p),
-        ('k_lo', C.c_void_p),
-        ('plane_stride', C.c_int64),
-        ('batch_stride', C.c_int64),
-        ('temperature', C.c_void_p),
-        ('workspace', C.c_void_p),
-        ('w_packed', C.c_void_p),
-        ('fmt', C.c_int32),
-        ('reserved1', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'heads', 'head_dim', 'products') + _ptr('q_hi', 'q_lo', 'k_hi', 'k_lo')
+        + _i64('plane_stride', 'batch_stride') + _ptr('temperature', 'workspace', 'w_packed') + _i32('fmt', 'reserved1')
+    )
 
 
 class DwConvParams(C.Structure):
     """Mirror of ``struct rsa_dwconv_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('planes', C.c_int32),
-        ('act', C.c_int32),
-        ('in_hi', C.c_void_p),
-        ('in_lo', C.c_void_p),
-        ('in_plane_stride', C.c_int64),
-        ('in_batch_stride', C.c_int64),
-        ('weight', C.c_void_p),
-        ('bias', C.c_void_p),
-        ('stats', C.c_void_p),
-        ('gamma', C.c_void_p),
-        ('beta', C.c_void_p),
-        ('mul_hi', C.c_void_p),
-        ('mul_lo', C.c_void_p),
-        ('mul_plane_stride', C.c_int64),
-        ('mul_batch_stride', C.c_int64),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('fmt', C.c_int32),
-        ('reserved1', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'planes', 'act') + _plane_fields('in') + _ptr('weight', 'bias', 'stats', 'gamma', 'beta')
+        + _plane_fields('mul') + _plane_fields('out') + _i32('fmt', 'reserved1')
+    )
 
 
 class ChannelGateParams(C.Structure):
     """Mirror of ``struct rsa_channel_gate_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('planes', C.c_int32),
-        ('hidden', C.c_int32),
-        ('in_hi', C.c_void_p),
-        ('in_lo', C.c_void_p),
-        ('in_plane_stride', C.c_int64),
-        ('in_batch_stride', C.c_int64),
-        ('w1', C.c_void_p),
-        ('b1', C.c_void_p),
-        ('w2', C.c_void_p),
-        ('b2', C.c_void_p),
-        ('workspace', C.c_void_p),
-        ('gate', C.c_void_p),
-        ('relu', C.c_int32),
-        ('fmt', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'planes', 'hidden') + _plane_fields('in') + _ptr('w1', 'b1', 'w2', 'b2', 'workspace', 'gate')
+        + _i32('relu', 'fmt')
+    )
 
 
 class GatedShuffleParams(C.Structure):
     """Mirror of ``struct rsa_gated_shuffle_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('g_planes', C.c_int32),
-        ('i_planes', C.c_int32),
-        ('f_hi', C.c_void_p),
-        ('f_lo', C.c_void_p),
-        ('f_plane_stride', C.c_int64),
-        ('f_batch_stride', C.c_int64),
-        ('c_hi', C.c_void_p),
-        ('c_lo', C.c_void_p),
-        ('c_plane_stride', C.c_int64),
-        ('c_batch_stride', C.c_int64),
-        ('gate', C.c_void_p),
-        ('gate_stride', C.c_int64),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'g_planes', 'i_planes') + _plane_fields('f') + _plane_fields('c') + _ptr('gate') + _i64('gate_stride')
+        + _plane_fields('out')
+    )
 
 
 class AimParams(C.Structure):
     """Mirror of ``struct rsa_aim_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('planes', C.c_int32),
-        ('hidden', C.c_int32),
-        ('mode', C.c_int32),
-        ('att_hi', C.c_void_p),
-        ('att_lo', C.c_void_p),
-        ('att_plane_stride', C.c_int64),
-        ('att_batch_stride', C.c_int64),
-        ('conv_hi', C.c_void_p),
-        ('conv_lo', C.c_void_p),
-        ('conv_plane_stride', C.c_int64),
-        ('conv_batch_stride', C.c_int64),
-        ('gate', C.c_void_p),
-        ('w1', C.c_void_p),
-        ('b1', C.c_void_p),
-        ('w2', C.c_void_p),
-        ('b2', C.c_float),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('fmt', C.c_int32),
-        ('reserved1', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'planes', 'hidden', 'mode') + _plane_fields('att') + _plane_fields('conv')
+        + _ptr('gate', 'w1', 'b1', 'w2') + _f32('b2') + _plane_fields('out') + _i32('fmt', 'reserved1')
+    )
 
 
 class PlkConvParams(C.Structure):
     """Mirror of ``struct rsa_plk_conv_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('ksize', C.c_int32),
-        ('planes', C.c_int32),
-        ('products', C.c_int32),
-        ('in_hi', C.c_void_p),
-        ('in_lo', C.c_void_p),
-        ('in_plane_stride', C.c_int64),
-        ('in_batch_stride', C.c_int64),
-        ('w_packed', C.c_void_p),
-        ('bias', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('out_plane_off', C.c_int32),
-        ('fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-        ('reserved1', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'ksize', 'planes', 'products') + _plane_fields('in') + _ptr('w_packed', 'bias') + _plane_fields('out')
+        + _i32('out_plane_off', 'fmt', 'reserved0', 'reserved1')
+    )
 
 
 class GroupNormApplyParams(C.Structure):
     """Mirror of ``struct rsa_group_norm_apply_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('groups', C.c_int32),
-        ('out_fmt', C.c_int32),
-        ('x_f32', C.c_void_p),
-        ('stats', C.c_void_p),
-        ('gamma', C.c_void_p),
-        ('beta', C.c_void_p),
-        ('skip_f32', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('out_f32', C.c_void_p),
-        ('reserved0', C.c_int32),
-        ('reserved1', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C', 'groups', 'out_fmt') + _ptr('x_f32', 'stats', 'gamma', 'beta', 'skip_f32') + _plane_fields('out')
+        + _ptr('out_f32') + _i32('reserved0', 'reserved1')
+    )
 
 
 class EaGateParams(C.Structure):
     """Mirror of ``struct rsa_ea_gate_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('C', C.c_int32),
-        ('g_f32', C.c_void_p),
-        ('x_hi', C.c_void_p),
-        ('x_lo', C.c_void_p),
-        ('x_plane_stride', C.c_int64),
-        ('x_batch_stride', C.c_int64),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = _i32('batch', 'H', 'W', 'C') + _ptr('g_f32') + _plane_fields('x') + _plane_fields('out') + _i32('fmt', 'reserved0')
 
 
 class ResampleConvParams(C.Structure):
     """Mirror of ``struct rsa_resample_conv_params`` (rsa_deconv / rsa_conv_s2)."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('ksize', C.c_int32),
-        ('stride', C.c_int32),
-        ('pad', C.c_int32),
-        ('cin_planes', C.c_int32),
-        ('cout', C.c_int32),
-        ('products', C.c_int32),
-        ('fmt', C.c_int32),
-        ('in_hi', C.c_void_p),
-        ('in_lo', C.c_void_p),
-        ('in_plane_stride', C.c_int64),
-        ('in_batch_stride', C.c_int64),
-        ('in_W', C.c_int32),
-        ('in_y0', C.c_int32),
-        ('in_x0', C.c_int32),
-        ('in_h', C.c_int32),
-        ('in_w', C.c_int32),
-        ('act', C.c_int32),
-        ('act_param', C.c_float),
-        ('reserved0', C.c_int32),
-        ('w_packed', C.c_void_p),
-        ('bias', C.c_void_p),
-        ('res_hi', C.c_void_p),
-        ('res_lo', C.c_void_p),
-        ('res_plane_stride', C.c_int64),
-        ('res_batch_stride', C.c_int64),
-        ('res_W', C.c_int32),
-        ('res_y0', C.c_int32),
-        ('res_x0', C.c_int32),
-        ('out_H', C.c_int32),
-        ('out_W', C.c_int32),
-        ('out_y0', C.c_int32),
-        ('out_x0', C.c_int32),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('out_f32', C.c_void_p),
-        ('reserved1', C.c_int32),
-    ]
+    _fields_ = (
+        _i32('batch', 'ksize', 'stride', 'pad', 'cin_planes', 'cout', 'products', 'fmt') + _plane_fields('in')
+        + _i32('in_W', 'in_y0', 'in_x0', 'in_h', 'in_w', 'act') + _f32('act_param') + _i32('reserved0') + _ptr('w_packed', 'bias')
+        + _plane_fields('res') + _i32('res_W', 'res_y0', 'res_x0', 'out_H', 'out_W', 'out_y0', 'out_x0') + _plane_fields('out')
+        + _ptr('out_f32') + _i32('reserved1')
+    )
 
 
 class RegionSEParams(C.Structure):
     """Mirror of ``struct rsa_region_se_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('planes', C.c_int32),
-        ('hidden', C.c_int32),
-        ('fmt', C.c_int32),
-        ('x_hi', C.c_void_p),
-        ('x_lo', C.c_void_p),
-        ('x_plane_stride', C.c_int64),
-        ('x_batch_stride', C.c_int64),
-        ('W', C.c_int32),
-        ('y0', C.c_int32),
-        ('x0', C.c_int32),
-        ('h', C.c_int32),
-        ('w', C.c_int32),
-        ('reserved0', C.c_int32),
-        ('w1', C.c_void_p),
-        ('b1', C.c_void_p),
-        ('w2', C.c_void_p),
-        ('b2', C.c_void_p),
-        ('workspace', C.c_void_p),
-        ('gate', C.c_void_p),
-    ]
+    _fields_ = (
+        _i32('batch', 'planes', 'hidden', 'fmt') + _plane_fields('x') + _i32('W', 'y0', 'x0', 'h', 'w', 'reserved0')
+        + _ptr('w1', 'b1', 'w2', 'b2', 'workspace', 'gate')
+    )
 
 
 class CuganInputParams(C.Structure):
     """Mirror of ``struct rsa_cugan_input_params``."""
 
-    _fields_ = [
-        ('x', C.c_void_p),
-        ('dtype', C.c_int32),
-        ('batch', C.c_int32),
-        ('C', C.c_int32),
-        ('h', C.c_int32),
-        ('w', C.c_int32),
-        ('pad_top', C.c_int32),
-        ('pad_left', C.c_int32),
-        ('unshuffle', C.c_int32),
-        ('in_scale', C.c_float),
-        ('in_shift', C.c_float),
-        ('out_H', C.c_int32),
-        ('out_W', C.c_int32),
-        ('fmt', C.c_int32),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = (
+        _ptr('x') + _i32('dtype', 'batch', 'C', 'h', 'w', 'pad_top', 'pad_left', 'unshuffle') + _f32('in_scale', 'in_shift')
+        + _i32('out_H', 'out_W', 'fmt') + _plane_fields('out') + _i32('reserved0')
+    )
 
 
 class CuganOutputParams(C.Structure):
     """Mirror of ``struct rsa_cugan_output_params``."""
 
-    _fields_ = [
-        ('map', C.c_void_p),
-        ('batch', C.c_int32),
-        ('C', C.c_int32),
-        ('map_H', C.c_int32),
-        ('map_W', C.c_int32),
-        ('y0', C.c_int32),
-        ('x0', C.c_int32),
-        ('pixel_shuffle', C.c_int32),
-        ('out_h', C.c_int32),
-        ('out_w', C.c_int32),
-        ('dtype', C.c_int32),
-        ('out', C.c_void_p),
-        ('base', C.c_void_p),
-        ('base_h', C.c_int32),
-        ('base_w', C.c_int32),
-        ('base_div', C.c_int32),
-        ('base_scale', C.c_float),
-        ('base_shift', C.c_float),
-        ('out_shift', C.c_float),
-        ('out_div', C.c_float),
-        ('reserved0', C.c_int32),
-    ]
+    _fields_ = (
+        _ptr('map') + _i32('batch', 'C', 'map_H', 'map_W', 'y0', 'x0', 'pixel_shuffle', 'out_h', 'out_w', 'dtype') + _ptr('out', 'base')
+        + _i32('base_h', 'base_w', 'base_div') + _f32('base_scale', 'base_shift', 'out_shift', 'out_div') + _i32('reserved0')
+    )
 
 
 class GatedDwConvSegment(C.Structure):
     """Mirror of ``struct rsa_gated_dwconv_segment``."""
 
-    _fields_ = [
-        ('planes', C.c_int32),
-        ('kh', C.c_int32),
-        ('kw', C.c_int32),
-        ('reserved0', C.c_int32),
-        ('weight', C.c_void_p),
-        ('bias', C.c_void_p),
-    ]
+    _fields_ = _i32('planes', 'kh', 'kw', 'reserved0') + _ptr('weight', 'bias')
 
 
 class GatedDwConvParams(C.Structure):
     """Mirror of ``struct rsa_gated_dwconv_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('fmt', C.c_int32),
-        ('i_planes', C.c_int32),
-        ('n_segments', C.c_int32),
-        ('seg', GatedDwConvSegment * 4),
-        ('g_hi', C.c_void_p),
-        ('g_lo', C.c_void_p),
-        ('g_plane_stride', C.c_int64),
-        ('g_batch_stride', C.c_int64),
-        ('x_hi', C.c_void_p),
-        ('x_lo', C.c_void_p),
-        ('x_plane_stride', C.c_int64),
-        ('x_batch_stride', C.c_int64),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'fmt', 'i_planes', 'n_segments') + [('seg', GatedDwConvSegment * 4)] + _plane_fields('g')
+        + _plane_fields('x') + _plane_fields('out')
+    )
 
 
 class BilinearAddParams(C.Structure):
     """Mirror of ``struct rsa_bilinear_add_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('C', C.c_int32),
-        ('h', C.c_int32),
-        ('w', C.c_int32),
-        ('pad_h', C.c_int32),
-        ('pad_w', C.c_int32),
-        ('scale', C.c_int32),
-        ('dtype', C.c_int32),
-        ('out_H', C.c_int32),
-        ('out_W', C.c_int32),
-        ('out_h', C.c_int32),
-        ('out_w', C.c_int32),
-        ('x', C.c_void_p),
-        ('out', C.c_void_p),
-    ]
+    _fields_ = _i32('batch', 'C', 'h', 'w', 'pad_h', 'pad_w', 'scale', 'dtype', 'out_H', 'out_W', 'out_h', 'out_w') + _ptr('x', 'out')
 
 
 class RgAttnParams(C.Structure):
     """Mirror of ``struct rsa_rg_attn_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('heads', C.c_int32),
-        ('nkeys', C.c_int32),
-        ('dim_qk', C.c_int32),
-        ('dim_v', C.c_int32),
-        ('products', C.c_int32),
-        ('fmt', C.c_int32),
-        ('reserved0', C.c_int32),
-        ('q_hi', C.c_void_p),
-        ('q_lo', C.c_void_p),
-        ('q_plane_stride', C.c_int64),
-        ('q_batch_stride', C.c_int64),
-        ('k_hi', C.c_void_p),
-        ('k_lo', C.c_void_p),
-        ('k_plane_stride', C.c_int64),
-        ('k_batch_stride', C.c_int64),
-        ('v_hi', C.c_void_p),
-        ('v_lo', C.c_void_p),
-        ('v_plane_stride', C.c_int64),
-        ('v_batch_stride', C.c_int64),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'heads', 'nkeys', 'dim_qk', 'dim_v', 'products', 'fmt', 'reserved0') + _plane_fields('q')
+        + _plane_fields('k') + _plane_fields('v') + _plane_fields('out')
+    )
 
 
 class RgReduceParams(C.Structure):
     """Mirror of ``struct rsa_rg_reduce_params``."""
 
-    _fields_ = [
-        ('batch', C.c_int32),
-        ('H', C.c_int32),
-        ('W', C.c_int32),
-        ('planes', C.c_int32),
-        ('times', C.c_int32),
-        ('fmt', C.c_int32),
-        ('in_hi', C.c_void_p),
-        ('in_lo', C.c_void_p),
-        ('in_plane_stride', C.c_int64),
-        ('in_batch_stride', C.c_int64),
-        ('weight', C.c_void_p),
-        ('bias', C.c_void_p),
-        ('out_hi', C.c_void_p),
-        ('out_lo', C.c_void_p),
-        ('out_plane_stride', C.c_int64),
-        ('out_batch_stride', C.c_int64),
-    ]
-
-
-def _plane_fields(prefix: str) -> list:
-    return [(f'{prefix}_hi', C.c_void_p), (f'{prefix}_lo', C.c_void_p), (f'{prefix}_plane_stride', C.c_int64), (f'{prefix}_batch_stride', C.c_int64)]
+    _fields_ = _i32('batch', 'H', 'W', 'planes', 'times', 'fmt') + _plane_fields('in') + _ptr('weight', 'bias') + _plane_fields('out')
 
 
 class FdatInteractParams(C.Structure):
     """Mirror of ``struct rsa_fdat_interact_params``."""
 
     _fields_ = (
-        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('mode', C.c_int32), ('fmt', C.c_int32)]
-        + _plane_fields('a')
-        + _plane_fields('c')
-        + [('cm', C.c_void_p), ('w', C.c_void_p), ('x', C.c_void_p), ('x_out', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p)]
-        + [('eps', C.c_float), ('reserved0', C.c_int32)]
-        + _plane_fields('out')
+        _i32('batch', 'H', 'W', 'C', 'mode', 'fmt') + _plane_fields('a') + _plane_fields('c')
+        + _ptr('cm', 'w', 'x', 'x_out', 'gamma', 'beta') + _f32('eps') + _i32('reserved0') + _plane_fields('out')
     )
 
 
@@ -749,11 +278,8 @@ class LdaOffsetsParams(C.Structure):
     """Mirror of ``struct rsa_lda_offsets_params``."""
 
     _fields_ = (
-        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Hout', C.c_int32), ('Wout', C.c_int32), ('hidden', C.c_int32)]
-        + [('groups', C.c_int32), ('fmt', C.c_int32)]
-        + _plane_fields('q')
-        + [('dw_weight', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('eps', C.c_float), ('reserved0', C.c_int32)]
-        + _plane_fields('out')
+        _i32('batch', 'H', 'W', 'Hout', 'Wout', 'hidden', 'groups', 'fmt') + _plane_fields('q') + _ptr('dw_weight', 'gamma', 'beta')
+        + _f32('eps') + _i32('reserved0') + _plane_fields('out')
     )
 
 
@@ -761,13 +287,8 @@ class LdaAttnParams(C.Structure):
     """Mirror of ``struct rsa_lda_attn_params``."""
 
     _fields_ = (
-        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Hout', C.c_int32), ('Wout', C.c_int32), ('hidden', C.c_int32)]
-        + [('C', C.c_int32), ('groups', C.c_int32), ('fmt', C.c_int32), ('range', C.c_float), ('scale', C.c_float), ('reserved0', C.c_int32)]
-        + _plane_fields('q')
-        + _plane_fields('k')
-        + _plane_fields('v')
-        + [('offset', C.c_void_p), ('rpb', C.c_void_p)]
-        + _plane_fields('out')
+        _i32('batch', 'H', 'W', 'Hout', 'Wout', 'hidden', 'C', 'groups', 'fmt') + _f32('range', 'scale') + _i32('reserved0')
+        + _plane_fields('q') + _plane_fields('k') + _plane_fields('v') + _ptr('offset', 'rpb') + _plane_fields('out')
     )
 
 
@@ -775,84 +296,63 @@ class OmniAttnParams(C.Structure):
     """Mirror of ``struct rsa_omni_attn_params``."""
 
     _fields_ = (
-        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('ws', C.c_int32), ('heads', C.c_int32), ('head_dim', C.c_int32)]
-        + [('grid', C.c_int32), ('fmt', C.c_int32)]
-        + _plane_fields('qkv')
-        + [('bias_table', C.c_void_p), ('temperature', C.c_void_p), ('workspace', C.c_void_p)]
-        + _plane_fields('out')
+        _i32('batch', 'H', 'W', 'ws', 'heads', 'head_dim', 'grid', 'fmt') + _plane_fields('qkv')
+        + _ptr('bias_table', 'temperature', 'workspace') + _plane_fields('out')
     )
 
 
 class GeluGateDwConvParams(C.Structure):
     """Mirror of ``struct rsa_gelu_gate_dwconv_params``."""
 
-    _fields_ = (
-        [('batch', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('planes', C.c_int32), ('fmt', C.c_int32), ('reserved0', C.c_int32)]
-        + _plane_fields('in')
-        + [('weight', C.c_void_p)]
-        + _plane_fields('out')
-    )
+    _fields_ = _i32('batch', 'H', 'W', 'planes', 'fmt', 'reserved0') + _plane_fields('in') + _ptr('weight') + _plane_fields('out')
 
 
 class EsaConvParams(C.Structure):
     """Mirror of ``struct rsa_esa_conv_params``."""
 
-    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'Hout', 'Wout', 'cin', 'cout', 'stride', 'pad', 'reserved0')] + [
-        ('in_', C.c_void_p),
-        ('weight', C.c_void_p),
-        ('bias', C.c_void_p),
-        ('out', C.c_void_p),
-    ]
+    _fields_ = _i32('batch', 'H', 'W', 'Hout', 'Wout', 'cin', 'cout', 'stride', 'pad', 'reserved0') + _ptr('in_', 'weight', 'bias', 'out')
 
 
 class EsaApplyParams(C.Structure):
     """Mirror of ``struct rsa_esa_apply_params``."""
 
-    _fields_ = (
-        [(k, C.c_int32) for k in ('batch', 'H', 'W', 'C', 'f', 'Hc', 'Wc', 'fmt')]
-        + [(k, C.c_void_p) for k in ('x', 'c1', 'c3', 'wf', 'bf', 'w4', 'b4', 'out')]
-        + _plane_fields('out')
-    )
+    _fields_ = _i32('batch', 'H', 'W', 'C', 'f', 'Hc', 'Wc', 'fmt') + _ptr('x', 'c1', 'c3', 'wf', 'bf', 'w4', 'b4', 'out') + _plane_fields('out')
 
 
 class AtdDictParams(C.Structure):
     """Mirror of ``struct rsa_atd_dict_params``."""
 
-    _fields_ = [(k, C.c_int32) for k in ('batch', 'C', 'm', 'rc')] + [(k, C.c_void_p) for k in ('td', 'wk', 'bk', 'wv', 'bv', 'kn', 'vt_hi', 'vt_lo')]
+    _fields_ = _i32('batch', 'C', 'm', 'rc') + _ptr('td', 'wk', 'bk', 'wv', 'bv', 'kn', 'vt_hi', 'vt_lo')
 
 
 class AtdCaParams(C.Structure):
     """Mirror of ``struct rsa_atd_ca_params``."""
 
-    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'C', 'm', 'rc', 'products', 'reserved0')] + [
-        (k, C.c_void_p) for k in ('xn', 'wq', 'bq', 'kn', 'scale', 'vt_hi', 'vt_lo', 'sim', 'ids', 'out')
-    ]
+    _fields_ = (
+        _i32('batch', 'H', 'W', 'C', 'm', 'rc', 'products', 'reserved0')
+        + _ptr('xn', 'wq', 'bq', 'kn', 'scale', 'vt_hi', 'vt_lo', 'sim', 'ids', 'out')
+    )
 
 
 class AtdAttnParams(C.Structure):
     """Mirror of ``struct rsa_atd_attn_params``."""
 
     _fields_ = (
-        [(k, C.c_int32) for k in ('batch', 'H', 'W', 'heads', 'head_dim', 'mode', 'ws', 'shift', 'gs', 'products')]
-        + [('scale', C.c_float), ('reserved0', C.c_int32)]
-        + _plane_fields('qkv')
-        + [('bias_table', C.c_void_p), ('perm', C.c_void_p)]
-        + _plane_fields('out')
+        _i32('batch', 'H', 'W', 'heads', 'head_dim', 'mode', 'ws', 'shift', 'gs', 'products') + _f32('scale') + _i32('reserved0')
+        + _plane_fields('qkv') + _ptr('bias_table', 'perm') + _plane_fields('out')
     )
 
 
 class AtdDwConvParams(C.Structure):
     """Mirror of ``struct rsa_atd_dwconv_params``."""
 
-    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'planes')] + _plane_fields('in') + [('weight', C.c_void_p), ('bias', C.c_void_p)] + _plane_fields('out')
+    _fields_ = _i32('batch', 'H', 'W', 'planes') + _plane_fields('in') + _ptr('weight', 'bias') + _plane_fields('out')
 
 
 class AtdRefineParams(C.Structure):
     """Mirror of ``struct rsa_atd_refine_params``."""
 
-    _fields_ = [(k, C.c_int32) for k in ('batch', 'H', 'W', 'C', 'm')] + [('eps', C.c_float)] + [
-        (k, C.c_void_p) for k in ('sim', 'x', 'gamma', 'beta', 'sigma', 'td', 'workspace')
-    ]
+    _fields_ = _i32('batch', 'H', 'W', 'C', 'm') + _f32('eps') + _ptr('sim', 'x', 'gamma', 'beta', 'sigma', 'td', 'workspace')
 
 
 # every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
@@ -941,6 +441,51 @@ EXPORTS = (
 )
 
 
+# the entry points that take (descriptor*, stream) and return a status: symbol -> descriptor
+DESCRIPTOR_CALLS = {
+    'rsa_conv2d': ConvParams,
+    'rsa_dysample': DySampleParams,
+    'rsa_layernorm': LayerNormParams,
+    'rsa_layernorm_gelu': LayerNormParams,
+    'rsa_window_attention': WindowAttnParams,
+    'rsa_swin_attn_block': SwinAttnBlockParams,
+    'rsa_swin_mlp_block': SwinMlpBlockParams,
+    'rsa_swin_block': SwinBlockParams,
+    'rsa_rect_attention': RectAttnParams,
+    'rsa_channel_attention_weights': ChannelAttnParams,
+    'rsa_dwconv3x3': DwConvParams,
+    'rsa_dwconv5x5': DwConvParams,
+    'rsa_channel_gate': ChannelGateParams,
+    'rsa_aim_combine': AimParams,
+    'rsa_gated_shuffle_mul': GatedShuffleParams,
+    'rsa_plk_conv': PlkConvParams,
+    'rsa_group_norm_apply': GroupNormApplyParams,
+    'rsa_ea_gate': EaGateParams,
+    'rsa_deconv': ResampleConvParams,
+    'rsa_conv_s2': ResampleConvParams,
+    'rsa_region_se': RegionSEParams,
+    'rsa_cugan_input': CuganInputParams,
+    'rsa_cugan_output': CuganOutputParams,
+    'rsa_gated_dwconv': GatedDwConvParams,
+    'rsa_bilinear_add': BilinearAddParams,
+    'rsa_rg_attention': RgAttnParams,
+    'rsa_rg_reduce': RgReduceParams,
+    'rsa_fdat_interact': FdatInteractParams,
+    'rsa_lda_offsets': LdaOffsetsParams,
+    'rsa_lda_attention': LdaAttnParams,
+    'rsa_omni_window_attention': OmniAttnParams,
+    'rsa_omni_channel_attention': OmniAttnParams,
+    'rsa_gelu_gate_dwconv': GeluGateDwConvParams,
+    'rsa_esa_conv3x3': EsaConvParams,
+    'rsa_esa_apply': EsaApplyParams,
+    'rsa_atd_dict': AtdDictParams,
+    'rsa_atd_ca': AtdCaParams,
+    'rsa_atd_attention': AtdAttnParams,
+    'rsa_atd_dwconv': AtdDwConvParams,
+    'rsa_atd_refine': AtdRefineParams,
+}
+
+
 def lib_path() -> str:
     """The in-tree library; RSA_LIB=path selects an experiment build instead (tools/variant.sh: A/B timing, ablations)."""
     override = os.environ.get('RSA_LIB')
@@ -987,135 +532,53 @@ def load() -> C.CDLL:
             raise RuntimeError(f'{path} does not export {name}; rebuild the library')
     lib.rsa_version.restype = C.c_int
     lib.rsa_last_error_string.restype = C.c_char_p
-    lib.rsa_conv2d.argtypes = [C.POINTER(ConvParams), C.c_void_p]
-    lib.rsa_conv2d.restype = C.c_int
-    lib.rsa_conv2d_list.argtypes = [C.POINTER(ConvParams), C.c_int32, C.c_void_p]
-    lib.rsa_conv2d_list.restype = C.c_int
-    lib.rsa_conv_cout_tiles.argtypes = [C.c_int32]
-    lib.rsa_conv_cout_tiles.restype = C.c_int
-    lib.rsa_packed_weight_bytes.argtypes = [C.c_int32] * 4
-    lib.rsa_packed_weight_bytes.restype = C.c_int64
-    lib.rsa_packed_weight_bytes_layout.argtypes = [C.c_int32] * 5
-    lib.rsa_packed_weight_bytes_layout.restype = C.c_int64
-    lib.rsa_conv_weight_layout.argtypes = [C.POINTER(ConvParams)]
-    lib.rsa_conv_weight_layout.restype = C.c_int
-    lib.rsa_pack_weights.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rsa_pack_weights.restype = C.c_int
-    lib.rsa_conv_kernel_name.argtypes = [C.POINTER(ConvParams)]
-    lib.rsa_conv_kernel_name.restype = C.c_char_p
-    lib.rsa_debug_ring_aborts.argtypes = []
-    lib.rsa_debug_ring_aborts.restype = C.c_int
-    lib.rsa_debug_set_ring.argtypes = [C.c_int32]
-    lib.rsa_debug_set_ring.restype = C.c_int
-    lib.rsa_debug_set_pair.argtypes = [C.c_int32]
-    lib.rsa_debug_set_pair.restype = C.c_int
-    lib.rsa_conv2d_pair.argtypes = [C.POINTER(ConvParams), C.POINTER(ConvParams), C.c_void_p]
-    lib.rsa_conv2d_pair.restype = C.c_int
-    lib.rsa_conv_pair_fusable.argtypes = [C.POINTER(ConvParams), C.POINTER(ConvParams)]
-    lib.rsa_conv_pair_fusable.restype = C.c_int
-    lib.rsa_debug_set_ring_spin_limit.argtypes = [C.c_int32]
-    lib.rsa_debug_set_ring_spin_limit.restype = C.c_int
-    lib.rsa_check_finite.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
-    lib.rsa_check_finite.restype = C.c_int
-    lib.rsa_check_status.argtypes = []
-    lib.rsa_check_status.restype = C.c_int
-    lib.rsa_nchw_to_planes.argtypes = [
-        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float,
-        C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
-    ]  # fmt: skip
-    lib.rsa_nchw_to_planes.restype = C.c_int
-    lib.rsa_planes_to_nchw.argtypes = [
-        C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-    ]  # fmt: skip
-    lib.rsa_planes_to_nchw.restype = C.c_int
-    lib.rsa_dysample.argtypes = [C.POINTER(DySampleParams), C.c_void_p]
-    lib.rsa_dysample.restype = C.c_int
-    lib.rsa_layernorm.argtypes = [C.POINTER(LayerNormParams), C.c_void_p]
-    lib.rsa_layernorm.restype = C.c_int
-    lib.rsa_window_attention.argtypes = [C.POINTER(WindowAttnParams), C.c_void_p]
-    lib.rsa_window_attention.restype = C.c_int
-    lib.rsa_swin_attn_block.argtypes = [C.POINTER(SwinAttnBlockParams), C.c_void_p]
-    lib.rsa_swin_attn_block.restype = C.c_int
-    lib.rsa_swin_mlp_block.argtypes = [C.POINTER(SwinMlpBlockParams), C.c_void_p]
-    lib.rsa_swin_mlp_block.restype = C.c_int
-    lib.rsa_swin_block.argtypes = [C.POINTER(SwinBlockParams), C.c_void_p]
-    lib.rsa_swin_block.restype = C.c_int
-    for name, struct in (('rsa_rect_attention', RectAttnParams), ('rsa_channel_attention_weights', ChannelAttnParams), ('rsa_dwconv3x3', DwConvParams),
-                         ('rsa_channel_gate', ChannelGateParams), ('rsa_aim_combine', AimParams)):  # fmt: skip
+    for name, struct in DESCRIPTOR_CALLS.items():
         getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
         getattr(lib, name).restype = C.c_int
-    lib.rsa_channel_attn_workspace_bytes.argtypes = [C.c_int32] * 4
-    lib.rsa_channel_attn_workspace_bytes.restype = C.c_int64
-    lib.rsa_channel_gate_workspace_bytes.argtypes = [C.c_int32] * 4
-    lib.rsa_channel_gate_workspace_bytes.restype = C.c_int64
-    lib.rsa_plane_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
-                                    C.c_void_p]  # fmt: skip
-    lib.rsa_plane_stats.restype = C.c_int
-    lib.rsa_plane_stats_fmt.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                        C.c_void_p, C.c_void_p]  # fmt: skip
-    lib.rsa_plane_stats_fmt.restype = C.c_int
-    lib.rsa_dwconv5x5.argtypes = [C.POINTER(DwConvParams), C.c_void_p]
-    lib.rsa_dwconv5x5.restype = C.c_int
-    lib.rsa_gated_shuffle_mul.argtypes = [C.POINTER(GatedShuffleParams), C.c_void_p]
-    lib.rsa_gated_shuffle_mul.restype = C.c_int
-    lib.rsa_rmsnorm.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_int64, C.c_int64, C.c_void_p]  # fmt: skip
-    lib.rsa_rmsnorm.restype = C.c_int
-    lib.rsa_unshuffle_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]  # fmt: skip
-    lib.rsa_unshuffle_pool.restype = C.c_int
-    lib.rsa_gated_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]  # fmt: skip
-    lib.rsa_gated_add.restype = C.c_int
-    lib.rsa_image_u8_to_nchw.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.rsa_image_u8_to_nchw.restype = C.c_int
-    lib.rsa_nchw_to_image_u8.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rsa_nchw_to_image_u8.restype = C.c_int
-    lib.rsa_plk_packed_weight_bytes.argtypes = [C.c_int32] * 3
-    lib.rsa_plk_packed_weight_bytes.restype = C.c_int64
-    lib.rsa_plk_conv.argtypes = [C.POINTER(PlkConvParams), C.c_void_p]
-    lib.rsa_plk_conv.restype = C.c_int
-    lib.rsa_group_norm_workspace_bytes.argtypes = [C.c_int32] * 4
-    lib.rsa_group_norm_workspace_bytes.restype = C.c_int64
-    lib.rsa_group_norm_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsa_group_norm_stats.restype = C.c_int
-    lib.rsa_group_norm_apply.argtypes = [C.POINTER(GroupNormApplyParams), C.c_void_p]
-    lib.rsa_group_norm_apply.restype = C.c_int
-    lib.rsa_ea_gate.argtypes = [C.POINTER(EaGateParams), C.c_void_p]
-    lib.rsa_ea_gate.restype = C.c_int
-    lib.rsa_resample_packed_weight_bytes.argtypes = [C.c_int32] * 6
-    lib.rsa_resample_packed_weight_bytes.restype = C.c_int64
-    lib.rsa_region_se_workspace_bytes.argtypes = [C.c_int32] * 3
-    lib.rsa_region_se_workspace_bytes.restype = C.c_int64
-    for name, struct in (('rsa_deconv', ResampleConvParams), ('rsa_conv_s2', ResampleConvParams), ('rsa_region_se', RegionSEParams),
-                         ('rsa_cugan_input', CuganInputParams), ('rsa_cugan_output', CuganOutputParams), ('rsa_gated_dwconv', GatedDwConvParams),
-                         ('rsa_bilinear_add', BilinearAddParams), ('rsa_rg_attention', RgAttnParams), ('rsa_rg_reduce', RgReduceParams),
-                         ('rsa_layernorm_gelu', LayerNormParams), ('rsa_fdat_interact', FdatInteractParams), ('rsa_lda_offsets', LdaOffsetsParams),
-                         ('rsa_lda_attention', LdaAttnParams), ('rsa_omni_window_attention', OmniAttnParams),
-                         ('rsa_omni_channel_attention', OmniAttnParams), ('rsa_gelu_gate_dwconv', GeluGateDwConvParams),
-                         ('rsa_esa_conv3x3', EsaConvParams), ('rsa_esa_apply', EsaApplyParams)):  # fmt: skip
-        getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
-        getattr(lib, name).restype = C.c_int
-    lib.rsa_scale_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.rsa_scale_add.restype = C.c_int
-    lib.rsa_pa_gate.argtypes = [C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsa_pa_gate.restype = C.c_int
-    lib.rsa_omni_channel_attn_workspace_bytes.argtypes = [C.c_int32] * 7
-    lib.rsa_omni_channel_attn_workspace_bytes.restype = C.c_int64
-    lib.rsa_omni_gate_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
-    lib.rsa_omni_gate_scale.restype = C.c_int
-    for name, struct in (('rsa_atd_dict', AtdDictParams), ('rsa_atd_ca', AtdCaParams), ('rsa_atd_attention', AtdAttnParams),
-                         ('rsa_atd_dwconv', AtdDwConvParams), ('rsa_atd_refine', AtdRefineParams)):  # fmt: skip
-        getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
-        getattr(lib, name).restype = C.c_int
-    lib.rsa_atd_sort_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
-    lib.rsa_atd_sort_workspace_bytes.restype = C.c_int64
-    lib.rsa_atd_sort.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsa_atd_sort.restype = C.c_int
-    lib.rsa_atd_refine_workspace_bytes.argtypes = [C.c_int32] * 5
-    lib.rsa_atd_refine_workspace_bytes.restype = C.c_int64
-    lib.rsa_esa_maxpool.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
-    lib.rsa_esa_maxpool.restype = C.c_int
+    i32, i64, f32, ptr, cp = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.POINTER(ConvParams)
+    for name, restype, argtypes in (
+        ('rsa_conv2d_list', C.c_int, [cp, i32, ptr]),
+        ('rsa_conv_cout_tiles', C.c_int, [i32]),
+        ('rsa_packed_weight_bytes', i64, [i32] * 4),
+        ('rsa_packed_weight_bytes_layout', i64, [i32] * 5),
+        ('rsa_conv_weight_layout', C.c_int, [cp]),
+        ('rsa_pack_weights', C.c_int, [ptr] + [i32] * 7 + [ptr, ptr]),
+        ('rsa_conv_kernel_name', C.c_char_p, [cp]),
+        ('rsa_debug_ring_aborts', C.c_int, []),
+        ('rsa_debug_set_ring', C.c_int, [i32]),
+        ('rsa_debug_set_pair', C.c_int, [i32]),
+        ('rsa_conv2d_pair', C.c_int, [cp, cp, ptr]),
+        ('rsa_conv_pair_fusable', C.c_int, [cp, cp]),
+        ('rsa_debug_set_ring_spin_limit', C.c_int, [i32]),
+        ('rsa_check_finite', C.c_int, [ptr, i32, i64, ptr]),
+        ('rsa_check_status', C.c_int, []),
+        ('rsa_nchw_to_planes', C.c_int, [ptr] + [i32] * 8 + [ptr, f32, ptr, ptr, i64, i64, i32, ptr]),
+        ('rsa_planes_to_nchw', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr]),
+        ('rsa_channel_attn_workspace_bytes', i64, [i32] * 4),
+        ('rsa_channel_gate_workspace_bytes', i64, [i32] * 4),
+        ('rsa_plane_stats', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [f32, ptr, ptr]),
+        ('rsa_plane_stats_fmt', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [f32, i32, ptr, ptr]),
+        ('rsa_rmsnorm', C.c_int, [ptr] + [i32] * 4 + [f32] + [ptr] * 4 + [i64, i64, ptr]),
+        ('rsa_unshuffle_pool', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [ptr] * 3 + [i64, i64, ptr]),
+        ('rsa_gated_add', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [ptr, f32, ptr, ptr, ptr]),
+        ('rsa_image_u8_to_nchw', C.c_int, [ptr] + [i32] * 4 + [ptr, i32, ptr]),
+        ('rsa_nchw_to_image_u8', C.c_int, [ptr] + [i32] * 5 + [ptr, ptr]),
+        ('rsa_plk_packed_weight_bytes', i64, [i32] * 3),
+        ('rsa_group_norm_workspace_bytes', i64, [i32] * 4),
+        ('rsa_group_norm_stats', C.c_int, [ptr] + [i32] * 5 + [f32, ptr, ptr, ptr]),
+        ('rsa_resample_packed_weight_bytes', i64, [i32] * 6),
+        ('rsa_region_se_workspace_bytes', i64, [i32] * 3),
+        ('rsa_scale_add', C.c_int, [ptr] * 3 + [i32] * 4 + [ptr]),
+        ('rsa_pa_gate', C.c_int, [ptr] * 4 + [i64] * 2 + [i32] * 4 + [f32, i32, ptr, ptr, ptr]),
+        ('rsa_omni_channel_attn_workspace_bytes', i64, [i32] * 7),
+        ('rsa_omni_gate_scale', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [ptr, i32] + [ptr] * 3),
+        ('rsa_atd_sort_workspace_bytes', i64, [i32, i64]),
+        ('rsa_atd_sort', C.c_int, [ptr, i32, i64, i32] + [ptr] * 4),
+        ('rsa_atd_refine_workspace_bytes', i64, [i32] * 5),
+        ('rsa_esa_maxpool', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr]),
+    ):
+        getattr(lib, name).argtypes = argtypes
+        getattr(lib, name).restype = restype
     _lib = lib
     return lib
 

@@ -21,6 +21,15 @@ PF_BF16, PF_F16 = 0, 1  # enum rsa_plane_fmt
 _PF_DTYPE = {PF_BF16: torch.bfloat16, PF_F16: torch.float16}
 
 
+def _bind(self, params, prefix: str, plane0: int = 0) -> None:
+    """Fill the split-plane operand ``prefix`` of a launch descriptor (``{prefix}_hi``, ``_lo``, ``_plane_stride``, ``_batch_stride``) from this
+    buffer, starting at plane ``plane0``.  ``_lo`` is NULL when the buffer carries no lo halves; nothing else of the descriptor is touched."""
+    setattr(params, f'{prefix}_hi', self.hi_ptr(plane0))
+    setattr(params, f'{prefix}_lo', self.lo_ptr(plane0))
+    setattr(params, f'{prefix}_plane_stride', self.plane_stride)
+    setattr(params, f'{prefix}_batch_stride', self.batch_stride)
+
+
 @dataclass
 class Planes:
     hi: torch.Tensor  # [N, P, H, W, 8] bf16 or fp16 (dense, or the first P planes of a [N, P + lo_planes, ...] allocation)
@@ -84,6 +93,8 @@ class Planes:
             return None
         return self.lo.data_ptr() + plane * self.plane_stride * 16
 
+    bind = _bind
+
     def has_lo(self, plane0: int, nplanes: int) -> bool:
         """Whether planes [plane0, plane0 + nplanes) all carry lo halves."""
         return self.lo is not None and plane0 + nplanes <= self.lo.shape[1]
@@ -129,6 +140,8 @@ class PlaneRows:
     def lo_ptr(self, plane: int = 0) -> int | None:
         p = self.base.lo_ptr(plane)
         return None if p is None else p + self.r0 * self.base.w * 16
+
+    bind = _bind
 
     def has_lo(self, plane0: int, nplanes: int) -> bool:
         return self.base.has_lo(plane0, nplanes)

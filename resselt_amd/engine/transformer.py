@@ -1,13 +1,15 @@
-"""Host-side plumbing shared by the window-attention transformers (SwinIR, HAT, DRCT, DAT).
+"""Host-side plumbing shared by the window-attention transformers (SwinIR, HAT, DRCT, DAT, RGT, ATD).
 
 Geometry and weight re-layouts are pure torch (CPU-testable): relative-position indices, shift masks, the head-padded qkv / proj
 permutations and the gathers of position-bias tables into the attention kernels' accumulator-fragment order.  The plan helpers emit
-the steps every one of these models shares: the per-layer weight packer, LayerNorm, the pixel-shuffle reconstruction head and the
-fused MLP half of csrc/swin_block.hip.
+the steps these models share: the per-layer weight packer, LayerNorm, the 1conv / 3conv residual tail, the reconstruction heads (each with
+its parameter shapes, packing, plan step and MAC count side by side), the two-branch rectangular-window attention, the depthwise 3x3
+convolution, the per-pixel statistics and the fused MLP half of csrc/swin_block.hip.
 """
 
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import torch
@@ -202,11 +204,115 @@ def layernorm(plan, W, name, n, H, Wd, C, x_f32, out_planes=None, out_f32=None) 
     lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, C, 1e-5
     lp.x_f32, lp.gamma, lp.beta = x_f32.data_ptr(), g.data_ptr(), b.data_ptr()
     if out_planes is not None:
-        lp.out_hi, lp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-        lp.out_plane_stride, lp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
+        out_planes.bind(lp, 'out')
         lp.out_fmt = out_planes.fmt
     lp.out_f32 = None if out_f32 is None else out_f32.data_ptr()
     plan.launch('rsa_layernorm', lp)
+
+
+def layernorm_on(plan, W, n, H, Wd, C_):
+    """``norm(name, x_f32, out_planes=None, out_f32=None)``: ``layernorm`` on one plan's token grid."""
+    return lambda name, x_f32, out_planes=None, out_f32=None: layernorm(plan, W, name, n, H, Wd, C_, x_f32, out_planes, out_f32)
+
+
+# ---------------------------------------------------------------- the 1conv / 3conv tail of a residual group (and conv_after_body)
+def tail_layers(name: str, resi: str) -> list[str]:
+    """Names of the convolutions of the tail ``name``: one 3x3, or 3x3 (C -> C/4), 1x1, 3x3 (C/4 -> C) with LeakyReLU(0.2) between."""
+    return [name] if resi == '1conv' else [f'{name}.0', f'{name}.2', f'{name}.4']
+
+
+def tail_shapes(s, name: str, C_: int, resi: str) -> None:
+    if resi == '1conv':
+        s.conv(name, C_, C_, 3)
+    else:
+        s.conv(f'{name}.0', C_ // 4, C_, 3)
+        s.conv(f'{name}.2', C_ // 4, C_ // 4, 1)
+        s.conv(f'{name}.4', C_, C_ // 4, 3)
+
+
+def tail_macs(C_: int, resi: str) -> int:
+    return 9 * C_ * C_ if resi == '1conv' else (9 * C_ * (C_ // 4) * 2 + (C_ // 4) ** 2)
+
+
+class ResidualTail:
+    """The plan step of the tail: ``tail(name, src_planes, res, out_f32, out_planes)`` emits the convolutions of ``name`` with the residual
+    add that follows them in the last one's epilogue.  A 3conv tail owns the two C/4 scratch planes, allocated once per plan."""
+
+    def __init__(self, plan, W, resi, n, H, Wd, C_, with_lo):
+        self.plan, self.W, self.resi, self.H, self.Wd, self.cp = plan, W, resi, H, Wd, (C_ + 7) // 8
+        self.q4_a = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if resi == '3conv' else None
+        self.q4_b = plan.planes(n, (C_ // 4 + 7) // 8, H, Wd, with_lo) if resi == '3conv' else None
+
+    def squeeze(self, name, src_planes):
+        """The first two convolutions of a 3conv tail; returns the planes its last convolution reads."""
+        lre = dict(act=L.ACT_LRELU, act_param=0.2)
+        self.plan.conv(ops.conv_params(self.W[f'{name}.0'], src_planes, self.H, self.Wd, cin_planes=self.cp, out=self.q4_a, **lre))
+        self.plan.conv(ops.conv_params(self.W[f'{name}.2'], self.q4_a, self.H, self.Wd, out=self.q4_b, **lre))
+        return self.q4_b
+
+    def __call__(self, name, src_planes, res, out_f32=None, out_planes=None):
+        if self.resi == '1conv':
+            last, src, kw = name, src_planes, dict(cin_planes=self.cp)
+        else:
+            last, src, kw = f'{name}.4', self.squeeze(name, src_planes), {}
+        self.plan.conv(ops.conv_params(self.W[last], src, self.H, self.Wd, res1=res, alpha=1.0, out_f32=out_f32, out=out_planes, **kw))
+
+
+# ---------------------------------------------------------------- reconstruction heads
+# 'pixelshuffle'        conv_before_upsample + LeakyReLU -> [conv + PixelShuffle] per factor 2 (or one for 3) -> conv_last
+# 'nearest+conv'        conv_before_upsample + LeakyReLU -> [nearest 2x + conv_up + LeakyReLU(0.2)] per factor 2 -> conv_hr -> conv_last
+# 'pixelshuffledirect'  one convolution (upsample.0) whose store shuffles
+# anything else         conv_last on the body's width, added to the caller's own input (denoising / artefact removal)
+HEAD_LAYERS = ('conv_before_upsample.0', 'conv_up1', 'conv_up2', 'conv_up3', 'conv_hr', 'conv_last', 'upsample.0', 'upsample.2', 'upsample.4')
+
+
+def head_shapes(s, upsampler: str, C_: int, nf: int, out_ch: int, upscale: int) -> None:
+    if upsampler == 'pixelshuffle':
+        s.pixelshuffle_head(C_, nf, out_ch, upscale)
+    elif upsampler == 'nearest+conv':
+        s.conv('conv_before_upsample.0', nf, C_, 3)
+        for u in range(1, int(math.log2(upscale)) + 1):
+            s.conv(f'conv_up{u}', nf, nf, 3)
+        s.conv('conv_hr', nf, nf, 3)
+        s.conv('conv_last', out_ch, nf, 3)
+    elif upsampler == 'pixelshuffledirect':
+        s.conv('upsample.0', upscale * upscale * out_ch, C_, 3)
+    else:
+        s.conv('conv_last', out_ch, C_, 3)
+
+
+def pack_head(pk: 'LayerPacker') -> None:
+    """Pack whichever head layers the state dict holds."""
+    for name in HEAD_LAYERS:
+        if f'{name}.weight' in pk.sd:
+            pk.conv(name)
+
+
+def pixelshuffle_macs(C_: int, nf: int, out_ch: int, scale: int) -> int:
+    """MACs per input pixel of the pixel-shuffle head, each convolution at its own resolution."""
+    macs = 9 * C_ * nf
+    res = 1
+    if scale == 3:
+        macs += 9 * nf * 9 * nf
+        res = 9
+    else:
+        for _ in range(int(math.log2(scale))):
+            macs += 9 * nf * 4 * nf * res
+            res *= 4
+    return macs + 9 * nf * out_ch * res
+
+
+def head_macs(upsampler: str, C_: int, nf: int, out_ch: int, scale: int) -> int:
+    if upsampler == 'pixelshuffle':
+        return pixelshuffle_macs(C_, nf, out_ch, scale)
+    if upsampler == 'nearest+conv':
+        macs = 9 * C_ * nf
+        res = 1
+        for _ in range(int(math.log2(scale))):
+            res *= 4
+            macs += 9 * nf * nf * res
+        return macs + (9 * nf * nf + 9 * nf * out_ch) * res
+    return 9 * C_ * scale * scale * out_ch  # one convolution: upsample.0, or conv_last at scale 1
 
 
 def pixelshuffle_buffers(plan, W, n, H, Wd, nf, with_lo) -> tuple:
@@ -225,8 +331,9 @@ def pixelshuffle_buffers(plan, W, n, H, Wd, nf, with_lo) -> tuple:
     return y0, stages
 
 
-def pixelshuffle_head(plan, W, buffers, src, cin_planes, H, Wd) -> tuple:
-    """Emit the head up to conv_last: returns (planes, h, w) that conv_last reads.  ``buffers`` from ``pixelshuffle_buffers``."""
+def pixelshuffle_head(plan, W, buffers, src, cin_planes, H, Wd, y_out=None, **final) -> tuple:
+    """Emit the head from ``buffers`` (``pixelshuffle_buffers``): returns (planes, h, w) that conv_last reads, and emits conv_last into
+    ``y_out`` with the ``final`` store arguments when ``y_out`` is given."""
     y, stages = buffers
     plan.conv(ops.conv_params(W['conv_before_upsample.0'], src, H, Wd, cin_planes=cin_planes, act=L.ACT_LRELU, act_param=0.01, out=y))
     hh, ww = H, Wd
@@ -236,7 +343,86 @@ def pixelshuffle_head(plan, W, buffers, src, cin_planes, H, Wd) -> tuple:
         plan.call(lambda src=shuffled, dst=ny: ops.nchw_to_planes(src, dst))
         plan.count_launches(1)
         y = ny
+    if y_out is not None:
+        plan.conv(ops.conv_params(W['conv_last'], y, hh, ww, out_nchw=y_out, **final))
     return y, hh, ww
+
+
+def reconstruction_head(plan, W, upsampler, src, cin_planes, n, H, Wd, scale, with_lo, y_out, out_scale, out_shift, x_sig, nf=64) -> None:
+    """Emit the head ``upsampler`` from the planes ``src`` into ``y_out``; the last store computes ``y * out_scale + out_shift``, or, for the
+    bare conv_last, ``y * out_scale`` plus the caller's own input ``x_sig`` = (shape, dtype): (x_norm + y) / range + mean == x + y / range."""
+    final = dict(out_scale=out_scale, out_shift=out_shift)
+    lre = dict(act=L.ACT_LRELU, act_param=0.2)
+    if upsampler == 'pixelshuffle':
+        pixelshuffle_head(plan, W, pixelshuffle_buffers(plan, W, n, H, Wd, nf, with_lo), src, cin_planes, H, Wd, y_out, **final)
+    elif upsampler == 'nearest+conv':
+        y = plan.planes(n, nf // 8, H, Wd, with_lo)
+        plan.conv(ops.conv_params(W['conv_before_upsample.0'], src, H, Wd, cin_planes=cin_planes, act=L.ACT_LRELU, act_param=0.01, out=y))
+        hh, ww = H, Wd
+        for u in range(1, int(math.log2(scale)) + 1):
+            hh, ww = hh * 2, ww * 2
+            ny = plan.planes(n, nf // 8, hh, ww, with_lo)
+            plan.conv(ops.conv_params(W[f'conv_up{u}'], y, hh, ww, upsample2x=True, out=ny, **lre))
+            y = ny
+        hr = plan.planes(n, nf // 8, hh, ww, with_lo)
+        plan.conv(ops.conv_params(W['conv_hr'], y, hh, ww, out=hr, **lre))
+        plan.conv(ops.conv_params(W['conv_last'], hr, hh, ww, out_nchw=y_out, **final))
+    elif upsampler == 'pixelshuffledirect':
+        plan.conv(ops.conv_params(W['upsample.0'], src, H, Wd, cin_planes=cin_planes, out_nchw=y_out, pixel_shuffle=scale, **final))
+    else:
+        plan.conv(ops.conv_params(W['conv_last'], src, H, Wd, cin_planes=cin_planes, out_nchw=y_out, out_scale=out_scale,
+                                  out_base=plan.input_ref(*x_sig), out_base_div=1))  # fmt: skip
+
+
+# ---------------------------------------------------------------- steps of the rectangular-window models (DAT, RGT)
+def branch_geometry(pair, idx: int):
+    """(h, w) of a per-branch quantity: branch 1 swaps the rectangle (DAT arch.py:186-191)."""
+    return (pair[0], pair[1]) if idx == 0 else (pair[1], pair[0])
+
+
+def rect_attention(plan, qkv_pl, out_pl, bias_frags, n, H, Wd, split, heads, shifted, products, fmt) -> None:
+    """The two branches of a rectangular-window attention (``split`` and its transpose on the two halves of the heads, shifted by half a
+    window where ``shifted``): one ``rsa_rect_attention`` launch each.  ``bias_frags`` = the two branches' position-bias fragments."""
+    m = max(split)
+    for idx in (0, 1):
+        ap = L.RectAttnParams()
+        ap.batch, ap.H, ap.W, ap.Hp, ap.Wp = n, H, Wd, H + (m - H % m) % m, Wd + (m - Wd % m) % m
+        ap.win_h, ap.win_w = branch_geometry(split, idx)
+        ap.shift_h, ap.shift_w = branch_geometry([split[0] // 2, split[1] // 2], idx) if shifted else (0, 0)
+        ap.heads, ap.head0, ap.heads_total, ap.products = heads // 2, idx * (heads // 2), heads, products
+        ap.fmt = fmt
+        qkv_pl.bind(ap, 'qkv')
+        ap.bias_frag = bias_frags[idx].data_ptr()
+        out_pl.bind(ap, 'out')
+        plan.launch('rsa_rect_attention', ap)
+
+
+def dwconv3x3(plan, weights, src, src_plane0, planes, out, out_plane0=0, act=L.ACT_NONE, stats=None, gamma=None, beta=None, mul=None) -> None:
+    """``rsa_dwconv3x3`` over ``planes`` planes of ``src`` from ``src_plane0`` into ``out`` from ``out_plane0``; ``weights`` = (weight, bias).
+    With ``stats`` / ``gamma`` / ``beta`` the input is layer-normalised per pixel first; with ``mul`` the result is multiplied by those planes.
+    (Source, multiplier and output planes of a call share their format.)"""
+    dp = L.DwConvParams()
+    dp.batch, dp.H, dp.W, dp.planes, dp.act = src.n, src.h, src.w, planes, act
+    dp.fmt = src.fmt
+    src.bind(dp, 'in', src_plane0)
+    dp.weight, dp.bias = weights[0].data_ptr(), weights[1].data_ptr()
+    if stats is not None:
+        dp.stats, dp.gamma, dp.beta = stats.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+    if mul is not None:
+        mul.bind(dp, 'mul')
+    out.bind(dp, 'out', out_plane0)
+    plan.launch('rsa_dwconv3x3', dp)
+
+
+def plane_stats(plan, src, plane0, channels, stats) -> None:
+    """Per-pixel LayerNorm statistics (eps 1e-5) of ``channels`` channels of ``src`` from ``plane0`` into ``stats`` [N, H*W, 2]."""
+
+    def run():
+        L.check(L.load().rsa_plane_stats_fmt(src.hi_ptr(plane0), src.lo_ptr(plane0), src.plane_stride, src.batch_stride, src.n, src.h, src.w,
+                                             channels, 1e-5, src.fmt, stats.data_ptr(), C.c_void_p(ops.current_stream_ptr(plan.device))), 'rsa_plane_stats')  # fmt: skip
+
+    plan.call(run)
+    plan.count_launches(1)
 
 
 MLP_MAX_C, MLP_MAX_HIDDEN = 256, 512  # limits of rsa_swin_mlp_block (include/resselt_amd.h)
@@ -262,6 +448,5 @@ def mlp_block(plan, norm, fc1, fc2, n, h, w, channels, hidden, products, x_f32, 
     mp.w2, mp.b2 = fc2.packed_for(0).data_ptr(), fc2.bias.data_ptr()
     mp.out = out_f32.data_ptr()
     if out_planes is not None:
-        mp.out_hi, mp.out_lo = out_planes.hi_ptr(), out_planes.lo_ptr()
-        mp.out_plane_stride, mp.out_batch_stride = out_planes.plane_stride, out_planes.batch_stride
+        out_planes.bind(mp, 'out')
     plan.launch('rsa_swin_mlp_block', mp)

@@ -14,6 +14,9 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from ..engine.paramtree import ParamShapes
+from ..engine.transformer import tail_shapes
+
 
 def synth_tensor(name: str, shape, fan_in: int, seed: int = 0, scale: float = 1.0) -> torch.Tensor:
     rng = np.random.Generator(np.random.PCG64([zlib.crc32(name.encode()), seed]))
@@ -33,6 +36,14 @@ def _conv(sd, name, cout, cin, k, seed, bias=True, scale=1.0):
     sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (cout, cin, k, k), fan_in, seed, scale)
     if bias:
         sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (cout,), fan_in, seed, scale)
+
+
+def _resi_conv(sd, name, C, resi, seed):
+    """The 1conv / 3conv tail of a residual group, from the shapes the models register (engine/transformer.py: ``tail_shapes``)."""
+    shapes = ParamShapes()
+    tail_shapes(shapes, name, C, resi)
+    for key, (cout, cin, k, _) in ((key, shape) for key, shape in shapes.items() if key.endswith('.weight')):
+        _conv(sd, key[: -len('.weight')], cout, cin, k, seed)
 
 
 def rrdbnet_state_dict(in_nc=3, out_nc=3, nf=64, nb=23, gc=32, scale=4, plus=False, seed=0, new_arch=False) -> 'OrderedDict[str, torch.Tensor]':
@@ -182,14 +193,6 @@ def swinir_state_dict(in_ch=3, embed_dim=60, depths=(2, 2), num_heads=(6, 6), wi
         sd[f'{name}.weight'] = 1.0 + synth_tensor(f'{name}.weight', (C,), 16, seed)
         sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (C,), 16, seed)
 
-    def resi_conv(name):
-        if resi == '1conv':
-            _conv(sd, name, C, C, 3, seed)
-        else:
-            _conv(sd, f'{name}.0', C // 4, C, 3, seed)
-            _conv(sd, f'{name}.2', C // 4, C // 4, 1, seed)
-            _conv(sd, f'{name}.4', C, C // 4, 3, seed)
-
     # relative_position_index buffer (arch.py:111-122)
     ch, cw = torch.arange(window), torch.arange(window)
     coords = torch.stack(torch.meshgrid([ch, cw], indexing='ij')).flatten(1)
@@ -227,9 +230,9 @@ def swinir_state_dict(in_ch=3, embed_dim=60, depths=(2, 2), num_heads=(6, 6), wi
             ln(f'{b}.norm2')
             lin(f'{b}.mlp.fc1', hidden, C)
             lin(f'{b}.mlp.fc2', C, hidden)
-        resi_conv(f'layers.{i}.conv')
+        _resi_conv(sd, f'layers.{i}.conv', C, resi, seed)
     ln('norm')
-    resi_conv('conv_after_body')
+    _resi_conv(sd, 'conv_after_body', C, resi, seed)
     nf = 64
     if upsampler == 'nearest+conv':
         _conv(sd, 'conv_before_upsample.0', nf, C, 3, seed)
@@ -323,14 +326,6 @@ def dat_state_dict(in_chans=3, embed_dim=64, split_size=(2, 4), depth=(2,), num_
         sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (c, 1, 3, 3), 9, seed)
         sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), 9, seed)
 
-    def resi_conv(name):
-        if resi == '1conv':
-            _conv(sd, name, C, C, 3, seed)
-        else:
-            _conv(sd, f'{name}.0', C // 4, C, 3, seed)
-            _conv(sd, f'{name}.2', C // 4, C // 4, 1, seed)
-            _conv(sd, f'{name}.4', C, C // 4, 3, seed)
-
     def aim(name):
         dw(f'{name}.dwconv.0', C)
         bn(f'{name}.dwconv.1', C)
@@ -384,9 +379,9 @@ def dat_state_dict(in_chans=3, embed_dim=64, split_size=(2, 4), depth=(2,), num_
             dw(f'{b}.ffn.sg.conv', hidden // 2)
             lin(f'{b}.ffn.fc2', C, hidden // 2)
             ln(f'{b}.norm2', C)
-        resi_conv(f'layers.{i}.conv')
+        _resi_conv(sd, f'layers.{i}.conv', C, resi, seed)
     ln('norm', C)
-    resi_conv('conv_after_body')
+    _resi_conv(sd, 'conv_after_body', C, resi, seed)
     if upsampler == 'pixelshuffle':
         _conv(sd, 'conv_before_upsample.0', 64, C, 3, seed)
         if upscale == 3:
@@ -847,14 +842,6 @@ def rgt_state_dict(in_chans=3, embed_dim=48, split_size=(2, 4), depth=(2,), num_
         sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (c, 1, k, k), k * k, seed, scale)
         sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), k * k, seed, scale)
 
-    def resi_conv(name):
-        if resi == '1conv':
-            _conv(sd, name, C, C, 3, seed)
-        else:
-            _conv(sd, f'{name}.0', C // 4, C, 3, seed)
-            _conv(sd, f'{name}.2', C // 4, C // 4, 1, seed)
-            _conv(sd, f'{name}.4', C, C // 4, 3, seed)
-
     def window_branch(name, idx, heads):
         hs, ws = dat_geometry(split_size, idx)
         bh, bw = torch.arange(1 - hs, hs), torch.arange(1 - ws, ws)
@@ -906,9 +893,9 @@ def rgt_state_dict(in_chans=3, embed_dim=48, split_size=(2, 4), depth=(2,), num_
             lin(f'{b}.mlp.fc2', C, hidden // 2)
             ln(f'{b}.norm2', C)
             sd[f'{b}.gamma'] = 0.55 + synth_tensor(f'{b}.gamma', (C,), 1, seed, 0.45)
-        resi_conv(f'layers.{i}.conv')
+        _resi_conv(sd, f'layers.{i}.conv', C, resi, seed)
     ln('norm', C)
-    resi_conv('conv_after_body')
+    _resi_conv(sd, 'conv_after_body', C, resi, seed)
     _conv(sd, 'conv_before_upsample.0', 64, C, 3, seed)
     if upscale == 3:
         _conv(sd, 'upsample.0', 9 * 64, 64, 3, seed)

@@ -163,6 +163,13 @@ typedef struct rsa_conv_params {
   int32_t lo8_flags;
   int32_t reserved_lo8;     /* must be 0 */
   int64_t lo8_batch_stride; /* 8-byte units between images of an lo8 buffer (shared by the flagged operands) */
+  /* Channel pooling in the epilogue (RCAN's channel attention, csrc/rcan.hip): NULL, the value of a zeroed descriptor, = off.  When set, the
+   * launch also writes per-output-channel partial sums of its f32 epilogue values (after bias and activation, before they are rounded to
+   * planes; pixels outside the map excluded) as f32 [batch][slots][16 * ceil(cout / 16)], slots = rsa_conv_pool_slots(p): every entry is
+   * written by exactly one wave, no atomics, a fixed reduction order -- two runs give the same bits, and the planes are the bits of the
+   * same launch without pooling.  Compiled for the ring schedule's 3x3 layers with 48 or 64 output channels, bias + LeakyReLU / linear,
+   * plane output (optionally the f32 map), no residual, in three bf16 products and in one fp16 product; anything else: RSA_E_UNSUPPORTED. */
+  float* pool_sums;
 } rsa_conv_params;
 #define RSA_LO8_RES1 1
 #define RSA_LO8_RES2 2
@@ -208,6 +215,10 @@ int64_t rsa_packed_weight_bytes_layout(int32_t cout, int32_t cin_planes, int32_t
 /* Number of 16-channel cout tiles one workgroup computes for `cout` output channels (1..4); the grid has
  * ceil(ceil(cout/16) / tiles) slabs in y.  Exposed so host code and tests can reason about launch geometry. */
 int rsa_conv_cout_tiles(int32_t cout);
+
+/* Slots per image of rsa_conv_params.pool_sums for this descriptor (its pool_sums field itself is not looked at): 16 x 32 pixel tiles of
+ * the map times the row groups of waves that own a tile.  RSA_E_UNSUPPORTED when the pooling epilogue is not compiled for the descriptor. */
+int rsa_conv_pool_slots(const rsa_conv_params* p);
 
 /*
  * Weight packing: OIHW f32 weights (device pointer, contiguous [cout][cin][k][k]) -> the MFMA A-fragment blob of
@@ -1319,6 +1330,30 @@ typedef struct rsa_atd_refine_params {
 } rsa_atd_refine_params;
 int64_t rsa_atd_refine_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t C, int32_t m);
 int rsa_atd_refine(const rsa_atd_refine_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------- RCAN ops
+ * (reference archs/rcan/arch.py, CALayer :148-164, RCAB :168-196, RCAN.forward :320-332; csrc/rcan.hip) */
+
+/* The tail of a residual channel attention block: out = x + gate[n][c] * y on split planes of format fmt, two kernels on `stream`.
+ *   1. pool_sums != NULL: one workgroup per image adds the `slots` partial sums per channel that the block's second convolution left
+ *      (rsa_conv_params.pool_sums, f32 [batch][slots][16 * ceil(C / 16)]) in f64 in a fixed order (strided partials in ascending slot
+ *      order, then the partials in order: the same bits on every run), divides by H * W and writes
+ *      gate[n][c] = sigmoid(W2 . relu(W1 . mean + b1) + b2), f32 [batch][C] (the matrix products in f64 too).
+ *      pool_sums == NULL: `gate` is an input (for instance from rsa_channel_gate with relu = 1), w1 .. b2 are not read.
+ *   2. one pass over the map: reads y (the convolution's planes) and x (the block's input), writes the planes the next convolution reads;
+ *      out may be x or y.  Every lo pointer may be NULL (the value is then hi alone / lo is not written).
+ * w1 [hidden][C], b1 [hidden], w2 [C][hidden], b2 [C], f32.  C % 8 == 0, C <= 512, hidden 1..128; strides in 16-byte units; plane pointers
+ * 16-byte aligned; H, W arbitrary. */
+int rsa_rcab_tail(const float* pool_sums, int32_t slots, const float* w1, const float* b1, const float* w2, const float* b2, int32_t hidden,
+                  float* gate, const void* y_hi, const void* y_lo, int64_t y_plane_stride, int64_t y_batch_stride, const void* x_hi,
+                  const void* x_lo, int64_t x_plane_stride, int64_t x_batch_stride, void* out_hi, void* out_lo, int64_t out_plane_stride,
+                  int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t fmt, void* stream);
+
+/* RCAN's input stage (forward :323-324): out[n][o][p] = bias[o] + sum_c weight[o][c] * (x[n][c][p] * scale), f32 [N][C][H][W], C <= 4 -- the
+ * `x * rgb_range` and the sub_mean 1x1 convolution as one pointwise step.  x is [N][C][H][W] of `dtype`, or RSA_U8 [N][H][W][C] (v = byte / 255).
+ * weight f32 [C][C], bias f32 [C]. */
+int rsa_rcan_input(const void* x, int32_t dtype, int32_t batch, int32_t C, int32_t H, int32_t W, float scale, const float* weight,
+                   const float* bias, float* out, void* stream);
 
 /* 8-bit images either side of the path (the reference leaves both steps to its callers):
  *   rsa_image_u8_to_nchw   uint8 [N][H][W][C] (interleaved, as image decoders deliver it) -> float [N][C][H][W], v / 255

@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -18,6 +18,7 @@ from .mosr import MoSRArch
 from .mosrv2 import MoSRv2Arch
 from .omnisr import OmniSRArch
 from .plksr import PLKSRArch
+from .rcan import RCANArch
 from .rgt import RGTArch
 from .rtmosr import RTMoSRArch
 from .span import SPANArch
@@ -26,7 +27,7 @@ from .spanpp import SpanPPArch
 from .swinir import SwinIRArch
 
 internal_registry = Registry()
-# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, Compact, ATD, RGT, OmniSR, MoSR, FDAT, CuGAN, PLKSR, MoSRv2, RTMoSR,
+# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, RCAN, Compact, ATD, RGT, OmniSR, MoSR, FDAT, CuGAN, PLKSR, MoSRv2, RTMoSR,
 # spanplus, SwinIR, SpanPP, ..., SPAN
-for _arch in (ESRGANArch, HATArch, DatArch, CompactArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
+for _arch in (ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
     internal_registry.add(_arch())

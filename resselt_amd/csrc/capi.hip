@@ -270,6 +270,13 @@ int rsa_check_finite(const void* data, int32_t dtype, int64_t count, void* strea
 
 int rsa_conv_cout_tiles(int32_t cout) { return rsa::conv_nct(cout); }
 
+int rsa_conv_pool_slots(const rsa_conv_params* p) {
+  if (p == nullptr) return rsa::set_error(RSA_E_ARG, "rsa_conv_pool_slots: null params");
+  if (p->H < 1 || p->W < 1 || !rsa::conv_pool_eligible(*p) || rsa::conv_pool_slots(*p) > 0x3fffffff)
+    return rsa::set_error(RSA_E_UNSUPPORTED, "rsa_conv_pool_slots: the pooling epilogue is not compiled for this descriptor");
+  return (int)rsa::conv_pool_slots(*p);
+}
+
 int rsa_conv_weight_layout(const rsa_conv_params* p) {
   if (p == nullptr) return rsa::set_error(RSA_E_ARG, "rsa_conv_weight_layout: null params");
   return rsa::conv_weight_layout(*p);

@@ -92,6 +92,20 @@ inline bool conv_pair_eligible(const rsa_conv_params& a, const rsa_conv_params& 
          a.out_hi == a.in_hi && a.out_plane_off == a.cin_planes && a.out_plane_stride == a.in_plane_stride && a.out_batch_stride == a.in_batch_stride &&
          (b.out_hi != b.in_hi || b.out_plane_off >= b.cin_planes) && a.w_packed != nullptr && b.w_packed != nullptr;
 }
+// Channel pooling in the epilogue (rsa_conv_params.pool_sums; conv_ring.h XRES 7, conv_common.h EM 5): the ring schedule's one-stream shapes --
+// 64 output channels over whole 32-channel chunks, 48 over an odd number of half chunks -- in three bf16 products or one fp16 product, bias +
+// LeakyReLU (slope in [0, 1]) / linear, plane output (hi, optionally lo and the f32 map), nothing else in the epilogue.
+inline bool conv_pool_eligible(const rsa_conv_params& p) {
+  const bool whole = (p.cin_planes & 3) == 0;
+  return conv_ring_enabled() && conv_ring_eligible(p) && !p.upsample2x && ((p.cout == 64 && whole) || (p.cout == 48 && !whole)) &&
+         ((p.products == 3 && p.in_fmt == RSA_PF_BF16) || (p.products == 1 && p.in_fmt == RSA_PF_F16)) && p.out_hi != nullptr && p.out_nchw == nullptr &&
+         p.res1 == nullptr && p.res2 == nullptr && p.res1_hi == nullptr && p.res2_hi == nullptr && p.lo8_flags == 0 &&
+         (p.act == RSA_ACT_NONE || (p.act == RSA_ACT_LRELU && p.act_param >= 0.f && p.act_param <= 1.f));
+}
+// slots per image of pool_sums: tiles of 16 x 32 pixels times the row groups of waves that own one (4 for 64 channels, 8 for 48)
+inline int64_t conv_pool_slots(const rsa_conv_params& p) { return (int64_t)((p.H + 15) / 16) * ((p.W + 31) / 32) * (p.cout == 48 ? 8 : 4); }
+int conv_launch_pool(const rsa_conv_params& p, hipStream_t stream);  // conv_inst_ringpool.hip
+unsigned int conv_ringpool_aborts();
 int conv_launch_pair(const rsa_conv_params& a, const rsa_conv_params& b, hipStream_t stream);  // conv_inst_ringpair.hip; the caller has validated both
 unsigned int conv_ring_pair_aborts();
 

@@ -255,6 +255,11 @@ struct GeoLW {
 // L8: the lo halves of the plane residuals / outputs as 8-bit codes (rsa_conv_params.lo8_flags): -1 = as the descriptor's flags say (the generic
 // body), 0 = none, 1 = every lo operand of the launch (the direct instantiation of conv5 inside an RRDBNet trunk: no runtime tests, no spills),
 // 2 = the residuals only (the trunk's last block hands fp16 lo halves to the three-product layers behind it)
+// EM 5 (conv_ring.h XRES 7: rsa_conv_params.pool_sums, the second convolution of RCAN's RCAB): bias + LeakyReLU / linear, plane output in the
+// descriptor's format (hi, and lo / the f32 map where it has them), no residual, whole cout tiles -- and the per-channel sums of the f32 values
+// of this wave's RPW rows of the tile, written to the wave's own slot (tile of the image) * (row groups) + wpx of pool_sums.  Reduction tree
+// of one slot entry: the lane adds its NPT values in order (NPT - 1 roundings, NPT <= 8), then four butterfly steps over the 16 lanes of a
+// row (xor 1, 2, 4, 8: every lane ends with the same bits), depth d = 7 + 4 = 11; |error| <= d * 2^-24 * sum|v| to first order.
 template <int NCT, int CTW, int NPT, int OUTK, int AC, int EM = 0, int PF = 0, int XL = 0, int L8 = -1>
 __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f32x4 (&acc)[NPT][CTW], int n, int y0, int x0, int slab, int wct,
                                               int wpx, int li, int lg, const uint4* x_lds = nullptr, uint32_t xslots = 0u, int x_slot = 0,
@@ -265,13 +270,14 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
   // plane output in format PF (hi, and lo where the descriptor has it), the gate's shortcut as plane residual 1 (hi, and lo where it has
   // it); no f32 map, no second residual, no PReLU, whole cout tiles
   constexpr bool S = EM == 4;
+  constexpr bool P = EM == 5;
   const bool R1F = G && p.res1 != nullptr, R2F = G && p.res2 != nullptr;                          // residuals as f32 maps
-  const bool R1P = G ? p.res1_hi != nullptr : (S ? AC == AC_GATE : EM >= 2), R2P = G ? p.res2_hi != nullptr : EM == 3;  // as planes
+  const bool R1P = G ? p.res1_hi != nullptr : (S ? AC == AC_GATE : (EM >= 2 && !P)), R2P = G ? p.res2_hi != nullptr : EM == 3;  // as planes
   const bool R1L = (G || S) ? p.res1_lo != nullptr : true, R2L = G ? p.res2_lo != nullptr : true;       // ... with lo planes
-  const bool OF32 = G && p.out_f32 != nullptr;
-  const bool OHI = G ? p.out_hi != nullptr : true, OLO = (G || S) ? p.out_lo != nullptr : !(EM == 1 && PF == RSA_PF_F16);
-  static_assert(EM >= 0 && EM <= 4, "epilogue shape");
-  const bool OF16 = G ? p.out_fmt == RSA_PF_F16 : PF == RSA_PF_F16;  // plane format of the outputs / of the plane residuals
+  const bool OF32 = (G || P) && p.out_f32 != nullptr;
+  const bool OHI = G ? p.out_hi != nullptr : true, OLO = (G || S || P) ? p.out_lo != nullptr : !(EM == 1 && PF == RSA_PF_F16);
+  static_assert(EM >= 0 && EM <= 5, "epilogue shape");
+  const bool OF16 = (G || P) ? p.out_fmt == RSA_PF_F16 : PF == RSA_PF_F16;  // plane format of the outputs / of the plane residuals
   const bool RF16 = G ? p.res_fmt == RSA_PF_F16 : PF == RSA_PF_F16;
   // lo halves as 8-bit codes (fp16 planes only; wave-uniform)
   const bool R1L8 = L8 < 0 ? (G && (p.lo8_flags & RSA_LO8_RES1) != 0) : L8 >= 1, R2L8 = L8 < 0 ? (G && (p.lo8_flags & RSA_LO8_RES2) != 0) : L8 >= 1,
@@ -439,6 +445,7 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
     char* olb = (char*)p.out_lo + ounit0 * 16;
     const uint32_t f32lane = (uint32_t)lg * (uint32_t)HW;                       // + lpix, in float4 units
     const uint32_t pllane = (uint32_t)(lg >> 1) * (uint32_t)p.out_plane_stride;  // + lpix, in 16-byte units
+    [[maybe_unused]] float psum[4] = {0.f, 0.f, 0.f, 0.f};  // EM 5: this lane's share of the channel sums of cout tile ct
     // pixel tiles are handled in PAIRS (2k, 2k+1) = the two 16-pixel halves of one row.  After the per-fragment math the two
     // lanes that hold the two halves of a 16-byte unit (lg, lg^1 = lanes l, l^16) exchange one half each, so that lane lg-even
     // stores the FULL unit of pixel-tile 2k and lane lg-odd the full unit of pixel-tile 2k+1: 16-byte stores, 512 contiguous
@@ -551,6 +558,10 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
               if (c0 + r >= p.cout) v[e][r] = 0.f;
           }
           if (OF32 && has_f32grp && ok[e]) *(f32x4*)(f32b + foff) = (f32x4){v[e][0], v[e][1], v[e][2], v[e][3]};
+          if constexpr (P) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) psum[r] += ok[e] ? v[e][r] : 0.f;
+          }
         }
       }
       if (OUTK == 0) {
@@ -702,6 +713,20 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
       // keep the fragment epilogues from being interleaved by the scheduler: interleaving them costs more registers than the
       // 168-VGPR budget of the 9-wave schedule has and turns the epilogue into scratch traffic
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (P) {
+      // the 16 lanes of a row (same lg = same four channels) -> one sum; lane li 0 of each row stores its four channels: 64 contiguous bytes
+      // of the wave's slot per cout tile
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) psum[r] += __shfl_xor(psum[r], o);
+      }
+      if (li == 0) {
+        const int tiles_x = (p.W + 31) >> 5, tiles_y = (p.H + 15) >> 4;
+        const int64_t slot = ((int64_t)n * tiles_y * tiles_x + (int64_t)(y0 >> 4) * tiles_x + (x0 >> 5)) * (16 / RPW) + wpx;
+        *(f32x4*)(p.pool_sums + slot * (((p.cout + 15) >> 4) << 4) + c0) = (f32x4){psum[0], psum[1], psum[2], psum[3]};
+      }
     }
   }
 }

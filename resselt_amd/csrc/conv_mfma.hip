@@ -112,6 +112,8 @@ bool conv_ring_enabled() {
 // Name of the kernel a descriptor dispatches to (bench.py groups its per-kernel roofline by it; matches the rocprofv3 kernel names).
 const char* conv_kernel_name(const rsa_conv_params& p) {
   if (p.w_layout == RSA_WL_UPPHASE) return "rsa::conv_ring_up2 (x2 upsampling as four 2x2 phases)";
+  if (p.pool_sums != nullptr && p.w_layout != RSA_WL_TAPS && p.w_layout != RSA_WL_UPPHASE && conv_pool_eligible(p))
+    return p.cout == 48 ? "rsa::conv_ring<3,0,0,HM,...,XRES 7> (Cout 48, channel sums in the epilogue)" : "rsa::conv_ring<1,0,0,0,...,XRES 7> (Cout 64, channel sums in the epilogue)";
   if (p.w_layout != RSA_WL_TAPS) {
     const int ct = (p.cout + 15) >> 4;
     if (p.products == 1) {
@@ -200,6 +202,13 @@ int conv_validate(const rsa_conv_params& p) {
 int conv_launch(const rsa_conv_params& p, hipStream_t stream) {
   const int vrc = conv_validate(p);
   if (vrc != RSA_OK) return vrc;
+  if (p.pool_sums != nullptr) {  // channel pooling in the epilogue: its own instantiations (conv_inst_ringpool.hip), nothing else has it
+    if (p.w_layout == RSA_WL_TAPS || p.w_layout == RSA_WL_UPPHASE || !conv_pool_eligible(p))
+      return set_error(RSA_E_UNSUPPORTED, "conv: pool_sums is compiled for ring-schedule 3x3 layers with 48 / 64 output channels, linear epilogue, plane output");
+    if ((uintptr_t)p.pool_sums & 15) return set_error(RSA_E_ALIGN, "conv: pool_sums must be 16-byte aligned");
+    const int rc = conv_launch_pool(p, stream);
+    return rc ? set_error(rc, "conv: pooling ring kernel launch failed") : RSA_OK;
+  }
   if (p.w_layout != RSA_WL_TAPS) {  // ring schedule (conv_ring.h)
     const int rc = conv_launch_ring(p, stream);
     return rc ? set_error(rc, "conv: ring kernel launch failed") : RSA_OK;

@@ -166,6 +166,8 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
   static_assert(XRES != 2 || (PROD == 1 && FMT == RSA_PF_F16 && OUTK == 0), "XRES 2: one fp16 product, hi-only plane output");
   static_assert(XRES != 3 || (SHAPE == 3 && PROD == 1 && FMT == RSA_PF_F16 && HM == 1 && UP == 0 && OUTK == 0), "XRES 3: the 48-channel SPAN-family layers");
   static_assert(XRES != 6 || (SHAPE == 2 && OUTK == 1 && UP == 0), "XRES 6: final stores with at most 16 output channels");
+  // XRES 7 (conv_inst_ringpool.hip): the schedule of XRES 0 with the channel-pooling epilogue (conv_common.h, EM 5: rsa_conv_params.pool_sums)
+  static_assert(XRES != 7 || (SHAPE != 2 && UP == 0 && OUTK == 0), "XRES 7: plane output, one tile stream");
   constexpr bool WL = XRES == 3;
   constexpr bool XR = XRES == 1 || XRES == 4 || XRES == 5;  // XRES 4 = XRES 1 with every lo operand (residuals, output) as 8-bit codes (rsa_conv_params.lo8_flags);
                                                             // XRES 5: the residuals' lo halves as codes, the output's as fp16 (the last block of a trunk)
@@ -335,7 +337,7 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
 
   // weights: per (chunk, K step 0..8, cout tile, hi|lo) one 1 KiB A fragment, streamed from L2 WD K steps ahead
   constexpr int KSU = HM ? 5 : 9;  // K steps per unit
-  constexpr int WD = (PROD == 3 || WL) ? 1 : (XRES ? RSA_RING_WDX : RSA_RING_WD1);  // K steps of weight prefetch (a one-product K step is 16 MFMAs = 256 cycles: less than an L2 hit under load)
+  constexpr int WD = (PROD == 3 || WL) ? 1 : ((XRES && XRES != 7) ? RSA_RING_WDX : RSA_RING_WD1);  // K steps of weight prefetch (a one-product K step is 16 MFMAs = 256 cycles: less than an L2 hit under load)
   const int nks = nq * KSU;
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_packed, 0, (uint32_t)((int64_t)nks * ct_total * NHL * 64 * 16), 0x00020000);
   uint32_t woff[CTW];
@@ -529,6 +531,8 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
         if (!RING_DBG(8)) epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 1, RSA_PF_F16>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg);
       } else if (XRES == 3) {
         if (!RING_DBG(8)) epilogue_impl<NCT, CTW, NPT, 0, XAC, 4, RSA_PF_F16>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg);
+      } else if constexpr (XRES == 7) {
+        if (!RING_DBG(8)) epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 5>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg);
       } else if (XR) {
         if (!RING_DBG(8)) {
           if (p.res2_hi != nullptr)

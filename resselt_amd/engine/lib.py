@@ -22,6 +22,7 @@ LO8_RES1, LO8_RES2, LO8_OUT = 1, 2, 4  # rsa_conv_params.lo8_flags
 # enum rsa_plane_fmt
 PF_BF16, PF_F16 = range(2)
 E_INTERNAL = -4
+E_UNSUPPORTED = -2
 
 
 def _i32(*names: str) -> list:
@@ -56,7 +57,7 @@ class ConvParams(C.Structure):
         + _i64('out_plane_stride', 'out_batch_stride') + _ptr('out_f32', 'out_nchw') + _i32('out_dtype', 'pixel_shuffle')
         + _f32('out_scale') + _ptr('out_shift', 'act_vec', 'out_base') + _i32('out_base_div', 'out_base_h', 'out_base_w', 'w_layout')
         + _ptr('res1_hi', 'res1_lo', 'res2_hi', 'res2_lo') + _i64('res_plane_stride', 'res_batch_stride')
-        + _i32('in_fmt', 'out_fmt', 'res_fmt', 'tile_order', 'lo8_flags', 'reserved_lo8') + _i64('lo8_batch_stride')
+        + _i32('in_fmt', 'out_fmt', 'res_fmt', 'tile_order', 'lo8_flags', 'reserved_lo8') + _i64('lo8_batch_stride') + _ptr('pool_sums')
     )
 
 
@@ -362,6 +363,7 @@ EXPORTS = (
     'rsa_conv2d',
     'rsa_conv2d_list',
     'rsa_conv_cout_tiles',
+    'rsa_conv_pool_slots',
     'rsa_packed_weight_bytes',
     'rsa_packed_weight_bytes_layout',
     'rsa_conv_weight_layout',
@@ -438,6 +440,8 @@ EXPORTS = (
     'rsa_atd_dwconv',
     'rsa_atd_refine_workspace_bytes',
     'rsa_atd_refine',
+    'rsa_rcab_tail',
+    'rsa_rcan_input',
 )
 
 
@@ -542,6 +546,7 @@ def load() -> C.CDLL:
         ('rsa_packed_weight_bytes', i64, [i32] * 4),
         ('rsa_packed_weight_bytes_layout', i64, [i32] * 5),
         ('rsa_conv_weight_layout', C.c_int, [cp]),
+        ('rsa_conv_pool_slots', C.c_int, [cp]),
         ('rsa_pack_weights', C.c_int, [ptr] + [i32] * 7 + [ptr, ptr]),
         ('rsa_conv_kernel_name', C.c_char_p, [cp]),
         ('rsa_debug_ring_aborts', C.c_int, []),
@@ -576,6 +581,8 @@ def load() -> C.CDLL:
         ('rsa_atd_sort', C.c_int, [ptr, i32, i64, i32] + [ptr] * 4),
         ('rsa_atd_refine_workspace_bytes', i64, [i32] * 5),
         ('rsa_esa_maxpool', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr]),
+        ('rsa_rcab_tail', C.c_int, [ptr, i32] + [ptr] * 4 + [i32, ptr] + [ptr, ptr, i64, i64] * 3 + [i32] * 5 + [ptr]),
+        ('rsa_rcan_input', C.c_int, [ptr] + [i32] * 5 + [f32, ptr, ptr, ptr, ptr]),
     ):
         getattr(lib, name).argtypes = argtypes
         getattr(lib, name).restype = restype

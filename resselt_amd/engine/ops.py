@@ -122,6 +122,7 @@ def conv_params(
     out_base: torch.Tensor | None = None,
     out_base_div: int = 0,
     out_lo8: bool = False,
+    pool_sums: torch.Tensor | None = None,
 ) -> L.ConvParams:
     """Fill one ``rsa_conv_params``. ``H``, ``W`` are the OUTPUT size of the convolution."""
     p = L.ConvParams()
@@ -247,7 +248,27 @@ def conv_params(
     p.w_layout = int(L.load().rsa_conv_weight_layout(C.byref(p)))
     p.w_packed = wts.packed_for(p.w_layout).data_ptr()
     p.true_cin = min(wts.cin, 8 * p.cin_planes)  # python-side only (not part of the C struct): FLOP accounting in bench.py
+    if pool_sums is not None:
+        # per-channel partial sums of the f32 epilogue values (rsa_conv_params.pool_sums): f32 [N, slots, cout rounded up to 16]
+        slots = conv_pool_slots(p)
+        if slots is None:
+            raise ValueError('pool_sums: the pooling epilogue is not compiled for this convolution (ask conv_pool_slots first)')
+        exp = (x.n, slots, (wts.cout + 15) // 16 * 16)
+        if tuple(pool_sums.shape) != exp or pool_sums.dtype != torch.float32 or not pool_sums.is_contiguous():
+            raise ValueError(f'pool_sums must be a contiguous f32 {exp} tensor, got {tuple(pool_sums.shape)} {pool_sums.dtype}')
+        p.pool_sums = pool_sums.data_ptr()
     return p
+
+
+def conv_pool_slots(p: L.ConvParams) -> int | None:
+    """Slots per image of ``pool_sums`` for this descriptor (``rsa_conv_pool_slots``), or None when the pooling epilogue is not compiled
+    for it -- the caller then computes the mean some other way (``rsa_channel_gate``)."""
+    rc = int(L.load().rsa_conv_pool_slots(C.byref(p)))
+    if rc == L.E_UNSUPPORTED:
+        return None
+    if rc < 0:
+        L.check(rc, 'rsa_conv_pool_slots')
+    return rc
 
 
 def run_convs(params: list[L.ConvParams], device) -> None:

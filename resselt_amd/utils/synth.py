@@ -1086,3 +1086,39 @@ def atd_state_dict(in_chans=3, embed_dim=48, depths=(2, 2), num_heads=(4, 4), wi
         else:  # a bias: the fan-in of its weight
             sd[name] = synth_tensor(name, shape, int(np.prod(shapes[name[: -len('bias')] + 'weight'][1:])), seed)
     return sd
+
+
+def rcan_state_dict(scale=4, n_resgroups=2, n_resblocks=2, n_feats=64, n_colors=3, reduction=16, norm=True, unshuffle_mod=False, kernel_size=3, seed=0):
+    """Keys of RCAN (archs/rcan/arch.py:236-332) in the module's registration order: sub_mean / add_mean (with ``norm``), head, the residual
+    groups of RCABs (two convolutions and the channel attention's conv_du pair), each group's and the body's closing convolution, the
+    Upsampler stack and the last convolution.  The mean shifts are full 3x3 matrices near the DIV2K ones (an identity plus a perturbation), so
+    that nothing downstream can get away with assuming a diagonal.  The module's MeanShift is nn.Conv2d(3, 3, 1) whatever ``n_colors`` is
+    (:48), so ``norm`` needs three channels -- in the reference too, whose forward fails on anything else."""
+    sd: OrderedDict = OrderedDict()
+    if norm and n_colors != 3:
+        raise ValueError('rcan_state_dict: norm=True needs n_colors == 3 (the mean shifts are 3 -> 3 convolutions)')
+    if norm:
+        eye = torch.eye(n_colors).view(n_colors, n_colors, 1, 1)
+        mean = 255.0 * torch.tensor((0.4488, 0.4371, 0.4040, 0.43)[:n_colors])
+        for name, sign in (('sub_mean', -1.0), ('add_mean', 1.0)):
+            sd[f'{name}.weight'] = eye + 0.1 * synth_tensor(f'{name}.weight', (n_colors, n_colors, 1, 1), n_colors, seed)
+            sd[f'{name}.bias'] = sign * mean + synth_tensor(f'{name}.bias', (n_colors,), 1, seed)
+    down = 4 // scale if (unshuffle_mod and scale <= 2) else 1
+    _conv(sd, 'head.1' if down > 1 else 'head.0', n_feats, n_colors * down * down, kernel_size, seed)
+    for g in range(n_resgroups):
+        for b in range(n_resblocks):
+            p = f'body.{g}.body.{b}.body'
+            _conv(sd, f'{p}.0', n_feats, n_feats, kernel_size, seed)
+            _conv(sd, f'{p}.2', n_feats, n_feats, kernel_size, seed)
+            _conv(sd, f'{p}.3.conv_du.0', n_feats // reduction, n_feats, 1, seed)
+            _conv(sd, f'{p}.3.conv_du.2', n_feats, n_feats // reduction, 1, seed)
+        _conv(sd, f'body.{g}.body.{n_resblocks}', n_feats, n_feats, kernel_size, seed)
+    _conv(sd, f'body.{n_resgroups}', n_feats, n_feats, kernel_size, seed)
+    net_scale = 4 if down > 1 else scale
+    if net_scale == 3:
+        _conv(sd, 'tail.0.0', 9 * n_feats, n_feats, 3, seed)
+    else:
+        for i in range(int(np.log2(net_scale))):
+            _conv(sd, f'tail.0.{2 * i}', 4 * n_feats, n_feats, 3, seed)
+    _conv(sd, 'tail.1', n_colors, n_feats, kernel_size, seed)
+    return sd

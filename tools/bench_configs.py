@@ -80,6 +80,9 @@ def main():
                                                        mlp_ratio=1.0, upscale=4, upsampler='pixelshuffledirect'), (1, 3, 256, 256), torch.bfloat16, None, None),
         'atd_x4_bf16_256': (synth.atd_state_dict(embed_dim=210, depths=(6,) * 6, num_heads=(6,) * 6, window_size=16, num_tokens=128, reducted_dim=10,
                                                  mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle'), (1, 3, 256, 256), torch.bfloat16, None, None),
+        # RCAN x4 as published (10 groups x 20 RCABs, 64 features, reduction 16) and a light configuration (5 x 10)
+        'rcan_x4_bf16_512': (synth.rcan_state_dict(scale=4, n_resgroups=10, n_resblocks=20, n_feats=64, reduction=16), (1, 3, 512, 512), torch.bfloat16, None, None),
+        'rcan_light_x4_bf16_512': (synth.rcan_state_dict(scale=4, n_resgroups=5, n_resblocks=10, n_feats=64, reduction=16), (1, 3, 512, 512), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
         # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
         'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),

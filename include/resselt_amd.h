@@ -1362,6 +1362,37 @@ int rsa_rcan_input(const void* x, int32_t dtype, int32_t batch, int32_t C, int32
 int rsa_image_u8_to_nchw(const uint8_t* img, int32_t batch, int32_t H, int32_t W, int32_t C, void* out, int32_t dtype, void* stream);
 int rsa_nchw_to_image_u8(const void* x, int32_t dtype, int32_t batch, int32_t C, int32_t H, int32_t W, uint8_t* img, void* stream);
 
+/* ---- GateR (reference archs/gater/arch.py) ----
+ * nn.RMSNorm over the channels of an f32 stream map [N][ceil(C/4)][H][W][4]:  out = x * rsqrt(mean_c(x^2) + eps) * weight[c], written as split
+ * planes of `fmt` (out_lo may be NULL).  NOT rsa_rmsnorm, which is RTMoSR's  x / (rms + eps) * scale + offset.  A pixel of zeros gives zeros. */
+int rsa_rmsnorm_torch(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, float eps, const float* weight, void* out_hi, void* out_lo,
+                      int64_t out_plane_stride, int64_t out_batch_stride, int32_t fmt, void* stream);
+
+/* PixelUnshuffle(2) of an f32 map: x_f32 [N][C/4][H][W][4] -> out_f32 [N][C][H/2][W/2][4] with output channel 4c + 2i + j at (y, x) = input
+ * channel c at (2y + i, 2x + j).  A permutation (bit-exact).  H, W even, C % 4 == 0, not in place. */
+int rsa_pixel_unshuffle2(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, float* out_f32, void* stream);
+
+/* cat(a, b) over channels as one f32 map: a_nchw is a plain f32 [N][Ca][H][W] tensor (e.g. a depth-to-space store), b_map an f32 map
+ * [N][Cb/4][H][W][4]; out_map [N][(Ca+Cb)/4][H][W][4].  Ca, Cb multiples of 4. */
+int rsa_f32map_concat(const float* a_nchw, int32_t Ca, const float* b_map, int32_t Cb, int32_t batch, int32_t H, int32_t W, float* out_map, void* stream);
+
+/* Focused linear attention (FLPVT2, eight heads of head_dim = C / 8 channels, head_dim 24 or 48) over the H x W tokens of each image.
+ * qkv: split planes of one 3C-wide linear layer, [q | k | v] with C / 8 planes each (qkv_lo may be NULL).  For t in q, k (whole tokens,
+ * before the head split):  t = (relu(t) + 1e-6) / softplus(scale[c]);  n0 = ||t||_2 over C;  t = t^factor[c];  t = t / ||t||_2 * n0.
+ *   rsa_fla_reduce  per image and head:  KV = k^T v / n  and  mean_n(k)  into the first batch * (8 d d + 8 d) floats of `workspace`.
+ *                   Two kernels, no atomics: partial sums per chunk of 128 consecutive tokens, added in ascending chunk order -- the
+ *                   result is bit-identical from run to run and does not depend on the launch geometry.
+ *   rsa_fla_apply   out = (q KV) / (q . mean(k) + 1e-6) + dwc(v): the 5x5 depthwise convolution (zero padding) whose head_dim filters
+ *                   dwc_weight [d][25], dwc_bias [d] are shared by all heads (channel c uses filter c % d).  out: C / 8 split planes.
+ * All arithmetic is f32.  workspace: rsa_fla_workspace_bytes(batch, H * W, head_dim) bytes, 16-byte aligned, the same for both calls. */
+int64_t rsa_fla_workspace_bytes(int32_t batch, int32_t tokens, int32_t head_dim);
+int rsa_fla_reduce(const void* qkv_hi, const void* qkv_lo, int64_t qkv_plane_stride, int64_t qkv_batch_stride, int32_t batch, int32_t H, int32_t W,
+                   int32_t head_dim, int32_t fmt, const float* scale, const float* factor, void* workspace, int64_t workspace_bytes, void* stream);
+int rsa_fla_apply(const void* qkv_hi, const void* qkv_lo, int64_t qkv_plane_stride, int64_t qkv_batch_stride, int32_t batch, int32_t H, int32_t W,
+                  int32_t head_dim, int32_t fmt, const float* scale, const float* factor, const void* workspace, int64_t workspace_bytes,
+                  const float* dwc_weight, const float* dwc_bias, void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride,
+                  void* stream);
+
 /* version / errors */
 int rsa_version(void);
 const char* rsa_last_error_string(void);

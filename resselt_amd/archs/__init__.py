@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -13,6 +13,7 @@ from .dat import DatArch
 from .drct import DRCTArch
 from .esrgan import ESRGANArch
 from .fdat import FDATArch
+from .gater import GateRArch
 from .hat import HATArch
 from .mosr import MoSRArch
 from .mosrv2 import MoSRv2Arch
@@ -27,7 +28,7 @@ from .spanpp import SpanPPArch
 from .swinir import SwinIRArch
 
 internal_registry = Registry()
-# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, RCAN, Compact, ATD, RGT, OmniSR, MoSR, FDAT, CuGAN, PLKSR, MoSRv2, RTMoSR,
+# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, RCAN, Compact, GateR, ATD, RGT, OmniSR, MoSR, FDAT, CuGAN, PLKSR, MoSRv2, RTMoSR,
 # spanplus, SwinIR, SpanPP, ..., SPAN
-for _arch in (ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
+for _arch in (ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, GateRArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
     internal_registry.add(_arch())

@@ -442,6 +442,12 @@ EXPORTS = (
     'rsa_atd_refine',
     'rsa_rcab_tail',
     'rsa_rcan_input',
+    'rsa_rmsnorm_torch',
+    'rsa_pixel_unshuffle2',
+    'rsa_f32map_concat',
+    'rsa_fla_workspace_bytes',
+    'rsa_fla_reduce',
+    'rsa_fla_apply',
 )
 
 
@@ -583,6 +589,12 @@ def load() -> C.CDLL:
         ('rsa_esa_maxpool', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr]),
         ('rsa_rcab_tail', C.c_int, [ptr, i32] + [ptr] * 4 + [i32, ptr] + [ptr, ptr, i64, i64] * 3 + [i32] * 5 + [ptr]),
         ('rsa_rcan_input', C.c_int, [ptr] + [i32] * 5 + [f32, ptr, ptr, ptr, ptr]),
+        ('rsa_rmsnorm_torch', C.c_int, [ptr] + [i32] * 4 + [f32] + [ptr] * 3 + [i64, i64, i32, ptr]),
+        ('rsa_pixel_unshuffle2', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr]),
+        ('rsa_f32map_concat', C.c_int, [ptr, i32, ptr, i32] + [i32] * 3 + [ptr, ptr]),
+        ('rsa_fla_workspace_bytes', i64, [i32] * 3),
+        ('rsa_fla_reduce', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr, ptr, i64, ptr]),
+        ('rsa_fla_apply', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr, i64, i64, ptr]),
     ):
         getattr(lib, name).argtypes = argtypes
         getattr(lib, name).restype = restype

@@ -1122,3 +1122,58 @@ def rcan_state_dict(scale=4, n_resgroups=2, n_resblocks=2, n_feats=64, n_colors=
             _conv(sd, f'tail.0.{2 * i}', 4 * n_feats, n_feats, 3, seed)
     _conv(sd, 'tail.1', n_colors, n_feats, kernel_size, seed)
     return sd
+
+
+def gater_state_dict(dim=48, in_ch=3, num_blocks=(3, 6, 6, 10, 6, 6, 3), latent_att=False, seed=0):
+    """Keys of GateR (archs/gater/arch.py:162-200) in the module's registration order.  Matrices and filters are uniform with variance
+    1 / fan_in (roughly unit gain through a block), norm weights lie in 0.5..1.5, biases in +-0.09.  The latent attention's ``scale`` and
+    ``focusing_factor`` are drawn PER CHANNEL (+-0.87 and 2..4): the module's own initialisation leaves them constant, which would hide a
+    per-channel indexing error.  The last convolution is scaled by 0.1 so that the output stays near the image range."""
+    sd: OrderedDict = OrderedDict()
+    g = float(np.sqrt(3.0))  # uniform(-g / sqrt(fan_in), ..): variance 1 / fan_in
+
+    def lin(name, co, ci):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci), ci, seed, g)
+        sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (co,), 1, seed, 0.05 * g)
+
+    def conv(name, co, ci, k, groups=1, gain=1.0):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci // groups, k, k), (ci // groups) * k * k, seed, g * gain)
+        sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (co,), 1, seed, 0.05 * g * gain)
+
+    def blocks(prefix, width, n, att=False):
+        hidden = int((1.5 if att else 8 / 3) * width)
+        for i in range(n):
+            b = f'{prefix}.gated.{i}'
+            sd[f'{b}.norm.weight'] = 1.0 + synth_tensor(f'{b}.norm.weight', (width,), 1, seed, 0.5)
+            lin(f'{b}.fc1', 2 * hidden, width)
+            if att:
+                sd[f'{b}.conv.focusing_factor'] = 3.0 + synth_tensor(f'{b}.conv.focusing_factor', (width,), 1, seed, 1.0)
+                sd[f'{b}.conv.scale'] = synth_tensor(f'{b}.conv.scale', (width,), 1, seed, 0.5 * g)
+                lin(f'{b}.conv.q', width, width)
+                lin(f'{b}.conv.kv', 2 * width, width)
+                lin(f'{b}.conv.proj', width, width)
+                conv(f'{b}.conv.dwc', width // 8, width // 8, 5, groups=width // 8)
+            else:
+                conv(f'{b}.conv.conv', width, width, 7, groups=width)
+            lin(f'{b}.fc2', width, hidden)
+
+    nb = tuple(num_blocks)
+    conv('in_to_dim', dim, in_ch, 3)
+    blocks('enc0', dim, nb[0])
+    conv('enc1.0.body.0', dim // 2, dim, 3)
+    blocks('enc1.1', 2 * dim, nb[1])
+    conv('enc2.0.body.0', dim, 2 * dim, 3)
+    blocks('enc2.1', 4 * dim, nb[2])
+    conv('latent.0.body.0', 2 * dim, 4 * dim, 3)
+    blocks('latent.1', 8 * dim, nb[3], latent_att)
+    conv('latent.2.body.0', 16 * dim, 8 * dim, 3)
+    conv('dec0.0', 4 * dim, 8 * dim, 1)
+    blocks('dec0.1', 4 * dim, nb[4])
+    conv('dec0.2.body.0', 8 * dim, 4 * dim, 3)
+    conv('dec1.0', 2 * dim, 4 * dim, 1)
+    blocks('dec1.1', 2 * dim, nb[5])
+    conv('dec1.2.body.0', 4 * dim, 2 * dim, 3)
+    blocks('dec2.0', 2 * dim, nb[6])
+    conv('dim_to_ch.0', dim, 2 * dim, 3)
+    conv('dim_to_ch.1', in_ch, dim, 3, gain=0.1)
+    return sd

@@ -53,6 +53,11 @@ inline bool conv_ring_xres_eligible(const rsa_conv_params& p) {
          (p.act == RSA_ACT_NONE || (p.act == RSA_ACT_LRELU && p.act_param >= 0.f && p.act_param <= 1.f)) &&
          (p.lo8_flags == 0 || (p.lo8_flags | RSA_LO8_OUT) == (RSA_LO8_RES1 | RSA_LO8_OUT | (p.res2_hi != nullptr ? RSA_LO8_RES2 : 0)));  // lo halves all fp16, all 8-bit, or 8-bit residuals with an fp16 lo output (the last block of a trunk)
 }
+// The coded forms of it (lo8_flags != 0: conv_ring.h XRES 4 / 5) run conv_common.h's epilogue_c5, whose lane offsets are 32-bit from a base four
+// planes below the wave's last one: four planes of 16-byte units must stay below 2^31 bytes, else the kernel with the generic epilogue runs.
+inline bool c5_epilogue_fits(const rsa_conv_params& p) {
+  return p.res_plane_stride > 0 && p.out_plane_stride > 0 && p.res_plane_stride <= (1 << 25) && p.out_plane_stride <= (1 << 25);
+}
 // The growth convolutions of a dense block in the one-product fp16 mode: hi-only fp16 plane output, LeakyReLU (slope in [0, 1]) or no
 // activation, whole cout tiles, no residual, no f32 map (conv_ring.h, XRES 2: the epilogue shape EM 1 called directly).
 inline bool conv_ring_em1_eligible(const rsa_conv_params& p) {

@@ -236,6 +236,29 @@ struct GeoLW {
 };
 
 
+#ifdef RSA_C5_STAMPS
+// diagnostic build only (tools/variant.sh c5_stamps "-DRSA_C5_STAMPS" conv_inst_ring1h; tools/c5_stamps.py): s_memtime totals per compute wave.
+// The wait for a step's residual data is made explicit (vmcnt(n): n = memory operations issued behind that data) and timed on its own.
+#define C5_TIME() __builtin_amdgcn_s_memtime()
+#define C5_VM1(k) \
+  case k:         \
+    asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); \
+    break;
+__device__ __forceinline__ void c5_timed_wait(unsigned long long* st, int n) {  // n is a constant after unrolling: one s_waitcnt
+  if (st == nullptr) return;
+  const unsigned long long t0 = C5_TIME();
+  switch (n) {
+    C5_VM1(1) C5_VM1(2) C5_VM1(3) C5_VM1(4) C5_VM1(5) C5_VM1(6) C5_VM1(7) C5_VM1(8) C5_VM1(9) C5_VM1(10) C5_VM1(11) C5_VM1(12)
+    C5_VM1(13) C5_VM1(14) C5_VM1(15) C5_VM1(16) C5_VM1(17) C5_VM1(18) C5_VM1(19) C5_VM1(20) C5_VM1(21) C5_VM1(22) C5_VM1(23) C5_VM1(24)
+    C5_VM1(25) C5_VM1(26) C5_VM1(27) C5_VM1(28) C5_VM1(29) C5_VM1(30) C5_VM1(31) C5_VM1(32) C5_VM1(33) C5_VM1(34) C5_VM1(35) C5_VM1(36)
+    C5_VM1(37) C5_VM1(38) C5_VM1(39) C5_VM1(40) C5_VM1(41) C5_VM1(42)
+    default:
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  st[2] += C5_TIME() - t0;
+}
+#endif
+
 // Epilogue of one finished tile.  Every address is  (uniform 64-bit base) + (32-bit per-lane byte offset):
 //   lane (li, lg) of wave (wct, wpx) owns, for pixel-tile pt and cout-tile c, the 4 consecutive channels
 //   c0 = 16*(slab*NCT + CTW*wct + c) + 4*lg .. +3  of pixel (y0 + RPW*wpx + (pt>>1), x0 + 16*(pt&1) + li),  RPW = NPT/2.
@@ -263,7 +286,12 @@ struct GeoLW {
 template <int NCT, int CTW, int NPT, int OUTK, int AC, int EM = 0, int PF = 0, int XL = 0, int L8 = -1>
 __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f32x4 (&acc)[NPT][CTW], int n, int y0, int x0, int slab, int wct,
                                               int wpx, int li, int lg, const uint4* x_lds = nullptr, uint32_t xslots = 0u, int x_slot = 0,
-                                              int x_ps = 0, int x_iw = 0) {
+                                              int x_ps = 0, int x_iw = 0
+#ifdef RSA_C5_STAMPS
+                                              ,
+                                              unsigned long long* st = nullptr
+#endif
+) {
   constexpr int RPW = NPT / 2;
   constexpr bool G = EM == 0;
   // EM 4 (conv_ring.h XRES 3: the re-parameterised layers of the SPAN family): ONE activation class AC (Mish / SiLU / SPAB gate / linear),
@@ -386,7 +414,9 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
 #endif
 #ifndef RSA_EPI_PDX
 #define RSA_EPI_PDX 1  // XL: the hi halves come from LDS at their use, only lo halves (and the second residual) are fetched ahead; one step
-                       // ahead measured best (deeper: the raw values spill; profiles/r03_i_conv5_epilogue_prefetch.txt)
+                       // ahead measured best (deeper: the raw values spill; profiles/r03_i_conv5_epilogue_prefetch.txt).  Depth is not what
+                       // this path waits for, though: behind the branches of the guarded loads below the compiler waits with vmcnt(0)
+                       // (see epilogue_c5, which the coded conv5 kernels use instead)
 #endif
   constexpr int PD = XL ? RSA_EPI_PDX : (EM == 2 ? RSA_EPI_PD : (EM == 3 ? (RSA_EPI_PD + 1) / 2 : 0));
   constexpr int NSTEPS_E = CTW * RPW;
@@ -460,6 +490,10 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
         if (EM == 2 || EM == 3) {
           const int s = ct * RPW + pp;
           if (s + PD < NSTEPS_E) fetch_raw(s + PD);
+#ifdef RSA_C5_STAMPS
+          // behind fetch_raw(s): the steps fetched since (2 loads each, 6 with a second residual) and the stores of the steps in between
+          if (XL) c5_timed_wait(st, (EM == 3 ? 6 : 2) * ((s + PD < NSTEPS_E - 1 ? s + PD : NSTEPS_E - 1) - s) + 2 * (s < PD ? s : PD));
+#endif
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             if (XL) {  // the hi halves of x: ring slot of the half chunk (plane >> 1), plane & 1 inside it, halo coordinates (row + 1, column + 1)
@@ -727,6 +761,169 @@ __device__ __forceinline__ void epilogue_impl(const rsa_conv_params& p, const f3
         const int64_t slot = ((int64_t)n * tiles_y * tiles_x + (int64_t)(y0 >> 4) * tiles_x + (x0 >> 5)) * (16 / RPW) + wpx;
         *(f32x4*)(p.pool_sums + slot * (((p.cout + 15) >> 4) << 4) + c0) = (f32x4){psum[0], psum[1], psum[2], psum[3]};
       }
+    }
+  }
+}
+
+// conv5 of a residual dense block on the coded residual stream (conv_ring.h XRES 4 / 5: four cout tiles, 2 per wave, 8 pixel tiles; fp16 hi
+// planes, every residual's lo half as 8-bit codes, x's hi halves in the ring): the shape EM 2 / 3 + XL + L8 of epilogue_impl as ONE basic block.
+//
+// Why a function of its own.  epilogue_impl guards every residual load and every store with `if (lane inside the map)`, which the compiler turns
+// into a branch around each of them.  Its vmcnt bookkeeping then no longer knows how many memory operations are in flight behind a load and waits
+// with vmcnt(0) -- for the loads it has just issued for the NEXT step and for the acknowledgement of every store of the steps before: four full
+// round trips per tile with the matrix pipes of the CU idle, whatever the prefetch depth (deeper only added spills).  Here the guard is the
+// buffer range check instead: a lane outside the map addresses C5_SKIP, past num_records, so its load touches no memory and returns zero and its
+// store is dropped.  No branch, one basic block, and every wait of a step is a counted vmcnt for that step's own loads:
+//   * one residual: the res1 code dwords of all eight steps are requested in one burst at entry (one dword per fragment: 16 registers), ahead
+//     of the first LDS read, and consumed in issue order; every load is issued before the first store;
+//   * TWO: both residuals' halves of a step (8 registers) are requested RSA_C5_D2 steps ahead -- the kernel has no registers for the burst
+//     beside them;
+//   * stores are never waited for.
+// The arithmetic is epilogue_impl's, value for value (outputs are bit-identical to that path).
+// Offsets are 32-bit from a base four planes below the wave's last one: c5_epilogue_fits() must hold (else the launcher takes epilogue_impl).
+#ifndef RSA_C5_D2
+#define RSA_C5_D2 1  // TWO: steps of prefetch of both residuals (registers per depth: DESIGN.md 4.1a)
+#endif
+constexpr uint32_t C5_SKIP = 0x80000000u;  // lane offset of a lane that loads / stores nothing: >= num_records, and + 12 does not wrap
+
+template <int TWO, int L8>
+__device__ __forceinline__ void epilogue_c5(const rsa_conv_params& p, const f32x4 (&acc)[8][2], int n, int y0, int x0, int wct, int wpx, int li, int lg,
+                                            const uint4* x_lds, uint32_t xslots, int x_slot, int x_ps, int x_iw,
+                                            [[maybe_unused]] unsigned long long* st = nullptr) {
+  constexpr int CTW = 2, RPW = 4, NS = CTW * RPW, D = RSA_C5_D2;
+  constexpr bool OL8 = L8 == 1;  // (L8 2: the residuals only; the output's lo halves are fp16)
+  static_assert(D >= 1 && D <= NS - 1, "RSA_C5_D2");
+  const float lin_slope = p.act == RSA_ACT_NONE ? 1.f : p.act_param;
+  asm volatile("" : "+v"(li), "+v"(lg));  // tile-local lane terms: see epilogue_impl
+  const int64_t pix0 = (int64_t)y0 * p.W + x0;  // uniform
+  const uint32_t lbase = (uint32_t)(wpx * RPW * p.W + li);
+  const bool xv0 = x0 + li < p.W, xv1 = x0 + 16 + li < p.W;
+  auto lpix_of = [&](int pt) -> uint32_t { return lbase + (uint32_t)((pt >> 1) * p.W + (pt & 1) * 16); };
+  auto pvalid_of = [&](int pt) -> bool { return (y0 + wpx * RPW + (pt >> 1) < p.H) && ((pt & 1) ? xv1 : xv0); };  // (Cout = 64: every channel is live)
+
+  // uniform bases at the wave's first plane (cout tile 2 * wct = plane 4 * wct), this tile's first pixel; cout tile ct adds two planes (scalar offset)
+  const uint32_t rps = (uint32_t)p.res_plane_stride, ops = (uint32_t)p.out_plane_stride;
+  const int64_t runit = (int64_t)n * p.res_batch_stride + (int64_t)(4 * wct) * p.res_plane_stride + pix0;
+  const int64_t runit8 = (int64_t)n * p.lo8_batch_stride + (int64_t)(4 * wct) * p.res_plane_stride + pix0;
+  const int64_t ounit = (int64_t)n * p.out_batch_stride + (int64_t)(p.out_plane_off + 4 * wct) * p.out_plane_stride + pix0;
+  const int64_t ounit8 = (int64_t)n * p.lo8_batch_stride + (int64_t)(p.out_plane_off + 4 * wct) * p.out_plane_stride + pix0;
+  auto rsrc = [](const void* base, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000); };
+  const __amdgpu_buffer_rsrc_t b_r1c = rsrc((const char*)p.res1_lo + runit8 * 8, 4u * rps * 8u);
+  const __amdgpu_buffer_rsrc_t b_r2h = rsrc((const char*)p.res2_hi + (TWO ? runit : 0) * 16, TWO ? 4u * rps * 16u : 0u);
+  const __amdgpu_buffer_rsrc_t b_r2c = rsrc((const char*)p.res2_lo + (TWO ? runit8 : 0) * 8, TWO ? 4u * rps * 8u : 0u);
+  const __amdgpu_buffer_rsrc_t b_oh = rsrc((const char*)p.out_hi + ounit * 16, 4u * ops * 16u);
+  const __amdgpu_buffer_rsrc_t b_ol = OL8 ? rsrc((const char*)p.out_lo + ounit8 * 8, 4u * ops * 8u) : rsrc((const char*)p.out_lo + ounit * 16, 4u * ops * 16u);
+  const uint32_t rlane = (uint32_t)(lg >> 1) * rps, pllane = (uint32_t)(lg >> 1) * ops;  // + lpix, in units
+  // residual unit half of (step, e): plane lg >> 1 of the cout tile, half lg & 1; in bytes of a code plane (8 per unit), hi planes: twice that
+  auto roff8 = [&](int pp, int e) -> uint32_t { return pvalid_of(pp * 2 + e) ? (rlane + lpix_of(pp * 2 + e)) * 8u + (uint32_t)(lg & 1) * 4u : C5_SKIP; };
+
+  // The bias vectors go first: they are two small loads that hit the cache, every step needs one of them, and vmcnt retires in order -- behind
+  // the burst, step 0 would wait for all of it.  No bias: num_records = 0, the loads return zeros (a test would be a branch: see above).
+  const __amdgpu_buffer_rsrc_t b_bias = rsrc(p.bias, p.bias != nullptr ? 64u * 4u : 0u);  // (padded to a multiple of 16 channels)
+  f32x4 biasv[CTW];
+#pragma unroll
+  for (int ct = 0; ct < CTW; ++ct)
+    biasv[ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_bias, (uint32_t)((wct * CTW + ct) * 4 + lg) * 16u, 0, 0));
+  // ---- every step's res1 codes, one burst ----
+  uint32_t c1[NS][2];
+  auto fetch1 = [&](int s) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) c1[s][e] = __builtin_amdgcn_raw_buffer_load_b32(b_r1c, roff8(s % RPW, e), (uint32_t)(s / RPW) * 2u * rps * 8u, 0);
+  };
+  if (!TWO) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) fetch1(s);
+  }
+  // ---- the second residual, D steps ahead ----
+  u32x2 h2[TWO ? D + 1 : 1][2];
+  uint32_t c2[TWO ? D + 1 : 1][2];
+  auto fetch2 = [&](int s) {
+    fetch1(s);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const uint32_t o8 = roff8(s % RPW, e);
+      h2[s % (D + 1)][e] = __builtin_amdgcn_raw_buffer_load_b64(b_r2h, pvalid_of((s % RPW) * 2 + e) ? o8 * 2u : C5_SKIP, (uint32_t)(s / RPW) * 2u * rps * 16u, 0);
+      c2[s % (D + 1)][e] = __builtin_amdgcn_raw_buffer_load_b32(b_r2c, o8, (uint32_t)(s / RPW) * 2u * rps * 8u, 0);
+    }
+  };
+  if (TWO) {
+#pragma unroll
+    for (int s = 0; s < D; ++s) fetch2(s);
+  }
+  // the hi halves of x, read from the ring one step ahead: ring slot of the half chunk (plane >> 1), plane & 1 inside it, halo coordinates
+  // (row + 1, column + 1)
+  auto read_x = [&](int s, int e) -> uint2 {
+    const int pt = (s % RPW) * 2 + e;
+    const int plane = 4 * wct + 2 * (s / RPW) + (lg >> 1);
+    const uint32_t u = ((xslots >> (4 * (plane >> 1))) & 15u) * (uint32_t)x_slot + (uint32_t)((plane & 1) * x_ps) +
+                       (uint32_t)((wpx * RPW + (pt >> 1) + 1) * x_iw + (pt & 1) * 16 + li + 1);
+    return *(const uint2*)((const char*)x_lds + u * 16u + (uint32_t)(lg & 1) * 8u);
+  };
+  uint2 xn[2] = {read_x(0, 0), read_x(0, 1)};
+
+#pragma unroll
+  for (int ct = 0; ct < CTW; ++ct) {
+    const f32x4 bias = biasv[ct];
+#pragma unroll
+    for (int pp = 0; pp < RPW; ++pp) {
+      const int s = ct * RPW + pp;
+      if (TWO && s + D < NS) fetch2(s + D);
+      float v[2][4];
+      f32x4 cr1[2], cr2[2];
+      const uint2 xh[2] = {xn[0], xn[1]};
+      if (s + 1 < NS) xn[0] = read_x(s + 1, 0), xn[1] = read_x(s + 1, 1);
+#ifdef RSA_C5_STAMPS
+      // behind this step's data: the rest of the burst and the stores so far (one residual: always 14 operations);
+      // TWO: the steps fetched behind fetch2(s) (4 loads each) and the stores issued since (2 per step)
+      c5_timed_wait(st, TWO ? 6 * ((s + D < NS - 1 ? s + D : NS - 1) - s) + 2 * (s < D ? s : D) : 14);
+#endif
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        cr1[e] = widen4_lo8(xh[e], c1[s][e]);
+        cr2[e] = TWO ? widen4_lo8(make_uint2(h2[TWO ? s % (D + 1) : 0][e].x, h2[TWO ? s % (D + 1) : 0][e].y), c2[TWO ? s % (D + 1) : 0][e]) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+      // epilogue_impl adds the residuals in lanes inside the map only.  A lane outside stores nothing, and the lane it exchanges halves with
+      // has the same pixel, so its values reach no store: the test is dropped, not replaced (a test here is a branch the loads above sink into).
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[e][r] = acc[pp * 2 + e][ct][r] + bias[r];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[e][r] = fmaxf(v[e][r], v[e][r] * lin_slope);  // none / LeakyReLU with a slope in [0, 1]
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[e][r] = v[e][r] * p.alpha + cr1[e][r];
+        if (TWO) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[e][r] = v[e][r] * p.beta + cr2[e][r];
+        }
+      }
+      uint32_t h[2][2], l[2][2], q8[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        if (OL8) {
+          split4_lo8(v[e][0], v[e][1], v[e][2], v[e][3], h[e][0], h[e][1], q8[e]);
+        } else {
+          split2<RSA_PF_F16>(v[e][0], v[e][1], h[e][0], l[e][0]);
+          split2<RSA_PF_F16>(v[e][2], v[e][3], h[e][1], l[e][1]);
+        }
+      }
+      // the two lanes that hold the halves of a unit exchange one half each (v_permlane16_swap: see epilogue_impl); even lane groups store the
+      // unit of pixel tile 2k, odd ones that of 2k + 1
+      const int pt = pp * 2 + (lg & 1);
+      const bool sv = pvalid_of(pt);
+      const uint32_t upix = pllane + lpix_of(pt);
+      const u32x2 h0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
+      const u32x2 h1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
+      __builtin_amdgcn_raw_buffer_store_b128((u32x4){h0.x, h1.x, h0.y, h1.y}, b_oh, sv ? upix * 16u : C5_SKIP, (uint32_t)ct * 2u * ops * 16u, 0);
+      if (OL8) {
+        const u32x2 l8 = __builtin_amdgcn_permlane16_swap(q8[0], q8[1], false, false);
+        __builtin_amdgcn_raw_buffer_store_b64(l8, b_ol, sv ? upix * 8u : C5_SKIP, (uint32_t)ct * 2u * ops * 8u, 0);
+      } else {
+        const u32x2 l0 = __builtin_amdgcn_permlane16_swap(l[0][0], l[1][0], false, false);
+        const u32x2 l1 = __builtin_amdgcn_permlane16_swap(l[0][1], l[1][1], false, false);
+        __builtin_amdgcn_raw_buffer_store_b128((u32x4){l0.x, l1.x, l0.y, l1.y}, b_ol, sv ? upix * 16u : C5_SKIP, (uint32_t)ct * 2u * ops * 16u, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // one step at a time: interleaving the steps costs more registers than the schedule has
     }
   }
 }

@@ -160,8 +160,24 @@ __device__ __forceinline__ void dma16_v(uint32_t lds_addr, gcptr vaddr) {
 // there -- a wave of this shape owns three cout tiles of only four pixel tiles, so its weight stream from L2 was 256 B per matrix
 // instruction, 2.3 x that of the RRDBNet shapes -- and the epilogue is instantiated for ONE activation class XAC (Mish / SiLU / SPAB gate /
 // linear) with its shape folded (conv_common.h, EM 4) instead of going through the generic dispatch (141 spilled scalar registers, 64 B of scratch).
-template <int SHAPE, int UP, int OUTK, int HM = 0, int FMT = 0, int PROD = 3, int XRES = 0, int XAC = 0>
+// XR2 (XRES 4 / 5): 0 / 1 = the layer has one / two plane residuals and the epilogue is conv_common.h's epilogue_c5 -- two kernels, so that the
+// registers of the one-residual form (46 of the 69 conv5 launches of an RRDBNet frame) are not set by the other; -1 = decided per tile on
+// epilogue_impl (XRES 1; XRES 4 / 5 on planes too large for epilogue_c5's 32-bit offsets, and in A/B builds with -DRSA_C5_EPI=0).
+#ifndef RSA_C5_EPI
+#define RSA_C5_EPI 1
+#endif
+#ifdef RSA_C5_STAMPS
+// diagnostic build only (tools/variant.sh c5_stamps "-DRSA_C5_STAMPS" conv_inst_ring1h; tools/c5_stamps.py): s_memtime totals of the conv5 kernels'
+// compute waves, written to memory no other code reads.  [workgroup][wave 0..7][slot]: 0 lifetime, 1 waiting for ring fills (FULL), 2 epilogue:
+// waiting for a step's residual data, 3 epilogue (whole), 4 tiles.  The K loop is what remains of the lifetime.
+static __device__ unsigned long long g_c5_stamps[256 * 8 * 8];
+#define C5_ST_ARG , st
+#else
+#define C5_ST_ARG
+#endif
+template <int SHAPE, int UP, int OUTK, int HM = 0, int FMT = 0, int PROD = 3, int XRES = 0, int XAC = 0, int XR2 = -1>
 __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(const rsa_conv_params p, const RingAux aux) {
+  static_assert(XR2 == -1 || XRES == 4 || XRES == 5, "XR2: the coded conv5 kernels only");
   static_assert((XRES != 1 && XRES != 4 && XRES != 5) || (SHAPE == 1 && PROD == 1 && HM == 0 && UP == 0 && OUTK == 0), "XRES 1 / 4 / 5: conv5 of a residual dense block only");
   static_assert(XRES != 2 || (PROD == 1 && FMT == RSA_PF_F16 && OUTK == 0), "XRES 2: one fp16 product, hi-only plane output");
   static_assert(XRES != 3 || (SHAPE == 3 && PROD == 1 && FMT == RSA_PF_F16 && HM == 1 && UP == 0 && OUTK == 0), "XRES 3: the 48-channel SPAN-family layers");
@@ -425,6 +441,10 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
   auto slot_of = [&](uint32_t k) -> int { return (STREAMS == 2) ? SPS * g + (int)(k & (SPS - 1)) : (int)(k & (NSLOT - 1)); };
   auto use_of = [&](uint32_t k) -> uint32_t { return k / SPS; };
   uint32_t xslots = 0;  // XRES: ring slots of x's four half chunks (4 bits each)
+#ifdef RSA_C5_STAMPS
+  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const unsigned long long t_begin = C5_TIME();
+#endif
   for (int j = (STREAMS == 2 ? g : 0); j < ntw; j += STREAMS) {
     for (int c = 0; c < nq; ++c) {
       const int sA = slot_of(kc), sB = HM ? sA : slot_of(kc + 1);
@@ -443,7 +463,13 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
         // again and multiply zero weights (finite data: 0 * finite = 0)
         uS = (hsel ? bB : bA) + 2 * IW + 2;
       }
+#ifdef RSA_C5_STAMPS
+      const unsigned long long twA = C5_TIME();
+#endif
       ring_wait(&f_full[sA], needA, f_abort, aux);
+#ifdef RSA_C5_STAMPS
+      st[1] += C5_TIME() - twA;
+#endif
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("" ::: "memory");
 
@@ -513,7 +539,13 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
         constexpr int FIRST_B = 4 * NPT - DEPTH;  // the step whose prefetch is the first read of the pairing step (half B)
 #pragma unroll
         for (int i = 0; i < FIRST_B; ++i) step(i);
+#ifdef RSA_C5_STAMPS
+        const unsigned long long twB = C5_TIME();
+#endif
         ring_wait(&f_full[sB], needB, f_abort, aux);
+#ifdef RSA_C5_STAMPS
+        st[1] += C5_TIME() - twB;
+#endif
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" ::: "memory");
 #pragma unroll
@@ -534,12 +566,22 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
       } else if constexpr (XRES == 7) {
         if (!RING_DBG(8)) epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 5>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg);
       } else if (XR) {
-        if (!RING_DBG(8)) {
+#ifdef RSA_C5_STAMPS
+        const unsigned long long te = C5_TIME();
+#endif
+        if (RING_DBG(8)) {
+        } else if constexpr (XR2 >= 0) {
+          epilogue_c5<XR2, XRES == 4 ? 1 : 2>(p, acc, n, ty * TH, tx * TW, wct, wpx, li, lg, s_ring, xslots, SLOT, PS, IW C5_ST_ARG);
+        } else {
           if (p.res2_hi != nullptr)
-            epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 3, RSA_PF_F16, 1, XRES == 4 ? 1 : (XRES == 5 ? 2 : 0)>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg, s_ring, xslots, SLOT, PS, IW);
+            epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 3, RSA_PF_F16, 1, XRES == 4 ? 1 : (XRES == 5 ? 2 : 0)>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg, s_ring, xslots, SLOT, PS, IW C5_ST_ARG);
           else
-            epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 2, RSA_PF_F16, 1, XRES == 4 ? 1 : (XRES == 5 ? 2 : 0)>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg, s_ring, xslots, SLOT, PS, IW);
+            epilogue_impl<NCT, CTW, NPT, 0, AC_LINEAR, 2, RSA_PF_F16, 1, XRES == 4 ? 1 : (XRES == 5 ? 2 : 0)>(p, acc, n, ty * TH, tx * TW, 0, wct, wpx, li, lg, s_ring, xslots, SLOT, PS, IW C5_ST_ARG);
         }
+#ifdef RSA_C5_STAMPS
+        st[3] += C5_TIME() - te;
+        st[4] += 1;
+#endif
         // the residual's LDS reads have been consumed (their values are in the stores above): hand x's four slots back
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (lane == 0) {
@@ -555,10 +597,19 @@ __global__ __launch_bounds__((8 + (SHAPE == 2 ? 2 : 1)) * 64, 3) void conv_ring(
 #pragma unroll
       for (int ct = 0; ct < CTW; ++ct) acc[pt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
+#ifdef RSA_C5_STAMPS
+  st[0] = C5_TIME() - t_begin;
+  if (XR && lane == 0 && blockIdx.x < 256)
+    for (int i = 0; i < 8; ++i) g_c5_stamps[((int)blockIdx.x * 8 + wave) * 8 + i] = st[i];
+#endif
 }
 
-template <int SHAPE, int UP, int OUTK, int HM = 0, int FMT = 0, int PROD = 3, int XRES = 0, int XAC = 0>
+template <int SHAPE, int UP, int OUTK, int HM = 0, int FMT = 0, int PROD = 3, int XRES = 0, int XAC = 0, int XR2 = -1>
 static int launch_ring(const rsa_conv_params& p, hipStream_t stream) {
+  if constexpr ((XRES == 4 || XRES == 5) && XR2 == -1 && RSA_C5_EPI) {  // the coded conv5: one kernel per number of residuals
+    if (c5_epilogue_fits(p))
+      return p.res2_hi != nullptr ? launch_ring<SHAPE, UP, OUTK, HM, FMT, PROD, XRES, XAC, 1>(p, stream) : launch_ring<SHAPE, UP, OUTK, HM, FMT, PROD, XRES, XAC, 0>(p, stream);
+  }
   constexpr int STREAMS = SHAPE == 2 ? 2 : 1;
   using R = RingGeoP<PROD>;
   const int tiles_x = (p.W + R::TW - 1) / R::TW;
@@ -573,7 +624,7 @@ static int launch_ring(const rsa_conv_params& p, hipStream_t stream) {
   }();
   int gx = cus;  // one persistent workgroup per CU (the ring takes the whole LDS)
   if (gx > num_tiles) gx = (int)num_tiles;
-  hipLaunchKernelGGL((conv_ring<SHAPE, UP, OUTK, HM, FMT, PROD, XRES, XAC>), dim3((unsigned)gx, 1, 1), dim3((8 + STREAMS) * 64), 0, stream, p, ring_aux());
+  hipLaunchKernelGGL((conv_ring<SHAPE, UP, OUTK, HM, FMT, PROD, XRES, XAC, XR2>), dim3((unsigned)gx, 1, 1), dim3((8 + STREAMS) * 64), 0, stream, p, ring_aux());
   return (int)hipGetLastError();
 }
 

@@ -1393,6 +1393,58 @@ int rsa_fla_apply(const void* qkv_hi, const void* qkv_lo, int64_t qkv_plane_stri
                   const float* dwc_weight, const float* dwc_bias, void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride,
                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- EIMN ops
+ * (reference archs/eimn/arch.py, DFFM :65-92, SADFFM :38-62, MOLRCM :103-146, EIMNBlock :149-171; csrc/eimn.hip)
+ * Plane operands are split planes of format fmt (every lo pointer may be NULL), strides in 16-byte units (a plane stride
+ * is at least H * W and, with batch > 1, a batch stride at least the operand's planes times its plane stride), pointers 16-byte aligned. */
+
+/* MOLRCM's depthwise chain in one launch: out = cat(spatial_1(r[a]), r[b], spatial_2(r[c])) with r = region(q): a 5x5 depthwise convolution
+ * with bias and zero padding 2 on every plane, then per plane group a 5x5 with dilation 2 and padding 4 (the first planes_a planes), nothing
+ * (the next planes_b) or a 7x7 with dilation 3 and padding 9 (the last planes_c), each with its bias.  The second stage zero-pads r: outside
+ * the map its input is 0.  gelu_in != 0 applies the exact (erf) GELU to q as it is read (proj_query's activation; GELU(0) = 0, so the zero
+ * padding is unaffected).  With P = planes_a + planes_b + planes_c, all f32 and 16-byte aligned, per half plane of four channels:
+ *   w1 [2P][25][4], b1 [2P][4], w2 [2P][49][4] (row-major taps; a 5x5 uses the first 25 rows, an identity plane none), b2 [2P][4].
+ * Not in place.  1 <= P <= 32767. */
+int rsa_eimn_query_chain(const void* q_hi, const void* q_lo, int64_t q_plane_stride, int64_t q_batch_stride, void* out_hi, void* out_lo,
+                         int64_t out_plane_stride, int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t planes_a, int32_t planes_b,
+                         int32_t planes_c, int32_t gelu_in, int32_t fmt, const float* w1, const float* b1, const float* w2, const float* b2,
+                         void* stream);
+
+/* SADFFM's middle (:58-59): out = GELU(dw3x3(x1) + b1) * (dw3x3(x2) + b2), zero padding 1, exact GELU: rsa_gelu_gate_dwconv with the
+ * biases of SAL.  x1 is planes [0, planes) and x2 planes [planes, 2 * planes) of the input; weight [2 * planes * 8][9] and
+ * bias [2 * planes * 8] in the same channel order.  Not in place. */
+int rsa_eimn_sal(const void* in_hi, const void* in_lo, int64_t in_plane_stride, int64_t in_batch_stride, void* out_hi, void* out_lo,
+                 int64_t out_plane_stride, int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t planes, int32_t fmt,
+                 const float* weight, const float* bias, void* stream);
+
+/* out = silu(f) * v = f * sigmoid(f) * v over `planes` planes (:145-146); out may be f or v. */
+int rsa_eimn_silu_mul(const void* f_hi, const void* f_lo, int64_t f_plane_stride, int64_t f_batch_stride, const void* v_hi, const void* v_lo,
+                      int64_t v_plane_stride, int64_t v_batch_stride, void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride,
+                      int32_t batch, int32_t H, int32_t W, int32_t planes, int32_t fmt, void* stream);
+
+/* DFFM behind linear_out, with the block's second residual and the stage's LayerNorm, on f32 maps [N][C/4][H][W][4]; C % 8 == 0,
+ * 8 <= C <= 128, reduced width rc in 1..32.  With n = gamma * (z - mean_c z) / sqrt(var_c z + eps) + beta per pixel (channels-first LayerNorm):
+ *   rsa_eimn_dffm_reduce  workspace[n][slot][c] = sum of n over the 256 pixels of the slot, slots = ceil(H * W / 256): the norm in f64, every
+ *                         value rounded to f32 once and added in a fixed f32 tree of depth RSA_EIMN_DFFM_DEPTH (that rounding included).
+ *                         Every entry is written; no atomics; the same bits on every run.
+ *   rsa_eimn_dffm_gates   one workgroup per image, f64: mean = ordered sum of the slots / (H * W), g = GELU(wg . mean + bg) [rc],
+ *                         gates[n][c] = sigmoid(wc . g + bc) for c < C and gates[n][C] = ws[rc:] . g + bs; gates is f32 [batch][C + 4].
+ *   rsa_eimn_dffm_apply   per pixel: l = GELU(wl . n + bl), s = sigmoid(ws[:rc] . l + gates[n][C]),
+ *                         v = x + scale[c] * z * gates[n][c] * s;  norm_gamma != NULL: v = LayerNorm_c(v) with norm_eps, norm_gamma, norm_beta;
+ *                         add != NULL: v += add.  Writes v to out_f32 (may be x) and as split planes.
+ * wg, wl [rc][C]; wc [C][rc]; ws [2 rc]; bs [1]; gamma, beta, scale, norm_gamma, norm_beta [C]; all f32.
+ * workspace: rsa_eimn_dffm_workspace_bytes(batch, H, W, C) bytes, 16-byte aligned. */
+#define RSA_EIMN_DFFM_DEPTH 10
+int64_t rsa_eimn_dffm_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t C);
+int rsa_eimn_dffm_reduce(const float* z, int32_t batch, int32_t H, int32_t W, int32_t C, const float* gamma, const float* beta, float eps,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int rsa_eimn_dffm_gates(const void* workspace, int64_t workspace_bytes, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t rc, const float* wg,
+                        const float* bg, const float* wc, const float* bc, const float* ws, const float* bs, float* gates, void* stream);
+int rsa_eimn_dffm_apply(const float* z, const float* x, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t rc, const float* gamma,
+                        const float* beta, float eps, const float* wl, const float* bl, const float* ws, const float* gates, const float* scale,
+                        const float* norm_gamma, const float* norm_beta, float norm_eps, const float* add, float* out_f32, void* out_hi,
+                        void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride, int32_t fmt, void* stream);
+
 /* version / errors */
 int rsa_version(void);
 const char* rsa_last_error_string(void);

@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -11,6 +11,7 @@ from .compact import CompactArch
 from .cugan import CUGANArch
 from .dat import DatArch
 from .drct import DRCTArch
+from .eimn import EIMNArch
 from .esrgan import ESRGANArch
 from .fdat import FDATArch
 from .gater import GateRArch
@@ -28,7 +29,7 @@ from .spanpp import SpanPPArch
 from .swinir import SwinIRArch
 
 internal_registry = Registry()
-# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): ESRGAN, HAT, dat, RCAN, Compact, GateR, ATD, RGT, OmniSR, MoSR, FDAT, CuGAN, PLKSR, MoSRv2, RTMoSR,
+# relative order follows the reference's registry walk (tests/golden/registry_claims.npz): eimn, ESRGAN, HAT, dat, RCAN, Compact, GateR, ATD, RGT, OmniSR, MoSR, FDAT, CuGAN, PLKSR, MoSRv2, RTMoSR,
 # spanplus, SwinIR, SpanPP, ..., SPAN
-for _arch in (ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, GateRArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
+for _arch in (EIMNArch, ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, GateRArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
     internal_registry.add(_arch())

@@ -448,6 +448,13 @@ EXPORTS = (
     'rsa_fla_workspace_bytes',
     'rsa_fla_reduce',
     'rsa_fla_apply',
+    'rsa_eimn_query_chain',
+    'rsa_eimn_sal',
+    'rsa_eimn_silu_mul',
+    'rsa_eimn_dffm_workspace_bytes',
+    'rsa_eimn_dffm_reduce',
+    'rsa_eimn_dffm_gates',
+    'rsa_eimn_dffm_apply',
 )
 
 
@@ -595,6 +602,13 @@ def load() -> C.CDLL:
         ('rsa_fla_workspace_bytes', i64, [i32] * 3),
         ('rsa_fla_reduce', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr, ptr, i64, ptr]),
         ('rsa_fla_apply', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr, i64, i64, ptr]),
+        ('rsa_eimn_query_chain', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 8 + [ptr] * 5),
+        ('rsa_eimn_sal', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 5 + [ptr] * 3),
+        ('rsa_eimn_silu_mul', C.c_int, [ptr, ptr, i64, i64] * 3 + [i32] * 5 + [ptr]),
+        ('rsa_eimn_dffm_workspace_bytes', i64, [i32] * 4),
+        ('rsa_eimn_dffm_reduce', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr, f32, ptr, i64, ptr]),
+        ('rsa_eimn_dffm_gates', C.c_int, [ptr, i64] + [i32] * 5 + [ptr] * 8),
+        ('rsa_eimn_dffm_apply', C.c_int, [ptr, ptr] + [i32] * 5 + [ptr, ptr, f32] + [ptr] * 7 + [f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr]),
     ):
         getattr(lib, name).argtypes = argtypes
         getattr(lib, name).restype = restype

@@ -1177,3 +1177,61 @@ def gater_state_dict(dim=48, in_ch=3, num_blocks=(3, 6, 6, 10, 6, 6, 3), latent_
     conv('dim_to_ch.0', dim, 2 * dim, 3)
     conv('dim_to_ch.1', in_ch, dim, 3, gain=0.1)
     return sd
+
+
+def eimn_state_dict(embed_dims=64, scale=2, depths=1, hidden=None, mlp_ratios=2.66, num_stages=2, seed=0):
+    """Keys of EIMN (archs/eimn/arch.py:174-241) in the module's registration order: head, tail, then per stage its blocks and its LayerNorm.
+    ``hidden`` defaults to the reference's ``int(embed_dims * mlp_ratios)``.  Matrices and filters are uniform with variance 1 / fan_in, every
+    bias is non-zero (+-0.09).  BatchNorm: weights in 0.5..1.5, running variances in 0.5..1.5, running means about +-0.3,
+    ``num_batches_tracked`` 100.  The layer scales lie in 0.1..0.6 -- the module initialises them to 1e-2, which would hide the blocks
+    behind the residual -- and the norm weights in 0.5..1.5."""
+    sd: OrderedDict = OrderedDict()
+    dim = embed_dims
+    hidden = int(dim * mlp_ratios) if hidden is None else hidden
+    rc = int(dim * 0.25)
+    c1, c3 = int(3 / 8 * dim), int(4 / 8 * dim)
+    g = float(np.sqrt(3.0))  # uniform(-g / sqrt(fan_in), ..): variance 1 / fan_in
+
+    def conv(name, co, ci, k, groups=1):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci // groups, k, k), (ci // groups) * k * k, seed, g)
+        b = synth_tensor(f'{name}.bias', (co,), 1, seed, 0.08 * g)
+        sd[f'{name}.bias'] = b + 0.01 * torch.where(b >= 0, 1.0, -1.0)  # never zero
+
+    def affine(name, c):
+        sd[f'{name}.weight'] = 1.0 + synth_tensor(f'{name}.weight', (c,), 1, seed, 0.5)
+        b = synth_tensor(f'{name}.bias', (c,), 1, seed, 0.08 * g)
+        sd[f'{name}.bias'] = b + 0.01 * torch.where(b >= 0, 1.0, -1.0)
+
+    def bn(name):
+        affine(name, dim)
+        sd[f'{name}.running_mean'] = synth_tensor(f'{name}.running_mean', (dim,), 1, seed, 0.3)
+        sd[f'{name}.running_var'] = 1.0 + synth_tensor(f'{name}.running_var', (dim,), 1, seed, 0.5)
+        sd[f'{name}.num_batches_tracked'] = torch.tensor(100, dtype=torch.long)
+
+    conv('head.0', dim, 3, 3)
+    conv('tail.0', 3 * scale * scale, dim, 3)
+    for i in range(1, num_stages + 1):
+        for j in range(depths):
+            p = f'block{i}.{j}'
+            for k in (1, 2):
+                sd[f'{p}.layer_scale_{k}'] = 0.35 + synth_tensor(f'{p}.layer_scale_{k}', (dim,), 1, seed, 0.25)
+            bn(f'{p}.norm1')
+            conv(f'{p}.attn.region', dim, dim, 5, groups=dim)
+            conv(f'{p}.attn.spatial_1', c1, c1, 5, groups=c1)
+            conv(f'{p}.attn.spatial_2', c3, c3, 7, groups=c3)
+            conv(f'{p}.attn.fusion', dim, dim, 1)
+            conv(f'{p}.attn.proj_value.0', dim, dim, 1)
+            conv(f'{p}.attn.proj_query.0', dim, dim, 1)
+            conv(f'{p}.attn.out', dim, dim, 1)
+            bn(f'{p}.norm2')
+            conv(f'{p}.mlp.linear_in', 2 * hidden, dim, 1)
+            conv(f'{p}.mlp.SAL', 2 * hidden, 2 * hidden, 3, groups=2 * hidden)
+            conv(f'{p}.mlp.linear_out', dim, hidden, 1)
+            q = f'{p}.mlp.DFFM'
+            affine(f'{q}.norm', dim)
+            conv(f'{q}.global_reduce', rc, dim, 1)
+            conv(f'{q}.local_reduce', rc, dim, 1)
+            conv(f'{q}.channel_expand', dim, rc, 1)
+            conv(f'{q}.spatial_expand', 1, 2 * rc, 1)
+        affine(f'norm{i}', dim)
+    return sd

@@ -1445,6 +1445,45 @@ int rsa_eimn_dffm_apply(const float* z, const float* x, int32_t batch, int32_t H
                         const float* norm_gamma, const float* norm_beta, float norm_eps, const float* add, float* out_f32, void* out_hi,
                         void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride, int32_t fmt, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- RHA ops
+ * (reference archs/rha/arch.py, FocusedLinearAttention :188-302, HybridAttention :398-415, GatedCNNBlock :418-450; csrc/rha.hip)
+ * Plane operands are split planes of format fmt (every lo pointer may be NULL), strides in 16-byte units (a plane stride is at least
+ * H * W and, with batch > 1, a batch stride at least the operand's planes times its plane stride), pointers 16-byte aligned.  A plane
+ * operand may start at a plane offset inside a wider buffer: pass the pointer of its first plane and the wider buffer's strides. */
+
+/* MaxPool(down) -> roll(-shift) -> FocusedLinearAttention on every window x window window -> roll(+shift) in one launch, one workgroup
+ * per (image, window) of the pooled map [H / down][W / down].  x: C2 / 8 planes at FULL resolution H x W (multiples of down * window);
+ * the maximum of a down x down cell is taken over hi + lo and starts from the cell's first element.  A token at window-local row r of
+ * window row wy is pooled row (wy * window + r + shift) mod (H / down), likewise for columns: the roll is cyclic and there is no mask.
+ * Per window, with N = window^2 tokens, 8 heads of d = C2 / 8 channels, all in f32:
+ *   q | k | v = token Wqkv^T + bqkv;  k += pos;  q, k = (relu(.) + 1e-6) * inv_scale[c];  u <- u^3 / ||u^3|| * ||u|| over all C2 channels
+ *   (evaluated on u / max(u), so that no intermediate leaves the f32 normal range);  per head kv = k^T v / N, z = 1 / (q . mean(k) + 1e-6);
+ *   out = (q kv) z + dwc(v) (5x5 depthwise, filter c % d, zero padding at the WINDOW border);  proj.
+ * out: f32 map [batch][C2 / 4][H / down][W / down][4] at the un-rolled pooled coordinates.
+ * wqkv_t [C2][3 C2] and wproj_t [C2][C2] are the TRANSPOSED Linear weights (input-major), pos_t [C2][N] the transposed positional
+ * encoding, inv_scale [C2] = 1 / softplus(scale), dwc_w [d][25], dwc_b [d], bqkv [3 C2], bproj [C2]; all f32.
+ * C2 in {8, 16, 24, 32}, down in {1, 2, 4, 8}, window in {4, 8}, 0 <= shift < window.  rsa_rha_window_attn_lds_bytes: the dynamic LDS of
+ * a workgroup, 4 * (4 C2 N + 4 C2^2 + C2 d + 6 C2 + 26 d) bytes (50,848 at C2 = 32, window 8), or RSA_E_ARG. */
+int64_t rsa_rha_window_attn_lds_bytes(int32_t C2, int32_t window);
+int rsa_rha_window_attn(const void* x_hi, const void* x_lo, int64_t x_plane_stride, int64_t x_batch_stride, int32_t batch, int32_t H, int32_t W,
+                        int32_t C2, int32_t down, int32_t window, int32_t shift, int32_t fmt, const float* wqkv_t, const float* bqkv,
+                        const float* pos_t, const float* inv_scale, const float* dwc_w, const float* dwc_b, const float* wproj_t, const float* bproj,
+                        float* out, void* stream);
+
+/* out = cat(dw5x5(x1) + bias, bilinear_up(att, down)): 2 * C2 / 8 planes.  x1: C2 / 8 planes, 5x5 depthwise with weight [C2][25], bias [C2]
+ * and zero padding 2 at the image border.  att: f32 map [batch][C2 / 4][H / down][W / down][4], sampled as
+ * F.interpolate(mode='bilinear', align_corners=False): src = (dst + 0.5) / down - 0.5 clamped at 0, the upper neighbour clamped to the edge;
+ * down = 1 is a copy.  down in {1, 2, 4, 8}; H and W multiples of down.  Not in place. */
+int rsa_rha_mix(const void* x_hi, const void* x_lo, int64_t x_plane_stride, int64_t x_batch_stride, const float* att, void* out_hi, void* out_lo,
+                int64_t out_plane_stride, int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t C2, int32_t down, int32_t fmt,
+                const float* weight, const float* bias, void* stream);
+
+/* out = mish(g) * cat(i, a * c) over hidden_planes planes: f holds [g | i | c] = hidden_planes + i_planes + (hidden_planes - i_planes)
+ * planes, a the hidden_planes - i_planes planes that multiply c.  0 <= i_planes < hidden_planes.  Not in place. */
+int rsa_rha_gate(const void* f_hi, const void* f_lo, int64_t f_plane_stride, int64_t f_batch_stride, const void* a_hi, const void* a_lo,
+                 int64_t a_plane_stride, int64_t a_batch_stride, void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride,
+                 int32_t batch, int32_t H, int32_t W, int32_t hidden_planes, int32_t i_planes, int32_t fmt, void* stream);
+
 /* version / errors */
 int rsa_version(void);
 const char* rsa_last_error_string(void);

@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -22,6 +22,7 @@ from .omnisr import OmniSRArch
 from .plksr import PLKSRArch
 from .rcan import RCANArch
 from .rgt import RGTArch
+from .rha import RHAArch
 from .rtmosr import RTMoSRArch
 from .span import SPANArch
 from .spanplus import SpanPlusArch
@@ -33,3 +34,7 @@ internal_registry = Registry()
 # spanplus, SwinIR, SpanPP, ..., SPAN
 for _arch in (EIMNArch, ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, GateRArch, ATDArch, RGTArch, OmniSRArch, MoSRArch, FDATArch, CUGANArch, PLKSRArch, MoSRv2Arch, RTMoSRArch, SpanPlusArch, SwinIRArch, SpanPPArch, DRCTArch, SPANArch):
     internal_registry.add(_arch())
+# RHA is consulted after the walk (``Registry.late``): no other architecture matches its keys and it matches nobody else's checkpoints
+# (tests/test_rha_loader.py checks both against every registered architecture), so where it stands cannot change who loads what.  The
+# reference walks it between dat and RCAN.
+internal_registry.add(RHAArch(), late=True)

@@ -455,6 +455,10 @@ EXPORTS = (
     'rsa_eimn_dffm_reduce',
     'rsa_eimn_dffm_gates',
     'rsa_eimn_dffm_apply',
+    'rsa_rha_window_attn_lds_bytes',
+    'rsa_rha_window_attn',
+    'rsa_rha_mix',
+    'rsa_rha_gate',
 )
 
 
@@ -609,6 +613,10 @@ def load() -> C.CDLL:
         ('rsa_eimn_dffm_reduce', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr, f32, ptr, i64, ptr]),
         ('rsa_eimn_dffm_gates', C.c_int, [ptr, i64] + [i32] * 5 + [ptr] * 8),
         ('rsa_eimn_dffm_apply', C.c_int, [ptr, ptr] + [i32] * 5 + [ptr, ptr, f32] + [ptr] * 7 + [f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr]),
+        ('rsa_rha_window_attn_lds_bytes', i64, [i32] * 2),
+        ('rsa_rha_window_attn', C.c_int, [ptr, ptr, i64, i64] + [i32] * 8 + [ptr] * 10),
+        ('rsa_rha_mix', C.c_int, [ptr, ptr, i64, i64, ptr, ptr, ptr, i64, i64] + [i32] * 6 + [ptr] * 3),
+        ('rsa_rha_gate', C.c_int, [ptr, ptr, i64, i64] * 3 + [i32] * 6 + [ptr]),
     ):
         getattr(lib, name).argtypes = argtypes
         getattr(lib, name).restype = restype

@@ -1235,3 +1235,96 @@ def eimn_state_dict(embed_dims=64, scale=2, depths=1, hidden=None, mlp_ratios=2.
             conv(f'{q}.spatial_expand', 1, 2 * rc, 1)
         affine(f'norm{i}', dim)
     return sd
+
+
+RHA_SAMPLE_MODS = ('conv', 'pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample')
+
+
+def rha_state_dict(dim=64, scale=4, in_ch=3, out_ch=3, mid_dim=32, down_list=(8, 4), expansion_ratio=1.5, group_blocks=4, res_blocks=6,
+                   upsample='pixelshuffledirect', window_size=8, seed=0):  # fmt: skip
+    """Keys of RHA (archs/rha/arch.py:483-565, without ``unshuffle_mod``) in the module's registration order, buffers included: every group's
+    ``down_sample``, ``to_img.MetaUpsample`` and the ``conv5x5_reparam`` pair of every OmniShift (which the reference overwrites from the
+    training parameters when it enters eval mode: the stored pair is drawn independently here, so that reading it shows).  Matrices and
+    filters are uniform with variance 1 / fan_in (fc2: a quarter of that), every bias is non-zero (+-0.09), norm weights lie in 0.5..1.5.
+    The attention's ``scale`` is drawn PER CHANNEL in +-1 (softplus 0.31..1.31), ``positional_encoding`` in +-0.5 and the OmniShift
+    ``alpha``s in 0.75..1.25: the module initialises them to constants, which would hide a per-channel or per-token indexing error."""
+    sd: OrderedDict = OrderedDict()
+    g = float(np.sqrt(3.0))  # uniform(-g / sqrt(fan_in), ..): variance 1 / fan_in
+    hidden = int(expansion_ratio * dim)
+    c2 = dim // 2
+    n_tok = window_size * window_size
+
+    def bias(name, co, gain=1.0):
+        b = synth_tensor(name, (co,), 1, seed, 0.08 * g * gain)
+        return b + 0.01 * gain * torch.where(b >= 0, 1.0, -1.0)  # never zero
+
+    def conv(name, co, ci, k, groups=1, gain=1.0, with_bias=True):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci // groups, k, k), (ci // groups) * k * k, seed, g * gain)
+        if with_bias:
+            sd[f'{name}.bias'] = bias(f'{name}.bias', co, gain)
+
+    def lin(name, co, ci):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci), ci, seed, g)
+        sd[f'{name}.bias'] = bias(f'{name}.bias', co)
+
+    def omnishift(name, c):
+        for k in (1, 2, 3, 4):
+            sd[f'{name}.alpha{k}'] = 1.0 + synth_tensor(f'{name}.alpha{k}', (1, c, 1, 1), 1, seed, 0.25)
+        for sub, ks in (('conv1x1', 1), ('conv3x3', 3), ('conv5x5', 5), ('conv5x5_reparam', 5)):
+            conv(f'{name}.{sub}', c, c, ks, groups=c, gain=0.5)
+
+    conv('to_feat', dim, in_ch, 3)
+    for gi in range(group_blocks):
+        grp = f'body.{gi}'
+        sd[f'{grp}.down_sample'] = torch.tensor(down_list[gi % len(down_list)], dtype=torch.uint8)
+        for bi in range(res_blocks):
+            b = f'{grp}.body.{bi}'
+            sd[f'{b}.norm.weight'] = 1.0 + synth_tensor(f'{b}.norm.weight', (dim,), 1, seed, 0.5)
+            sd[f'{b}.norm.bias'] = bias(f'{b}.norm.bias', dim)
+            conv(f'{b}.fc1', 2 * hidden, dim, 3)
+            a = f'{b}.conv.att.2'
+            sd[f'{a}.scale'] = synth_tensor(f'{a}.scale', (1, 1, c2), 1, seed, 1.0)
+            sd[f'{a}.positional_encoding'] = synth_tensor(f'{a}.positional_encoding', (1, n_tok, c2), 1, seed, 0.5)
+            lin(f'{a}.qkv', 3 * c2, c2)
+            lin(f'{a}.proj', c2, c2)
+            conv(f'{a}.dwc', c2 // 8, c2 // 8, 5, groups=c2 // 8)
+            omnishift(f'{b}.conv.conv', c2)
+            conv(f'{b}.conv.aggr.0', dim, dim, 1)
+            conv(f'{b}.fc2', dim, hidden, 3, gain=0.5)
+        omnishift(f'{grp}.body.{res_blocks}', dim)
+        conv(f'{grp}.body.{res_blocks + 1}', dim, dim, 1, gain=0.5)
+    up, s = upsample, scale
+    if up not in RHA_SAMPLE_MODS:
+        raise ValueError(f'unknown RHA upsampler {up!r}')
+    sd['to_img.MetaUpsample'] = torch.tensor([2, RHA_SAMPLE_MODS.index(up), s, dim, out_ch, mid_dim, 4], dtype=torch.uint8)
+    pow2 = s & (s - 1) == 0
+    if s == 1 or up == 'conv':
+        conv('to_img.0', out_ch, dim, 3, gain=0.2)
+    elif up == 'pixelshuffledirect':
+        conv('to_img.0', out_ch * s * s, dim, 3, gain=0.2)
+    elif up == 'pixelshuffle':
+        conv('to_img.0', mid_dim, dim, 3)
+        i = 2
+        for r in [2] * (s.bit_length() - 1) if pow2 else [3]:
+            conv(f'to_img.{i}', r * r * mid_dim, mid_dim, 3)
+            i += 2
+        conv(f'to_img.{i}', out_ch, mid_dim, 3, gain=0.2)
+    elif up == 'nearest+conv':
+        i = 0
+        for _ in range(s.bit_length() - 1 if pow2 else 1):
+            conv(f'to_img.{i}', dim, dim, 3)
+            i += 3
+        conv(f'to_img.{i}', dim, dim, 3)
+        conv(f'to_img.{i + 2}', out_ch, dim, 3, gain=0.2)
+    else:
+        i, dys_dim = 0, dim
+        if mid_dim != dim:
+            conv('to_img.0', mid_dim, dim, 3)
+            i, dys_dim = 2, mid_dim
+        oc = 8 * s * s
+        h = torch.arange((-s + 1) / 2, (s - 1) / 2 + 1) / s
+        sd[f'to_img.{i}.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+        conv(f'to_img.{i}.end_conv', out_ch, dys_dim, 1, gain=0.2)
+        conv(f'to_img.{i}.offset', oc, dys_dim, 1, gain=0.5)
+        conv(f'to_img.{i}.scope', oc, dys_dim, 1, with_bias=False)
+    return sd

@@ -1484,6 +1484,45 @@ int rsa_rha_gate(const void* f_hi, const void* f_lo, int64_t f_plane_stride, int
                  int64_t a_plane_stride, int64_t a_batch_stride, void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride,
                  int32_t batch, int32_t H, int32_t W, int32_t hidden_planes, int32_t i_planes, int32_t fmt, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------- FlexNet ops
+ * (reference archs/flexnet/arch.py, OmniShift :65-125, LMLTVIT :137-229, ChannelMix :232-263, TransformerBlock :266-281; csrc/flexnet.hip)
+ * Plane operands are split planes of format fmt (every lo pointer may be NULL unless said otherwise), strides in 16-byte units (a plane
+ * stride is at least H * W and, with batch > 1, a batch stride at least the operand's planes times its plane stride), pointers 16-byte
+ * aligned.  A plane operand may start at a plane offset inside a wider buffer: pass the pointer of its first plane and the wider
+ * buffer's strides.  f32 maps are [batch][C / 4][H][W][4]. */
+
+/* out = dw5x5(rmsnorm(x)): y = x * (1 / sqrt(mean_c(x^2) + eps)) * norm_weight[c] over the C channels of a pixel (nn.RMSNorm), then the
+ * bias-free 5x5 depthwise filter weight [C][25] over the NORMALISED map with zero padding 2 at the image border (a position outside the
+ * image contributes 0).  x_f32: f32 map; out: C / 8 planes.  One launch; the normalised map never reaches memory.  A pixel of zeros
+ * normalises to zeros.  C a multiple of 8, eps >= 0. */
+int rsa_flex_norm_shift(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, float eps, const float* norm_weight, const float* weight,
+                        void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride, int32_t fmt, void* stream);
+
+/* out = softmax(q k^T) v + lepe(v) on every 8 x 8 window of the map (windows anchored at the origin; H and W multiples of 8), ONE head of
+ * C channels; q is expected pre-scaled.  qkv: [q | k | v] = 3 C / 8 planes; out: C / 8 planes, not the qkv buffer.  Both products run on
+ * v_mfma_f32_16x16x32_{bf16,f16}: products == 3 multiplies hi and lo of q, k, v and of the probabilities (hi hi + lo hi + hi lo; qkv_lo
+ * required), products == 1 the hi planes only (qkv_lo is ignored, by lepe too).  The softmax is f32 with the row maximum subtracted.
+ * lepe: 3x3 depthwise convolution of v with bias and zero padding at the WINDOW border, lepe_w [9][C] (tap-major), lepe_b [C], f32.
+ * C a multiple of 16 from 16 to 128; nothing is padded to 32 channels in memory.  rsa_flex_window_attn_lds_bytes: the dynamic LDS of a
+ * workgroup, (products == 3 ? 2 : 1) * C * 144 bytes, or RSA_E_ARG. */
+int64_t rsa_flex_window_attn_lds_bytes(int32_t C, int32_t products);
+int rsa_flex_window_attn(const void* qkv_hi, const void* qkv_lo, int64_t qkv_plane_stride, int64_t qkv_batch_stride, void* out_hi, void* out_lo,
+                         int64_t out_plane_stride, int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t products,
+                         int32_t fmt, const float* lepe_w, const float* lepe_b, void* stream);
+
+/* out = relu(in)^2 over hidden / 8 planes; with norm != 0 followed by k * (1 / sqrt(mean(k^2) + eps)) over the hidden channels of a pixel
+ * (nn.RMSNorm without its weight).  A pixel without a positive value gives zeros.  In place is allowed (out_hi == in_hi, same strides).
+ * hidden a multiple of 8. */
+int rsa_flex_sqrelu(const void* in_hi, const void* in_lo, int64_t in_plane_stride, int64_t in_batch_stride, void* out_hi, void* out_lo,
+                    int64_t out_plane_stride, int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t hidden, int32_t norm, float eps,
+                    int32_t fmt, void* stream);
+
+/* v = base + sigmoid(r) * kv over C channels: r and kv are C / 8 planes, base an f32 map.  v goes to the f32 map out_f32 (may be base
+ * itself, may be NULL) and / or to the C / 8 planes out_hi (may be NULL; out_lo optional); at least one of the two. */
+int rsa_flex_gate_add(const void* r_hi, const void* r_lo, int64_t r_plane_stride, int64_t r_batch_stride, const void* kv_hi, const void* kv_lo,
+                      int64_t kv_plane_stride, int64_t kv_batch_stride, const float* base_f32, float* out_f32, void* out_hi, void* out_lo,
+                      int64_t out_plane_stride, int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t fmt, void* stream);
+
 /* version / errors */
 int rsa_version(void);
 const char* rsa_last_error_string(void);

@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -14,6 +14,7 @@ from .drct import DRCTArch
 from .eimn import EIMNArch
 from .esrgan import ESRGANArch
 from .fdat import FDATArch
+from .flexnet import FlexNetArch
 from .gater import GateRArch
 from .hat import HATArch
 from .mosr import MoSRArch
@@ -38,3 +39,6 @@ for _arch in (EIMNArch, ESRGANArch, HATArch, DatArch, RCANArch, CompactArch, Gat
 # (tests/test_rha_loader.py checks both against every registered architecture), so where it stands cannot change who loads what.  The
 # reference walks it between dat and RCAN.
 internal_registry.add(RHAArch(), late=True)
+# FlexNet likewise (tests/test_flexnet_loader.py checks the same two properties), one tier further back (``Registry.last``): the contents
+# of ``late`` and what iterating over the registry yields stay what they were.  The reference walks it between ESRGAN and HAT.
+internal_registry.add(FlexNetArch(), last=True)

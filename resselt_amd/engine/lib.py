@@ -459,6 +459,11 @@ EXPORTS = (
     'rsa_rha_window_attn',
     'rsa_rha_mix',
     'rsa_rha_gate',
+    'rsa_flex_norm_shift',
+    'rsa_flex_window_attn_lds_bytes',
+    'rsa_flex_window_attn',
+    'rsa_flex_sqrelu',
+    'rsa_flex_gate_add',
 )
 
 
@@ -617,6 +622,11 @@ def load() -> C.CDLL:
         ('rsa_rha_window_attn', C.c_int, [ptr, ptr, i64, i64] + [i32] * 8 + [ptr] * 10),
         ('rsa_rha_mix', C.c_int, [ptr, ptr, i64, i64, ptr, ptr, ptr, i64, i64] + [i32] * 6 + [ptr] * 3),
         ('rsa_rha_gate', C.c_int, [ptr, ptr, i64, i64] * 3 + [i32] * 6 + [ptr]),
+        ('rsa_flex_norm_shift', C.c_int, [ptr] + [i32] * 4 + [C.c_float, ptr, ptr, ptr, ptr, i64, i64, i32, ptr]),
+        ('rsa_flex_window_attn_lds_bytes', i64, [i32] * 2),
+        ('rsa_flex_window_attn', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 6 + [ptr] * 3),
+        ('rsa_flex_sqrelu', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 5 + [C.c_float, i32, ptr]),
+        ('rsa_flex_gate_add', C.c_int, [ptr, ptr, i64, i64] * 2 + [ptr, ptr] + [ptr, ptr, i64, i64] + [i32] * 5 + [ptr]),
     ):
         getattr(lib, name).argtypes = argtypes
         getattr(lib, name).restype = restype

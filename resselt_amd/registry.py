@@ -7,7 +7,7 @@ Behaviour kept from the reference:
     anything else raises ``ValueError`` (registry.py:79-104);
   * the restricted unpickler only admits OrderedDict, ``_rebuild_tensor_v2`` and six storage classes and
     raises ``pickle.UnpicklingError`` for every other global (registry.py:20-46);
-  * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``), builds the first
+  * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``, then ``Registry.last``), builds the first
     match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
   * no match raises ``ArchitectureNotFound``.
 
@@ -89,14 +89,17 @@ class Registry:
     """``store`` is the ordered walk: the first architecture whose keys match builds the model, so the order matters wherever two
     architectures share keys, and it follows the reference's walk.  ``late`` holds architectures that are consulted after the whole walk
     has declined: only for an architecture whose detection keys no other one matches and which matches no other one's checkpoints, so
-    that its position cannot change who loads what."""
+    that its position cannot change who loads what.  ``last`` is a further tier of the same kind, consulted after ``late``; ``walk()`` yields
+    all three in the order ``load_from_state_dict`` consults them.  Iterating over the registry and ``len()`` cover ``store`` and ``late``
+    only, as they did before ``last`` existed."""
 
     def __init__(self):
         self.store: Dict[str, Architecture] = {}
         self.late: Dict[str, Architecture] = {}
+        self.last: Dict[str, Architecture] = {}
 
     def __contains__(self, uid: str) -> bool:
-        return uid in self.store or uid in self.late
+        return uid in self.store or uid in self.late or uid in self.last
 
     def __iter__(self) -> Iterator[Architecture]:
         return iter(list(self.store.values()) + list(self.late.values()))
@@ -104,16 +107,24 @@ class Registry:
     def __len__(self) -> int:
         return len(self.store) + len(self.late)
 
-    def add(self, arch: Architecture, late: bool = False) -> None:
+    def walk(self) -> Iterator[Architecture]:
+        """Every registered architecture in the order ``load_from_state_dict`` consults them: ``store``, ``late``, ``last``."""
+        return iter(list(self.store.values()) + list(self.late.values()) + list(self.last.values()))
+
+    def add(self, arch: Architecture, late: bool = False, last: bool = False) -> None:
         """Register an architecture *instance*; re-using an id replaces it in place."""
-        if late and arch.id not in self.store:
+        if last and arch.id not in self.store and arch.id not in self.late:
+            self.last[arch.id] = arch
+        elif late and arch.id not in self.store:
+            self.last.pop(arch.id, None)
             self.late[arch.id] = arch
         else:
             self.late.pop(arch.id, None)
+            self.last.pop(arch.id, None)
             self.store[arch.id] = arch
 
     def get(self, uid: str) -> Architecture:
-        arch = self.late[uid] if uid in self.late else self.store[uid]  # KeyError for unknown ids, as in the reference
+        arch = self.late[uid] if uid in self.late else self.last[uid] if uid in self.last else self.store[uid]  # KeyError for unknown ids, as in the reference
         if not arch:
             raise ArchitectureNotFound
         return arch
@@ -123,7 +134,7 @@ class Registry:
 
     def load_from_state_dict(self, state_dict: Mapping[str, object]):
         state_dict = canonicalize_state_dict(state_dict)
-        for arch in self:
+        for arch in self.walk():
             if arch.detect(state_dict):
                 model = arch.load(state_dict)
                 model.load_state_dict(state_dict)

@@ -1328,3 +1328,98 @@ def rha_state_dict(dim=64, scale=4, in_ch=3, out_ch=3, mid_dim=32, down_list=(8,
         conv(f'to_img.{i}.offset', oc, dys_dim, 1, gain=0.5)
         conv(f'to_img.{i}.scope', oc, dys_dim, 1, with_bias=False)
     return sd
+
+
+FLEXNET_UPSAMPLERS = ('ps', 'dys', 'n+c')
+
+
+def flexnet_state_dict(seed=0, dim=64, num_blocks=(6, 6, 6, 6, 6, 6), scale=4, inp_channels=3, out_channels=3, hidden_rate=4, channel_norm=False,
+                       upsampler='ps'):  # fmt: skip
+    """Keys of FlexNet's linear pipeline (archs/flexnet/arch.py:437-489) in the module's registration order, buffers included: ``window_size``
+    (always 8: the only size the reference runs), ``scale_factor`` for ``n+c``, DySample's ``init_pos``, and the ``conv5x5_reparam`` weight of
+    every OmniShift, which the reference overwrites from the training parameters on its first forward: the stored one is drawn independently
+    here, so that reading it shows.  Matrices and filters are uniform with variance 1 / fan_in, every bias is non-zero, RMSNorm weights lie
+    in 0.5..1.5, the four ``alpha``s of an OmniShift in 0.19..0.31 (the module draws them from N(0, 1); their sum is the gain of the identity
+    path) and ``gamma1`` / ``gamma2`` PER CHANNEL in 0.1..0.3: relu^2 and a dozen residual blocks grow fast, and the module's own
+    initialisation (ones) would hide a per-channel indexing error.  The ``ps`` head of the reference's loader takes ``out_channels`` from
+    ``inp_channels``: pass them equal for a checkpoint it is to load."""
+    if upsampler not in FLEXNET_UPSAMPLERS:
+        raise ValueError(f'unknown FlexNet upsampler {upsampler!r}')
+    sd: OrderedDict = OrderedDict()
+    g = float(np.sqrt(3.0))  # uniform(-g / sqrt(fan_in), ..): variance 1 / fan_in
+    hidden = int(hidden_rate * dim)
+    s = int(scale)
+
+    def bias(name, co, gain=1.0):
+        b = synth_tensor(name, (co,), 1, seed, 0.08 * g * gain)
+        return b + 0.01 * gain * torch.where(b >= 0, 1.0, -1.0)  # never zero
+
+    def conv(name, co, ci, k, groups=1, gain=1.0, with_bias=True):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci // groups, k, k), (ci // groups) * k * k, seed, g * gain)
+        if with_bias:
+            sd[f'{name}.bias'] = bias(f'{name}.bias', co, gain)
+
+    def lin(name, co, ci, with_bias=True, gain=1.0):
+        sd[f'{name}.weight'] = synth_tensor(f'{name}.weight', (co, ci), ci, seed, g * gain)
+        if with_bias:
+            sd[f'{name}.bias'] = bias(f'{name}.bias', co, gain)
+
+    def rms(name, c):
+        sd[f'{name}.weight'] = 1.0 + synth_tensor(f'{name}.weight', (c,), 1, seed, 0.5)
+
+    def omnishift(name, c):
+        sd[f'{name}.alpha'] = 0.25 + synth_tensor(f'{name}.alpha', (4,), 1, seed, 0.06)
+        for sub, ks in (('conv1x1', 1), ('conv3x3', 3), ('conv5x5', 5), ('conv5x5_reparam', 5)):
+            conv(f'{name}.{sub}', c, c, ks, groups=c, with_bias=False)
+
+    def convblock(name, ci, co):
+        conv(f'{name}.block.0', co, ci, 3)
+        conv(f'{name}.block.2', co, co, 3)
+        conv(f'{name}.conv11', co, ci, 1, gain=0.5)
+
+    sd['window_size'] = torch.tensor(8, dtype=torch.uint8)
+    if upsampler == 'n+c':
+        sd['scale_factor'] = torch.tensor(s, dtype=torch.uint8)
+    convblock('short_cut', inp_channels, dim)
+    conv('in_to_feat', dim, inp_channels, 3)
+    for li, nb in enumerate(num_blocks):
+        for bi in range(nb):
+            b = f'pipeline.att.{li}.t_blocks.{bi}'
+            sd[f'{b}.gamma1'] = 0.2 + synth_tensor(f'{b}.gamma1', (dim,), 1, seed, 0.1)
+            sd[f'{b}.gamma2'] = 0.2 + synth_tensor(f'{b}.gamma2', (dim,), 1, seed, 0.1)
+            rms(f'{b}.rn1', dim)
+            rms(f'{b}.rn2', dim)
+            lin(f'{b}.att.qkv', 3 * dim, dim, gain=1.5)  # (wider logits: a softmax over near-equal logits would hide a wrong key order)
+            lin(f'{b}.att.proj', dim, dim)
+            omnishift(f'{b}.att.omni_shift', dim)
+            conv(f'{b}.att.get_v', dim, dim, 3, groups=dim)
+            lin(f'{b}.ffn.key', hidden, dim, with_bias=False)
+            omnishift(f'{b}.ffn.omni_shift', dim)
+            if channel_norm:
+                rms(f'{b}.ffn.key_norm', hidden)
+            lin(f'{b}.ffn.receptance', dim, dim, with_bias=False)
+            lin(f'{b}.ffn.value', dim, hidden, with_bias=False)
+        convblock(f'pipeline.att.{li}.conv', 2 * dim, dim)
+    if upsampler == 'n+c':
+        conv('to_img.0', dim, 2 * dim, 3)
+        i = 0
+        if s & (s - 1) == 0:
+            for _ in range(s.bit_length() - 1):
+                conv(f'to_img.1.{i}', dim, dim, 3)
+                i += 3
+            conv(f'to_img.1.{i}', dim, dim, 3)
+            i += 2
+        elif s == 3:
+            conv('to_img.1.0', dim, dim, 3)
+            conv('to_img.1.3', dim, dim, 3)
+            i = 5
+        conv(f'to_img.1.{i}', out_channels, dim, 3, gain=0.5)
+    elif upsampler == 'dys':
+        h = torch.arange((-s + 1) / 2, (s - 1) / 2 + 1) / s
+        sd['to_img.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+        conv('to_img.end_conv', out_channels, 2 * dim, 1, gain=0.5)
+        conv('to_img.offset', 8 * s * s, 2 * dim, 1, gain=0.5)
+        conv('to_img.scope', 8 * s * s, 2 * dim, 1, with_bias=False)
+    else:
+        conv('to_img.0', out_channels * s * s, 2 * dim, 3, gain=0.5)
+    return sd

@@ -90,6 +90,8 @@ def main():
         'eimn_x2_512': (synth.eimn_state_dict(embed_dims=64, scale=2, num_stages=16), (1, 3, 512, 512), torch.bfloat16, None, None),
         # RHA x4 at the reference's defaults (dim 64, 4 groups x 6 blocks pooling by 8 / 4, window 8, pixelshuffledirect)
         'rha_x4_512': (synth.rha_state_dict(), (1, 3, 512, 512), torch.bfloat16, None, None),
+        # FlexNet x4 at the reference's defaults (linear pipeline, dim 64, 6 LBlocks of 6 blocks, hidden_rate 4, ps head)
+        'flexnet_x4_512': (synth.flexnet_state_dict(), (1, 3, 512, 512), torch.bfloat16, None, None),
         'compact_x4_fp16_b8_512': (synth.compact_state_dict(num_feat=64, num_conv=16, upscale=4), (8, 3, 512, 512), torch.float16, None, None),
         # Real-CUGAN: the 2x model at 1080p and the 4x model at 540p
         'cugan_x2_fp16_1080p': (synth.cugan_state_dict('2x'), (1, 3, 1080, 1920), torch.float16, None, None),

@@ -18,7 +18,6 @@ category path observable: ``atd_record`` (per layer, the ids and permutations us
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -229,7 +228,6 @@ class ATD(EngineModule):
         dev = plan.device
         lib = L.load()
         model = self
-        stream = lambda: C.c_void_p(ops.current_stream_ptr(dev))  # noqa: E731
 
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, with_lo)
         mean = W['mean']
@@ -294,6 +292,8 @@ class ATD(EngineModule):
             ap.sim, ap.ids, ap.out = sim.data_ptr(), ids.data_ptr(), xatd.data_ptr()
             plan.launch('rsa_atd_ca', ap)
 
+        sort = plan.bound('rsa_atd_sort', dict(ids=ids, batch=n, n=ntok, m=m, perm=perm, inv=inv, workspace=sort_ws))
+
         def categorise(layer_index):
             def run():
                 forced = model.atd_force
@@ -303,7 +303,7 @@ class ATD(EngineModule):
                         raise ValueError('atd_force: a permutation entry is outside [0, n)')
                     perm.copy_(f.to(torch.int32))
                 else:
-                    L.check(lib.rsa_atd_sort(ids.data_ptr(), n, ntok, m, perm.data_ptr(), inv.data_ptr(), sort_ws.data_ptr(), stream()), 'rsa_atd_sort')
+                    sort()
                 if model.atd_record:
                     model.atd_recorded.append((ids.clone(), perm.clone()))
 

@@ -27,8 +27,6 @@ DFFM pools the whole input: under tiled ``upscale()`` and tile sharding every ti
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from ...engine import lib as L
@@ -241,9 +239,6 @@ class EIMN(EngineModule):
         px = n * h * w
         unit = 16 * (2 if with_lo else 1)
 
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
-
         x_pl = plan.planes(n, 1, h, w, with_lo)
 
         def set_input(x):
@@ -261,7 +256,9 @@ class EIMN(EngineModule):
         work = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
         gates = torch.empty((n, dim + 4), dtype=torch.float32, device=dev)
         plan.keep += [work, gates]
-        fmt = X_pl.fmt
+        geo = dict(batch=n, H=h, W=w, fmt=X_pl.fmt)
+        size = dict(batch=n, H=h, W=w, C=dim)
+        scratch = dict(workspace=work, workspace_bytes=ws_bytes)
 
         plan.conv(ops.conv_params(W['head'], x_pl, h, w, out=X_pl, out_f32=ident))
         cur = ident
@@ -269,52 +266,30 @@ class EIMN(EngineModule):
         for i, j, p in self._blocks():
             blk = W[p]
             plan.conv(ops.conv_params(blk['vq'], X_pl, h, w, out=VQ_pl))
-
-            def chain(blk=blk):
-                L.check(lib.rsa_eimn_query_chain(VQ_pl.hi_ptr(pd), VQ_pl.lo_ptr(pd), VQ_pl.plane_stride, VQ_pl.batch_stride, Q_pl.hi_ptr(), Q_pl.lo_ptr(),
-                                                 Q_pl.plane_stride, Q_pl.batch_stride, n, h, w, pa, pb, pc, 1, fmt, blk['w1'].data_ptr(), blk['b1'].data_ptr(),
-                                                 blk['w2'].data_ptr(), blk['b2'].data_ptr(), stream()), 'rsa_eimn_query_chain')  # fmt: skip
-
             # byte models: every operand touched once (halo re-reads stay on chip)
-            plan.call(chain, dict(kernel='rsa_eimn_query_chain', flop=2 * px * 8 * (25 * qp + 25 * pa + 49 * pc), bytes=px * qp * unit * 2))
-            plan.count_launches(1)
+            plan.launch('rsa_eimn_query_chain', dict(q=(VQ_pl, pd), out=Q_pl, planes_a=pa, planes_b=pb, planes_c=pc, gelu_in=1, w1=blk['w1'], b1=blk['b1'],
+                                                     w2=blk['w2'], b2=blk['b2'], **geo),
+                        meta=dict(kernel='rsa_eimn_query_chain', flop=2 * px * 8 * (25 * qp + 25 * pa + 49 * pc), bytes=px * qp * unit * 2))  # fmt: skip
             plan.conv(ops.conv_params(blk['fusion'], Q_pl, h, w, out=F_pl))
-
-            def mul():
-                L.check(lib.rsa_eimn_silu_mul(F_pl.hi_ptr(), F_pl.lo_ptr(), F_pl.plane_stride, F_pl.batch_stride, VQ_pl.hi_ptr(), VQ_pl.lo_ptr(),
-                                              VQ_pl.plane_stride, VQ_pl.batch_stride, F_pl.hi_ptr(), F_pl.lo_ptr(), F_pl.plane_stride, F_pl.batch_stride,
-                                              n, h, w, pd, fmt, stream()), 'rsa_eimn_silu_mul')  # fmt: skip
-
-            plan.call(mul, dict(kernel='rsa_eimn_silu_mul', flop=px * dim * 2, bytes=px * pd * unit * 3))
-            plan.count_launches(1)
+            plan.launch('rsa_eimn_silu_mul', dict(f=F_pl, v=VQ_pl, out=F_pl, planes=pd, **geo),
+                        meta=dict(kernel='rsa_eimn_silu_mul', flop=px * dim * 2, bytes=px * pd * unit * 3))  # fmt: skip
             plan.conv(ops.conv_params(blk['out'], F_pl, h, w, res1=cur, alpha=1.0, out_f32=A, out=X1_pl))
             plan.conv(ops.conv_params(blk['lin'], X1_pl, h, w, out=S_pl))
-
-            def sal(blk=blk):
-                L.check(lib.rsa_eimn_sal(S_pl.hi_ptr(), S_pl.lo_ptr(), S_pl.plane_stride, S_pl.batch_stride, G_pl.hi_ptr(), G_pl.lo_ptr(), G_pl.plane_stride,
-                                         G_pl.batch_stride, n, h, w, hp, fmt, blk['sal_w'].data_ptr(), blk['sal_b'].data_ptr(), stream()), 'rsa_eimn_sal')  # fmt: skip
-
-            plan.call(sal, dict(kernel='rsa_eimn_sal', flop=2 * px * 16 * hp * 9, bytes=px * hp * unit * 3))
-            plan.count_launches(1)
+            plan.launch('rsa_eimn_sal', dict(in_=S_pl, out=G_pl, planes=hp, weight=blk['sal_w'], bias=blk['sal_b'], **geo),
+                        meta=dict(kernel='rsa_eimn_sal', flop=2 * px * 16 * hp * 9, bytes=px * hp * unit * 3))  # fmt: skip
             plan.conv(ops.conv_params(blk['lout'], G_pl, h, w, out_f32=Z))
             ng, nb = W[f'norm{i}'] if j == self.depths - 1 else (None, None)
             add = ident if (i, j) == last else None
-
-            def dffm(blk=blk, ng=ng, nb=nb, add=add):
-                st = stream()
-                L.check(lib.rsa_eimn_dffm_reduce(Z.data_ptr(), n, h, w, dim, blk['gamma'].data_ptr(), blk['beta'].data_ptr(), DFFM_LN_EPS, work.data_ptr(),
-                                                 ws_bytes, st), 'rsa_eimn_dffm_reduce')  # fmt: skip
-                L.check(lib.rsa_eimn_dffm_gates(work.data_ptr(), ws_bytes, n, h, w, dim, rc, blk['wg'].data_ptr(), blk['bg'].data_ptr(), blk['wc'].data_ptr(),
-                                                blk['bc'].data_ptr(), blk['ws'].data_ptr(), blk['bs'].data_ptr(), gates.data_ptr(), st), 'rsa_eimn_dffm_gates')  # fmt: skip
-                L.check(lib.rsa_eimn_dffm_apply(Z.data_ptr(), A.data_ptr(), n, h, w, dim, rc, blk['gamma'].data_ptr(), blk['beta'].data_ptr(), DFFM_LN_EPS,
-                                                blk['wl'].data_ptr(), blk['bl'].data_ptr(), blk['ws'].data_ptr(), gates.data_ptr(), blk['ls2'].data_ptr(),
-                                                None if ng is None else ng.data_ptr(), None if nb is None else nb.data_ptr(), STAGE_LN_EPS,
-                                                None if add is None else add.data_ptr(), B.data_ptr(), X_pl.hi_ptr(), X_pl.lo_ptr(), X_pl.plane_stride,
-                                                X_pl.batch_stride, fmt, st), 'rsa_eimn_dffm_apply')  # fmt: skip
-
+            ln = dict(gamma=blk['gamma'], beta=blk['beta'], eps=DFFM_LN_EPS)
+            dffm = (
+                ('rsa_eimn_dffm_reduce', dict(z=Z, **size, **ln, **scratch)),
+                ('rsa_eimn_dffm_gates', dict(**scratch, **size, rc=rc, wg=blk['wg'], bg=blk['bg'], wc=blk['wc'], bc=blk['bc'], ws=blk['ws'], bs=blk['bs'], gates=gates)),
+                ('rsa_eimn_dffm_apply', dict(z=Z, x=A, rc=rc, **ln, wl=blk['wl'], bl=blk['bl'], ws=blk['ws'], gates=gates, scale=blk['ls2'], norm_gamma=ng,
+                                             norm_beta=nb, norm_eps=STAGE_LN_EPS, add=add, out_f32=B, out=X_pl, C=dim, **geo)),
+            )  # fmt: skip
             # z read by both passes, x read, the stream and the planes written (+ the added map)
-            plan.call(dffm, dict(kernel='rsa_eimn_dffm', flop=2 * px * dim * (rc + 8), bytes=px * dim * 4 * (4 + (add is not None)) + px * pd * unit))
-            plan.count_launches(3)
+            plan.launch(dffm, kernels=3,
+                        meta=dict(kernel='rsa_eimn_dffm', flop=2 * px * dim * (rc + 8), bytes=px * dim * 4 * (4 + (add is not None)) + px * pd * unit))  # fmt: skip
             cur = B
         s = self.scale
         y = plan.output((n, 3, h * s, w * s), dtype)

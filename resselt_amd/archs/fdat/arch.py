@@ -23,7 +23,6 @@ convolutions and rsa_pa_gate; lda on rsa_lda_offsets -> a block-diagonal 3x3 off
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 
@@ -417,13 +416,7 @@ class FDAT(EngineModule):
             ip.x_out = f.data_ptr()
             plan.launch('rsa_fdat_interact', ip)
             res = f_map if inplace else x
-
-            def run():
-                L.check(lib.rsa_scale_add(res.data_ptr(), ones.data_ptr(), x_out.data_ptr(), n, H, Wd, C_, C.c_void_p(ops.current_stream_ptr(dev))),
-                        'rsa_scale_add')  # fmt: skip
-
-            plan.call(run)
-            plan.count_launches(1)
+            plan.launch('rsa_scale_add', dict(res=res, gamma=ones, out=x_out, batch=n, H=H, W=Wd, C=C_))
             layernorm(plan, W, f'{b}.n2', n, H, Wd, C_, x_out, out_planes=a_pl)
 
         plan.conv(ops.conv_params(W['conv_first.1' if u > 1 else 'conv_first'], x_pl, H, Wd, out_f32=first))
@@ -525,15 +518,8 @@ class FDAT(EngineModule):
 
     @staticmethod
     def _pa_gate(plan, x, logit, n, h, w, planes):
-        lib = L.load()
-        dev = plan.device
-
-        def run():
-            L.check(lib.rsa_pa_gate(x.hi_ptr(), x.lo_ptr(), logit.hi_ptr(), logit.lo_ptr(), x.plane_stride, x.batch_stride, n, h, w, planes, 0.2, x.fmt,
-                                    x.hi_ptr(), x.lo_ptr(), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_pa_gate')  # fmt: skip
-
-        plan.call(run)
-        plan.count_launches(1)
+        plan.launch('rsa_pa_gate', dict(x_hi=x.hi_ptr(), x_lo=x.lo_ptr(), logit_hi=logit.hi_ptr(), logit_lo=logit.lo_ptr(), plane_stride=x.plane_stride,
+                                        batch_stride=x.batch_stride, batch=n, H=h, W=w, planes=planes, slope=0.2, fmt=x.fmt, out_hi=x.hi_ptr(), out_lo=x.lo_ptr()))  # fmt: skip
 
     def _emit_lda(self, plan, W, fe, fe32, y, n, H, Wd, with_lo):
         mid, s = self.mid_dim, self.s_int

@@ -29,8 +29,6 @@ under tiled ``upscale()`` every tile computes what the reference computes on tha
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from ...engine import dysample as dys
@@ -238,13 +236,9 @@ class FlexNet(EngineModule):
         pd, hp = dim // 8, hidden // 8
         with_lo = products == 3
         prod = int(products)
-        lib, dev = L.load(), plan.device
         px = n * H * Wd
         unit = 16 * (2 if with_lo else 1)
         MISH = L.ACT_MISH
-
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
 
         x_pl = plan.planes(n, 1, H, Wd, with_lo)
 
@@ -260,7 +254,7 @@ class FlexNet(EngineModule):
         A_pl = plan.planes(n, pd, H, Wd, with_lo)  # attention + lepe
         KR = plan.planes(n, hp + pd, H, Wd, with_lo)  # [key | receptance]
         KV = plan.planes(n, pd, H, Wd, with_lo)
-        fmt = NS.fmt
+        geo = dict(batch=n, H=H, W=Wd, fmt=NS.fmt)
 
         def convblock(w, src, out, out_plane_off=0, out_f32=None):
             plan.conv(ops.conv_params(w['c11'], src, H, Wd, out_f32=c11))
@@ -268,13 +262,9 @@ class FlexNet(EngineModule):
             plan.conv(ops.conv_params(w['b2'], T_pl, H, Wd, act=MISH, res1=c11, alpha=1.0, out=out, out_plane_off=out_plane_off, out_f32=out_f32))
 
         def norm_shift(src, nw, w):
-            def run():
-                L.check(lib.rsa_flex_norm_shift(src.data_ptr(), n, H, Wd, dim, RMS_EPS, nw.data_ptr(), w.data_ptr(), NS.hi_ptr(), NS.lo_ptr(), NS.plane_stride,
-                                                NS.batch_stride, fmt, stream()), 'rsa_flex_norm_shift')  # fmt: skip
-
             # bytes: the stream is read twice (once for the norms, once plane by plane: the second pass hits L2), the planes written once
-            plan.call(run, dict(kernel='rsa_flex_norm_shift', flop=px * dim * (2 + 2 + 50), bytes=px * dim * 4 + px * pd * unit))
-            plan.count_launches(1)
+            plan.launch('rsa_flex_norm_shift', dict(x_f32=src, eps=RMS_EPS, norm_weight=nw, weight=w, out=NS, C=dim, **geo),
+                        meta=dict(kernel='rsa_flex_norm_shift', flop=px * dim * (2 + 2 + 50), bytes=px * dim * 4 + px * pd * unit))  # fmt: skip
 
         convblock(W['short_cut'], x_pl, SC, out_plane_off=pd)
         plan.conv(ops.conv_params(W['in_to_feat'], x_pl, H, Wd, out=CAT, out_f32=sa))
@@ -284,35 +274,19 @@ class FlexNet(EngineModule):
                 blk = W[f'pipeline.att.{li}.t_blocks.{bi}']
                 norm_shift(sa, blk['rn1'], blk['shift1'])
                 plan.conv(ops.conv_params(blk['qkv'], NS, H, Wd, out=QKV))
-
-                def attn(blk=blk):
-                    L.check(lib.rsa_flex_window_attn(QKV.hi_ptr(), QKV.lo_ptr(), QKV.plane_stride, QKV.batch_stride, A_pl.hi_ptr(), A_pl.lo_ptr(), A_pl.plane_stride,
-                                                     A_pl.batch_stride, n, H, Wd, dim, prod, fmt, blk['lepe_w'].data_ptr(), blk['lepe_b'].data_ptr(), stream()),
-                            'rsa_flex_window_attn')  # fmt: skip
-
-                plan.call(attn, dict(kernel='rsa_flex_window_attn', flop=2 * px * (2 * 64 * dim + 9 * dim), bytes=px * (3 * pd + pd) * unit))
-                plan.count_launches(1)
+                plan.launch('rsa_flex_window_attn', dict(qkv=QKV, out=A_pl, C=dim, products=prod, lepe_w=blk['lepe_w'], lepe_b=blk['lepe_b'], **geo),
+                            meta=dict(kernel='rsa_flex_window_attn', flop=2 * px * (2 * 64 * dim + 9 * dim), bytes=px * (3 * pd + pd) * unit))  # fmt: skip
                 plan.conv(ops.conv_params(blk['proj'], A_pl, H, Wd, res1=sa, alpha=1.0, out_f32=sb))
                 norm_shift(sb, blk['rn2'], blk['shift2'])
                 plan.conv(ops.conv_params(blk['kr'], NS, H, Wd, out=KR))
-
-                def sqrelu():
-                    L.check(lib.rsa_flex_sqrelu(KR.hi_ptr(), KR.lo_ptr(), KR.plane_stride, KR.batch_stride, KR.hi_ptr(), KR.lo_ptr(), KR.plane_stride, KR.batch_stride,
-                                                n, H, Wd, hidden, 1 if self.channel_norm else 0, RMS_EPS, fmt, stream()), 'rsa_flex_sqrelu')  # fmt: skip
-
-                plan.call(sqrelu, dict(kernel='rsa_flex_sqrelu', flop=px * hidden * (4 if self.channel_norm else 2), bytes=2 * px * hp * unit))
-                plan.count_launches(1)
+                plan.launch('rsa_flex_sqrelu', dict(in_=KR, out=KR, hidden=hidden, norm=1 if self.channel_norm else 0, eps=RMS_EPS, **geo),
+                            meta=dict(kernel='rsa_flex_sqrelu', flop=px * hidden * (4 if self.channel_norm else 2), bytes=2 * px * hp * unit))  # fmt: skip
                 plan.conv(ops.conv_params(blk['value'], KR, H, Wd, in_plane0=0, cin_planes=hp, out=KV))
                 last = bi == nb - 1
-
-                def gate(last=last):
-                    L.check(lib.rsa_flex_gate_add(KR.hi_ptr(hp), KR.lo_ptr(hp), KR.plane_stride, KR.batch_stride, KV.hi_ptr(), KV.lo_ptr(), KV.plane_stride,
-                                                  KV.batch_stride, sb.data_ptr(), None if last else sa.data_ptr(), CAT.hi_ptr(pd) if last else None,
-                                                  CAT.lo_ptr(pd) if last else None, CAT.plane_stride, CAT.batch_stride, n, H, Wd, dim, fmt, stream()),
-                            'rsa_flex_gate_add')  # fmt: skip
-
-                plan.call(gate, dict(kernel='rsa_flex_gate_add', flop=px * dim * 4, bytes=px * (2 * pd * unit + dim * 4 + (pd * unit if last else dim * 4))))
-                plan.count_launches(1)
+                # a block's last gate writes the planes the LBlock's ConvBlock reads; the others write the f32 stream
+                out = dict(out=(CAT, pd), out_f32=None) if last else dict(out_hi=None, out_lo=None, out_plane_stride=CAT.plane_stride, out_batch_stride=CAT.batch_stride, out_f32=sa)
+                plan.launch('rsa_flex_gate_add', dict(r=(KR, hp), kv=KV, base_f32=sb, C=dim, **out, **geo),
+                            meta=dict(kernel='rsa_flex_gate_add', flop=px * dim * 4, bytes=px * (2 * pd * unit + dim * 4 + (pd * unit if last else dim * 4))))  # fmt: skip
             w = W[f'pipeline.att.{li}.conv']
             if li < last_l:
                 convblock(w, CAT, CAT, out_f32=sa)  # (the third convolution reads T_pl: CAT's first half is free by then)

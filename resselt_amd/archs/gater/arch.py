@@ -23,7 +23,6 @@ over the cropped region.  The caller's input is never written.
 
 from __future__ import annotations
 
-import ctypes as C
 from fractions import Fraction
 
 import torch
@@ -166,18 +165,11 @@ class GateR(EngineModule):
     # ---- plan ----
     def _emit_block(self, plan: Plan, blk, n, H, Wd, width, cur, bufs):
         """norm -> fc1 -> (attention ->) gate; returns the planes fc2 reads."""
-        lib = L.load()
-        dev = plan.device
         N_pl, F_pl, M_pl = bufs['norm'], bufs['fc1'], bufs['gate']
-        wn = blk['norm']
-
-        def rms(src=cur, wn=wn):
-            L.check(lib.rsa_rmsnorm_torch(src.data_ptr(), n, H, Wd, width, RMS_EPS, wn.data_ptr(), N_pl.hi_ptr(), N_pl.lo_ptr(), N_pl.plane_stride,
-                                          N_pl.batch_stride, N_pl.fmt, C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_rmsnorm_torch')  # fmt: skip
-
+        geo = dict(batch=n, H=H, W=Wd, fmt=N_pl.fmt)
         unit = 16 * (2 if N_pl.lo is not None else 1)
-        plan.call(rms, meta=dict(kernel='rsa_rmsnorm_torch', flop=0, bytes=n * H * Wd * (4 * width + unit * (width // 8))))
-        plan.count_launches(1)
+        plan.launch('rsa_rmsnorm_torch', dict(x_f32=cur, C=width, eps=RMS_EPS, weight=blk['norm'], out=N_pl, **geo),
+                    meta=dict(kernel='rsa_rmsnorm_torch', flop=0, bytes=n * H * Wd * (4 * width + unit * (width // 8))))  # fmt: skip
         plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
         hp = blk['planes']
         if blk['att']:
@@ -186,25 +178,17 @@ class GateR(EngineModule):
             Q_pl, A_pl, ws = bufs['qkv'], bufs['attn'], bufs['ws']
             plan.conv(ops.conv_params(blk['qkv'], F_pl, H, Wd, in_plane0=c0, out=Q_pl))
             d = width // HEADS
-            common = (Q_pl.hi_ptr(), Q_pl.lo_ptr(), Q_pl.plane_stride, Q_pl.batch_stride, n, H, Wd, d, Q_pl.fmt, blk['scale'].data_ptr(), blk['factor'].data_ptr(),
-                      ws.data_ptr(), ws.numel() * 4)  # fmt: skip
-            tail = (blk['dwc_w'].data_ptr(), blk['dwc_b'].data_ptr(), A_pl.hi_ptr(), A_pl.lo_ptr(), A_pl.plane_stride, A_pl.batch_stride)
+            common = dict(qkv=Q_pl, head_dim=d, scale=blk['scale'], factor=blk['factor'], workspace=ws, workspace_bytes=ws.numel() * 4, **geo)
             rec = 4 * (HEADS * d * d + HEADS * d)
             tokens = H * Wd
-
-            def reduce_(common=common):
-                L.check(lib.rsa_fla_reduce(*common, C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_fla_reduce')
-
-            def apply_(common=common, tail=tail):
-                L.check(lib.rsa_fla_apply(*common, *tail, C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_fla_apply')
 
             # byte model: k and v read once, one partial record per chunk written and read, the finished record written; then q and v read
             # once (the halo re-reads of v stay on chip), the record read once per image, the output planes written
             chunks = (tokens + 127) // 128
-            plan.call(reduce_, meta=dict(kernel='rsa_fla_reduce', flop=2 * n * tokens * width * d, bytes=n * (tokens * 2 * cp * unit + (2 * chunks + 1) * rec)))
-            plan.count_launches(2)
-            plan.call(apply_, meta=dict(kernel='rsa_fla_apply', flop=2 * n * tokens * (width * d + 25 * width), bytes=n * (tokens * 3 * cp * unit + rec)))
-            plan.count_launches(1)
+            plan.launch('rsa_fla_reduce', common, kernels=2,
+                        meta=dict(kernel='rsa_fla_reduce', flop=2 * n * tokens * width * d, bytes=n * (tokens * 2 * cp * unit + (2 * chunks + 1) * rec)))  # fmt: skip
+            plan.launch('rsa_fla_apply', dict(dwc_weight=blk['dwc_w'], dwc_bias=blk['dwc_b'], out=A_pl, **common),
+                        meta=dict(kernel='rsa_fla_apply', flop=2 * n * tokens * (width * d + 25 * width), bytes=n * (tokens * 3 * cp * unit + rec)))  # fmt: skip
             plan.conv(ops.conv_params(blk['proj'], A_pl, H, Wd, out=F_pl, out_plane_off=c0))
         gp = L.GatedDwConvParams()
         gp.batch, gp.H, gp.W, gp.fmt, gp.i_planes, gp.n_segments = n, H, Wd, F_pl.fmt, blk['i_planes'], len(blk['segs'])
@@ -252,16 +236,11 @@ class GateR(EngineModule):
 
     def _down(self, plan: Plan, wts, src: Planes, in_plane0, n, H, Wd, width_out):
         """Downsample: 3x3 convolution (f32 map) + PixelUnshuffle(2) into a new stream of ``width_out`` channels at H/2 x W/2."""
-        lib, dev = L.load(), plan.device
         t = plan.f32map(n, width_out // 4, H, Wd)
         s = plan.f32map(n, width_out, H // 2, Wd // 2)
         plan.conv(ops.conv_params(wts, src, H, Wd, in_plane0=in_plane0, out_f32=t))
-
-        def unshuffle():
-            L.check(lib.rsa_pixel_unshuffle2(t.data_ptr(), n, H, Wd, width_out // 4, s.data_ptr(), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_pixel_unshuffle2')
-
-        plan.call(unshuffle, meta=dict(kernel='rsa_pixel_unshuffle2', flop=0, bytes=2 * n * H * Wd * width_out))
-        plan.count_launches(1)
+        plan.launch('rsa_pixel_unshuffle2', dict(x_f32=t, batch=n, H=H, W=Wd, C=width_out // 4, out_f32=s),
+                    meta=dict(kernel='rsa_pixel_unshuffle2', flop=0, bytes=2 * n * H * Wd * width_out))  # fmt: skip
         return s
 
     def _up(self, plan: Plan, wts, src: Planes, n, H, Wd, width_in):
@@ -280,7 +259,6 @@ class GateR(EngineModule):
             raise RuntimeError('input is too small for reflect padding to a multiple of 8')
         dim = self.dim
         with_lo = products == 3
-        lib, dev = L.load(), plan.device
         cache: dict = {}
         x_pl = plan.planes(n, 1, Hp, Wp, with_lo)
 
@@ -319,13 +297,8 @@ class GateR(EngineModule):
             self._stage(plan, W, 4 + j, n, 2 * hh, 2 * ww, sd_, with_lo, cache, prev)
         shuffled = self._up(plan, W['dec1.2.body.0'], prev, n, H1, W1, 2 * dim)
         sc = plan.f32map(n, 2 * dim, Hp, Wp)
-
-        def concat():
-            L.check(lib.rsa_f32map_concat(shuffled.data_ptr(), dim, e0.data_ptr(), dim, n, Hp, Wp, sc.data_ptr(), C.c_void_p(ops.current_stream_ptr(dev))),
-                    'rsa_f32map_concat')  # fmt: skip
-
-        plan.call(concat, meta=dict(kernel='rsa_f32map_concat', flop=0, bytes=n * Hp * Wp * 4 * 4 * dim))
-        plan.count_launches(1)
+        plan.launch('rsa_f32map_concat', dict(a_nchw=shuffled, Ca=dim, b_map=e0, Cb=dim, batch=n, H=Hp, W=Wp, out_map=sc),
+                    meta=dict(kernel='rsa_f32map_concat', flop=0, bytes=n * Hp * Wp * 4 * 4 * dim))  # fmt: skip
         p2 = plan.planes(n, 2 * pd, Hp, Wp, with_lo)
         self._stage(plan, W, 6, n, Hp, Wp, sc, with_lo, cache, p2)
         t = plan.planes(n, pd, Hp, Wp, with_lo)

@@ -15,7 +15,6 @@ relative-position tables are gathered once, at pack time, into the kernel's accu
 
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import torch
@@ -277,13 +276,8 @@ class HAT(EngineModule):
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
             plan.launch('rsa_channel_gate', gp, kernels=2)
-
-            def run():
-                L.check(lib.rsa_gated_add(cab_b.hi_ptr(), cab_b.lo_ptr(), cab_b.plane_stride, cab_b.batch_stride, n, H, Wd, C_, gate.data_ptr(),
-                                          self.conv_scale, shortcut.data_ptr(), out_f32.data_ptr(), C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_gated_add')  # fmt: skip
-
-            plan.call(run)
-            plan.count_launches(1)
+            plan.launch('rsa_gated_add', dict(x_hi=cab_b.hi_ptr(), x_lo=cab_b.lo_ptr(), plane_stride=cab_b.plane_stride, batch_stride=cab_b.batch_stride,
+                                              batch=n, H=H, W=Wd, C=C_, gate=gate, scale=self.conv_scale, base_f32=shortcut, out_f32=out_f32))  # fmt: skip
 
         def mlp(b, x1, x2, out_planes=None):
             if fuse_mlp:  # one launch (csrc/swin_block.hip), nothing between leaves the chip

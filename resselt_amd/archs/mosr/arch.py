@@ -20,8 +20,6 @@ folded in f64) and ``dys`` (the shared DySample head).
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from ...engine import dysample as dys
@@ -151,19 +149,11 @@ class _GatedBase(EngineModule):
 
     def _emit_block(self, plan: Plan, blk, n, H, Wd, cur, bufs):
         """norm -> fc1 -> rsa_gated_dwconv; returns the planes fc2 reads."""
-        lib = L.load()
-        dev = plan.device
         N_pl, F_pl, M_pl = bufs['norm'], bufs['fc1'], bufs['gate']
         sc, off = blk['norm']
         dim = self.dim
         if self.rms_norm:
-
-            def rms(src=cur, sc=sc, off=off):
-                L.check(lib.rsa_rmsnorm(src.data_ptr(), n, H, Wd, dim, 1e-6, sc.data_ptr(), off.data_ptr(), N_pl.hi_ptr(), N_pl.lo_ptr(),
-                                        N_pl.plane_stride, N_pl.batch_stride, C.c_void_p(ops.current_stream_ptr(dev))), 'rsa_rmsnorm')  # fmt: skip
-
-            plan.call(rms)
-            plan.count_launches(1)
+            plan.launch('rsa_rmsnorm', dict(x_f32=cur, batch=n, H=H, W=Wd, C=dim, eps=1e-6, scale=sc, offset=off, out=N_pl))
         else:
             lp = L.LayerNormParams()
             lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, dim, LN_EPS

@@ -15,8 +15,6 @@ the optional mid_dim conv + LeakyReLU 0.01).  ``self.short`` -- bilinear upsampl
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from ...engine import dysample as dys

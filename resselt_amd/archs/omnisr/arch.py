@@ -18,8 +18,6 @@ Heads: 4 heads of C/4 channels each own ceil(C/32) whole planes (qkv rows and th
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from ...engine import lib as L
@@ -207,7 +205,6 @@ class OmniSR(EngineModule):
         ap = HEADS * hp  # attention planes
         dev = plan.device
         lib = L.load()
-        stream = lambda: C.c_void_p(ops.current_stream_ptr(dev))  # noqa: E731
 
         x_pl = plan.planes(n, (cin + 7) // 8, H, Wd, with_lo)
         xpad = None
@@ -280,13 +277,8 @@ class OmniSR(EngineModule):
             gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
             gp.workspace, gp.gate = ws_gate.data_ptr(), gate.data_ptr()
             plan.launch('rsa_channel_gate', gp, kernels=2)
-
-            def scale():
-                L.check(lib.rsa_omni_gate_scale(h_pl.hi_ptr(), h_pl.lo_ptr(), h_pl.plane_stride, h_pl.batch_stride, n, H, Wd, cp, gate.data_ptr(), fmt,
-                                                h_pl.hi_ptr(), h_pl.lo_ptr(), stream()), 'rsa_omni_gate_scale')  # fmt: skip
-
-            plan.call(scale)
-            plan.count_launches(1)
+            plan.launch('rsa_omni_gate_scale', dict(in_hi=h_pl.hi_ptr(), in_lo=h_pl.lo_ptr(), plane_stride=h_pl.plane_stride, batch_stride=h_pl.batch_stride,
+                                                    batch=n, H=H, W=Wd, planes=cp, gate=gate, fmt=fmt, out_hi=h_pl.hi_ptr(), out_lo=h_pl.lo_ptr()))  # fmt: skip
             plan.conv(ops.conv_params(W[f'{b}.0.fn.5'], h_pl, H, Wd, res1=x, alpha=1.0, out_f32=out))
 
         def window_attention(b, i, x, out, grid):
@@ -324,12 +316,7 @@ class OmniSR(EngineModule):
             for name, src, dst, hi, wi, ho, wo, stride, pad in ((f'{e}.conv2', c1f, c2f, H, Wd, H2, W2, 2, 0), (None, c2f, pmf, H2, W2, Hc, Wc, 0, 0),
                                                                (f'{e}.conv3', pmf, c3f, Hc, Wc, Hc, Wc, 1, 1)):  # fmt: skip
                 if name is None:
-
-                    def pool_():
-                        L.check(lib.rsa_esa_maxpool(c2f.data_ptr(), n, f, H2, W2, pmf.data_ptr(), stream()), 'rsa_esa_maxpool')
-
-                    plan.call(pool_)
-                    plan.count_launches(1)
+                    plan.launch('rsa_esa_maxpool', dict(in_=c2f, batch=n, C=f, H=H2, W=W2, out=pmf))
                     continue
                 cpar = L.EsaConvParams()
                 cpar.batch, cpar.H, cpar.W, cpar.Hout, cpar.Wout, cpar.cin, cpar.cout, cpar.stride, cpar.pad = n, hi, wi, ho, wo, f, f, stride, pad

@@ -122,7 +122,6 @@ class _PLKBase(EngineModule):
         pf, pp = dim // 8, pdim // 8
         with_lo = products == 3
         dev = plan.device
-        stream = lambda: ops.current_stream_ptr(dev)  # noqa: E731
         # block buffers: feature planes + one plane for the image (read by feats.0, and by the DySample head's last convolution)
         X = [plan.planes(n, pf + 1, h, w, with_lo) for _ in range(2)]
         Xf = [plan.f32map(n, dim, h, w) for _ in range(2)]
@@ -159,13 +158,8 @@ class _PLKBase(EngineModule):
                 plan.conv(ops.conv_params(W[f'{p}.refine'], M, h, w, out_f32=R))
                 gamma, beta = W[f'{p}.norm']
                 ap = plk.group_norm_apply_params(R, dim, NORM_GROUPS, stats, gamma, beta, Xf[xi], X[xo], Xf[xo])
-
-                def run_norm(ap=ap):
-                    plk.group_norm_stats(R, dim, NORM_GROUPS, ws, stats, stream())
-                    plk.group_norm_apply(ap, stream())
-
-                plan.call(run_norm)
-                plan.count_launches(3)
+                stats_args = plk.group_norm_stats_args(R, dim, NORM_GROUPS, ws, stats)
+                plan.launch((('rsa_group_norm_stats', stats_args), ('rsa_group_norm_apply', ap)), kernels=3)
             else:
                 plan.conv(ops.conv_params(W[f'{p}.refine'], M, h, w, res1=Xf[xi], out=X[xo], out_f32=Xf[xo]))
 

@@ -24,7 +24,6 @@ convolution's planes for the mean, then the same apply pass.  Shapes the pooling
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -148,9 +147,6 @@ class RCAN(EngineModule):
         lib = L.load()
         u8 = dtype == torch.uint8
 
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
-
         x_pl = plan.planes(n, (c * df * df + 7) // 8, h, w, with_lo)
         if self.norm:
             shifted = torch.empty((n, c, h_in, w_in), dtype=torch.float32, device=dev)
@@ -158,8 +154,8 @@ class RCAN(EngineModule):
             sw, sb = W['sub_mean']
 
             def set_input(x):
-                L.check(lib.rsa_rcan_input(x.data_ptr(), ops.rsa_dtype(x.dtype), n, c, h_in, w_in, float(self.rgb_range), sw.data_ptr(), sb.data_ptr(),
-                                           shifted.data_ptr(), stream()), 'rsa_rcan_input')  # fmt: skip
+                ops.call('rsa_rcan_input', dev, x=x, dtype=ops.rsa_dtype(x.dtype), batch=n, C=c, H=h_in, W=w_in, scale=float(self.rgb_range), weight=sw, bias=sb,
+                         out=shifted)  # fmt: skip
                 ops.nchw_to_planes(shifted, x_pl, unshuffle=df)  # check_img_size's reflect padding commutes with the pointwise step
         else:
 
@@ -199,15 +195,9 @@ class RCAN(EngineModule):
                 gp.w1, gp.b1, gp.w2, gp.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
                 gp.workspace, gp.gate, gp.fmt = ws_gate.data_ptr(), gate.data_ptr(), y_pl.fmt
                 plan.launch('rsa_channel_gate', gp, kernels=2)
-
-            def tail():
-                L.check(lib.rsa_rcab_tail(sums.data_ptr() if fused else None, slots if fused else 0, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                          w1.shape[0], gate.data_ptr(), y_pl.hi_ptr(), y_pl.lo_ptr(), y_pl.plane_stride, y_pl.batch_stride,
-                                          x.hi_ptr(), x.lo_ptr(), x.plane_stride, x.batch_stride, out.hi_ptr(), out.lo_ptr(), out.plane_stride,
-                                          out.batch_stride, n, h, w, nf, y_pl.fmt, stream()), 'rsa_rcab_tail')  # fmt: skip
-
-            plan.call(tail, tail_meta)
-            plan.count_launches(2 if fused else 1)
+            plan.launch('rsa_rcab_tail', dict(pool_sums=sums if fused else None, slots=slots if fused else 0, w1=w1, b1=b1, w2=w2, b2=b2, hidden=w1.shape[0],
+                                              gate=gate, y=y_pl, x=x, out=out, batch=n, H=h, W=w, C=nf, fmt=y_pl.fmt),
+                        kernels=2 if fused else 1, meta=tail_meta)  # fmt: skip
 
         cur = head_pl
         for g in range(self.n_resgroups):

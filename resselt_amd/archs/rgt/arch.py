@@ -17,7 +17,6 @@ depthwise conv of v side by side (planes [0, 4*heads) and [4*heads, 8*heads)) wi
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -282,10 +281,8 @@ class RGT(EngineModule):
         half = self.hidden // 2
         P1 = (half + 7) // 8
         dev = plan.device
-        lib = L.load()
         max_heads = max(self.num_heads)
         hp_max = max_heads * HEAD_PAD // 8
-        stream = lambda: C.c_void_p(ops.current_stream_ptr(dev))  # noqa: E731
 
         x_pl = plan.planes(n, (c + 7) // 8, H, Wd, with_lo)
         mean = W['mean']
@@ -344,11 +341,7 @@ class RGT(EngineModule):
             plan.launch('rsa_rg_attention', ap)
 
         def scale_add(res, gamma, out):
-            def run():
-                L.check(lib.rsa_scale_add(res.data_ptr(), gamma.data_ptr(), out.data_ptr(), n, H, Wd, C_, stream()), 'rsa_scale_add')
-
-            plan.call(run)
-            plan.count_launches(1)
+            plan.launch('rsa_scale_add', dict(res=res, gamma=gamma, out=out, batch=n, H=H, W=Wd, C=C_))
 
         plan.conv(ops.conv_params(W['conv_first'], x_pl, H, Wd, out_f32=first))
         free = list(pool)

@@ -23,7 +23,6 @@ the reference computes on that tile.  The caller's input is never written.
 
 from __future__ import annotations
 
-import ctypes as C
 from fractions import Fraction
 
 import torch
@@ -209,12 +208,8 @@ class RHA(EngineModule):
         p2 = c2 // 8
         c0 = hp + ip  # c's first plane in the fc1 buffer: [g | i | c], c = [x1 | x2]
         with_lo = products == 3
-        lib, dev = L.load(), plan.device
         px = n * H * Wd
         unit = 16 * (2 if with_lo else 1)
-
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
 
         x_pl = plan.planes(n, 1, H, Wd, with_lo)
 
@@ -232,6 +227,7 @@ class RHA(EngineModule):
         fe = plan.planes(n, pd, H, Wd, with_lo)
         att = {d: plan.f32map(n, c2, H // d, Wd // d) for d in sorted({self.down(g) for g in range(self.group_blocks)})}
         fmt = F_pl.fmt
+        geo = dict(batch=n, H=H, W=Wd, fmt=fmt)
 
         plan.conv(ops.conv_params(W['to_feat'], x_pl, H, Wd, out_f32=top))
         gin, gout = top, ga
@@ -250,32 +246,18 @@ class RHA(EngineModule):
                 plan.launch('rsa_layernorm', lp)
                 plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
 
-                def attn(blk=blk, down=down, shift=shift, A32=A32):
-                    L.check(lib.rsa_rha_window_attn(F_pl.hi_ptr(c0 + p2), F_pl.lo_ptr(c0 + p2), F_pl.plane_stride, F_pl.batch_stride, n, H, Wd, c2, down, ws, shift,
-                                                    fmt, blk['wqkv_t'].data_ptr(), blk['bqkv'].data_ptr(), blk['pos_t'].data_ptr(), blk['isc'].data_ptr(),
-                                                    blk['dww'].data_ptr(), blk['dwb'].data_ptr(), blk['wproj_t'].data_ptr(), blk['bproj'].data_ptr(),
-                                                    A32.data_ptr(), stream()), 'rsa_rha_window_attn')  # fmt: skip
-
-                def mix(blk=blk, down=down, A32=A32):
-                    L.check(lib.rsa_rha_mix(F_pl.hi_ptr(c0), F_pl.lo_ptr(c0), F_pl.plane_stride, F_pl.batch_stride, A32.data_ptr(), X_pl.hi_ptr(), X_pl.lo_ptr(),
-                                            X_pl.plane_stride, X_pl.batch_stride, n, H, Wd, c2, down, fmt, blk['omni_w'].data_ptr(), blk['omni_b'].data_ptr(),
-                                            stream()), 'rsa_rha_mix')  # fmt: skip
-
-                def gate():
-                    L.check(lib.rsa_rha_gate(F_pl.hi_ptr(), F_pl.lo_ptr(), F_pl.plane_stride, F_pl.batch_stride, A_pl.hi_ptr(), A_pl.lo_ptr(), A_pl.plane_stride,
-                                             A_pl.batch_stride, M_pl.hi_ptr(), M_pl.lo_ptr(), M_pl.plane_stride, M_pl.batch_stride, n, H, Wd, hp, ip, fmt,
-                                             stream()), 'rsa_rha_gate')  # fmt: skip
-
                 # byte models: every operand touched once (halo and neighbour re-reads stay on chip); the pooled map is 1 / down^2 of a map
                 ppx = px // (down * down)
                 hd = c2 // HEADS
-                plan.call(attn, dict(kernel='rsa_rha_window_attn', flop=2 * ppx * (4 * c2 * c2 + 2 * c2 * hd + 25 * c2), bytes=px * p2 * unit + ppx * c2 * 4))
-                plan.count_launches(1)
-                plan.call(mix, dict(kernel='rsa_rha_mix', flop=2 * px * (25 * c2 + 4 * c2), bytes=px * p2 * unit + ppx * c2 * 4 + px * pd * unit))
-                plan.count_launches(1)
+                plan.launch('rsa_rha_window_attn', dict(x=(F_pl, c0 + p2), C2=c2, down=down, window=ws, shift=shift, wqkv_t=blk['wqkv_t'], bqkv=blk['bqkv'],
+                                                        pos_t=blk['pos_t'], inv_scale=blk['isc'], dwc_w=blk['dww'], dwc_b=blk['dwb'], wproj_t=blk['wproj_t'],
+                                                        bproj=blk['bproj'], out=A32, **geo),
+                            meta=dict(kernel='rsa_rha_window_attn', flop=2 * ppx * (4 * c2 * c2 + 2 * c2 * hd + 25 * c2), bytes=px * p2 * unit + ppx * c2 * 4))  # fmt: skip
+                plan.launch('rsa_rha_mix', dict(x=(F_pl, c0), att=A32, out=X_pl, C2=c2, down=down, weight=blk['omni_w'], bias=blk['omni_b'], **geo),
+                            meta=dict(kernel='rsa_rha_mix', flop=2 * px * (25 * c2 + 4 * c2), bytes=px * p2 * unit + ppx * c2 * 4 + px * pd * unit))  # fmt: skip
                 plan.conv(ops.conv_params(blk['aggr'], X_pl, H, Wd, act=L.ACT_MISH, out=A_pl))
-                plan.call(gate, dict(kernel='rsa_rha_gate', flop=px * (2 * dim + 8 * hidden), bytes=px * unit * (2 * hp + pd + hp)))
-                plan.count_launches(1)
+                plan.launch('rsa_rha_gate', dict(f=F_pl, a=A_pl, out=M_pl, hidden_planes=hp, i_planes=ip, **geo),
+                            meta=dict(kernel='rsa_rha_gate', flop=px * (2 * dim + 8 * hidden), bytes=px * unit * (2 * hp + pd + hp)))  # fmt: skip
                 if i < self.res_blocks - 1:
                     plan.conv(ops.conv_params(blk['fc2'], M_pl, H, Wd, act=L.ACT_MISH, res1=cur, alpha=1.0, out_f32=nxt))
                     cur, nxt = nxt, (sb if nxt is sa else sa)

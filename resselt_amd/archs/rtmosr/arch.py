@@ -14,7 +14,6 @@ depth-to-space with the nearest-upsampled input added in the same store.
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -136,13 +135,6 @@ class RTMoSR(EngineModule):
         pd, ph = dim // 8, hidden // 8
         gi = (hidden - dim) // 8  # planes of i
 
-        def stream():
-            return C.c_void_p(ops.current_stream_ptr(dev))
-
-        def call(fn):
-            plan.call(fn)
-            plan.count_launches(1)
-
         x_pl = plan.planes(n, (3 * u * u + 7) // 8, H, Wd, with_lo)
 
         def set_input(x):
@@ -166,20 +158,9 @@ class RTMoSR(EngineModule):
         for i in range(self.n_blocks):
             b = f'body.{i}'
             sc, off = W[f'{b}.norm']
-
-            def rms(src=cur, sc=sc, off=off):
-                L.check(lib.rsa_rmsnorm(src.data_ptr(), n, H, Wd, dim, 1e-6, sc.data_ptr(), off.data_ptr(), a_pl.hi_ptr(), a_pl.lo_ptr(), a_pl.plane_stride,
-                                        a_pl.batch_stride, stream()), 'rsa_rmsnorm')  # fmt: skip
-
-            call(rms)
+            plan.launch('rsa_rmsnorm', dict(x_f32=cur, batch=n, H=H, W=Wd, C=dim, eps=1e-6, scale=sc, offset=off, out=a_pl))
             plan.conv(ops.conv_params(W[f'{b}.fc1'], a_pl, H, Wd, out=f_pl))
-
-            def unshuffle_pool():
-                L.check(lib.rsa_unshuffle_pool(f_pl.hi_ptr(ph + gi), f_pl.lo_ptr(ph + gi), f_pl.plane_stride, f_pl.batch_stride, n, H, Wd, pd, pu.data_ptr(),
-                                               pool_pl.hi_ptr(), pool_pl.lo_ptr(), pool_pl.plane_stride, pool_pl.batch_stride, stream()),
-                        'rsa_unshuffle_pool')  # fmt: skip
-
-            call(unshuffle_pool)
+            plan.launch('rsa_unshuffle_pool', dict(in_=(f_pl, ph + gi), batch=n, H=H, W=Wd, planes=pd, unshuffled_f32=pu, pool=pool_pl))
             plan.conv(ops.conv_params(W[f'{b}.conv.0.poll.1'], pool_pl, H // 2, Wd // 2, res1=pu, alpha=1.0, out=c_pl))
             ow, ob = W[f'{b}.omni']
             dp = L.DwConvParams()

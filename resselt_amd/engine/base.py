@@ -81,6 +81,9 @@ def conv_algorithmic_bytes(p: L.ConvParams) -> int:
     return total
 
 
+_CONV_POINTERS = [k for k, t in L.ConvParams._fields_ if t is C.c_void_p]
+
+
 class Plan:
     """Buffers + launch list for one (batch, H, W, dtype, device, precision) signature."""
 
@@ -100,7 +103,7 @@ class Plan:
         self.serpentine = True
         self._n_conv = 0
         # the forward's output and the caller's input (``output`` / ``input_ref``): the tensor currently held, the address of the placeholder the
-        # descriptors were built against, and the (struct, field, byte offset) of every pointer field into it
+        # descriptors were built against, and the (container, key, byte offset) of every pointer field or pointer argument into it
         self._y = self._x = None
         self._out_spec = None
         self._y0 = self._x0 = (0, 0)
@@ -136,22 +139,28 @@ class Plan:
         self._x0 = (self._x.data_ptr(), self._x.numel() * self._x.element_size())
         return self._x
 
-    def _bind(self, struct) -> None:
-        """Record the pointer fields of a descriptor that point into the output or input placeholder (build time)."""
-        for name, typ in struct._fields_:
-            if typ is C.c_void_p:
-                ptr = getattr(struct, name) or 0
-                for (base, size), binds in ((self._y0, self._out_binds), (self._x0, self._in_binds)):
-                    if base <= ptr < base + size:
-                        binds.append((struct, name, ptr - base))
+    def _bind(self, container, keys) -> None:
+        """Record the pointer slots ``keys`` of ``container`` -- fields of a descriptor, or positions of a positional argument list -- that
+        point into the output or input placeholder (build time)."""
+        for key in keys:
+            ptr = (getattr(container, key) if isinstance(key, str) else container[key]) or 0
+            for (base, size), binds in ((self._y0, self._out_binds), (self._x0, self._in_binds)):
+                if base <= ptr < base + size:
+                    binds.append((container, key, ptr - base))
+
+    @staticmethod
+    def _repoint(binds, base: int) -> None:
+        for container, key, off in binds:
+            if isinstance(key, str):
+                setattr(container, key, base + off)
+            else:
+                container[key] = base + off
 
     def _prepare_output(self) -> None:
         if self._y is None:
             shape, dtype, _ = self._out_spec
             self._y = torch.empty(shape, dtype=dtype, device=self.device)
-            base = self._y.data_ptr()
-            for struct, name, off in self._out_binds:
-                setattr(struct, name, base + off)
+            self._repoint(self._out_binds, self._y.data_ptr())
 
     def current_output(self) -> torch.Tensor:
         """The output tensor of the running forward (for host steps that write it directly)."""
@@ -159,9 +168,7 @@ class Plan:
 
     def feed(self, x: torch.Tensor) -> None:
         """Point every descriptor field that reads the caller's input at ``x``, and hold ``x`` until ``take_output``."""
-        base = x.data_ptr()
-        for struct, name, off in self._in_binds:
-            setattr(struct, name, base + off)
+        self._repoint(self._in_binds, x.data_ptr())
         self._x = x
 
     def take_output(self) -> torch.Tensor:
@@ -188,7 +195,7 @@ class Plan:
             return None
         arr = (L.ConvParams * len(self._pending))(*self._pending)
         for p in arr:
-            self._bind(p)
+            self._bind(p, _CONV_POINTERS)
         self._n_launches = getattr(self, '_n_launches', 0) + len(self._pending)
         self._pending = []
         self.conv_arrays.append(arr)
@@ -214,11 +221,31 @@ class Plan:
             except AttributeError:  # a callable that takes no attributes (functools.partial does; builtins do not): not priced
                 pass
 
-    def launch(self, fn_name: str, params, kernels: int = 1, meta: dict | None = None) -> None:
-        """A ``call`` step of one C-ABI entry point that takes ``(params*, stream)``; it launches ``kernels`` kernels."""
-        self._bind(params)
+    def bound(self, name: str, args) -> Callable[[], None]:
+        """One C-ABI call as a callable that makes it on the current stream.  ``args`` is the descriptor of a ``(params*, stream)`` entry
+        point, or a dict of keyword arguments for a positional one (``lib.bind``): resolved into the argument list here, once; the
+        pointers among them that point into the output or input placeholder are re-pointed per forward like descriptor fields."""
         dev = self.device
-        self.call(lambda: L.launch(fn_name, params, ops.current_stream_ptr(dev)), meta)
+        if isinstance(args, C.Structure):
+            self._bind(args, [k for k, t in args._fields_ if t is C.c_void_p])
+            return lambda: L.launch(name, args, ops.current_stream_ptr(dev))
+        argv = L.bind(name, **args)
+        self._bind(argv, [i for i, (_, t) in enumerate(L.SIGNATURES[name][1][: len(argv)]) if t is C.c_void_p])
+        return lambda: L.invoke(name, argv, ops.current_stream_ptr(dev))
+
+    def launch(self, name, args=None, kernels: int = 1, meta: dict | None = None) -> None:
+        """A ``call`` step of one C-ABI entry point (``name``, ``args``: see ``bound``), or of several priced as one: ``name`` is then a
+        sequence of ``(name, args)`` pairs.  The step launches ``kernels`` kernels."""
+        calls = [self.bound(*c) for c in ([(name, args)] if isinstance(name, str) else name)]
+        if len(calls) == 1:
+            step = calls[0]
+        else:
+
+            def step():
+                for c in calls:
+                    c()
+
+        self.call(step, meta)
         self.count_launches(kernels)
 
     def run(self) -> None:

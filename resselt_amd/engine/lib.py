@@ -23,6 +23,7 @@ LO8_RES1, LO8_RES2, LO8_OUT = 1, 2, 4  # rsa_conv_params.lo8_flags
 PF_BF16, PF_F16 = range(2)
 E_INTERNAL = -4
 E_UNSUPPORTED = -2
+E_FP16_RANGE = -5  # RSA_E_FP16_RANGE
 
 
 def _i32(*names: str) -> list:
@@ -356,160 +357,128 @@ class AtdRefineParams(C.Structure):
     _fields_ = _i32('batch', 'H', 'W', 'C', 'm') + _f32('eps') + _ptr('sim', 'x', 'gamma', 'beta', 'sigma', 'td', 'workspace')
 
 
-# every symbol include/resselt_amd.h declares (checked by tests/test_capi_symbols.py)
-EXPORTS = (
-    'rsa_version',
-    'rsa_last_error_string',
-    'rsa_conv2d',
-    'rsa_conv2d_list',
-    'rsa_conv_cout_tiles',
-    'rsa_conv_pool_slots',
-    'rsa_packed_weight_bytes',
-    'rsa_packed_weight_bytes_layout',
-    'rsa_conv_weight_layout',
-    'rsa_pack_weights',
-    'rsa_conv_kernel_name',
-    'rsa_check_status',
-    'rsa_check_finite',
-    'rsa_debug_ring_aborts',
-    'rsa_debug_set_ring_spin_limit',
-    'rsa_debug_set_ring',
-    'rsa_debug_set_pair',
-    'rsa_conv2d_pair',
-    'rsa_conv_pair_fusable',
-    'rsa_nchw_to_planes',
-    'rsa_planes_to_nchw',
-    'rsa_dysample',
-    'rsa_layernorm',
-    'rsa_window_attention',
-    'rsa_swin_attn_block',
-    'rsa_swin_mlp_block',
-    'rsa_swin_block',
-    'rsa_rect_attention',
-    'rsa_channel_attn_workspace_bytes',
-    'rsa_channel_attention_weights',
-    'rsa_dwconv3x3',
-    'rsa_plane_stats',
-    'rsa_plane_stats_fmt',
-    'rsa_channel_gate_workspace_bytes',
-    'rsa_channel_gate',
-    'rsa_aim_combine',
-    'rsa_gated_add',
-    'rsa_dwconv5x5',
-    'rsa_rmsnorm',
-    'rsa_unshuffle_pool',
-    'rsa_gated_shuffle_mul',
-    'rsa_image_u8_to_nchw',
-    'rsa_nchw_to_image_u8',
-    'rsa_plk_packed_weight_bytes',
-    'rsa_plk_conv',
-    'rsa_group_norm_workspace_bytes',
-    'rsa_group_norm_stats',
-    'rsa_group_norm_apply',
-    'rsa_ea_gate',
-    'rsa_resample_packed_weight_bytes',
-    'rsa_deconv',
-    'rsa_conv_s2',
-    'rsa_region_se_workspace_bytes',
-    'rsa_region_se',
-    'rsa_cugan_input',
-    'rsa_cugan_output',
-    'rsa_gated_dwconv',
-    'rsa_bilinear_add',
-    'rsa_rg_attention',
-    'rsa_rg_reduce',
-    'rsa_layernorm_gelu',
-    'rsa_scale_add',
-    'rsa_fdat_interact',
-    'rsa_pa_gate',
-    'rsa_lda_offsets',
-    'rsa_lda_attention',
-    'rsa_omni_window_attention',
-    'rsa_omni_channel_attn_workspace_bytes',
-    'rsa_omni_channel_attention',
-    'rsa_gelu_gate_dwconv',
-    'rsa_omni_gate_scale',
-    'rsa_esa_conv3x3',
-    'rsa_esa_maxpool',
-    'rsa_esa_apply',
-    'rsa_atd_dict',
-    'rsa_atd_ca',
-    'rsa_atd_sort_workspace_bytes',
-    'rsa_atd_sort',
-    'rsa_atd_attention',
-    'rsa_atd_dwconv',
-    'rsa_atd_refine_workspace_bytes',
-    'rsa_atd_refine',
-    'rsa_rcab_tail',
-    'rsa_rcan_input',
-    'rsa_rmsnorm_torch',
-    'rsa_pixel_unshuffle2',
-    'rsa_f32map_concat',
-    'rsa_fla_workspace_bytes',
-    'rsa_fla_reduce',
-    'rsa_fla_apply',
-    'rsa_eimn_query_chain',
-    'rsa_eimn_sal',
-    'rsa_eimn_silu_mul',
-    'rsa_eimn_dffm_workspace_bytes',
-    'rsa_eimn_dffm_reduce',
-    'rsa_eimn_dffm_gates',
-    'rsa_eimn_dffm_apply',
-    'rsa_rha_window_attn_lds_bytes',
-    'rsa_rha_window_attn',
-    'rsa_rha_mix',
-    'rsa_rha_gate',
-    'rsa_flex_norm_shift',
-    'rsa_flex_window_attn_lds_bytes',
-    'rsa_flex_window_attn',
-    'rsa_flex_sqrelu',
-    'rsa_flex_gate_add',
-)
+def _conv(*names: str) -> list:
+    return [(k, C.POINTER(ConvParams)) for k in names]
 
 
-# the entry points that take (descriptor*, stream) and return a status: symbol -> descriptor
-DESCRIPTOR_CALLS = {
-    'rsa_conv2d': ConvParams,
-    'rsa_dysample': DySampleParams,
-    'rsa_layernorm': LayerNormParams,
-    'rsa_layernorm_gelu': LayerNormParams,
-    'rsa_window_attention': WindowAttnParams,
-    'rsa_swin_attn_block': SwinAttnBlockParams,
-    'rsa_swin_mlp_block': SwinMlpBlockParams,
-    'rsa_swin_block': SwinBlockParams,
-    'rsa_rect_attention': RectAttnParams,
-    'rsa_channel_attention_weights': ChannelAttnParams,
-    'rsa_dwconv3x3': DwConvParams,
-    'rsa_dwconv5x5': DwConvParams,
-    'rsa_channel_gate': ChannelGateParams,
-    'rsa_aim_combine': AimParams,
-    'rsa_gated_shuffle_mul': GatedShuffleParams,
-    'rsa_plk_conv': PlkConvParams,
-    'rsa_group_norm_apply': GroupNormApplyParams,
-    'rsa_ea_gate': EaGateParams,
-    'rsa_deconv': ResampleConvParams,
-    'rsa_conv_s2': ResampleConvParams,
-    'rsa_region_se': RegionSEParams,
-    'rsa_cugan_input': CuganInputParams,
-    'rsa_cugan_output': CuganOutputParams,
-    'rsa_gated_dwconv': GatedDwConvParams,
-    'rsa_bilinear_add': BilinearAddParams,
-    'rsa_rg_attention': RgAttnParams,
-    'rsa_rg_reduce': RgReduceParams,
-    'rsa_fdat_interact': FdatInteractParams,
-    'rsa_lda_offsets': LdaOffsetsParams,
-    'rsa_lda_attention': LdaAttnParams,
-    'rsa_omni_window_attention': OmniAttnParams,
-    'rsa_omni_channel_attention': OmniAttnParams,
-    'rsa_gelu_gate_dwconv': GeluGateDwConvParams,
-    'rsa_esa_conv3x3': EsaConvParams,
-    'rsa_esa_apply': EsaApplyParams,
-    'rsa_atd_dict': AtdDictParams,
-    'rsa_atd_ca': AtdCaParams,
-    'rsa_atd_attention': AtdAttnParams,
-    'rsa_atd_dwconv': AtdDwConvParams,
-    'rsa_atd_refine': AtdRefineParams,
+def _descriptor(struct) -> tuple:
+    """An entry point that takes ``(const struct* p, void* stream)`` and returns a status."""
+    return (C.c_int, [('p', C.POINTER(struct))] + _ptr('stream'))
+
+
+# Every entry point include/resselt_amd.h declares: name -> (restype, [(parameter name, ctype), ...]), the header's names in the header's
+# order, the trailing ``void* stream`` included.  ``load()`` sets argtypes / restype from it, ``bind`` resolves keyword arguments against
+# it, and tests/test_capi_signatures.py compares every row with its prototype.  A new entry point = its prototype there + its row here.
+SIGNATURES = {
+    'rsa_conv2d': _descriptor(ConvParams),
+    'rsa_conv2d_list': (C.c_int, _conv('list') + _i32('n') + _ptr('stream')),
+    'rsa_conv2d_pair': (C.c_int, _conv('a', 'b') + _ptr('stream')),
+    'rsa_conv_pair_fusable': (C.c_int, _conv('a', 'b')),
+    'rsa_check_status': (C.c_int, []),
+    'rsa_check_finite': (C.c_int, _ptr('data') + _i32('dtype') + _i64('count') + _ptr('stream')),
+    'rsa_packed_weight_bytes': (C.c_int64, _i32('cout', 'cin_planes', 'ksize', 'products')),
+    'rsa_packed_weight_bytes_layout': (C.c_int64, _i32('cout', 'cin_planes', 'ksize', 'products', 'layout')),
+    'rsa_conv_cout_tiles': (C.c_int, _i32('cout')),
+    'rsa_conv_pool_slots': (C.c_int, _conv('p')),
+    'rsa_conv_weight_layout': (C.c_int, _conv('p')),
+    'rsa_pack_weights': (C.c_int, _ptr('w_oihw') + _i32('cout', 'cin', 'cin_planes', 'ksize', 'products', 'layout', 'fmt') + _ptr('out', 'stream')),
+    'rsa_conv_kernel_name': (C.c_char_p, _conv('p')),
+    'rsa_debug_ring_aborts': (C.c_int, []),
+    'rsa_debug_set_ring_spin_limit': (C.c_int, _i32('polls')),
+    'rsa_debug_set_ring': (C.c_int, _i32('mode')),
+    'rsa_debug_set_pair': (C.c_int, _i32('mode')),
+    'rsa_nchw_to_planes': (C.c_int, _ptr('x') + _i32('dtype', 'batch', 'C', 'H', 'W', 'src_h', 'src_w', 'unshuffle') + _ptr('mean') + _f32('scale') + _plane_fields('out') + _i32('out_fmt') + _ptr('stream')),
+    'rsa_planes_to_nchw': (C.c_int, _ptr('hi', 'lo') + _i64('plane_stride', 'batch_stride') + _i32('batch', 'C', 'H', 'W', 'fmt') + _ptr('out', 'stream')),
+    'rsa_dysample': _descriptor(DySampleParams),
+    'rsa_layernorm': _descriptor(LayerNormParams),
+    'rsa_window_attention': _descriptor(WindowAttnParams),
+    'rsa_swin_attn_block': _descriptor(SwinAttnBlockParams),
+    'rsa_swin_mlp_block': _descriptor(SwinMlpBlockParams),
+    'rsa_swin_block': _descriptor(SwinBlockParams),
+    'rsa_rect_attention': _descriptor(RectAttnParams),
+    'rsa_channel_attn_workspace_bytes': (C.c_int64, _i32('batch', 'H', 'W', 'heads')),
+    'rsa_channel_attention_weights': _descriptor(ChannelAttnParams),
+    'rsa_dwconv3x3': _descriptor(DwConvParams),
+    'rsa_dwconv5x5': _descriptor(DwConvParams),
+    'rsa_plane_stats': (C.c_int, _ptr('in_hi', 'in_lo') + _i64('plane_stride', 'batch_stride') + _i32('batch', 'H', 'W', 'C') + _f32('eps') + _ptr('stats', 'stream')),
+    'rsa_plane_stats_fmt': (C.c_int, _ptr('in_hi', 'in_lo') + _i64('plane_stride', 'batch_stride') + _i32('batch', 'H', 'W', 'C') + _f32('eps') + _i32('fmt') + _ptr('stats', 'stream')),
+    'rsa_channel_gate_workspace_bytes': (C.c_int64, _i32('batch', 'H', 'W', 'planes')),
+    'rsa_channel_gate': _descriptor(ChannelGateParams),
+    'rsa_aim_combine': _descriptor(AimParams),
+    'rsa_gated_add': (C.c_int, _ptr('x_hi', 'x_lo') + _i64('plane_stride', 'batch_stride') + _i32('batch', 'H', 'W', 'C') + _ptr('gate') + _f32('scale') + _ptr('base_f32', 'out_f32', 'stream')),
+    'rsa_rmsnorm': (C.c_int, _ptr('x_f32') + _i32('batch', 'H', 'W', 'C') + _f32('eps') + _ptr('scale', 'offset') + _plane_fields('out') + _ptr('stream')),
+    'rsa_unshuffle_pool': (C.c_int, _plane_fields('in') + _i32('batch', 'H', 'W', 'planes') + _ptr('unshuffled_f32') + _plane_fields('pool') + _ptr('stream')),
+    'rsa_gated_shuffle_mul': _descriptor(GatedShuffleParams),
+    'rsa_plk_packed_weight_bytes': (C.c_int64, _i32('ksize', 'planes', 'products')),
+    'rsa_plk_conv': _descriptor(PlkConvParams),
+    'rsa_group_norm_workspace_bytes': (C.c_int64, _i32('batch', 'H', 'W', 'groups')),
+    'rsa_group_norm_stats': (C.c_int, _ptr('x_f32') + _i32('batch', 'H', 'W', 'C', 'groups') + _f32('eps') + _ptr('workspace', 'stats', 'stream')),
+    'rsa_group_norm_apply': _descriptor(GroupNormApplyParams),
+    'rsa_ea_gate': _descriptor(EaGateParams),
+    'rsa_resample_packed_weight_bytes': (C.c_int64, _i32('ksize', 'stride', 'transposed', 'cin_planes', 'cout', 'products')),
+    'rsa_deconv': _descriptor(ResampleConvParams),
+    'rsa_conv_s2': _descriptor(ResampleConvParams),
+    'rsa_region_se_workspace_bytes': (C.c_int64, _i32('batch', 'h', 'planes')),
+    'rsa_region_se': _descriptor(RegionSEParams),
+    'rsa_cugan_input': _descriptor(CuganInputParams),
+    'rsa_cugan_output': _descriptor(CuganOutputParams),
+    'rsa_gated_dwconv': _descriptor(GatedDwConvParams),
+    'rsa_bilinear_add': _descriptor(BilinearAddParams),
+    'rsa_rg_attention': _descriptor(RgAttnParams),
+    'rsa_rg_reduce': _descriptor(RgReduceParams),
+    'rsa_layernorm_gelu': _descriptor(LayerNormParams),
+    'rsa_scale_add': (C.c_int, _ptr('res', 'gamma', 'out') + _i32('batch', 'H', 'W', 'C') + _ptr('stream')),
+    'rsa_fdat_interact': _descriptor(FdatInteractParams),
+    'rsa_pa_gate': (C.c_int, _ptr('x_hi', 'x_lo', 'logit_hi', 'logit_lo') + _i64('plane_stride', 'batch_stride') + _i32('batch', 'H', 'W', 'planes') + _f32('slope') + _i32('fmt') + _ptr('out_hi', 'out_lo', 'stream')),
+    'rsa_lda_offsets': _descriptor(LdaOffsetsParams),
+    'rsa_lda_attention': _descriptor(LdaAttnParams),
+    'rsa_omni_window_attention': _descriptor(OmniAttnParams),
+    'rsa_omni_channel_attn_workspace_bytes': (C.c_int64, _i32('batch', 'H', 'W', 'ws', 'heads', 'head_dim', 'grid')),
+    'rsa_omni_channel_attention': _descriptor(OmniAttnParams),
+    'rsa_gelu_gate_dwconv': _descriptor(GeluGateDwConvParams),
+    'rsa_omni_gate_scale': (C.c_int, _ptr('in_hi', 'in_lo') + _i64('plane_stride', 'batch_stride') + _i32('batch', 'H', 'W', 'planes') + _ptr('gate') + _i32('fmt') + _ptr('out_hi', 'out_lo', 'stream')),
+    'rsa_esa_conv3x3': _descriptor(EsaConvParams),
+    'rsa_esa_maxpool': (C.c_int, _ptr('in') + _i32('batch', 'C', 'H', 'W') + _ptr('out', 'stream')),
+    'rsa_esa_apply': _descriptor(EsaApplyParams),
+    'rsa_atd_dict': _descriptor(AtdDictParams),
+    'rsa_atd_ca': _descriptor(AtdCaParams),
+    'rsa_atd_sort_workspace_bytes': (C.c_int64, _i32('batch') + _i64('n')),
+    'rsa_atd_sort': (C.c_int, _ptr('ids') + _i32('batch') + _i64('n') + _i32('m') + _ptr('perm', 'inv', 'workspace', 'stream')),
+    'rsa_atd_attention': _descriptor(AtdAttnParams),
+    'rsa_atd_dwconv': _descriptor(AtdDwConvParams),
+    'rsa_atd_refine_workspace_bytes': (C.c_int64, _i32('batch', 'H', 'W', 'C', 'm')),
+    'rsa_atd_refine': _descriptor(AtdRefineParams),
+    'rsa_rcab_tail': (C.c_int, _ptr('pool_sums') + _i32('slots') + _ptr('w1', 'b1', 'w2', 'b2') + _i32('hidden') + _ptr('gate') + _plane_fields('y') + _plane_fields('x') + _plane_fields('out') + _i32('batch', 'H', 'W', 'C', 'fmt') + _ptr('stream')),
+    'rsa_rcan_input': (C.c_int, _ptr('x') + _i32('dtype', 'batch', 'C', 'H', 'W') + _f32('scale') + _ptr('weight', 'bias', 'out', 'stream')),
+    'rsa_image_u8_to_nchw': (C.c_int, _ptr('img') + _i32('batch', 'H', 'W', 'C') + _ptr('out') + _i32('dtype') + _ptr('stream')),
+    'rsa_nchw_to_image_u8': (C.c_int, _ptr('x') + _i32('dtype', 'batch', 'C', 'H', 'W') + _ptr('img', 'stream')),
+    'rsa_rmsnorm_torch': (C.c_int, _ptr('x_f32') + _i32('batch', 'H', 'W', 'C') + _f32('eps') + _ptr('weight') + _plane_fields('out') + _i32('fmt') + _ptr('stream')),
+    'rsa_pixel_unshuffle2': (C.c_int, _ptr('x_f32') + _i32('batch', 'H', 'W', 'C') + _ptr('out_f32', 'stream')),
+    'rsa_f32map_concat': (C.c_int, _ptr('a_nchw') + _i32('Ca') + _ptr('b_map') + _i32('Cb', 'batch', 'H', 'W') + _ptr('out_map', 'stream')),
+    'rsa_fla_workspace_bytes': (C.c_int64, _i32('batch', 'tokens', 'head_dim')),
+    'rsa_fla_reduce': (C.c_int, _plane_fields('qkv') + _i32('batch', 'H', 'W', 'head_dim', 'fmt') + _ptr('scale', 'factor', 'workspace') + _i64('workspace_bytes') + _ptr('stream')),
+    'rsa_fla_apply': (C.c_int, _plane_fields('qkv') + _i32('batch', 'H', 'W', 'head_dim', 'fmt') + _ptr('scale', 'factor', 'workspace') + _i64('workspace_bytes') + _ptr('dwc_weight', 'dwc_bias') + _plane_fields('out') + _ptr('stream')),
+    'rsa_eimn_query_chain': (C.c_int, _plane_fields('q') + _plane_fields('out') + _i32('batch', 'H', 'W', 'planes_a', 'planes_b', 'planes_c', 'gelu_in', 'fmt') + _ptr('w1', 'b1', 'w2', 'b2', 'stream')),
+    'rsa_eimn_sal': (C.c_int, _plane_fields('in') + _plane_fields('out') + _i32('batch', 'H', 'W', 'planes', 'fmt') + _ptr('weight', 'bias', 'stream')),
+    'rsa_eimn_silu_mul': (C.c_int, _plane_fields('f') + _plane_fields('v') + _plane_fields('out') + _i32('batch', 'H', 'W', 'planes', 'fmt') + _ptr('stream')),
+    'rsa_eimn_dffm_workspace_bytes': (C.c_int64, _i32('batch', 'H', 'W', 'C')),
+    'rsa_eimn_dffm_reduce': (C.c_int, _ptr('z') + _i32('batch', 'H', 'W', 'C') + _ptr('gamma', 'beta') + _f32('eps') + _ptr('workspace') + _i64('workspace_bytes') + _ptr('stream')),
+    'rsa_eimn_dffm_gates': (C.c_int, _ptr('workspace') + _i64('workspace_bytes') + _i32('batch', 'H', 'W', 'C', 'rc') + _ptr('wg', 'bg', 'wc', 'bc', 'ws', 'bs', 'gates', 'stream')),
+    'rsa_eimn_dffm_apply': (C.c_int, _ptr('z', 'x') + _i32('batch', 'H', 'W', 'C', 'rc') + _ptr('gamma', 'beta') + _f32('eps') + _ptr('wl', 'bl', 'ws', 'gates', 'scale', 'norm_gamma', 'norm_beta') + _f32('norm_eps') + _ptr('add', 'out_f32') + _plane_fields('out') + _i32('fmt') + _ptr('stream')),
+    'rsa_rha_window_attn_lds_bytes': (C.c_int64, _i32('C2', 'window')),
+    'rsa_rha_window_attn': (C.c_int, _plane_fields('x') + _i32('batch', 'H', 'W', 'C2', 'down', 'window', 'shift', 'fmt') + _ptr('wqkv_t', 'bqkv', 'pos_t', 'inv_scale', 'dwc_w', 'dwc_b', 'wproj_t', 'bproj', 'out', 'stream')),
+    'rsa_rha_mix': (C.c_int, _plane_fields('x') + _ptr('att') + _plane_fields('out') + _i32('batch', 'H', 'W', 'C2', 'down', 'fmt') + _ptr('weight', 'bias', 'stream')),
+    'rsa_rha_gate': (C.c_int, _plane_fields('f') + _plane_fields('a') + _plane_fields('out') + _i32('batch', 'H', 'W', 'hidden_planes', 'i_planes', 'fmt') + _ptr('stream')),
+    'rsa_flex_norm_shift': (C.c_int, _ptr('x_f32') + _i32('batch', 'H', 'W', 'C') + _f32('eps') + _ptr('norm_weight', 'weight') + _plane_fields('out') + _i32('fmt') + _ptr('stream')),
+    'rsa_flex_window_attn_lds_bytes': (C.c_int64, _i32('C', 'products')),
+    'rsa_flex_window_attn': (C.c_int, _plane_fields('qkv') + _plane_fields('out') + _i32('batch', 'H', 'W', 'C', 'products', 'fmt') + _ptr('lepe_w', 'lepe_b', 'stream')),
+    'rsa_flex_sqrelu': (C.c_int, _plane_fields('in') + _plane_fields('out') + _i32('batch', 'H', 'W', 'hidden', 'norm') + _f32('eps') + _i32('fmt') + _ptr('stream')),
+    'rsa_flex_gate_add': (C.c_int, _plane_fields('r') + _plane_fields('kv') + _ptr('base_f32', 'out_f32') + _plane_fields('out') + _i32('batch', 'H', 'W', 'C', 'fmt') + _ptr('stream')),
+    'rsa_version': (C.c_int, []),
+    'rsa_last_error_string': (C.c_char_p, []),
 }
+
+EXPORTS = tuple(SIGNATURES)  # every symbol the header declares (tests/test_pack_and_capi.py)
 
 
 def lib_path() -> str:
@@ -556,85 +525,11 @@ def load() -> C.CDLL:
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise RuntimeError(f'{path} does not export {name}; rebuild the library')
-    lib.rsa_version.restype = C.c_int
-    lib.rsa_last_error_string.restype = C.c_char_p
-    for name, struct in DESCRIPTOR_CALLS.items():
-        getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
-        getattr(lib, name).restype = C.c_int
-    i32, i64, f32, ptr, cp = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.POINTER(ConvParams)
-    for name, restype, argtypes in (
-        ('rsa_conv2d_list', C.c_int, [cp, i32, ptr]),
-        ('rsa_conv_cout_tiles', C.c_int, [i32]),
-        ('rsa_packed_weight_bytes', i64, [i32] * 4),
-        ('rsa_packed_weight_bytes_layout', i64, [i32] * 5),
-        ('rsa_conv_weight_layout', C.c_int, [cp]),
-        ('rsa_conv_pool_slots', C.c_int, [cp]),
-        ('rsa_pack_weights', C.c_int, [ptr] + [i32] * 7 + [ptr, ptr]),
-        ('rsa_conv_kernel_name', C.c_char_p, [cp]),
-        ('rsa_debug_ring_aborts', C.c_int, []),
-        ('rsa_debug_set_ring', C.c_int, [i32]),
-        ('rsa_debug_set_pair', C.c_int, [i32]),
-        ('rsa_conv2d_pair', C.c_int, [cp, cp, ptr]),
-        ('rsa_conv_pair_fusable', C.c_int, [cp, cp]),
-        ('rsa_debug_set_ring_spin_limit', C.c_int, [i32]),
-        ('rsa_check_finite', C.c_int, [ptr, i32, i64, ptr]),
-        ('rsa_check_status', C.c_int, []),
-        ('rsa_nchw_to_planes', C.c_int, [ptr] + [i32] * 8 + [ptr, f32, ptr, ptr, i64, i64, i32, ptr]),
-        ('rsa_planes_to_nchw', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr]),
-        ('rsa_channel_attn_workspace_bytes', i64, [i32] * 4),
-        ('rsa_channel_gate_workspace_bytes', i64, [i32] * 4),
-        ('rsa_plane_stats', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [f32, ptr, ptr]),
-        ('rsa_plane_stats_fmt', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [f32, i32, ptr, ptr]),
-        ('rsa_rmsnorm', C.c_int, [ptr] + [i32] * 4 + [f32] + [ptr] * 4 + [i64, i64, ptr]),
-        ('rsa_unshuffle_pool', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [ptr] * 3 + [i64, i64, ptr]),
-        ('rsa_gated_add', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [ptr, f32, ptr, ptr, ptr]),
-        ('rsa_image_u8_to_nchw', C.c_int, [ptr] + [i32] * 4 + [ptr, i32, ptr]),
-        ('rsa_nchw_to_image_u8', C.c_int, [ptr] + [i32] * 5 + [ptr, ptr]),
-        ('rsa_plk_packed_weight_bytes', i64, [i32] * 3),
-        ('rsa_group_norm_workspace_bytes', i64, [i32] * 4),
-        ('rsa_group_norm_stats', C.c_int, [ptr] + [i32] * 5 + [f32, ptr, ptr, ptr]),
-        ('rsa_resample_packed_weight_bytes', i64, [i32] * 6),
-        ('rsa_region_se_workspace_bytes', i64, [i32] * 3),
-        ('rsa_scale_add', C.c_int, [ptr] * 3 + [i32] * 4 + [ptr]),
-        ('rsa_pa_gate', C.c_int, [ptr] * 4 + [i64] * 2 + [i32] * 4 + [f32, i32, ptr, ptr, ptr]),
-        ('rsa_omni_channel_attn_workspace_bytes', i64, [i32] * 7),
-        ('rsa_omni_gate_scale', C.c_int, [ptr, ptr, i64, i64] + [i32] * 4 + [ptr, i32] + [ptr] * 3),
-        ('rsa_atd_sort_workspace_bytes', i64, [i32, i64]),
-        ('rsa_atd_sort', C.c_int, [ptr, i32, i64, i32] + [ptr] * 4),
-        ('rsa_atd_refine_workspace_bytes', i64, [i32] * 5),
-        ('rsa_esa_maxpool', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr]),
-        ('rsa_rcab_tail', C.c_int, [ptr, i32] + [ptr] * 4 + [i32, ptr] + [ptr, ptr, i64, i64] * 3 + [i32] * 5 + [ptr]),
-        ('rsa_rcan_input', C.c_int, [ptr] + [i32] * 5 + [f32, ptr, ptr, ptr, ptr]),
-        ('rsa_rmsnorm_torch', C.c_int, [ptr] + [i32] * 4 + [f32] + [ptr] * 3 + [i64, i64, i32, ptr]),
-        ('rsa_pixel_unshuffle2', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr]),
-        ('rsa_f32map_concat', C.c_int, [ptr, i32, ptr, i32] + [i32] * 3 + [ptr, ptr]),
-        ('rsa_fla_workspace_bytes', i64, [i32] * 3),
-        ('rsa_fla_reduce', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr, ptr, i64, ptr]),
-        ('rsa_fla_apply', C.c_int, [ptr, ptr, i64, i64] + [i32] * 5 + [ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr, i64, i64, ptr]),
-        ('rsa_eimn_query_chain', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 8 + [ptr] * 5),
-        ('rsa_eimn_sal', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 5 + [ptr] * 3),
-        ('rsa_eimn_silu_mul', C.c_int, [ptr, ptr, i64, i64] * 3 + [i32] * 5 + [ptr]),
-        ('rsa_eimn_dffm_workspace_bytes', i64, [i32] * 4),
-        ('rsa_eimn_dffm_reduce', C.c_int, [ptr] + [i32] * 4 + [ptr, ptr, f32, ptr, i64, ptr]),
-        ('rsa_eimn_dffm_gates', C.c_int, [ptr, i64] + [i32] * 5 + [ptr] * 8),
-        ('rsa_eimn_dffm_apply', C.c_int, [ptr, ptr] + [i32] * 5 + [ptr, ptr, f32] + [ptr] * 7 + [f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr]),
-        ('rsa_rha_window_attn_lds_bytes', i64, [i32] * 2),
-        ('rsa_rha_window_attn', C.c_int, [ptr, ptr, i64, i64] + [i32] * 8 + [ptr] * 10),
-        ('rsa_rha_mix', C.c_int, [ptr, ptr, i64, i64, ptr, ptr, ptr, i64, i64] + [i32] * 6 + [ptr] * 3),
-        ('rsa_rha_gate', C.c_int, [ptr, ptr, i64, i64] * 3 + [i32] * 6 + [ptr]),
-        ('rsa_flex_norm_shift', C.c_int, [ptr] + [i32] * 4 + [C.c_float, ptr, ptr, ptr, ptr, i64, i64, i32, ptr]),
-        ('rsa_flex_window_attn_lds_bytes', i64, [i32] * 2),
-        ('rsa_flex_window_attn', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 6 + [ptr] * 3),
-        ('rsa_flex_sqrelu', C.c_int, [ptr, ptr, i64, i64] * 2 + [i32] * 5 + [C.c_float, i32, ptr]),
-        ('rsa_flex_gate_add', C.c_int, [ptr, ptr, i64, i64] * 2 + [ptr, ptr] + [ptr, ptr, i64, i64] + [i32] * 5 + [ptr]),
-    ):
-        getattr(lib, name).argtypes = argtypes
+    for name, (restype, params) in SIGNATURES.items():
+        getattr(lib, name).argtypes = [ctype for _, ctype in params]
         getattr(lib, name).restype = restype
     _lib = lib
     return lib
-
-
-E_FP16_RANGE = -5  # RSA_E_FP16_RANGE
 
 
 class Fp16RangeError(RuntimeError):
@@ -649,9 +544,58 @@ def check(rc: int, what: str) -> None:
         raise cls(f'{what} failed (status {rc}): {msg.decode() if msg else "?"}')
 
 
+def bind(name: str, **kwargs) -> list:
+    """Resolve keyword arguments against ``SIGNATURES[name]`` into the positional argument list of the entry point, without its trailing
+    stream.  Keys are the header's parameter names (a trailing underscore is dropped: ``in_``).  Values:
+
+    ``Planes`` / ``PlaneRows`` under key ``k`` fill ``k_hi``, ``k_lo``, ``k_plane_stride`` and ``k_batch_stride`` (``(planes, plane0)`` from
+    that plane on, as in ``ops.conv_params(res1=...)``); an explicit ``k_lo=`` beside it replaces the lo pointer (``None`` for a reader that
+    must not see lo halves).  A tensor becomes its ``data_ptr()``, ``None`` becomes NULL, numbers and descriptors pass through.
+    A missing, unknown or doubly given parameter raises ``TypeError``: nothing has been launched by then."""
+    params = [k for k, _ in SIGNATURES[name][1]]
+    given = {'stream': None} if params and params[-1] == 'stream' else {}  # the caller of the entry point supplies it
+
+    def put(key, value, replace=False):
+        if key not in params:
+            raise TypeError(f'{name}: no parameter {key!r}')
+        if key in given and not replace:
+            raise TypeError(f'{name}: parameter {key!r} given twice')
+        given[key] = value
+
+    scalars = {}
+    for key, v in kwargs.items():
+        key = key[:-1] if key.endswith('_') else key
+        v, plane0 = v if isinstance(v, tuple) else (v, 0)
+        if hasattr(v, 'hi_ptr'):
+            put(f'{key}_hi', v.hi_ptr(plane0))
+            put(f'{key}_lo', v.lo_ptr(plane0))
+            put(f'{key}_plane_stride', v.plane_stride)
+            put(f'{key}_batch_stride', v.batch_stride)
+        elif plane0:
+            raise TypeError(f'{name}: {key!r} has a plane offset but is no plane buffer')
+        else:
+            scalars[key] = v.data_ptr() if hasattr(v, 'data_ptr') else v
+    for key, v in scalars.items():
+        put(key, v, replace=key.endswith('_lo') and key in given)
+    missing = [k for k in params if k not in given]
+    if missing:
+        raise TypeError(f'{name}: missing parameter {", ".join(map(repr, missing))}')
+    return [given[k] for k in params if k != 'stream']
+
+
+def invoke(name: str, args, stream: int) -> None:
+    """Call entry point ``name`` with the positional ``args`` of ``bind`` on ``stream`` and raise if it fails."""
+    check(getattr(load(), name)(*args, stream), name)
+
+
+def call(name: str, stream: int, **kwargs) -> None:
+    """One immediate C-ABI call by parameter name (see ``bind``) on ``stream``; raises if it fails."""
+    invoke(name, bind(name, **kwargs), stream)
+
+
 def launch(name: str, params, stream: int) -> None:
     """Call the C-ABI entry point ``name`` that takes ``(params*, stream)`` and raise if it fails."""
-    check(getattr(load(), name)(C.byref(params), C.c_void_p(stream)), name)
+    invoke(name, [params], stream)
 
 
 def check_finite(t, stream: int) -> None:
@@ -662,17 +606,13 @@ def check_finite(t, stream: int) -> None:
     dt = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}[t.dtype]
     if not t.is_contiguous():
         raise ValueError('check_finite: the tensor must be contiguous')
-    check(load().rsa_check_finite(t.data_ptr(), dt, t.numel(), C.c_void_p(stream)), 'rsa_check_finite')
+    call('rsa_check_finite', stream, data=t, dtype=dt, count=t.numel())
 
 
 def conv2d_list(params: 'C.Array[ConvParams] | list[ConvParams]', stream: int) -> None:
     """Launch a list of fused convolutions in order on ``stream`` with one host call."""
-    lib = load()
-    if isinstance(params, list):
-        arr = (ConvParams * len(params))(*params)
-    else:
-        arr = params
-    check(lib.rsa_conv2d_list(arr, len(arr), C.c_void_p(stream)), 'rsa_conv2d_list')
+    arr = (ConvParams * len(params))(*params) if isinstance(params, list) else params
+    invoke('rsa_conv2d_list', [arr, len(arr)], stream)
 
 
 def conv_kernel_name(p: ConvParams) -> str:
@@ -691,7 +631,7 @@ def check_status(what: str = 'forward') -> None:
 
 def conv2d_pair(a: ConvParams, b: ConvParams, stream: int) -> None:
     """Two consecutive growth convolutions of a residual dense block as ONE launch (``rsa_conv2d_pair``; csrc/conv_ring_pair.h)."""
-    check(load().rsa_conv2d_pair(C.byref(a), C.byref(b), C.c_void_p(stream)), 'rsa_conv2d_pair')
+    call('rsa_conv2d_pair', stream, a=a, b=b)
 
 
 def conv_pair_fusable(a: ConvParams, b: ConvParams) -> bool:

@@ -2,7 +2,6 @@
 
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import torch
@@ -25,6 +24,11 @@ def current_stream_ptr(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def call(name: str, device, **kwargs) -> None:
+    """One immediate C-ABI call by parameter name (``lib.call``) on ``device``'s current stream."""
+    L.call(name, current_stream_ptr(device), **kwargs)
+
+
 def require_cuda(x: torch.Tensor, what: str) -> None:
     """The engine has no CPU path: fail loudly instead of silently computing elsewhere."""
     if not x.is_cuda:
@@ -40,14 +44,12 @@ def pack_weights_device(w: torch.Tensor, cin_planes: int, products: int, layout:
     require_cuda(w, 'pack_weights')
     w = w.to(torch.float32).contiguous()
     cout, cin, k, _ = w.shape
-    lib = L.load()
-    nbytes = int(lib.rsa_packed_weight_bytes_layout(cout, cin_planes, k, products, layout))
+    nbytes = int(L.load().rsa_packed_weight_bytes_layout(cout, cin_planes, k, products, layout))
     if nbytes <= 0:
         raise ValueError(f'unsupported convolution shape cout={cout} cin_planes={cin_planes} k={k} products={products}')
     out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w.device)
     with torch.cuda.device(w.device):
-        L.check(lib.rsa_pack_weights(w.data_ptr(), cout, cin, cin_planes, k, products, layout, fmt, out.data_ptr(),
-                                     C.c_void_p(current_stream_ptr(w.device))), 'rsa_pack_weights')  # fmt: skip
+        call('rsa_pack_weights', w.device, w_oihw=w, cout=cout, cin=cin, cin_planes=cin_planes, ksize=k, products=products, layout=layout, fmt=fmt, out=out)
     return out
 
 
@@ -245,7 +247,7 @@ def conv_params(
             raise ValueError('PReLU needs f32 slopes padded to a multiple of 16')
         p.act_vec = act_vec.data_ptr()
     # the schedule this descriptor dispatches to decides the K order of the weight blob
-    p.w_layout = int(L.load().rsa_conv_weight_layout(C.byref(p)))
+    p.w_layout = int(L.load().rsa_conv_weight_layout(p))
     p.w_packed = wts.packed_for(p.w_layout).data_ptr()
     p.true_cin = min(wts.cin, 8 * p.cin_planes)  # python-side only (not part of the C struct): FLOP accounting in bench.py
     if pool_sums is not None:
@@ -263,7 +265,7 @@ def conv_params(
 def conv_pool_slots(p: L.ConvParams) -> int | None:
     """Slots per image of ``pool_sums`` for this descriptor (``rsa_conv_pool_slots``), or None when the pooling epilogue is not compiled
     for it -- the caller then computes the mean some other way (``rsa_channel_gate``)."""
-    rc = int(L.load().rsa_conv_pool_slots(C.byref(p)))
+    rc = int(L.load().rsa_conv_pool_slots(p))
     if rc == L.E_UNSUPPORTED:
         return None
     if rc < 0:
@@ -291,28 +293,16 @@ def nchw_to_planes(x: torch.Tensor, out: Planes, mean: torch.Tensor | None = Non
     r = unshuffle
     if out.n != n or out.h * r < h or out.w * r < w or out.planes < (c * r * r + 7) // 8:
         raise ValueError('output planes do not match the input tensor')
-    lib = L.load()
-    L.check(
-        lib.rsa_nchw_to_planes(
-            x.data_ptr(), rsa_dtype(x.dtype), n, c, out.h, out.w, h, w, r, None if mean is None else mean.data_ptr(), scale,
-            out.hi_ptr(), out.lo_ptr() if out.has_lo(0, (c * r * r + 7) // 8) else None, out.plane_stride, out.batch_stride, out.fmt,
-            C.c_void_p(current_stream_ptr(x.device)),
-        ),
-        'rsa_nchw_to_planes',
-    )  # fmt: skip
+    lo = out.lo_ptr() if out.has_lo(0, (c * r * r + 7) // 8) else None  # (lo halves only where every written plane carries them)
+    call('rsa_nchw_to_planes', x.device, x=x, dtype=rsa_dtype(x.dtype), batch=n, C=c, H=out.h, W=out.w, src_h=h, src_w=w, unshuffle=r, mean=mean,
+         scale=scale, out=out, out_lo=lo, out_fmt=out.fmt)  # fmt: skip
 
 
 def planes_to_nchw(p: Planes, channels: int) -> torch.Tensor:
     """Split planes -> f32 [N,C,H,W] on the GPU (rsa_planes_to_nchw); for parity checks of intermediates."""
     out = torch.empty((p.n, channels, p.h, p.w), dtype=torch.float32, device=p.hi.device)
-    lib = L.load()
-    L.check(
-        lib.rsa_planes_to_nchw(
-            p.hi_ptr(), p.lo_ptr() if p.has_lo(0, (channels + 7) // 8) else None, p.plane_stride, p.batch_stride, p.n, channels, p.h, p.w, p.fmt,
-            out.data_ptr(), C.c_void_p(current_stream_ptr(out.device)),
-        ),
-        'rsa_planes_to_nchw',
-    )  # fmt: skip
+    call('rsa_planes_to_nchw', out.device, hi=p.hi_ptr(), lo=p.lo_ptr() if p.has_lo(0, (channels + 7) // 8) else None, plane_stride=p.plane_stride,
+         batch_stride=p.batch_stride, batch=p.n, C=channels, H=p.h, W=p.w, fmt=p.fmt, out=out)  # fmt: skip
     return out
 
 
@@ -326,8 +316,7 @@ def image_u8_to_nchw(img: torch.Tensor, dtype: torch.dtype = torch.float32) -> t
     img = img.contiguous()
     n, h, w, c = img.shape
     out = torch.empty((n, c, h, w), dtype=dtype, device=img.device)
-    L.check(L.load().rsa_image_u8_to_nchw(img.data_ptr(), n, h, w, c, out.data_ptr(), rsa_dtype(dtype), C.c_void_p(current_stream_ptr(img.device))),
-            'rsa_image_u8_to_nchw')  # fmt: skip
+    call('rsa_image_u8_to_nchw', img.device, img=img, batch=n, H=h, W=w, C=c, out=out, dtype=rsa_dtype(dtype))
     return out
 
 
@@ -339,6 +328,5 @@ def nchw_to_image_u8(x: torch.Tensor) -> torch.Tensor:
     x = x.contiguous()
     n, c, h, w = x.shape
     out = torch.empty((n, h, w, c), dtype=torch.uint8, device=x.device)
-    L.check(L.load().rsa_nchw_to_image_u8(x.data_ptr(), rsa_dtype(x.dtype), n, c, h, w, out.data_ptr(), C.c_void_p(current_stream_ptr(x.device))),
-            'rsa_nchw_to_image_u8')  # fmt: skip
+    call('rsa_nchw_to_image_u8', x.device, x=x, dtype=rsa_dtype(x.dtype), batch=n, C=c, H=h, W=w, img=out)
     return out

@@ -4,8 +4,6 @@ nothing here runs in ``forward``."""
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn.functional as F
 
@@ -108,10 +106,14 @@ def group_norm_workspace(n: int, h: int, w: int, groups: int, device) -> torch.T
     return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
 
 
-def group_norm_stats(x_f32: torch.Tensor, C_: int, groups: int, workspace: torch.Tensor, stats: torch.Tensor, stream: int, eps: float = GN_EPS) -> None:
+def group_norm_stats_args(x_f32: torch.Tensor, C_: int, groups: int, workspace: torch.Tensor, stats: torch.Tensor, eps: float = GN_EPS) -> dict:
+    """The keyword arguments of ``rsa_group_norm_stats`` (for ``Plan.launch`` / ``lib.call``)."""
     n, _, h, w, _ = x_f32.shape
-    L.check(L.load().rsa_group_norm_stats(x_f32.data_ptr(), n, h, w, C_, groups, eps, workspace.data_ptr(), stats.data_ptr(), C.c_void_p(stream)),
-            'rsa_group_norm_stats')  # fmt: skip
+    return dict(x_f32=x_f32, batch=n, H=h, W=w, C=C_, groups=groups, eps=eps, workspace=workspace, stats=stats)
+
+
+def group_norm_stats(x_f32: torch.Tensor, C_: int, groups: int, workspace: torch.Tensor, stats: torch.Tensor, stream: int, eps: float = GN_EPS) -> None:
+    L.call('rsa_group_norm_stats', stream, **group_norm_stats_args(x_f32, C_, groups, workspace, stats, eps))
 
 
 def group_norm_apply_params(x_f32: torch.Tensor, C_: int, groups: int, stats: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,

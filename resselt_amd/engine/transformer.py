@@ -416,13 +416,8 @@ def dwconv3x3(plan, weights, src, src_plane0, planes, out, out_plane0=0, act=L.A
 
 def plane_stats(plan, src, plane0, channels, stats) -> None:
     """Per-pixel LayerNorm statistics (eps 1e-5) of ``channels`` channels of ``src`` from ``plane0`` into ``stats`` [N, H*W, 2]."""
-
-    def run():
-        L.check(L.load().rsa_plane_stats_fmt(src.hi_ptr(plane0), src.lo_ptr(plane0), src.plane_stride, src.batch_stride, src.n, src.h, src.w,
-                                             channels, 1e-5, src.fmt, stats.data_ptr(), C.c_void_p(ops.current_stream_ptr(plan.device))), 'rsa_plane_stats')  # fmt: skip
-
-    plan.call(run)
-    plan.count_launches(1)
+    plan.launch('rsa_plane_stats_fmt', dict(in_hi=src.hi_ptr(plane0), in_lo=src.lo_ptr(plane0), plane_stride=src.plane_stride, batch_stride=src.batch_stride,
+                                            batch=src.n, H=src.h, W=src.w, C=channels, eps=1e-5, fmt=src.fmt, stats=stats))  # fmt: skip
 
 
 MLP_MAX_C, MLP_MAX_HIDDEN = 256, 512  # limits of rsa_swin_mlp_block (include/resselt_amd.h)

@@ -1,8 +1,10 @@
 """The output / input contract of ``Plan`` on the host: hand-filled descriptors over CPU tensors, with the library's launchers replaced by
-recorders of the pointers they would pass (no library, no GPU)."""
+recorders of the pointers they would pass (no library, no GPU); and, on the GPU, one positional launch whose pointer arguments follow the
+output and the input like descriptor fields."""
 
 import weakref
 
+import pytest
 import torch
 
 from resselt_amd.engine import lib as L
@@ -87,3 +89,37 @@ def test_plan_crops_u8_nhwc_rows_and_columns(monkeypatch):
     plan.run()
     out = plan.take_output()
     assert out.shape == (1, 9, 11, 3) and out.data_ptr() == y.data_ptr()
+
+
+@pytest.mark.gpu
+def test_positional_launch_follows_the_output_and_the_input(device):
+    """``rsa_scale_add`` (out += gamma[c] * res on f32 NCHW4c maps) of a 1x4x8x8 map, with ``out`` the plan's output and ``res`` the caller's
+    input: its argument list is resolved once, when the step is built, and the two pointers are re-pointed per forward.  Small integers times
+    powers of two: every value is exact in f32, whether or not the kernel fuses the multiply-add."""
+    shape = (1, 1, 8, 8, 4)
+    plan = Plan(device)
+    gamma = torch.tensor([0.5, 2.0, -1.0, 4.0], device=device)
+    y0 = plan.output(shape, torch.float32)
+    x0 = plan.input_ref(shape, torch.float32)
+    plan.call(lambda: plan.current_output().fill_(3.0))
+    plan.launch('rsa_scale_add', dict(res=x0, gamma=gamma, out=y0, batch=1, H=8, W=8, C=4))
+    plan.flush()
+    y0_ptr = y0.data_ptr()
+    assert plan.n_launches() == 1
+    del y0
+
+    def forward(x):
+        plan.feed(x)
+        plan.run()
+        return plan.take_output()
+
+    g = torch.Generator().manual_seed(3)
+    x1, x2 = (torch.randint(-64, 64, shape, generator=g).float().to(device) for _ in range(2))
+    y1 = forward(x1)
+    y1_copy = y1.clone()
+    y2 = forward(x2)
+    torch.cuda.synchronize()
+    assert y1.data_ptr() == y0_ptr and y2.data_ptr() != y1.data_ptr()  # the placeholder first, then a fresh tensor
+    assert torch.equal(y2, 3.0 + x2 * gamma) and not torch.equal(y2, y1)
+    assert torch.equal(y1, y1_copy) and torch.equal(y1, 3.0 + x1 * gamma)  # the first result is left alone
+    L.check_status('positional launch')

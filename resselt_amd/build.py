@@ -66,6 +66,16 @@ def _unit_hash(src: str) -> str:
     return h.hexdigest()
 
 
+def compile_command(hipcc: str, src: str, out: str, csrc: str = CSRC, include: str = os.path.join(ROOT, 'include')) -> list[str]:
+    """The hipcc line of one translation unit (tools/device_asm_diff.py compiles with the same flags)."""
+    cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', '-I' + include, '-I' + csrc, src, '-o', out]
+    if os.path.basename(src).startswith('conv_inst_ring'):
+        # SLP vectorisation packs the epilogue's f32 adds / multiplies into v_pk_* instructions, which are slower beside MFMAs
+        # (MI355X guide, 'price of one filler beside MFMAs'; measured +0.4..2 % per layer: profiles/r02_i_*)
+        cmd.insert(3, '-fno-slp-vectorize')
+    return cmd
+
+
 def _compile(args) -> str:
     hipcc, src, obj, verbose = args
     want = _unit_hash(src)
@@ -74,11 +84,7 @@ def _compile(args) -> str:
         with open(stamp) as fh:
             if fh.read().strip() == want:
                 return obj  # this unit and everything it includes are unchanged
-    cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, src, '-o', obj]
-    if os.path.basename(src).startswith('conv_inst_ring'):
-        # SLP vectorisation packs the epilogue's f32 adds / multiplies into v_pk_* instructions, which are slower beside MFMAs
-        # (MI355X guide, 'price of one filler beside MFMAs'; measured +0.4..2 % per layer: profiles/r02_i_*)
-        cmd.insert(3, '-fno-slp-vectorize')
+    cmd = compile_command(hipcc, src, obj)
     if verbose:
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)

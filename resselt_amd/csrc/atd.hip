@@ -11,28 +11,11 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ f32x16 mfma32(const bf16x8 a, const bf16x8 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)v[j];
-  return r;
-}
-
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
 constexpr int ATD_MAX_C = 256, ATD_MAX_M = 128, ATD_MAX_RC = 16;
 
@@ -215,12 +198,12 @@ __global__ __launch_bounds__(256) void atd_ca_kernel(const rsa_atd_ca_params p) 
   bf16x8 ph[MS], pl[MS];
 #pragma unroll
   for (int s = 0; s < MS; ++s) {
-    ph[s] = pack8(pr[s]);
+    ph[s] = pack16<RSA_PF_BF16>(pr[s]);
     if (PROD == 3) {
       float r8[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) r8[j] = pr[s][j] - (float)ph[s][j];
-      pl[s] = pack8(r8);
+      pl[s] = pack16<RSA_PF_BF16>(r8);
     }
   }
   const __bf16* vth = (const __bf16*)p.vt_hi + (int64_t)n * Cp * 128;
@@ -236,10 +219,10 @@ __global__ __launch_bounds__(256) void atd_ca_kernel(const rsa_atd_ca_params p) 
       const bf16x8 vh = *(const bf16x8*)(vth + row + 16 * s);
       if (PROD == 3) {
         const bf16x8 vl = *(const bf16x8*)(vtl + row + 16 * s);
-        acc = mfma32(vl, ph[s], acc);
-        acc = mfma32(vh, pl[s], acc);
+        acc = mfma32<RSA_PF_BF16>(vl, ph[s], acc);
+        acc = mfma32<RSA_PF_BF16>(vh, pl[s], acc);
       }
-      acc = mfma32(vh, ph[s], acc);
+      acc = mfma32<RSA_PF_BF16>(vh, ph[s], acc);
     }
     if (valid) {
 #pragma unroll
@@ -481,10 +464,10 @@ __global__ __launch_bounds__(256) void atd_attention_kernel(const rsa_atd_attn_p
           const bf16x8 kh = *(const bf16x8*)&s_k[0][off];
           if (PROD == 3) {
             const bf16x8 kl = *(const bf16x8*)&s_k[NHL - 1][off];
-            a = mfma32(kl, qh[qi][s], a);
-            a = mfma32(kh, ql[qi][s], a);
+            a = mfma32<RSA_PF_BF16>(kl, qh[qi][s], a);
+            a = mfma32<RSA_PF_BF16>(kh, ql[qi][s], a);
           }
-          a = mfma32(kh, qh[qi][s], a);
+          a = mfma32<RSA_PF_BF16>(kh, qh[qi][s], a);
         }
         const int kbase = 32 * (kt0 + kt);
         float tm = -3.0e38f;
@@ -521,12 +504,12 @@ __global__ __launch_bounds__(256) void atd_attention_kernel(const rsa_atd_attn_p
           float e8[8], r8[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) e8[j] = a[8 * s + j];
-          const bf16x8 ph = pack8(e8);
+          const bf16x8 ph = pack16<RSA_PF_BF16>(e8);
           bf16x8 pl8 = zero8;
           if (PROD == 3) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) r8[j] = e8[j] - (float)ph[j];
-            pl8 = pack8(r8);
+            pl8 = pack16<RSA_PF_BF16>(r8);
           }
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
@@ -545,10 +528,10 @@ __global__ __launch_bounds__(256) void atd_attention_kernel(const rsa_atd_attn_p
               }
             }
             if (PROD == 3) {
-              ot[qi][dt] = mfma32(vl, ph, ot[qi][dt]);
-              ot[qi][dt] = mfma32(vh, pl8, ot[qi][dt]);
+              ot[qi][dt] = mfma32<RSA_PF_BF16>(vl, ph, ot[qi][dt]);
+              ot[qi][dt] = mfma32<RSA_PF_BF16>(vh, pl8, ot[qi][dt]);
             }
-            ot[qi][dt] = mfma32(vh, ph, ot[qi][dt]);
+            ot[qi][dt] = mfma32<RSA_PF_BF16>(vh, ph, ot[qi][dt]);
           }
         }
       }
@@ -800,8 +783,6 @@ __global__ __launch_bounds__(256) void atd_refine_finish_kernel(const rsa_atd_re
   *td = sg * *td + (1.f - sg) * (acc / se);
 }
 
-bool misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
 }  // namespace
 }  // namespace rsa
 
@@ -813,11 +794,10 @@ extern "C" int rsa_atd_dict(const rsa_atd_dict_params* p, void* stream) {
   if (p->C < 1 || p->C > ATD_MAX_C || p->m < 1 || p->m > ATD_MAX_M || p->rc < 1 || p->rc > ATD_MAX_RC)
     return set_error(RSA_E_UNSUPPORTED, "atd_dict: C in [1, 256], m in [1, 128], rc in [1, 16]");
   if (!p->td || !p->wk || !p->wv || !p->kn || !p->vt_hi || !p->vt_lo) return set_error(RSA_E_ARG, "atd_dict: null pointer");
-  if (misaligned(p->kn) || misaligned(p->vt_hi) || misaligned(p->vt_lo)) return set_error(RSA_E_ALIGN, "atd_dict: outputs must be 16-byte aligned");
+  if (misaligned16(p->kn) || misaligned16(p->vt_hi) || misaligned16(p->vt_lo)) return set_error(RSA_E_ALIGN, "atd_dict: outputs must be 16-byte aligned");
   const int Cp = (p->C + 31) & ~31;
   hipLaunchKernelGGL(atd_dict_kernel, dim3((unsigned)(Cp / 2 + 1), (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p, Cp);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "atd_dict: launch failed") : RSA_OK;
+  return launch_status("atd_dict: launch failed");
 }
 
 extern "C" int rsa_atd_ca(const rsa_atd_ca_params* p, void* stream) {
@@ -827,7 +807,7 @@ extern "C" int rsa_atd_ca(const rsa_atd_ca_params* p, void* stream) {
     return set_error(RSA_E_UNSUPPORTED, "atd_ca: C in [1, 256], m in [1, 128], rc in [1, 16]");
   if (p->products != 1 && p->products != 3) return set_error(RSA_E_UNSUPPORTED, "atd_ca: products must be 3 or 1");
   if (!p->xn || !p->wq || !p->kn || !p->scale || !p->vt_hi || !p->vt_lo || !p->out) return set_error(RSA_E_ARG, "atd_ca: null pointer");
-  if (misaligned(p->xn) || misaligned(p->kn) || misaligned(p->vt_hi) || misaligned(p->vt_lo) || misaligned(p->out) || misaligned(p->sim))
+  if (misaligned16(p->xn) || misaligned16(p->kn) || misaligned16(p->vt_hi) || misaligned16(p->vt_lo) || misaligned16(p->out) || misaligned16(p->sim))
     return set_error(RSA_E_ALIGN, "atd_ca: pointers must be 16-byte aligned");
   const int64_t blocks = ((int64_t)p->H * p->W + 127) / 128;
   if (blocks > 0x7fffffff || (int64_t)p->H * p->W > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "atd_ca: map too large");
@@ -844,8 +824,7 @@ extern "C" int rsa_atd_ca(const rsa_atd_ca_params* p, void* stream) {
     else
       hipLaunchKernelGGL((atd_ca_kernel<8, 1>), grid, dim3(256), 0, s, *p);
   }
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "atd_ca: launch failed") : RSA_OK;
+  return launch_status("atd_ca: launch failed");
 }
 
 extern "C" int64_t rsa_atd_sort_workspace_bytes(int32_t batch, int64_t n) {
@@ -863,8 +842,7 @@ extern "C" int rsa_atd_sort(const int32_t* ids, int32_t batch, int64_t n, int32_
   hipLaunchKernelGGL(atd_sort_hist_kernel, grid, dim3(256), 0, s, ids, n, (int32_t*)workspace);
   hipLaunchKernelGGL(atd_sort_scan_kernel, dim3((unsigned)batch), dim3(128), 0, s, (int32_t*)workspace, (int)chunks);
   hipLaunchKernelGGL(atd_sort_scatter_kernel, grid, dim3(256), 0, s, ids, n, (const int32_t*)workspace, perm, inv);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "atd_sort: launch failed") : RSA_OK;
+  return launch_status("atd_sort: launch failed");
 }
 
 extern "C" int rsa_atd_attention(const rsa_atd_attn_params* p, void* stream) {
@@ -891,7 +869,7 @@ extern "C" int rsa_atd_attention(const rsa_atd_attn_params* p, void* stream) {
   }
   if (groups > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "atd_attention: too many groups");
   if (!p->qkv_hi || !p->out_hi || (p->products == 3 && !p->qkv_lo)) return set_error(RSA_E_ARG, "atd_attention: null pointer");
-  if (misaligned(p->qkv_hi) || misaligned(p->qkv_lo) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->qkv_hi) || misaligned16(p->qkv_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "atd_attention: planes must be 16-byte aligned");
   if (p->qkv_plane_stride < n_tok || p->out_plane_stride < n_tok) return set_error(RSA_E_ARG, "atd_attention: a plane stride is smaller than the map");
   const int hp = (p->head_dim + 7) >> 3;
@@ -908,22 +886,20 @@ extern "C" int rsa_atd_attention(const rsa_atd_attn_params* p, void* stream) {
     else
       hipLaunchKernelGGL((atd_attention_kernel<4, 1>), grid, dim3(256), 0, s, *p, hp, G, n_tok);
   }
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "atd_attention: launch failed") : RSA_OK;
+  return launch_status("atd_attention: launch failed");
 }
 
 extern "C" int rsa_atd_dwconv(const rsa_atd_dwconv_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "atd_dwconv: null params");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->planes < 1 || p->planes > 65535) return set_error(RSA_E_ARG, "atd_dwconv: bad geometry");
   if (!p->in_hi || !p->weight || !p->bias || !p->out_hi) return set_error(RSA_E_ARG, "atd_dwconv: null pointer");
-  if (misaligned(p->in_hi) || misaligned(p->in_lo) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "atd_dwconv: planes must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   if (p->in_plane_stride < HW || p->out_plane_stride < HW) return set_error(RSA_E_ARG, "atd_dwconv: a plane stride is smaller than the map");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "atd_dwconv: map too large");
   hipLaunchKernelGGL(atd_dwconv_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)p->planes, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "atd_dwconv: launch failed") : RSA_OK;
+  return launch_status("atd_dwconv: launch failed");
 }
 
 extern "C" int64_t rsa_atd_refine_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t C, int32_t m) {
@@ -936,7 +912,7 @@ extern "C" int rsa_atd_refine(const rsa_atd_refine_params* p, void* stream) {
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || !(p->eps > 0.f)) return set_error(RSA_E_ARG, "atd_refine: bad geometry");
   if (p->C < 1 || p->C > ATD_MAX_C || p->m < 1 || p->m > ATD_MAX_M) return set_error(RSA_E_UNSUPPORTED, "atd_refine: C in [1, 256], m in [1, 128]");
   if (!p->sim || !p->x || !p->gamma || !p->beta || !p->sigma || !p->td || !p->workspace) return set_error(RSA_E_ARG, "atd_refine: null pointer");
-  if (misaligned(p->x) || misaligned(p->workspace)) return set_error(RSA_E_ALIGN, "atd_refine: x and workspace must be 16-byte aligned");
+  if (misaligned16(p->x) || misaligned16(p->workspace)) return set_error(RSA_E_ALIGN, "atd_refine: x and workspace must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   if (HW > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "atd_refine: map too large");
   const RfWs w = rf_layout(p->batch, HW, p->C);
@@ -953,6 +929,5 @@ extern "C" int rsa_atd_refine(const rsa_atd_refine_params* p, void* stream) {
                      pacc, pse, w.Cp);
   hipLaunchKernelGGL(atd_refine_finish_kernel, dim3((unsigned)p->m, (unsigned)p->batch), dim3(256), 0, s, *p, (const float*)pacc, (const float*)pse, w.chunks,
                      w.Cp);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "atd_refine: launch failed") : RSA_OK;
+  return launch_status("atd_refine: launch failed");
 }

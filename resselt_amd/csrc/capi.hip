@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
@@ -22,7 +23,6 @@ int set_error(int code, const char* msg) {
   return code;
 }
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 template <typename T>
 __device__ __forceinline__ float ld_as_float(const void* p, int64_t i) {
@@ -35,18 +35,6 @@ __device__ __forceinline__ float ld_as_float(const void* p, int64_t i) {
 // unshuffle = r > 1: torch.pixel_unshuffle(x, r) fused into the read: plane channel c*r*r + i*r + j at (y, x) comes from source
 // channel c at (y*r + i, x*r + j) (RRDBNet x2plus / x1 front end, archs/esrgan/arch.py:130-137); C is then the SOURCE channel count.
 typedef __attribute__((ext_vector_type(8))) uint16_t u16x8;
-__device__ __forceinline__ void split_elem(float v, int fmt, uint16_t& hi, uint16_t& lo) {  // (hi, lo) halves of plane format fmt
-  if (fmt == RSA_PF_F16) {
-    asm("" : "+v"(v));  // opaque: see conv_common.h, split2
-    const _Float16 h = (_Float16)v;
-    hi = __builtin_bit_cast(uint16_t, h);
-    lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
-  } else {
-    const __bf16 h = (__bf16)v;
-    hi = __builtin_bit_cast(uint16_t, h);
-    lo = __builtin_bit_cast(uint16_t, (__bf16)(v - (float)h));
-  }
-}
 
 __global__ void nchw_to_planes_kernel(const void* x, int dtype, int batch, int C, int H, int W, int srcH, int srcW, int unshuffle,
                                       const float* mean, float scale, void* out_hi, void* out_lo, int64_t plane_stride,
@@ -251,7 +239,7 @@ int rsa_debug_set_pair(int32_t mode) {
 
 int rsa_check_finite(const void* data, int32_t dtype, int64_t count, void* stream) {
   if (data == nullptr || count < 1) return rsa::set_error(RSA_E_ARG, "check_finite: bad argument");
-  if ((uintptr_t)data & 15) return rsa::set_error(RSA_E_ALIGN, "check_finite: data must be 16-byte aligned");
+  if (rsa::misaligned16(data)) return rsa::set_error(RSA_E_ALIGN, "check_finite: data must be 16-byte aligned");
   unsigned int* word = rsa::range_word();
   if (word == nullptr) return rsa::set_error(RSA_E_INTERNAL, "check_finite: no host-visible status word (pinned allocation failed)");
   const int64_t vecs = count / (dtype == RSA_F32 ? 4 : 8);
@@ -264,8 +252,7 @@ int rsa_check_finite(const void* data, int32_t dtype, int64_t count, void* strea
     hipLaunchKernelGGL(rsa::check_finite_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const __bf16*)data, count, word);
   else
     return rsa::set_error(RSA_E_ARG, "check_finite: dtype must be RSA_F32, RSA_F16 or RSA_BF16");
-  const int rc = (int)hipGetLastError();
-  return rc ? rsa::set_error(rc, "check_finite: launch failed") : RSA_OK;
+  return rsa::launch_status("check_finite: launch failed");
 }
 
 int rsa_conv_cout_tiles(int32_t cout) { return rsa::conv_nct(cout); }
@@ -309,7 +296,7 @@ int64_t rsa_packed_weight_bytes(int32_t cout, int32_t cin_planes, int32_t ksize,
 int rsa_nchw_to_planes(const void* x, int32_t dtype, int32_t batch, int32_t C, int32_t H, int32_t W, int32_t src_h, int32_t src_w,
                        int32_t unshuffle, const float* mean, float scale, void* out_hi, void* out_lo, int64_t out_plane_stride,
                        int64_t out_batch_stride, int32_t out_fmt, void* stream) {
-  if (out_fmt != RSA_PF_BF16 && out_fmt != RSA_PF_F16) return rsa::set_error(RSA_E_ARG, "nchw_to_planes: out_fmt must be an rsa_plane_fmt");
+  if (!rsa::plane_fmt_ok(out_fmt)) return rsa::set_error(RSA_E_ARG, "nchw_to_planes: out_fmt must be an rsa_plane_fmt");
   if (unshuffle < 1) return rsa::set_error(RSA_E_ARG, "nchw_to_planes: unshuffle must be >= 1");
   if (x == nullptr || out_hi == nullptr || batch < 1 || C < 1 || H < 1 || W < 1) return rsa::set_error(RSA_E_ARG, "nchw_to_planes: bad argument");
   {
@@ -318,23 +305,21 @@ int rsa_nchw_to_planes(const void* x, int32_t dtype, int32_t batch, int32_t C, i
       return rsa::set_error(RSA_E_ARG, "nchw_to_planes: source size must satisfy src <= plane size * unshuffle < 2*src (reflect padding)");
   }
   if (dtype < RSA_F32 || dtype > RSA_U8) return rsa::set_error(RSA_E_ARG, "nchw_to_planes: bad dtype");
-  if (((uintptr_t)out_hi | (uintptr_t)out_lo) & 15) return rsa::set_error(RSA_E_ALIGN, "nchw_to_planes: outputs must be 16-byte aligned");
+  if (rsa::misaligned16(out_hi) || rsa::misaligned16(out_lo)) return rsa::set_error(RSA_E_ALIGN, "nchw_to_planes: outputs must be 16-byte aligned");
   const int64_t total = (int64_t)batch * ((C * unshuffle * unshuffle + 7) / 8) * H * W;
   hipLaunchKernelGGL(rsa::nchw_to_planes_kernel, dim3(rsa::grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, dtype, batch, C, H, W,
                      src_h, src_w, unshuffle, mean, scale, out_hi, out_lo, out_plane_stride, out_batch_stride, out_fmt);
-  const int rc = (int)hipGetLastError();
-  return rc ? rsa::set_error(rc, "nchw_to_planes: launch failed") : RSA_OK;
+  return rsa::launch_status("nchw_to_planes: launch failed");
 }
 
 int rsa_planes_to_nchw(const void* hi, const void* lo, int64_t plane_stride, int64_t batch_stride, int32_t batch, int32_t C, int32_t H, int32_t W,
                        int32_t fmt, float* out, void* stream) {
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return rsa::set_error(RSA_E_ARG, "planes_to_nchw: fmt must be an rsa_plane_fmt");
+  if (!rsa::plane_fmt_ok(fmt)) return rsa::set_error(RSA_E_ARG, "planes_to_nchw: fmt must be an rsa_plane_fmt");
   if (hi == nullptr || out == nullptr || batch < 1 || C < 1 || H < 1 || W < 1) return rsa::set_error(RSA_E_ARG, "planes_to_nchw: bad argument");
   const int64_t total = (int64_t)batch * C * H * W;
   hipLaunchKernelGGL(rsa::planes_to_nchw_kernel, dim3(rsa::grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, hi, lo, plane_stride,
                      batch_stride, batch, C, H, W, fmt, out);
-  const int rc = (int)hipGetLastError();
-  return rc ? rsa::set_error(rc, "planes_to_nchw: launch failed") : RSA_OK;
+  return rsa::launch_status("planes_to_nchw: launch failed");
 }
 
 }  // extern "C"
@@ -344,8 +329,7 @@ int rsa_image_u8_to_nchw(const uint8_t* img, int32_t batch, int32_t H, int32_t W
   if (dtype < RSA_F32 || dtype > RSA_BF16) return rsa::set_error(RSA_E_ARG, "image_u8_to_nchw: bad dtype");
   hipLaunchKernelGGL(rsa::image_u8_to_nchw_kernel, dim3(rsa::grid_for((int64_t)batch * H * W, 256)), dim3(256), 0, (hipStream_t)stream, img, batch, H,
                      W, C, out, dtype);
-  const hipError_t rc = hipGetLastError();
-  return rc ? rsa::set_error(rc, "image_u8_to_nchw: launch failed") : RSA_OK;
+  return rsa::launch_status("image_u8_to_nchw: launch failed");
 }
 
 int rsa_nchw_to_image_u8(const void* x, int32_t dtype, int32_t batch, int32_t C, int32_t H, int32_t W, uint8_t* img, void* stream) {
@@ -353,6 +337,5 @@ int rsa_nchw_to_image_u8(const void* x, int32_t dtype, int32_t batch, int32_t C,
   if (dtype < RSA_F32 || dtype > RSA_BF16) return rsa::set_error(RSA_E_ARG, "nchw_to_image_u8: bad dtype");
   hipLaunchKernelGGL(rsa::nchw_to_image_u8_kernel, dim3(rsa::grid_for((int64_t)batch * H * W, 256)), dim3(256), 0, (hipStream_t)stream, x, dtype, batch,
                      C, H, W, img);
-  const hipError_t rc = hipGetLastError();
-  return rc ? rsa::set_error(rc, "nchw_to_image_u8: launch failed") : RSA_OK;
+  return rsa::launch_status("nchw_to_image_u8: launch failed");
 }

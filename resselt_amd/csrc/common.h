@@ -3,12 +3,32 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "resselt_amd.h"
 
 namespace rsa {
 
 // Records a message for rsa_last_error_string() (thread-local) and returns `code`.
 int set_error(int code, const char* msg);
+
+// What every entry point says about its operands and its launch
+inline bool misaligned16(const void* a) { return ((uintptr_t)a & 15) != 0; }
+inline bool plane_fmt_ok(int fmt) { return fmt == RSA_PF_BF16 || fmt == RSA_PF_F16; }
+// after a kernel launch: RSA_OK, or the launch error recorded under `msg` ("<entry point>: launch failed")
+inline int launch_status(const char* msg) {
+  const int rc = (int)hipGetLastError();
+  return rc ? set_error(rc, msg) : RSA_OK;
+}
+// Run-time plane format -> compile-time constant: f(std::integral_constant<int, FMT>{}), so a launch site names its kernel as
+// kernel<decltype(F)::value> and spells its argument list once.
+template <class F>
+inline void with_fmt(int fmt, F&& f) {
+  if (fmt == RSA_PF_F16)
+    f(std::integral_constant<int, RSA_PF_F16>{});
+  else
+    f(std::integral_constant<int, RSA_PF_BF16>{});
+}
 
 // conv_mfma.hip
 int conv_launch(const rsa_conv_params& p, hipStream_t stream);

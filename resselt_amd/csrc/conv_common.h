@@ -1,32 +1,16 @@
 // conv_common.h — pieces shared by the fused-convolution schedules (conv_mfma.hip, gemm_k1.hip):
-// vector types, activation functions, the bf16 hi/lo split and the tile epilogue.
+// activation functions, the 8-bit lo codes and the tile epilogue (vector types, MFMA wrappers and the hi / lo split: plane_unit.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;  // also the 128-bit container of an fp16 fragment (bit-cast at the MFMA)
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
 constexpr int NPL = 4;  // planes per K chunk (32 channels = one MFMA K)
-
-// D[16][16] += A[16][32] * B[32][16] on 16-bit fragments of plane format FMT (enum rsa_plane_fmt: 0 = bf16, 1 = fp16); same fragment
-// layout, same cycles
-template <int FMT>
-__device__ __forceinline__ f32x4 mfma16(const bf16x8 a, const bf16x8 b, const f32x4 c) {
-  if constexpr (FMT == RSA_PF_F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // Activation CLASS of an epilogue instantiation.  The epilogue is compiled once per class and selected by ONE wave-uniform
 // switch per tile: with a per-value runtime switch every one of the 64 value sites of the unrolled epilogue carried the inlined
@@ -97,8 +81,6 @@ __device__ __forceinline__ int act_class(int act) {
   }
 }
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
 // Workgroup barrier WITHOUT the vmcnt(0) drain that __syncthreads() carries: only this wave's LDS traffic is waited for, so
 // weight prefetches and epilogue stores stay in flight across it.  A wave whose LDS-DMA must have landed calls dma_wait() first.
 __device__ __forceinline__ void wg_barrier() {
@@ -108,53 +90,6 @@ __device__ __forceinline__ void wg_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// (a, b) -> packed 16-bit pair (RNE) of plane format FMT and the pair's rounding residuals, also packed
-template <int FMT = 0>
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  if constexpr (FMT == RSA_PF_F16) {
-    // The values are made opaque first: with a = x * y still visible, the compiler fuses the conversion of the residual into
-    // v_fma_mix*_f16 (x * y - hi rounded once from the exact product) while hi itself is v_cvt_pk_f16_f32 of the f32 product -- the two
-    // roundings of x * y can differ by an fp16 ulp, and hi + lo is then off by that ulp instead of being a 22-bit value (seen on the
-    // Mish / SiLU / gate epilogues: 2.4e-4 on single elements).
-    asm("" : "+v"(a), "+v"(b));
-    const f16x2 h = {(_Float16)a, (_Float16)b};
-    hi = __builtin_bit_cast(uint32_t, h);
-    const f16x2 l = {(_Float16)(a - (float)h[0]), (_Float16)(b - (float)h[1])};
-    lo = __builtin_bit_cast(uint32_t, l);
-  } else {
-    const bf16x2 h = {(__bf16)a, (__bf16)b};
-    hi = __builtin_bit_cast(uint32_t, h);
-    const float ra = a - __builtin_bit_cast(float, hi << 16);
-    const float rb = b - __builtin_bit_cast(float, hi & 0xffff0000u);
-    const bf16x2 l = {(__bf16)ra, (__bf16)rb};
-    lo = __builtin_bit_cast(uint32_t, l);
-  }
-}
-// runtime format (wave-uniform): the generic epilogue
-__device__ __forceinline__ void split2_rt(bool f16, float a, float b, uint32_t& hi, uint32_t& lo) {
-  if (f16)
-    split2<RSA_PF_F16>(a, b, hi, lo);
-  else
-    split2<RSA_PF_BF16>(a, b, hi, lo);
-}
-// four channels of a unit half: hi (+ lo) -> f32
-template <int FMT>
-__device__ __forceinline__ f32x4 widen4(uint2 h, uint2 l) {
-  if constexpr (FMT == RSA_PF_F16) {
-    const f16x2 h0 = __builtin_bit_cast(f16x2, h.x), h1 = __builtin_bit_cast(f16x2, h.y);
-    const f16x2 l0 = __builtin_bit_cast(f16x2, l.x), l1 = __builtin_bit_cast(f16x2, l.y);
-    return (f32x4){(float)h0[0] + (float)l0[0], (float)h0[1] + (float)l0[1], (float)h1[0] + (float)l1[0], (float)h1[1] + (float)l1[1]};
-  } else {
-    return (f32x4){__builtin_bit_cast(float, h.x << 16) + __builtin_bit_cast(float, l.x << 16),
-                   __builtin_bit_cast(float, h.x & 0xffff0000u) + __builtin_bit_cast(float, l.x & 0xffff0000u),
-                   __builtin_bit_cast(float, h.y << 16) + __builtin_bit_cast(float, l.y << 16),
-                   __builtin_bit_cast(float, h.y & 0xffff0000u) + __builtin_bit_cast(float, l.y & 0xffff0000u)};
-  }
-}
-
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // lo halves as 8-bit codes (rsa_conv_params.lo8_flags): four channels of a unit half = one dword.  The code of v = hi + lo is the distance
 // from f32(hi) to v counted in steps of 32 f32 ulps along the f32 bit patterns (sign-magnitude: both have the sign of v), a signed byte:
@@ -173,7 +108,6 @@ __device__ __forceinline__ f32x4 widen4_lo8(uint2 h, uint32_t l8) {  // fp16 hi 
   const f16x2 h0 = __builtin_bit_cast(f16x2, h.x), h1 = __builtin_bit_cast(f16x2, h.y);
   return (f32x4){lo8_decode<0>((float)h0[0], l8), lo8_decode<1>((float)h0[1], l8), lo8_decode<2>((float)h1[0], l8), lo8_decode<3>((float)h1[1], l8)};
 }
-typedef __attribute__((ext_vector_type(2))) short s16x2;
 // two values -> their codes in the low bytes of two int16 (saturating 32 -> 16 bit pack, then packed 16-bit arithmetic)
 __device__ __forceinline__ s16x2 lo8_encode2(float v0, float v1, uint32_t hi01) {
   const f16x2 h = __builtin_bit_cast(f16x2, hi01);

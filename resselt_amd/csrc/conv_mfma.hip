@@ -161,16 +161,16 @@ int conv_validate(const rsa_conv_params& p) {
   if ((p.res1_hi != nullptr || p.res2_hi != nullptr) && (p.res_plane_stride * 32 >= (int64_t)1 << 32 || (p.cout & 7)))
     return set_error(RSA_E_UNSUPPORTED, "conv: plane residuals need cout % 8 == 0 and planes below 128 Mpx");
   if (p.act < 0 || p.act > RSA_ACT_PRELU) return set_error(RSA_E_ARG, "conv: bad act");
-  if (p.act == RSA_ACT_PRELU && (p.act_vec == nullptr || ((uintptr_t)p.act_vec & 15))) return set_error(RSA_E_ARG, "conv: PReLU needs 16-byte aligned act_vec");
+  if (p.act == RSA_ACT_PRELU && (p.act_vec == nullptr || misaligned16(p.act_vec))) return set_error(RSA_E_ARG, "conv: PReLU needs 16-byte aligned act_vec");
   if (p.out_base != nullptr && p.out_nchw == nullptr) return set_error(RSA_E_ARG, "conv: out_base only applies to the out_nchw store");
-  if (((uintptr_t)p.in_hi | (uintptr_t)p.in_lo | (uintptr_t)p.w_packed | (uintptr_t)p.out_hi | (uintptr_t)p.out_lo | (uintptr_t)p.out_f32 |
-       (uintptr_t)p.res1 | (uintptr_t)p.res2 | (uintptr_t)p.res1_hi | (uintptr_t)p.res1_lo | (uintptr_t)p.res2_hi | (uintptr_t)p.res2_lo) & 15)
-    return set_error(RSA_E_ALIGN, "conv: pointers must be 16-byte aligned");
-  if (p.pixel_shuffle > 1 && ((uintptr_t)p.out_nchw & 15)) return set_error(RSA_E_ALIGN, "conv: out_nchw must be 16-byte aligned for a depth-to-space store (vector stores)");
+  const void* ptrs[] = {p.in_hi, p.in_lo, p.w_packed, p.out_hi, p.out_lo, p.out_f32, p.res1, p.res2, p.res1_hi, p.res1_lo, p.res2_hi, p.res2_lo};
+  for (const void* q : ptrs)
+    if (misaligned16(q)) return set_error(RSA_E_ALIGN, "conv: pointers must be 16-byte aligned");
+  if (p.pixel_shuffle > 1 && misaligned16(p.out_nchw)) return set_error(RSA_E_ALIGN, "conv: out_nchw must be 16-byte aligned for a depth-to-space store (vector stores)");
   if (p.in_plane_stride * 64 >= (int64_t)1 << 32) return set_error(RSA_E_UNSUPPORTED, "conv: input plane too large for a 4-plane buffer descriptor (>= 64 Mpx); band the image");
   if (p.out_plane_stride * 32 >= (int64_t)1 << 32 || (int64_t)p.H * p.W * 64 >= (int64_t)1 << 32)
     return set_error(RSA_E_UNSUPPORTED, "conv: output plane too large for 32-bit lane offsets; band the image");
-  if ((uintptr_t)p.bias & 15) return set_error(RSA_E_ALIGN, "conv: bias must be 16-byte aligned (and padded to a multiple of 16 floats)");
+  if (misaligned16(p.bias)) return set_error(RSA_E_ALIGN, "conv: bias must be 16-byte aligned (and padded to a multiple of 16 floats)");
   if (p.out_nchw != nullptr) {
     if (p.out_hi != nullptr || p.out_f32 != nullptr || p.res1 != nullptr || p.res2 != nullptr || p.res1_hi != nullptr || p.res2_hi != nullptr ||
         p.act == RSA_ACT_SPAB_GATE)
@@ -208,7 +208,7 @@ int conv_launch(const rsa_conv_params& p, hipStream_t stream) {
   if (p.pool_sums != nullptr) {  // channel pooling in the epilogue: its own instantiations (conv_inst_ringpool.hip), nothing else has it
     if (p.w_layout == RSA_WL_TAPS || p.w_layout == RSA_WL_UPPHASE || !conv_pool_eligible(p))
       return set_error(RSA_E_UNSUPPORTED, "conv: pool_sums is compiled for ring-schedule 3x3 layers with 48 / 64 output channels, linear epilogue, plane output");
-    if ((uintptr_t)p.pool_sums & 15) return set_error(RSA_E_ALIGN, "conv: pool_sums must be 16-byte aligned");
+    if (misaligned16(p.pool_sums)) return set_error(RSA_E_ALIGN, "conv: pool_sums must be 16-byte aligned");
     const int rc = conv_launch_pool(p, stream);
     return rc ? set_error(rc, "conv: pooling ring kernel launch failed") : RSA_OK;
   }

@@ -14,8 +14,6 @@
 
 namespace rsa {
 
-static bool cg_aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------------------------ deconv / conv_s2
 // Implicit GEMM on v_mfma_f32_16x16x32_{bf16,f16}: D[cout 16][cell 16] += A[cout][k 32] * B[k][cell], k = 4 units of 8 channels, a unit
 // being (tap, input plane) in tap-major order.  A "cell" is one output pixel of one phase: rsa_deconv's output pixel o = stride * q + r - pad
@@ -202,8 +200,8 @@ static int rs_validate(const rsa_resample_conv_params* p, bool trans, const char
   if (!p->in_hi || !p->w_packed || !p->bias || (!p->out_hi && !p->out_f32) || (p->products == 3 && !p->in_lo) || (p->res_lo && !p->res_hi) ||
       (p->out_lo && !p->out_hi))
     return set_error(RSA_E_ARG, "resample conv: null operand");
-  if (!cg_aligned16(p->in_hi) || !cg_aligned16(p->in_lo) || !cg_aligned16(p->w_packed) || !cg_aligned16(p->bias) || !cg_aligned16(p->out_hi) ||
-      !cg_aligned16(p->out_lo) || !cg_aligned16(p->out_f32) || !cg_aligned16(p->res_hi) || !cg_aligned16(p->res_lo))
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo) || misaligned16(p->w_packed) || misaligned16(p->bias) || misaligned16(p->out_hi) ||
+      misaligned16(p->out_lo) || misaligned16(p->out_f32) || misaligned16(p->res_hi) || misaligned16(p->res_lo))
     return set_error(RSA_E_ALIGN, "resample conv: operands must be 16-byte aligned");
   if (!((p->fmt == RSA_PF_BF16 && p->products == 3) || (p->fmt == RSA_PF_F16 && p->products == 1)))
     return set_error(RSA_E_UNSUPPORTED, "resample conv: compiled for bf16 planes with three products and fp16 planes with one product");
@@ -212,25 +210,6 @@ static int rs_validate(const rsa_resample_conv_params* p, bool trans, const char
 
 // ------------------------------------------------------------------------------------------------------------------ region SE
 constexpr int SE_ROWS_PER_CHUNK = 16;
-
-template <int FMT>
-__device__ __forceinline__ void cg_load_unit(const char* hi, const char* lo, int64_t byte_off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + byte_off);
-  const uint4 l = lo ? *(const uint4*)(lo + byte_off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
-template <int FMT>
-__device__ __forceinline__ void cg_store_unit(char* hi, char* lo, int64_t byte_off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + byte_off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + byte_off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // stage 1: grid (chunks, planes, batch); the 8 channel sums of one plane over SE_ROWS_PER_CHUNK window rows, a fixed-shape tree in LDS
 template <int FMT>
@@ -245,7 +224,7 @@ __global__ __launch_bounds__(256) void region_se_sum_kernel(const rsa_region_se_
   for (int64_t i = tid; i < npx; i += 256) {
     const int yy = r0 + (int)(i / p.w), xx = (int)(i % p.w);
     float v[8];
-    cg_load_unit<FMT>(hi, lo, ((int64_t)(p.y0 + yy) * p.W + p.x0 + xx) << 4, v);
+    load_unit<FMT>(hi, lo, ((int64_t)(p.y0 + yy) * p.W + p.x0 + xx) << 4, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] += v[j];
   }
@@ -294,11 +273,11 @@ __global__ __launch_bounds__(256) void region_se_apply_kernel(const rsa_region_s
   const int yy = (int)(i / p.w), xx = (int)(i % p.w);
   const int64_t off = ((int64_t)n * p.x_batch_stride + (int64_t)pl * p.x_plane_stride + (int64_t)(p.y0 + yy) * p.W + p.x0 + xx) << 4;
   float v[8];
-  cg_load_unit<FMT>((const char*)p.x_hi, (const char*)p.x_lo, off, v);
+  load_unit<FMT>((const char*)p.x_hi, (const char*)p.x_lo, off, v);
   const float* g = p.gate + (int64_t)n * 8 * p.planes + 8 * pl;
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] *= g[j];
-  cg_store_unit<FMT>((char*)p.x_hi, (char*)p.x_lo, off, v);
+  store_unit<FMT>((char*)p.x_hi, (char*)p.x_lo, off, v);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ input / output stages
@@ -342,7 +321,7 @@ __global__ __launch_bounds__(256) void cugan_input_kernel(const rsa_cugan_input_
         v[j] = cg_read(p.x, p.dtype, src) * p.in_scale + p.in_shift;
       }
     }
-    cg_store_unit<FMT>((char*)p.out_hi, (char*)p.out_lo, ((int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride + i) << 4, v);
+    store_unit<FMT>((char*)p.out_hi, (char*)p.out_lo, ((int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride + i) << 4, v);
   }
 }
 
@@ -421,30 +400,24 @@ extern "C" int rsa_region_se(const rsa_region_se_params* p, void* stream) {
     return set_error(RSA_E_ARG, "region_se: bad geometry (C = 8 planes <= 256, hidden <= 64)");
   if (p->h < 1 || p->w < 1 || p->y0 < 0 || p->x0 < 0 || p->x0 + p->w > p->W || p->x_plane_stride < (int64_t)(p->y0 + p->h) * p->W)
     return set_error(RSA_E_ARG, "region_se: the window leaves the planes");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "region_se: bad fmt");
-  if (!cg_aligned16(p->x_hi) || !cg_aligned16(p->x_lo)) return set_error(RSA_E_ALIGN, "region_se: planes must be 16-byte aligned");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "region_se: bad fmt");
+  if (misaligned16(p->x_hi) || misaligned16(p->x_lo)) return set_error(RSA_E_ALIGN, "region_se: planes must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int chunks = (p->h + SE_ROWS_PER_CHUNK - 1) / SE_ROWS_PER_CHUNK;
-  if (p->fmt == RSA_PF_F16)
-    region_se_sum_kernel<RSA_PF_F16><<<dim3(chunks, p->planes, p->batch), 256, 0, s>>>(*p, chunks);
-  else
-    region_se_sum_kernel<RSA_PF_BF16><<<dim3(chunks, p->planes, p->batch), 256, 0, s>>>(*p, chunks);
+  with_fmt(p->fmt, [&](auto F) { region_se_sum_kernel<decltype(F)::value><<<dim3(chunks, p->planes, p->batch), 256, 0, s>>>(*p, chunks); });
   int e = (int)hipGetLastError();
   if (e) return e;
   region_se_gate_kernel<<<p->batch, 256, 0, s>>>(*p, chunks);
   e = (int)hipGetLastError();
   if (e) return e;
   const dim3 grid((unsigned)(((int64_t)p->h * p->w + 255) / 256), p->planes, p->batch);
-  if (p->fmt == RSA_PF_F16)
-    region_se_apply_kernel<RSA_PF_F16><<<grid, 256, 0, s>>>(*p);
-  else
-    region_se_apply_kernel<RSA_PF_BF16><<<grid, 256, 0, s>>>(*p);
+  with_fmt(p->fmt, [&](auto F) { region_se_apply_kernel<decltype(F)::value><<<grid, 256, 0, s>>>(*p); });
   return (int)hipGetLastError();
 }
 
 extern "C" int rsa_cugan_input(const rsa_cugan_input_params* p, void* stream) {
   if (!p || !p->x || !p->out_hi) return set_error(RSA_E_ARG, "cugan_input: null operand");
-  if (p->dtype < RSA_F32 || p->dtype > RSA_U8 || (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) || p->reserved0 != 0)
+  if (p->dtype < RSA_F32 || p->dtype > RSA_U8 || !plane_fmt_ok(p->fmt) || p->reserved0 != 0)
     return set_error(RSA_E_ARG, "cugan_input: bad dtype / fmt");
   if (p->batch < 1 || p->C < 1 || p->h < 1 || p->w < 1 || (p->unshuffle != 1 && p->unshuffle != 2) || p->out_H < 1 || p->out_W < 1)
     return set_error(RSA_E_ARG, "cugan_input: bad geometry");
@@ -452,12 +425,9 @@ extern "C" int rsa_cugan_input(const rsa_cugan_input_params* p, void* stream) {
   if (p->pad_top < 0 || p->pad_left < 0 || pb < 0 || pr < 0 || p->pad_top >= p->h || pb >= p->h || p->pad_left >= p->w || pr >= p->w)
     return set_error(RSA_E_ARG, "cugan_input: reflect pads must be in [0, size)");
   if (p->C * r * r > 8 * 32 || p->out_plane_stride < (int64_t)p->out_H * p->out_W) return set_error(RSA_E_ARG, "cugan_input: bad planes");
-  if (!cg_aligned16(p->out_hi) || !cg_aligned16(p->out_lo)) return set_error(RSA_E_ALIGN, "cugan_input: planes must be 16-byte aligned");
+  if (misaligned16(p->out_hi) || misaligned16(p->out_lo)) return set_error(RSA_E_ALIGN, "cugan_input: planes must be 16-byte aligned");
   const dim3 grid((unsigned)(((int64_t)p->out_H * p->out_W + 255) / 256), p->batch);
-  if (p->fmt == RSA_PF_F16)
-    cugan_input_kernel<RSA_PF_F16><<<grid, 256, 0, (hipStream_t)stream>>>(*p);
-  else
-    cugan_input_kernel<RSA_PF_BF16><<<grid, 256, 0, (hipStream_t)stream>>>(*p);
+  with_fmt(p->fmt, [&](auto F) { cugan_input_kernel<decltype(F)::value><<<grid, 256, 0, (hipStream_t)stream>>>(*p); });
   return (int)hipGetLastError();
 }
 
@@ -470,7 +440,7 @@ extern "C" int rsa_cugan_output(const rsa_cugan_output_params* p, void* stream) 
   if (p->y0 + (p->out_h + r - 1) / r > p->map_H || p->x0 + (p->out_w + r - 1) / r > p->map_W) return set_error(RSA_E_ARG, "cugan_output: the crop leaves the map");
   if (p->base && (p->base_div < 1 || (p->out_h - 1) / p->base_div >= p->base_h || (p->out_w - 1) / p->base_div >= p->base_w))
     return set_error(RSA_E_ARG, "cugan_output: the base image does not cover the output");
-  if (!cg_aligned16(p->map)) return set_error(RSA_E_ALIGN, "cugan_output: the map must be 16-byte aligned");
+  if (misaligned16(p->map)) return set_error(RSA_E_ALIGN, "cugan_output: the map must be 16-byte aligned");
   const dim3 grid((unsigned)(((int64_t)p->out_h * p->out_w + 255) / 256), p->batch);
   cugan_output_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(*p);
   return (int)hipGetLastError();

@@ -14,24 +14,19 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-
 // one 16-byte unit (8 channels of a pixel) of planes in format fmt (enum rsa_plane_fmt, wave-uniform) -> f32: hi (+ lo where the buffer has it)
+// Not plane_unit.h's get_unit: without a lo plane this form adds nothing (get_unit adds 0.f), and the kernels' code differs
 __device__ __forceinline__ void unit_f32(const bf16x8* hi, const bf16x8* lo, int64_t u, float (&v)[8], int fmt = RSA_PF_BF16) {
   const bf16x8 h = hi[u];
   if (fmt == RSA_PF_F16) {
-    const f16x8_t hf = __builtin_bit_cast(f16x8_t, h);
+    const f16x8 hf = __builtin_bit_cast(f16x8, h);
     if (lo != nullptr) {
-      const f16x8_t lf = __builtin_bit_cast(f16x8_t, lo[u]);
+      const f16x8 lf = __builtin_bit_cast(f16x8, lo[u]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = (float)hf[j] + (float)lf[j];
     } else {
@@ -53,7 +48,7 @@ __device__ __forceinline__ void unit_f32(const bf16x8* hi, const bf16x8* lo, int
 // a raw 16-byte unit already in registers -> f32 (the loads issued earlier, several at a time)
 __device__ __forceinline__ void raw_f32(const bf16x8 h, const bf16x8 l, bool has_lo, float (&v)[8], int fmt) {
   if (fmt == RSA_PF_F16) {
-    const f16x8_t hf = __builtin_bit_cast(f16x8_t, h), lf = __builtin_bit_cast(f16x8_t, l);
+    const f16x8 hf = __builtin_bit_cast(f16x8, h), lf = __builtin_bit_cast(f16x8, l);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = has_lo ? (float)hf[j] + (float)lf[j] : (float)hf[j];
   } else {
@@ -62,90 +57,10 @@ __device__ __forceinline__ void raw_f32(const bf16x8 h, const bf16x8 l, bool has
   }
 }
 
-__device__ __forceinline__ void store_unit(bf16x8* hi, bf16x8* lo, int64_t u, const float (&v)[8], int fmt = RSA_PF_BF16) {
-  if (fmt == RSA_PF_F16) {
-    f16x8_t h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float vj = v[j];
-      asm("" : "+v"(vj));  // opaque: see conv_common.h, split2
-      const _Float16 hb = (_Float16)vj;
-      h[j] = hb;
-      l[j] = (_Float16)(vj - (float)hb);
-    }
-    hi[u] = __builtin_bit_cast(bf16x8, h);
-    if (lo != nullptr) lo[u] = __builtin_bit_cast(bf16x8, l);
-    return;
-  }
-  bf16x8 h, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 hb = (__bf16)v[j];
-    h[j] = hb;
-    l[j] = (__bf16)(v[j] - (float)hb);
-  }
-  hi[u] = h;
-  if (lo != nullptr) lo[u] = l;
-}
-
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-__device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
-
 // ------------------------------------------------------------------------------------------------ rectangular window attention
-__device__ __forceinline__ bf16x8 pack_bf16(const float (&v)[8]) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)v[j];
-  return r;
-}
-
 // One-product fp16 form (round 3, FMT = RSA_PF_F16): q / k / v planes and the output planes hold fp16 values, the contractions run on
 // v_mfma_f32_32x32x16_f16.  The 16-byte units, the LDS images and the transpose reads are format-agnostic (16-bit elements); what
-// changes is the matrix instruction, how the probabilities are packed and how the output is rounded.
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-template <int FMT>
-__device__ __forceinline__ f32x16 mfma32(const bf16x8 a, const bf16x8 b, const f32x16 c) {
-  if constexpr (FMT == RSA_PF_F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-template <int FMT>
-__device__ __forceinline__ bf16x8 pack16(const float (&v)[8]) {
-  if constexpr (FMT == RSA_PF_F16) {
-    f16x8_t h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
-    return __builtin_bit_cast(bf16x8, h);
-  } else {
-    return pack_bf16(v);
-  }
-}
-// four output values -> the 8-byte half of a plane unit (hi, and the rounding residual for a lo plane)
-template <int FMT>
-__device__ __forceinline__ void round4(const float (&v)[4], bf16x4& h, bf16x4& lo4) {
-  if constexpr (FMT == RSA_PF_F16) {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
-    f16x4_t hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float ve = v[e];
-      asm("" : "+v"(ve));  // opaque: keeps the conversion of the residual from being fused with the arithmetic that made v (conv_common.h, split2)
-      hh[e] = (_Float16)ve;
-      ll[e] = (_Float16)(ve - (float)hh[e]);
-    }
-    h = __builtin_bit_cast(bf16x4, hh);
-    lo4 = __builtin_bit_cast(bf16x4, ll);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const __bf16 hb = (__bf16)v[e];
-      h[e] = hb;
-      lo4[e] = (__bf16)(v[e] - (float)hb);
-    }
-  }
-}
-
+// changes is the matrix instruction, how the probabilities are packed and how the output is rounded (plane_unit.h: mfma32, pack16, round4).
 // One workgroup (4 waves) = one (window, head).  T = tiles of 32 tokens the LDS images hold.
 //   self mode  (kwin == 0): keys = the window's own tokens (<= 32*T), staged once;
 //   cross mode (kwin > 0) : keys = the (kwin_h x kwin_w) window that starts kpad pixels up-left of the query window (HAT's
@@ -353,7 +268,7 @@ __global__ __launch_bounds__(256, 2) void rect_attention_kernel(const rsa_rect_a
           if (PROD == 3) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) r8[j] = e8[j] - (float)ph[j];
-            const bf16x8 pl = pack_bf16(r8);
+            const bf16x8 pl = pack16<RSA_PF_BF16>(r8);
             ot[qi] = mfma32<FMT>(vl, ph, ot[qi]);
             ot[qi] = mfma32<FMT>(vh, pl, ot[qi]);
           }
@@ -561,7 +476,7 @@ __global__ __launch_bounds__(512, 1) void rect_attention_wide_kernel(const rsa_r
         if (PROD == 3) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) r8[j] = e8[j] - (float)ph[j];
-          pl8 = pack_bf16(r8);
+          pl8 = pack16<RSA_PF_BF16>(r8);
         }
 #pragma unroll
         for (int c = 0; c < DC; ++c) {
@@ -779,11 +694,11 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const rsa_dwconv_params p) 
     for (int t = 0; t < KS; ++t) {
       float v[8];
       if (p.fmt == RSA_PF_F16) {
-        const f16x8_t hf = __builtin_bit_cast(f16x8_t, rh[t]);
+        const f16x8 hf = __builtin_bit_cast(f16x8, rh[t]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (float)hf[j];
         if (has_lo) {
-          const f16x8_t lf = __builtin_bit_cast(f16x8_t, rl[t]);
+          const f16x8 lf = __builtin_bit_cast(f16x8, rl[t]);
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] += (float)lf[j];
         }
@@ -822,7 +737,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const rsa_dwconv_params p) 
   }
   bf16x8* o_hi = (bf16x8*)p.out_hi + (int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride;
   bf16x8* o_lo = p.out_lo ? (bf16x8*)p.out_lo + (int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride : nullptr;
-  store_unit(o_hi, o_lo, pix, acc, p.fmt);
+  put_unit(o_hi, o_lo, pix, acc, p.fmt);
 }
 
 // ------------------------------------------------------------------------------------------------ per-pixel LN statistics
@@ -932,13 +847,13 @@ __global__ __launch_bounds__(256) void channel_gate_kernel(const rsa_channel_gat
     const int k = threadIdx.x;
     float s = p.b1[k];
     for (int c = 0; c < C; ++c) s += p.w1[(int64_t)k * C + c] * s_mean[c];
-    s_hid[k] = p.relu == 3 ? s * sigmoidf(s) : p.relu ? fmaxf(s, 0.f) : gelu_erf(s);
+    s_hid[k] = p.relu == 3 ? s * sigmoid_exact(s) : p.relu ? fmaxf(s, 0.f) : gelu_erf(s);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {
     float s = p.b2[c];
     for (int k = 0; k < p.hidden; ++k) s += p.w2[(int64_t)c * p.hidden + k] * s_hid[k];
-    p.gate[(int64_t)n * C + c] = p.relu == 2 ? fminf(fmaxf(s * (1.f / 6.f) + 0.5f, 0.f), 1.f) : sigmoidf(s);
+    p.gate[(int64_t)n * C + c] = p.relu == 2 ? fminf(fmaxf(s * (1.f / 6.f) + 0.5f, 0.f), 1.f) : sigmoid_exact(s);
   }
 }
 
@@ -976,7 +891,7 @@ __global__ __launch_bounds__(256) void aim_kernel(const rsa_aim_params p) {
 #pragma unroll
   for (int k = 0; k < 16; ++k)
     if (k < p.hidden) s += p.w2[k] * gelu_erf(h[k] + p.b1[k]);
-  const float sg = sigmoidf(s);
+  const float sg = sigmoid_exact(s);
   const float* gate = p.gate + (int64_t)n * C;
   bf16x8* o_hi = (bf16x8*)p.out_hi + (int64_t)n * p.out_batch_stride;
   bf16x8* o_lo = p.out_lo ? (bf16x8*)p.out_lo + (int64_t)n * p.out_batch_stride : nullptr;
@@ -989,7 +904,7 @@ __global__ __launch_bounds__(256) void aim_kernel(const rsa_aim_params p) {
       const float g = gate[pl * 8 + j];
       o[j] = p.mode == 0 ? a[j] * g + sg * c[j] : a[j] * sg + c[j] * g;
     }
-    store_unit(o_hi, o_lo, pl * p.out_plane_stride + pix, o, p.fmt);
+    put_unit(o_hi, o_lo, pl * p.out_plane_stride + pix, o, p.fmt);
   }
 }
 
@@ -1019,8 +934,6 @@ __global__ __launch_bounds__(256) void gated_add_kernel(const bf16x8* x_hi, cons
   }
 }
 
-static bool misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
 }  // namespace rsa
 
 using namespace rsa;
@@ -1035,10 +948,10 @@ extern "C" int rsa_rect_attention(const rsa_rect_attn_params* p, void* stream) {
   if (p->shift_h < 0 || p->shift_h >= p->win_h || p->shift_w < 0 || p->shift_w >= p->win_w || ((p->shift_h == 0) != (p->shift_w == 0)))
     return set_error(RSA_E_ARG, "rect_attention: shifts must both be 0 or both be in (0, window)");
   if (p->products != 1 && p->products != 3) return set_error(RSA_E_UNSUPPORTED, "rect_attention: products must be 1 or 3");
-  if ((p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) || p->reserved0 != 0 || (p->fmt == RSA_PF_F16 && p->products != 1))
+  if (!plane_fmt_ok(p->fmt) || p->reserved0 != 0 || (p->fmt == RSA_PF_F16 && p->products != 1))
     return set_error(RSA_E_ARG, "rect_attention: fmt must be an rsa_plane_fmt (fp16 planes: the one-product form only)");
   if (!p->qkv_hi || !p->bias_frag || !p->out_hi || (p->products == 3 && !p->qkv_lo)) return set_error(RSA_E_ARG, "rect_attention: null pointer");
-  if (misaligned(p->qkv_hi) || misaligned(p->qkv_lo) || misaligned(p->bias_frag) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->qkv_hi) || misaligned16(p->qkv_lo) || misaligned16(p->bias_frag) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "rect_attention: pointers must be 16-byte aligned");
   const bool cross = p->kwin_h > 0 || p->kwin_w > 0;
   const int DCh = p->head_chunks < 1 ? 1 : p->head_chunks;
@@ -1067,8 +980,7 @@ extern "C" int rsa_rect_attention(const rsa_rect_attn_params* p, void* stream) {
       if (DCh == 2) RSA_RAW(1, 2); else if (DCh == 3) RSA_RAW(1, 3); else RSA_RAW(1, 4);
     }
 #undef RSA_RAW
-    const hipError_t rcw = hipGetLastError();
-    return rcw ? set_error(rcw, "rect_attention: launch failed") : RSA_OK;
+    return launch_status("rect_attention: launch failed");
   }
   const dim3 grid((unsigned)blocks), block(256);
 #define RSA_RA(PROD, TT) hipLaunchKernelGGL((rect_attention_kernel<PROD, TT>), grid, block, 0, s, *p)
@@ -1082,8 +994,7 @@ extern "C" int rsa_rect_attention(const rsa_rect_attn_params* p, void* stream) {
     if (T == 1) RSA_RA(1, 1); else if (T == 2) RSA_RA(1, 2); else if (T == 4) RSA_RA(1, 4); else RSA_RA(1, 8);
   }
 #undef RSA_RA
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "rect_attention: launch failed") : RSA_OK;
+  return launch_status("rect_attention: launch failed");
 }
 
 extern "C" int64_t rsa_channel_attn_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t heads) {
@@ -1094,30 +1005,29 @@ extern "C" int64_t rsa_channel_attn_workspace_bytes(int32_t batch, int32_t H, in
 
 extern "C" int rsa_channel_attention_weights(const rsa_channel_attn_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "channel_attention_weights: null params");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "channel_attention_weights: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "channel_attention_weights: fmt must be an rsa_plane_fmt");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->heads < 1 || p->head_dim < 1 || p->head_dim > 32)
     return set_error(RSA_E_ARG, "channel_attention_weights: bad geometry (head_dim must be 1..32)");
   if (p->products != 1 && p->products != 3) return set_error(RSA_E_UNSUPPORTED, "channel_attention_weights: products must be 1 or 3");
   if (!p->q_hi || !p->k_hi || !p->temperature || !p->workspace || !p->w_packed) return set_error(RSA_E_ARG, "channel_attention_weights: null pointer");
-  if (misaligned(p->q_hi) || misaligned(p->q_lo) || misaligned(p->k_hi) || misaligned(p->k_lo) || misaligned(p->workspace) || misaligned(p->w_packed))
+  if (misaligned16(p->q_hi) || misaligned16(p->q_lo) || misaligned16(p->k_hi) || misaligned16(p->k_lo) || misaligned16(p->workspace) || misaligned16(p->w_packed))
     return set_error(RSA_E_ALIGN, "channel_attention_weights: pointers must be 16-byte aligned");
   const int64_t chunks = ((int64_t)p->H * p->W + CA_TOK - 1) / CA_TOK;
   if (chunks > 65535 || p->heads > 65535 || p->batch > 65535) return set_error(RSA_E_UNSUPPORTED, "channel_attention_weights: map too large");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(channel_gram_kernel, dim3((unsigned)chunks, (unsigned)p->heads, (unsigned)p->batch), dim3(64), 0, s, *p, (int)chunks);
   hipLaunchKernelGGL(channel_attn_finish_kernel, dim3((unsigned)p->heads, (unsigned)p->batch), dim3(1024), 0, s, *p, (int)chunks);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "channel_attention_weights: launch failed") : RSA_OK;
+  return launch_status("channel_attention_weights: launch failed");
 }
 
 extern "C" int rsa_dwconv3x3(const rsa_dwconv_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "dwconv3x3: null params");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "dwconv3x3: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "dwconv3x3: fmt must be an rsa_plane_fmt");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->planes < 1 || p->planes > 65535 || p->batch > 65535) return set_error(RSA_E_ARG, "dwconv3x3: bad geometry");
   if (p->act != RSA_ACT_NONE && p->act != RSA_ACT_GELU) return set_error(RSA_E_UNSUPPORTED, "dwconv3x3: act must be none or gelu");
   if (!p->in_hi || !p->weight || !p->bias || !p->out_hi) return set_error(RSA_E_ARG, "dwconv3x3: null pointer");
   if (p->stats && (!p->gamma || !p->beta)) return set_error(RSA_E_ARG, "dwconv3x3: stats need gamma and beta");
-  if (misaligned(p->in_hi) || misaligned(p->in_lo) || misaligned(p->mul_hi) || misaligned(p->mul_lo) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo) || misaligned16(p->mul_hi) || misaligned16(p->mul_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "dwconv3x3: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   const int64_t tiles = (int64_t)((p->W + DW_TW - 1) / DW_TW) * ((p->H + DW_TH - 1) / DW_TH);
@@ -1132,36 +1042,33 @@ extern "C" int rsa_dwconv3x3(const rsa_dwconv_params* p, void* stream) {
     if (gelu) hipLaunchKernelGGL((dwconv_kernel<false, true, 3>), grid, block, 0, s, *p);
     else hipLaunchKernelGGL((dwconv_kernel<false, false, 3>), grid, block, 0, s, *p);
   }
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "dwconv3x3: launch failed") : RSA_OK;
+  return launch_status("dwconv3x3: launch failed");
 }
 
 extern "C" int rsa_dwconv5x5(const rsa_dwconv_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "dwconv5x5: null params");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "dwconv5x5: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "dwconv5x5: fmt must be an rsa_plane_fmt");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->planes < 1 || p->planes > 65535 || p->batch > 65535) return set_error(RSA_E_ARG, "dwconv5x5: bad geometry");
   if (p->act != RSA_ACT_NONE || p->stats != nullptr) return set_error(RSA_E_UNSUPPORTED, "dwconv5x5: no activation / normalisation variant is compiled");
   if (!p->in_hi || !p->weight || !p->bias || !p->out_hi) return set_error(RSA_E_ARG, "dwconv5x5: null pointer");
-  if (misaligned(p->in_hi) || misaligned(p->in_lo) || misaligned(p->mul_hi) || misaligned(p->mul_lo) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo) || misaligned16(p->mul_hi) || misaligned16(p->mul_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "dwconv5x5: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   const int64_t tiles = (int64_t)((p->W + DW_TW - 1) / DW_TW) * ((p->H + DW_TH - 1) / DW_TH);
   if (tiles > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "dwconv5x5: map too large");
   hipLaunchKernelGGL((dwconv_kernel<false, false, 5>), dim3((unsigned)tiles, (unsigned)p->planes, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "dwconv5x5: launch failed") : RSA_OK;
+  return launch_status("dwconv5x5: launch failed");
 }
 
 extern "C" int rsa_plane_stats_fmt(const void* in_hi, const void* in_lo, int64_t plane_stride, int64_t batch_stride, int32_t batch, int32_t H, int32_t W,
                                    int32_t C, float eps, int32_t fmt, float* stats, void* stream) {
   if (!in_hi || !stats || batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 1) return set_error(RSA_E_ARG, "plane_stats: bad argument");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "plane_stats: fmt must be an rsa_plane_fmt");
-  if (misaligned(in_hi) || misaligned(in_lo)) return set_error(RSA_E_ALIGN, "plane_stats: maps must be 16-byte aligned");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "plane_stats: fmt must be an rsa_plane_fmt");
+  if (misaligned16(in_hi) || misaligned16(in_lo)) return set_error(RSA_E_ALIGN, "plane_stats: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(plane_stats_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)in_hi,
                      (const bf16x8*)in_lo, plane_stride, batch_stride, HW, C, eps, stats, fmt);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "plane_stats: launch failed") : RSA_OK;
+  return launch_status("plane_stats: launch failed");
 }
 extern "C" int rsa_plane_stats(const void* in_hi, const void* in_lo, int64_t plane_stride, int64_t batch_stride, int32_t batch, int32_t H, int32_t W,
                                int32_t C, float eps, float* stats, void* stream) {
@@ -1176,43 +1083,40 @@ extern "C" int64_t rsa_channel_gate_workspace_bytes(int32_t batch, int32_t H, in
 
 extern "C" int rsa_channel_gate(const rsa_channel_gate_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "channel_gate: null params");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "channel_gate: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "channel_gate: fmt must be an rsa_plane_fmt");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->planes < 1 || p->planes > 64 || p->hidden < 1 || p->hidden > 128)
     return set_error(RSA_E_ARG, "channel_gate: bad geometry (planes <= 64, hidden <= 128)");
   if (p->relu < 0 || p->relu > 3) return set_error(RSA_E_ARG, "channel_gate: relu must be 0..3");
   if (!p->in_hi || !p->w1 || !p->b1 || !p->w2 || !p->b2 || !p->workspace || !p->gate) return set_error(RSA_E_ARG, "channel_gate: null pointer");
-  if (misaligned(p->in_hi) || misaligned(p->in_lo)) return set_error(RSA_E_ALIGN, "channel_gate: maps must be 16-byte aligned");
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo)) return set_error(RSA_E_ALIGN, "channel_gate: maps must be 16-byte aligned");
   const int64_t chunks = ((int64_t)p->H * p->W + CG_PIX - 1) / CG_PIX;
   if (chunks > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "channel_gate: map too large");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(channel_sum_kernel, dim3((unsigned)chunks, (unsigned)p->planes, (unsigned)p->batch), dim3(256), 0, s, *p, (int)chunks);
   hipLaunchKernelGGL(channel_gate_kernel, dim3((unsigned)p->batch), dim3(256), 0, s, *p, (int)chunks);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "channel_gate: launch failed") : RSA_OK;
+  return launch_status("channel_gate: launch failed");
 }
 
 extern "C" int rsa_aim_combine(const rsa_aim_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "aim_combine: null params");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "aim_combine: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "aim_combine: fmt must be an rsa_plane_fmt");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->planes < 1 || p->hidden < 1 || p->hidden > 16 || (p->mode != 0 && p->mode != 1))
     return set_error(RSA_E_ARG, "aim_combine: bad geometry (hidden <= 16, mode 0 or 1)");
   if (!p->att_hi || !p->conv_hi || !p->gate || !p->w1 || !p->b1 || !p->w2 || !p->out_hi) return set_error(RSA_E_ARG, "aim_combine: null pointer");
-  if (misaligned(p->att_hi) || misaligned(p->att_lo) || misaligned(p->conv_hi) || misaligned(p->conv_lo) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->att_hi) || misaligned16(p->att_lo) || misaligned16(p->conv_hi) || misaligned16(p->conv_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "aim_combine: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   hipLaunchKernelGGL(aim_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "aim_combine: launch failed") : RSA_OK;
+  return launch_status("aim_combine: launch failed");
 }
 
 extern "C" int rsa_gated_add(const void* x_hi, const void* x_lo, int64_t plane_stride, int64_t batch_stride, int32_t batch, int32_t H, int32_t W,
                              int32_t C, const float* gate, float scale, const float* base_f32, float* out_f32, void* stream) {
   if (!x_hi || !gate || !base_f32 || !out_f32 || batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 1 || C > 8 * 65535)
     return set_error(RSA_E_ARG, "gated_add: bad argument");
-  if (misaligned(x_hi) || misaligned(x_lo) || misaligned(base_f32) || misaligned(out_f32)) return set_error(RSA_E_ALIGN, "gated_add: maps must be 16-byte aligned");
+  if (misaligned16(x_hi) || misaligned16(x_lo) || misaligned16(base_f32) || misaligned16(out_f32)) return set_error(RSA_E_ALIGN, "gated_add: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(gated_add_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)((C + 7) / 8), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
                      (const bf16x8*)x_hi, (const bf16x8*)x_lo, plane_stride, batch_stride, HW, C, gate, scale, (const f32x4*)base_f32, (f32x4*)out_f32);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "gated_add: launch failed") : RSA_OK;
+  return launch_status("gated_add: launch failed");
 }

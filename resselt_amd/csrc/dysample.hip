@@ -14,11 +14,11 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 constexpr int DYS_MAX_OUT = 8;
 
 __global__ __launch_bounds__(256) void dysample_kernel(const rsa_dysample_params p) {
@@ -114,11 +114,10 @@ extern "C" int rsa_dysample(const rsa_dysample_params* p, void* stream) {
   if (!p->x_f32 || !p->offscope || !p->init_pos || !p->out_nchw) return set_error(RSA_E_ARG, "dysample: null pointer");
   if (!p->end_w && (p->C != 4 * p->groups || p->out_ch > 4)) return set_error(RSA_E_ARG, "dysample: pre-projected input needs C == 4*groups and out_ch <= 4");
   if (p->out_dtype < RSA_F32 || p->out_dtype > RSA_BF16) return set_error(RSA_E_ARG, "dysample: bad out_dtype");
-  if (((uintptr_t)p->x_f32 | (uintptr_t)p->offscope) & 15) return set_error(RSA_E_ALIGN, "dysample: maps must be 16-byte aligned");
+  if (misaligned16(p->x_f32) || misaligned16(p->offscope)) return set_error(RSA_E_ALIGN, "dysample: maps must be 16-byte aligned");
   const int64_t total = (int64_t)p->batch * p->H * p->scale * p->W * p->scale;
   int64_t g = (total + 255) / 256;
   if (g > 256 * 64) g = 256 * 64;
   hipLaunchKernelGGL(dysample_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *p);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "dysample: launch failed") : RSA_OK;
+  return launch_status("dysample: launch failed");
 }

@@ -9,35 +9,11 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
-
-bool eq_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
-__device__ __forceinline__ float eq_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-__device__ __forceinline__ float eq_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-
-template <int FMT>
-__device__ __forceinline__ void eq_load(const char* hi, const char* lo, int64_t off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + off);
-  const uint4 l = lo ? *(const uint4*)(lo + off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
-template <int FMT>
-__device__ __forceinline__ void eq_store(char* hi, char* lo, int64_t off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // ------------------------------------------------------------------------------------------------ the depthwise chain
 // A workgroup is a 32 x 16 pixel tile of one HALF plane (four channels: the low or the high 8 bytes of the 16-byte units), 256 threads, two
@@ -90,7 +66,7 @@ __device__ __forceinline__ void chain_tile(const char* qhi, const char* qlo, cha
       v = widen4<FMT>(h, l);
       if (gelu) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = eq_gelu(v[j]);
+        for (int j = 0; j < 4; ++j) v[j] = gelu_erf(v[j]);
       }
     }
     s_in[idx] = v;
@@ -195,8 +171,8 @@ __global__ __launch_bounds__(256) void eimn_sal_kernel(const char* ihi, const ch
     if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
     const int64_t q = ((int64_t)yy * W + xx) * 16;
     float u[8], v[8];
-    eq_load<FMT>(ihi, ilo, base1 + q, u);
-    eq_load<FMT>(ihi, ilo, base2 + q, v);
+    load_unit<FMT>(ihi, ilo, base1 + q, u);
+    load_unit<FMT>(ihi, ilo, base2 + q, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       a[j] = fmaf(w1[j * 9 + tap], u[j], a[j]);
@@ -205,8 +181,8 @@ __global__ __launch_bounds__(256) void eimn_sal_kernel(const char* ihi, const ch
   }
   float o[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = eq_gelu(a[j]) * b[j];
-  eq_store<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pix) * 16, o);
+  for (int j = 0; j < 8; ++j) o[j] = gelu_erf(a[j]) * b[j];
+  store_unit<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pix) * 16, o);
 }
 
 // grid (ceil(HW / 256), planes, batch): thread = one 16-byte unit; out may be f or v
@@ -217,11 +193,11 @@ __global__ __launch_bounds__(256) void eimn_silu_mul_kernel(const char* fhi, con
   const int pl = blockIdx.y, n = blockIdx.z;
   if (pix >= HW) return;
   float f[8], v[8], o[8];
-  eq_load<FMT>(fhi, flo, ((int64_t)n * f_bs + (int64_t)pl * f_ps + pix) * 16, f);
-  eq_load<FMT>(vhi, vlo, ((int64_t)n * v_bs + (int64_t)pl * v_ps + pix) * 16, v);
+  load_unit<FMT>(fhi, flo, ((int64_t)n * f_bs + (int64_t)pl * f_ps + pix) * 16, f);
+  load_unit<FMT>(vhi, vlo, ((int64_t)n * v_bs + (int64_t)pl * v_ps + pix) * 16, v);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (f[j] * eq_sigmoid(f[j])) * v[j];
-  eq_store<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pix) * 16, o);
+  for (int j = 0; j < 8; ++j) o[j] = (f[j] * sigmoid_exact(f[j])) * v[j];
+  store_unit<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pix) * 16, o);
 }
 
 // ------------------------------------------------------------------------------------------------ DFFM
@@ -405,8 +381,8 @@ __global__ __launch_bounds__(ED_THREADS) void dffm_apply_kernel(const ApplyArgs 
   }
   float pre = gates[C];  // s_g
 #pragma unroll
-  for (int r = 0; r < RCP; ++r) pre = fmaf(s_ws[r], eq_gelu(l[r] + s_bl[r]), pre);
-  const float s = eq_sigmoid(pre);
+  for (int r = 0; r < RCP; ++r) pre = fmaf(s_ws[r], gelu_erf(l[r] + s_bl[r]), pre);
+  const float s = sigmoid_exact(pre);
   const bool norm = a.ngamma != nullptr;
   char* ohi = a.o_hi + ((int64_t)n * a.o_bs + pix) * 16;
   char* olo = a.o_lo ? a.o_lo + ((int64_t)n * a.o_bs + pix) * 16 : nullptr;
@@ -425,7 +401,7 @@ __global__ __launch_bounds__(ED_THREADS) void dffm_apply_kernel(const ApplyArgs 
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[4 * h + j] = r[j];
       }
-      eq_store<FMT>(ohi, olo, (int64_t)p * a.o_ps * 16, o);
+      store_unit<FMT>(ohi, olo, (int64_t)p * a.o_ps * 16, o);
     }
     return;
   }
@@ -459,7 +435,7 @@ __global__ __launch_bounds__(ED_THREADS) void dffm_apply_kernel(const ApplyArgs 
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[4 * h + j] = r[j];
     }
-    eq_store<FMT>(ohi, olo, (int64_t)p * a.o_ps * 16, o);
+    store_unit<FMT>(ohi, olo, (int64_t)p * a.o_ps * 16, o);
   }
 }
 
@@ -482,14 +458,14 @@ extern "C" int rsa_eimn_query_chain(const void* q_hi, const void* q_lo, int64_t 
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || planes_a < 0 || planes_b < 0 || planes_c < 0) return set_error(RSA_E_ARG, "eimn_query_chain: bad geometry");
   const int64_t planes = (int64_t)planes_a + planes_b + planes_c;
   if (planes < 1 || 2 * planes > 65535) return set_error(RSA_E_ARG, "eimn_query_chain: total planes must be in [1, 32767]");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "eimn_query_chain: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "eimn_query_chain: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (q_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "eimn_query_chain: a plane stride is smaller than the map");
   if (batch > 1 && (q_batch_stride < planes * q_plane_stride || out_batch_stride < planes * out_plane_stride))
     return set_error(RSA_E_ARG, "eimn_query_chain: a batch stride is smaller than the planes of an image");
   if (q_hi == out_hi) return set_error(RSA_E_ARG, "eimn_query_chain: not in place (a tile reads its neighbours' pixels)");
-  if (eq_misaligned(q_hi) || eq_misaligned(q_lo) || eq_misaligned(out_hi) || eq_misaligned(out_lo) || eq_misaligned(w1) || eq_misaligned(b1) ||
-      eq_misaligned(w2) || eq_misaligned(b2))
+  if (misaligned16(q_hi) || misaligned16(q_lo) || misaligned16(out_hi) || misaligned16(out_lo) || misaligned16(w1) || misaligned16(b1) ||
+      misaligned16(w2) || misaligned16(b2))
     return set_error(RSA_E_ALIGN, "eimn_query_chain: planes and weights must be 16-byte aligned");
   const int64_t tiles = (int64_t)((W + EQ_TW - 1) / EQ_TW) * ((H + EQ_TH - 1) / EQ_TH);
   if (tiles > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "eimn_query_chain: map too large");
@@ -499,12 +475,10 @@ extern "C" int rsa_eimn_query_chain(const void* q_hi, const void* q_lo, int64_t 
   a.H = H, a.W = W, a.planes_a = planes_a, a.planes_b = planes_b, a.gelu_in = gelu_in;
   a.w1 = (const f32x4*)w1, a.b1 = (const f32x4*)b1, a.w2 = (const f32x4*)w2, a.b2 = (const f32x4*)b2;
   const dim3 grid((unsigned)tiles, (unsigned)(2 * planes), (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(eimn_chain_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(eimn_chain_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "eimn_query_chain: launch failed") : RSA_OK;
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(eimn_chain_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  });
+  return launch_status("eimn_query_chain: launch failed");
 }
 
 extern "C" int rsa_eimn_sal(const void* in_hi, const void* in_lo, int64_t in_plane_stride, int64_t in_batch_stride, void* out_hi, void* out_lo,
@@ -512,23 +486,20 @@ extern "C" int rsa_eimn_sal(const void* in_hi, const void* in_lo, int64_t in_pla
                             const float* weight, const float* bias, void* stream) {
   if (!in_hi || !out_hi || !weight || !bias) return set_error(RSA_E_ARG, "eimn_sal: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || planes < 1 || planes > 32767) return set_error(RSA_E_ARG, "eimn_sal: bad geometry");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "eimn_sal: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "eimn_sal: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (in_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "eimn_sal: a plane stride is smaller than the map");
   if (batch > 1 && (in_batch_stride < 2 * (int64_t)planes * in_plane_stride || out_batch_stride < (int64_t)planes * out_plane_stride))
     return set_error(RSA_E_ARG, "eimn_sal: a batch stride is smaller than the planes of an image");
   if (in_hi == out_hi) return set_error(RSA_E_ARG, "eimn_sal: not in place (a pixel reads its neighbours)");
-  if (eq_misaligned(in_hi) || eq_misaligned(in_lo) || eq_misaligned(out_hi) || eq_misaligned(out_lo)) return set_error(RSA_E_ALIGN, "eimn_sal: planes must be 16-byte aligned");
+  if (misaligned16(in_hi) || misaligned16(in_lo) || misaligned16(out_hi) || misaligned16(out_lo)) return set_error(RSA_E_ALIGN, "eimn_sal: planes must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "eimn_sal: map too large");
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)planes, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(eimn_sal_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)in_hi, (const char*)in_lo, in_plane_stride, in_batch_stride,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(eimn_sal_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)in_hi, (const char*)in_lo, in_plane_stride, in_batch_stride,
                        (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, (int)H, (int)W, (int)planes, weight, bias);
-  else
-    hipLaunchKernelGGL(eimn_sal_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)in_hi, (const char*)in_lo, in_plane_stride, in_batch_stride,
-                       (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, (int)H, (int)W, (int)planes, weight, bias);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "eimn_sal: launch failed") : RSA_OK;
+  });
+  return launch_status("eimn_sal: launch failed");
 }
 
 extern "C" int rsa_eimn_silu_mul(const void* f_hi, const void* f_lo, int64_t f_plane_stride, int64_t f_batch_stride, const void* v_hi, const void* v_lo,
@@ -536,24 +507,21 @@ extern "C" int rsa_eimn_silu_mul(const void* f_hi, const void* f_lo, int64_t f_p
                                  int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t planes, int32_t fmt, void* stream) {
   if (!f_hi || !v_hi || !out_hi) return set_error(RSA_E_ARG, "eimn_silu_mul: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || planes < 1 || planes > 65535) return set_error(RSA_E_ARG, "eimn_silu_mul: bad geometry");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "eimn_silu_mul: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "eimn_silu_mul: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (f_plane_stride < HW || v_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "eimn_silu_mul: a plane stride is smaller than the map");
   if (batch > 1 && (f_batch_stride < (int64_t)planes * f_plane_stride || v_batch_stride < (int64_t)planes * v_plane_stride ||
                     out_batch_stride < (int64_t)planes * out_plane_stride))
     return set_error(RSA_E_ARG, "eimn_silu_mul: a batch stride is smaller than the planes of an image");
-  if (eq_misaligned(f_hi) || eq_misaligned(f_lo) || eq_misaligned(v_hi) || eq_misaligned(v_lo) || eq_misaligned(out_hi) || eq_misaligned(out_lo))
+  if (misaligned16(f_hi) || misaligned16(f_lo) || misaligned16(v_hi) || misaligned16(v_lo) || misaligned16(out_hi) || misaligned16(out_lo))
     return set_error(RSA_E_ALIGN, "eimn_silu_mul: planes must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "eimn_silu_mul: map too large");
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)planes, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(eimn_silu_mul_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)f_hi, (const char*)f_lo, f_plane_stride, f_batch_stride,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(eimn_silu_mul_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)f_hi, (const char*)f_lo, f_plane_stride, f_batch_stride,
                        (const char*)v_hi, (const char*)v_lo, v_plane_stride, v_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW);
-  else
-    hipLaunchKernelGGL(eimn_silu_mul_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)f_hi, (const char*)f_lo, f_plane_stride, f_batch_stride,
-                       (const char*)v_hi, (const char*)v_lo, v_plane_stride, v_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "eimn_silu_mul: launch failed") : RSA_OK;
+  });
+  return launch_status("eimn_silu_mul: launch failed");
 }
 
 extern "C" int64_t rsa_eimn_dffm_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t C) {
@@ -567,12 +535,11 @@ extern "C" int rsa_eimn_dffm_reduce(const float* z, int32_t batch, int32_t H, in
   if (g != RSA_OK) return set_error(g, "eimn_dffm_reduce: bad geometry (C % 8 == 0, 8 <= C <= 128)");
   if (!z || !gamma || !beta || !workspace) return set_error(RSA_E_ARG, "eimn_dffm_reduce: null operand");
   if (workspace_bytes < rsa_eimn_dffm_workspace_bytes(batch, H, W, C)) return set_error(RSA_E_ARG, "eimn_dffm_reduce: workspace too small");
-  if (eq_misaligned(z) || eq_misaligned(workspace)) return set_error(RSA_E_ALIGN, "eimn_dffm_reduce: the map and the workspace must be 16-byte aligned");
+  if (misaligned16(z) || misaligned16(workspace)) return set_error(RSA_E_ALIGN, "eimn_dffm_reduce: the map and the workspace must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(dffm_reduce_kernel, dim3((unsigned)((HW + ED_THREADS - 1) / ED_THREADS), (unsigned)batch), dim3(ED_THREADS), 0, (hipStream_t)stream, z, HW,
                      (int)C, gamma, beta, (double)eps, (float*)workspace);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "eimn_dffm_reduce: launch failed") : RSA_OK;
+  return launch_status("eimn_dffm_reduce: launch failed");
 }
 
 extern "C" int rsa_eimn_dffm_gates(const void* workspace, int64_t workspace_bytes, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t rc,
@@ -583,12 +550,11 @@ extern "C" int rsa_eimn_dffm_gates(const void* workspace, int64_t workspace_byte
   if (rc < 1 || rc > ED_MAX_RC) return set_error(RSA_E_ARG, "eimn_dffm_gates: the reduced width must be in 1..32");
   if (!workspace || !wg || !bg || !wc || !bc || !ws || !bs || !gates) return set_error(RSA_E_ARG, "eimn_dffm_gates: null operand");
   if (workspace_bytes < rsa_eimn_dffm_workspace_bytes(batch, H, W, C)) return set_error(RSA_E_ARG, "eimn_dffm_gates: workspace too small");
-  if (eq_misaligned(workspace) || eq_misaligned(gates)) return set_error(RSA_E_ALIGN, "eimn_dffm_gates: the workspace and the gates must be 16-byte aligned");
+  if (misaligned16(workspace) || misaligned16(gates)) return set_error(RSA_E_ALIGN, "eimn_dffm_gates: the workspace and the gates must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(dffm_gates_kernel, dim3((unsigned)batch), dim3(ED_THREADS), 0, (hipStream_t)stream, (const float*)workspace,
                      (int)((HW + ED_THREADS - 1) / ED_THREADS), (int)C, (int)rc, 1.0 / (double)HW, wg, bg, wc, bc, ws, bs, gates);
-  const int r = (int)hipGetLastError();
-  return r ? set_error(r, "eimn_dffm_gates: launch failed") : RSA_OK;
+  return launch_status("eimn_dffm_gates: launch failed");
 }
 
 extern "C" int rsa_eimn_dffm_apply(const float* z, const float* x, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t rc, const float* gamma,
@@ -600,13 +566,13 @@ extern "C" int rsa_eimn_dffm_apply(const float* z, const float* x, int32_t batch
   if (rc < 1 || rc > ED_MAX_RC) return set_error(RSA_E_ARG, "eimn_dffm_apply: the reduced width must be in 1..32");
   if (!z || !x || !gamma || !beta || !wl || !bl || !ws || !gates || !scale || !out_f32 || !out_hi) return set_error(RSA_E_ARG, "eimn_dffm_apply: null operand");
   if ((norm_gamma == nullptr) != (norm_beta == nullptr)) return set_error(RSA_E_ARG, "eimn_dffm_apply: the stage norm needs both gamma and beta");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "eimn_dffm_apply: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "eimn_dffm_apply: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (out_plane_stride < HW) return set_error(RSA_E_ARG, "eimn_dffm_apply: the plane stride is smaller than the map");
   if (batch > 1 && out_batch_stride < (int64_t)(C / 8) * out_plane_stride)
     return set_error(RSA_E_ARG, "eimn_dffm_apply: the batch stride is smaller than the planes of an image");
   if (out_f32 == z || out_f32 == add) return set_error(RSA_E_ARG, "eimn_dffm_apply: out_f32 may alias x only");
-  if (eq_misaligned(z) || eq_misaligned(x) || eq_misaligned(add) || eq_misaligned(out_f32) || eq_misaligned(out_hi) || eq_misaligned(out_lo) || eq_misaligned(gates))
+  if (misaligned16(z) || misaligned16(x) || misaligned16(add) || misaligned16(out_f32) || misaligned16(out_hi) || misaligned16(out_lo) || misaligned16(gates))
     return set_error(RSA_E_ALIGN, "eimn_dffm_apply: maps, planes and gates must be 16-byte aligned");
   ApplyArgs a;
   a.z = z, a.x = x, a.add = add, a.out = out_f32, a.HW = HW, a.C = C, a.rc = rc, a.gamma = gamma, a.beta = beta, a.eps = eps, a.wl = wl, a.bl = bl, a.wsp = ws;
@@ -625,6 +591,5 @@ extern "C" int rsa_eimn_dffm_apply(const float* z, const float* x, int32_t batch
     else
       hipLaunchKernelGGL((dffm_apply_kernel<RSA_PF_BF16, 32>), grid, dim3(ED_THREADS), 0, s, a);
   }
-  const int r = (int)hipGetLastError();
-  return r ? set_error(r, "eimn_dffm_apply: launch failed") : RSA_OK;
+  return launch_status("eimn_dffm_apply: launch failed");
 }

@@ -9,35 +9,13 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
 
-bool fd_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
 // one unit (8 channels) of a split plane at byte offset `off`: hi (+ lo) -> f32
-template <int FMT>
-__device__ __forceinline__ void fd_load(const char* hi, const char* lo, int64_t off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + off);
-  const uint4 l = lo ? *(const uint4*)(lo + off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
-template <int FMT>
-__device__ __forceinline__ void fd_store(char* hi, char* lo, int64_t off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-__device__ __forceinline__ float fd_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 
 // ------------------------------------------------------------------------------------------------ AIM interaction + residual + norm2
 // A workgroup (4 waves) owns 64 pixels of ONE image; wave w holds planes w, w + 4, ... of its lane's pixel in registers (MAXP per wave),
@@ -68,8 +46,8 @@ __global__ __launch_bounds__(256) void fdat_interact_kernel(const rsa_fdat_inter
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[k][j] = cv[k][j] = 0.f;
     if (pl < planes) {
-      fd_load<FMT>(ahi, alo, (int64_t)pl * p.a_plane_stride * 16, v[k]);
-      fd_load<FMT>(chi, clo, (int64_t)pl * p.c_plane_stride * 16, cv[k]);
+      load_unit<FMT>(ahi, alo, (int64_t)pl * p.a_plane_stride * 16, v[k]);
+      load_unit<FMT>(chi, clo, (int64_t)pl * p.c_plane_stride * 16, cv[k]);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         if (pl * 8 + j >= C) v[k][j] = cv[k][j] = 0.f;  // uniform test
@@ -89,7 +67,7 @@ __global__ __launch_bounds__(256) void fdat_interact_kernel(const rsa_fdat_inter
     }
     s_red[0][wave][lane] = dot;
     __syncthreads();
-    gate = fd_sigmoid((s_red[0][0][lane] + s_red[0][1][lane]) + (s_red[0][2][lane] + s_red[0][3][lane]));
+    gate = sigmoid_exact((s_red[0][0][lane] + s_red[0][1][lane]) + (s_red[0][2][lane] + s_red[0][3][lane]));
   }
   const float* cm = MODE == 0 ? p.cm + (int64_t)n * planes * 8 : nullptr;  // rows of rsa_channel_gate's gate: 8 * planes
   const f32x4* xb = p.x ? (const f32x4*)p.x + (int64_t)n * p4 * HW + px : nullptr;  // NULL: x_out receives f alone
@@ -157,7 +135,7 @@ __global__ __launch_bounds__(256) void fdat_interact_kernel(const rsa_fdat_inter
         const int ch = pl * 8 + j;
         o[j] = ch < C ? (v[k][j] - mean) * rstd * p.gamma[ch] + p.beta[ch] : 0.f;
       }
-      fd_store<FMT>(ohi, olo, (int64_t)pl * p.out_plane_stride * 16, o);
+      store_unit<FMT>(ohi, olo, (int64_t)pl * p.out_plane_stride * 16, o);
     }
   }
 }
@@ -173,14 +151,14 @@ __global__ __launch_bounds__(256) void pa_gate_kernel(const char* xhi, const cha
   const int64_t pl = r / HW, pix = r - pl * HW;
   const int64_t off = (n * batch_stride + pl * plane_stride + pix) * 16;
   float x[8], g[8], o[8];
-  fd_load<FMT>(xhi, xlo, off, x);
-  fd_load<FMT>(ghi, glo, off, g);
+  load_unit<FMT>(xhi, xlo, off, x);
+  load_unit<FMT>(ghi, glo, off, g);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float v = x[j] * fd_sigmoid(g[j]);
+    const float v = x[j] * sigmoid_exact(g[j]);
     o[j] = v > 0.f ? v : v * slope;
   }
-  fd_store<FMT>(ohi, olo, off, o);
+  store_unit<FMT>(ohi, olo, off, o);
 }
 
 // ------------------------------------------------------------------------------------------------ LDA_AQU
@@ -207,10 +185,10 @@ __device__ __forceinline__ void lda_q_at(const char* hi, const char* lo, int64_t
     if (pl >= hp) break;
     float a[8], b[8], c[8], d[8];
     const int64_t base = (int64_t)pl * plane_stride;
-    fd_load<FMT>(hi, lo, (base + (int64_t)ly.i0 * W + lx.i0) * 16, a);
-    fd_load<FMT>(hi, lo, (base + (int64_t)ly.i0 * W + lx.i1) * 16, b);
-    fd_load<FMT>(hi, lo, (base + (int64_t)ly.i1 * W + lx.i0) * 16, c);
-    fd_load<FMT>(hi, lo, (base + (int64_t)ly.i1 * W + lx.i1) * 16, d);
+    load_unit<FMT>(hi, lo, (base + (int64_t)ly.i0 * W + lx.i0) * 16, a);
+    load_unit<FMT>(hi, lo, (base + (int64_t)ly.i0 * W + lx.i1) * 16, b);
+    load_unit<FMT>(hi, lo, (base + (int64_t)ly.i1 * W + lx.i0) * 16, c);
+    load_unit<FMT>(hi, lo, (base + (int64_t)ly.i1 * W + lx.i1) * 16, d);
 #pragma unroll
     for (int j = 0; j < 8; ++j) q[pl * 8 + j] = ly.w0 * (lx.w0 * a[j] + lx.w1 * b[j]) + ly.w1 * (lx.w0 * c[j] + lx.w1 * d[j]);
   }
@@ -257,7 +235,7 @@ __global__ __launch_bounds__(256) void lda_offsets_kernel(const rsa_lda_offsets_
     for (int c = 0; c < LDA_MAX_HIDDEN; ++c)
       if (c >= g * gc && c < (g + 1) * gc) {
         const float t = (acc[c] - mean) * rstd * p.gamma[c - g * gc] + p.beta[c - g * gc];
-        acc[c] = t * fd_sigmoid(t);
+        acc[c] = t * sigmoid_exact(t);
       }
   }
   char* ohi = (char*)p.out_hi + (n * p.out_batch_stride + pix) * 16;
@@ -268,7 +246,7 @@ __global__ __launch_bounds__(256) void lda_offsets_kernel(const rsa_lda_offsets_
     float o[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = pl * 8 + e < p.hidden ? acc[pl * 8 + e] : 0.f;
-    fd_store<FMT>(ohi, olo, (int64_t)pl * p.out_plane_stride * 16, o);
+    store_unit<FMT>(ohi, olo, (int64_t)pl * p.out_plane_stride * 16, o);
   }
 }
 
@@ -347,7 +325,7 @@ __global__ __launch_bounds__(256) void lda_attention_kernel(const rsa_lda_attn_p
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float u[8];
-          fd_load<FMT>(khi, klo, ((int64_t)pl * p.k_plane_stride + cr.o[k]) * 16, u);
+          load_unit<FMT>(khi, klo, ((int64_t)pl * p.k_plane_stride + cr.o[k]) * 16, u);
 #pragma unroll
           for (int e = 0; e < 8; ++e) kv[e] = fmaf(cr.w[k], u[e], kv[e]);
         }
@@ -388,12 +366,12 @@ __global__ __launch_bounds__(256) void lda_attention_kernel(const rsa_lda_attn_p
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float u[8];
-          fd_load<FMT>(vhi, vlo, ((int64_t)pl * p.v_plane_stride + cr[t].o[k]) * 16, u);
+          load_unit<FMT>(vhi, vlo, ((int64_t)pl * p.v_plane_stride + cr[t].o[k]) * 16, u);
           const float wk = s[t] * cr[t].w[k];
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = fmaf(wk, u[e], o[e]);
         }
-      fd_store<FMT>(ohi, olo, (int64_t)pl * p.out_plane_stride * 16, o);
+      store_unit<FMT>(ohi, olo, (int64_t)pl * p.out_plane_stride * 16, o);
     }
   }
 }
@@ -414,14 +392,14 @@ extern "C" int rsa_fdat_interact(const rsa_fdat_interact_params* p, void* stream
   if (p == nullptr) return set_error(RSA_E_ARG, "fdat_interact: null params");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->C < 1 || p->C > 256 || (p->mode != 0 && p->mode != 1) || p->reserved0 != 0)
     return set_error(RSA_E_ARG, "fdat_interact: bad geometry (C 1..256, mode 0 or 1, reserved0 0)");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "fdat_interact: bad plane format");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "fdat_interact: bad plane format");
   if (!p->a_hi || !p->c_hi || !p->x_out || (p->mode == 0 && !p->cm) || (p->mode == 1 && !p->w))
     return set_error(RSA_E_ARG, "fdat_interact: null operand");
   if (!p->x && p->out_hi) return set_error(RSA_E_ARG, "fdat_interact: norm2 needs the stream x (x NULL writes the interaction alone)");
   if (p->out_hi && (!p->gamma || !p->beta || !(p->eps > 0.f))) return set_error(RSA_E_ARG, "fdat_interact: norm2 needs gamma, beta and eps > 0");
   if (p->out_lo && !p->out_hi) return set_error(RSA_E_ARG, "fdat_interact: out_lo without out_hi");
-  if (fd_misaligned(p->a_hi) || fd_misaligned(p->a_lo) || fd_misaligned(p->c_hi) || fd_misaligned(p->c_lo) || fd_misaligned(p->x) ||
-      fd_misaligned(p->x_out) || fd_misaligned(p->out_hi) || fd_misaligned(p->out_lo))
+  if (misaligned16(p->a_hi) || misaligned16(p->a_lo) || misaligned16(p->c_hi) || misaligned16(p->c_lo) || misaligned16(p->x) ||
+      misaligned16(p->x_out) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "fdat_interact: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   if (p->a_plane_stride < HW || p->c_plane_stride < HW || (p->out_hi && p->out_plane_stride < HW))
@@ -454,31 +432,27 @@ extern "C" int rsa_fdat_interact(const rsa_fdat_interact_params* p, void* stream
 #undef FD_FMT
 #undef FD_MODE
 #undef FD_GO
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "fdat_interact: launch failed") : RSA_OK;
+  return launch_status("fdat_interact: launch failed");
 }
 
 extern "C" int rsa_pa_gate(const void* x_hi, const void* x_lo, const void* logit_hi, const void* logit_lo, int64_t plane_stride, int64_t batch_stride,
                            int32_t batch, int32_t H, int32_t W, int32_t planes, float slope, int32_t fmt, void* out_hi, void* out_lo, void* stream) {
   if (!x_hi || !logit_hi || !out_hi) return set_error(RSA_E_ARG, "pa_gate: null operand");
-  if (batch < 1 || H < 1 || W < 1 || planes < 1 || (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16))
+  if (batch < 1 || H < 1 || W < 1 || planes < 1 || !plane_fmt_ok(fmt))
     return set_error(RSA_E_ARG, "pa_gate: bad geometry or plane format");
   const int64_t HW = (int64_t)H * W;
   if (plane_stride < HW || batch_stride < (int64_t)planes * plane_stride) return set_error(RSA_E_ARG, "pa_gate: strides smaller than the map");
-  if (fd_misaligned(x_hi) || fd_misaligned(x_lo) || fd_misaligned(logit_hi) || fd_misaligned(logit_lo) || fd_misaligned(out_hi) || fd_misaligned(out_lo))
+  if (misaligned16(x_hi) || misaligned16(x_lo) || misaligned16(logit_hi) || misaligned16(logit_lo) || misaligned16(out_hi) || misaligned16(out_lo))
     return set_error(RSA_E_ALIGN, "pa_gate: planes must be 16-byte aligned");
   const int64_t total = (int64_t)batch * planes * HW;
   unsigned blocks;
   if (fd_grid(total, blocks)) return set_error(RSA_E_ARG, "pa_gate: map too large");
   const hipStream_t s = (hipStream_t)stream;
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(pa_gate_kernel<RSA_PF_F16>, dim3(blocks), dim3(256), 0, s, (const char*)x_hi, (const char*)x_lo, (const char*)logit_hi,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(pa_gate_kernel<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, (const char*)x_hi, (const char*)x_lo, (const char*)logit_hi,
                        (const char*)logit_lo, plane_stride, batch_stride, HW, planes, total, slope, (char*)out_hi, (char*)out_lo);
-  else
-    hipLaunchKernelGGL(pa_gate_kernel<RSA_PF_BF16>, dim3(blocks), dim3(256), 0, s, (const char*)x_hi, (const char*)x_lo, (const char*)logit_hi,
-                       (const char*)logit_lo, plane_stride, batch_stride, HW, planes, total, slope, (char*)out_hi, (char*)out_lo);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "pa_gate: launch failed") : RSA_OK;
+  });
+  return launch_status("pa_gate: launch failed");
 }
 
 extern "C" int rsa_lda_offsets(const rsa_lda_offsets_params* p, void* stream) {
@@ -487,21 +461,19 @@ extern "C" int rsa_lda_offsets(const rsa_lda_offsets_params* p, void* stream) {
     return set_error(RSA_E_ARG, "lda_offsets: bad geometry (Hout, Wout >= 2, eps > 0, reserved0 0)");
   if (p->groups != 2 || p->hidden < 2 || p->hidden > LDA_MAX_HIDDEN || p->hidden % 2)
     return set_error(RSA_E_ARG, "lda_offsets: groups must be 2 and hidden even in 2..64");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "lda_offsets: bad plane format");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "lda_offsets: bad plane format");
   if (!p->q_hi || !p->dw_weight || !p->gamma || !p->beta || !p->out_hi) return set_error(RSA_E_ARG, "lda_offsets: null operand");
-  if (fd_misaligned(p->q_hi) || fd_misaligned(p->q_lo) || fd_misaligned(p->out_hi) || fd_misaligned(p->out_lo))
+  if (misaligned16(p->q_hi) || misaligned16(p->q_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "lda_offsets: planes must be 16-byte aligned");
   if (p->q_plane_stride < (int64_t)p->H * p->W || p->out_plane_stride < (int64_t)p->Hout * p->Wout)
     return set_error(RSA_E_ARG, "lda_offsets: a plane stride is smaller than its map");
   unsigned blocks;
   if (fd_grid((int64_t)p->batch * p->Hout * p->Wout, blocks)) return set_error(RSA_E_ARG, "lda_offsets: map too large");
   const hipStream_t s = (hipStream_t)stream;
-  if (p->fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(lda_offsets_kernel<RSA_PF_F16>, dim3(blocks), dim3(256), 0, s, *p);
-  else
-    hipLaunchKernelGGL(lda_offsets_kernel<RSA_PF_BF16>, dim3(blocks), dim3(256), 0, s, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "lda_offsets: launch failed") : RSA_OK;
+  with_fmt(p->fmt, [&](auto F) {
+    hipLaunchKernelGGL(lda_offsets_kernel<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, *p);
+  });
+  return launch_status("lda_offsets: launch failed");
 }
 
 extern "C" int rsa_lda_attention(const rsa_lda_attn_params* p, void* stream) {
@@ -510,10 +482,10 @@ extern "C" int rsa_lda_attention(const rsa_lda_attn_params* p, void* stream) {
     return set_error(RSA_E_ARG, "lda_attention: bad geometry (Hout, Wout >= 2, reserved0 0)");
   if (p->groups != 2 || p->hidden < 2 || p->hidden > LDA_MAX_HIDDEN || p->hidden % 2 || p->C < 16 || p->C > 256 || p->C % 16)
     return set_error(RSA_E_ARG, "lda_attention: groups 2, hidden even in 2..64, C a multiple of 16 up to 256");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "lda_attention: bad plane format");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "lda_attention: bad plane format");
   if (!p->q_hi || !p->k_hi || !p->v_hi || !p->offset || !p->rpb || !p->out_hi) return set_error(RSA_E_ARG, "lda_attention: null operand");
-  if (fd_misaligned(p->q_hi) || fd_misaligned(p->q_lo) || fd_misaligned(p->k_hi) || fd_misaligned(p->k_lo) || fd_misaligned(p->v_hi) ||
-      fd_misaligned(p->v_lo) || fd_misaligned(p->offset) || fd_misaligned(p->out_hi) || fd_misaligned(p->out_lo))
+  if (misaligned16(p->q_hi) || misaligned16(p->q_lo) || misaligned16(p->k_hi) || misaligned16(p->k_lo) || misaligned16(p->v_hi) ||
+      misaligned16(p->v_lo) || misaligned16(p->offset) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "lda_attention: maps must be 16-byte aligned");
   const int64_t hw = (int64_t)p->H * p->W;
   if (p->q_plane_stride < hw || p->k_plane_stride < hw || p->v_plane_stride < hw || p->out_plane_stride < (int64_t)p->Hout * p->Wout)
@@ -521,10 +493,8 @@ extern "C" int rsa_lda_attention(const rsa_lda_attn_params* p, void* stream) {
   unsigned blocks;
   if (fd_grid((int64_t)p->batch * p->Hout * p->Wout, blocks)) return set_error(RSA_E_ARG, "lda_attention: map too large");
   const hipStream_t s = (hipStream_t)stream;
-  if (p->fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(lda_attention_kernel<RSA_PF_F16>, dim3(blocks), dim3(256), 0, s, *p);
-  else
-    hipLaunchKernelGGL(lda_attention_kernel<RSA_PF_BF16>, dim3(blocks), dim3(256), 0, s, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "lda_attention: launch failed") : RSA_OK;
+  with_fmt(p->fmt, [&](auto F) {
+    hipLaunchKernelGGL(lda_attention_kernel<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, *p);
+  });
+  return launch_status("lda_attention: launch failed");
 }

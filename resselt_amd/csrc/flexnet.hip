@@ -9,32 +9,11 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
-
-bool fx_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
-template <int FMT>
-__device__ __forceinline__ void fx_load(const char* hi, const char* lo, int64_t off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + off);
-  const uint4 l = lo ? *(const uint4*)(lo + off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
-template <int FMT>
-__device__ __forceinline__ void fx_store(char* hi, char* lo, int64_t off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // ------------------------------------------------------------------------------------------------ RMSNorm + 5x5 depthwise
 // grid (tiles of 32 x 8 pixels, batch), 256 threads: thread = pixel.  Pass 1 gives every pixel of the (8 + 4) x (32 + 4) halo its
@@ -121,7 +100,7 @@ __global__ __launch_bounds__(256) void flex_norm_shift_kernel(const NormShiftArg
           }
         }
       }
-      fx_store<FMT>(a.o_hi, a.o_lo, ((int64_t)n * a.o_bs + (int64_t)pl * a.o_ps + (int64_t)y * a.W + x) * 16, o);
+      store_unit<FMT>(a.o_hi, a.o_lo, ((int64_t)n * a.o_bs + (int64_t)pl * a.o_ps + (int64_t)y * a.W + x) * 16, o);
     }
     __syncthreads();  // the next plane overwrites the staged halo
   }
@@ -155,21 +134,6 @@ struct AttnArgs {
   const float* lw;  // [9][C]: tap-major LePE weights
   const float* lb;  // [C]
 };
-
-template <int FMT>
-__device__ __forceinline__ bf16x8 fx_pack16(const float (&v)[8]) {
-  if constexpr (FMT == RSA_PF_F16) {
-    f16x8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
-    return __builtin_bit_cast(bf16x8, h);
-  } else {
-    bf16x8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (__bf16)v[j];
-    return h;
-  }
-}
 
 template <int FMT>
 __device__ __forceinline__ float fx_elem(const bf16x8 h, int j) {
@@ -275,12 +239,12 @@ __global__ __launch_bounds__(256) void flex_window_attn_kernel(const AttnArgs a)
     float e8[8], r8[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) e8[j] = acc[2 * c][j], e8[4 + j] = acc[2 * c + 1][j];
-    ph[c] = fx_pack16<FMT>(e8);
+    ph[c] = pack16<FMT>(e8);
     pl2[c] = zero8;
     if (PROD == 3) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) r8[j] = e8[j] - fx_elem<FMT>(ph[c], j);
-      pl2[c] = fx_pack16<FMT>(r8);
+      pl2[c] = pack16<FMT>(r8);
     }
   }
   __syncthreads();  // V^T is staged
@@ -343,18 +307,18 @@ __global__ __launch_bounds__(256) void flex_sqrelu_kernel(const char* hi, const 
   float v[8];
   if (!norm) {
     const int pl = blockIdx.y;
-    fx_load<FMT>(hi, lo, ib + (int64_t)pl * ps * 16, v);
+    load_unit<FMT>(hi, lo, ib + (int64_t)pl * ps * 16, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float k = fmaxf(v[j], 0.f);
       v[j] = k * k;
     }
-    fx_store<FMT>(ohi, olo, ob + (int64_t)pl * o_ps * 16, v);
+    store_unit<FMT>(ohi, olo, ob + (int64_t)pl * o_ps * 16, v);
     return;
   }
   float ss = 0.f;
   for (int pl = 0; pl < P; ++pl) {
-    fx_load<FMT>(hi, lo, ib + (int64_t)pl * ps * 16, v);
+    load_unit<FMT>(hi, lo, ib + (int64_t)pl * ps * 16, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float k = fmaxf(v[j], 0.f), k2 = k * k;
@@ -363,13 +327,13 @@ __global__ __launch_bounds__(256) void flex_sqrelu_kernel(const char* hi, const 
   }
   const float r = 1.f / sqrtf(ss / (float)(8 * P) + eps);
   for (int pl = 0; pl < P; ++pl) {
-    fx_load<FMT>(hi, lo, ib + (int64_t)pl * ps * 16, v);
+    load_unit<FMT>(hi, lo, ib + (int64_t)pl * ps * 16, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float k = fmaxf(v[j], 0.f);
       v[j] = k * k * r;
     }
-    fx_store<FMT>(ohi, olo, ob + (int64_t)pl * o_ps * 16, v);
+    store_unit<FMT>(ohi, olo, ob + (int64_t)pl * o_ps * 16, v);
   }
 }
 
@@ -385,8 +349,8 @@ __global__ __launch_bounds__(256) void flex_gate_add_kernel(const char* rhi, con
   const int pl = blockIdx.y, n = blockIdx.z;
   if (pixel >= HW) return;
   float r[8], kv[8], o[8];
-  fx_load<FMT>(rhi, rlo, ((int64_t)n * r_bs + (int64_t)pl * r_ps + pixel) * 16, r);
-  fx_load<FMT>(khi, klo, ((int64_t)n * k_bs + (int64_t)pl * k_ps + pixel) * 16, kv);
+  load_unit<FMT>(rhi, rlo, ((int64_t)n * r_bs + (int64_t)pl * r_ps + pixel) * 16, r);
+  load_unit<FMT>(khi, klo, ((int64_t)n * k_bs + (int64_t)pl * k_ps + pixel) * 16, kv);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int64_t i = ((int64_t)n * 2 * P + 2 * pl + h) * HW + pixel;
@@ -398,10 +362,8 @@ __global__ __launch_bounds__(256) void flex_gate_add_kernel(const char* rhi, con
     }
     if (out) out[i] = b;
   }
-  if (ohi) fx_store<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pixel) * 16, o);
+  if (ohi) store_unit<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pixel) * 16, o);
 }
-
-bool fx_fmt_ok(int fmt) { return fmt == RSA_PF_BF16 || fmt == RSA_PF_F16; }
 
 }  // namespace
 }  // namespace rsa
@@ -414,12 +376,12 @@ extern "C" int rsa_flex_norm_shift(const float* x_f32, int32_t batch, int32_t H,
   if (!x_f32 || !norm_weight || !weight || !out_hi) return set_error(RSA_E_ARG, "flex_norm_shift: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 8 || (C & 7) || !(eps >= 0.f))
     return set_error(RSA_E_ARG, "flex_norm_shift: bad geometry (C a multiple of 8, eps >= 0)");
-  if (!fx_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_norm_shift: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_norm_shift: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (out_plane_stride < HW) return set_error(RSA_E_ARG, "flex_norm_shift: the plane stride is smaller than the map");
   if (batch > 1 && out_batch_stride < (int64_t)(C / 8) * out_plane_stride)
     return set_error(RSA_E_ARG, "flex_norm_shift: the batch stride is smaller than the planes of an image");
-  if (fx_misaligned(x_f32) || fx_misaligned(norm_weight) || fx_misaligned(out_hi) || fx_misaligned(out_lo))
+  if (misaligned16(x_f32) || misaligned16(norm_weight) || misaligned16(out_hi) || misaligned16(out_lo))
     return set_error(RSA_E_ALIGN, "flex_norm_shift: the map, the norm weight and the planes must be 16-byte aligned");
   const int64_t tiles = (int64_t)((W + NS_TW - 1) / NS_TW) * ((H + NS_TH - 1) / NS_TH);
   if (tiles > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "flex_norm_shift: map too large");
@@ -427,12 +389,10 @@ extern "C" int rsa_flex_norm_shift(const float* x_f32, int32_t batch, int32_t H,
   a.x = x_f32, a.nw = norm_weight, a.w = weight, a.o_hi = (char*)out_hi, a.o_lo = (char*)out_lo, a.o_ps = out_plane_stride, a.o_bs = out_batch_stride;
   a.H = H, a.W = W, a.C = C, a.eps = eps;
   const dim3 grid((unsigned)tiles, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(flex_norm_shift_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(flex_norm_shift_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "flex_norm_shift: launch failed") : RSA_OK;
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(flex_norm_shift_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  });
+  return launch_status("flex_norm_shift: launch failed");
 }
 
 extern "C" int64_t rsa_flex_window_attn_lds_bytes(int32_t C, int32_t products) {
@@ -448,14 +408,14 @@ extern "C" int rsa_flex_window_attn(const void* qkv_hi, const void* qkv_lo, int6
   if (C < 16 || C > 128 || (C & 15)) return set_error(RSA_E_ARG, "flex_window_attn: C must be a multiple of 16 from 16 to 128");
   if (products != 1 && products != 3) return set_error(RSA_E_ARG, "flex_window_attn: products must be 1 or 3");
   if (products == 3 && !qkv_lo) return set_error(RSA_E_ARG, "flex_window_attn: three products need lo planes");
-  if (!fx_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_window_attn: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_window_attn: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   const int P = C / 8;
   if (qkv_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "flex_window_attn: a plane stride is smaller than the map");
   if (batch > 1 && (qkv_batch_stride < 3 * (int64_t)P * qkv_plane_stride || out_batch_stride < (int64_t)P * out_plane_stride))
     return set_error(RSA_E_ARG, "flex_window_attn: a batch stride is smaller than the planes of an image");
   if (out_hi == qkv_hi) return set_error(RSA_E_ARG, "flex_window_attn: not in place");
-  if (fx_misaligned(qkv_hi) || fx_misaligned(qkv_lo) || fx_misaligned(out_hi) || fx_misaligned(out_lo) || fx_misaligned(lepe_w) || fx_misaligned(lepe_b))
+  if (misaligned16(qkv_hi) || misaligned16(qkv_lo) || misaligned16(out_hi) || misaligned16(out_lo) || misaligned16(lepe_w) || misaligned16(lepe_b))
     return set_error(RSA_E_ALIGN, "flex_window_attn: planes and the LePE weights must be 16-byte aligned");
   const int64_t windows = (int64_t)(H / 8) * (W / 8);
   if (windows > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "flex_window_attn: map too large");
@@ -474,8 +434,7 @@ extern "C" int rsa_flex_window_attn(const void* qkv_hi, const void* qkv_lo, int6
     hipLaunchKernelGGL((flex_window_attn_kernel<1, RSA_PF_F16>), grid, dim3(256), lds, st, a);
   else
     hipLaunchKernelGGL((flex_window_attn_kernel<1, RSA_PF_BF16>), grid, dim3(256), lds, st, a);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "flex_window_attn: launch failed") : RSA_OK;
+  return launch_status("flex_window_attn: launch failed");
 }
 
 extern "C" int rsa_flex_sqrelu(const void* in_hi, const void* in_lo, int64_t in_plane_stride, int64_t in_batch_stride, void* out_hi, void* out_lo,
@@ -484,7 +443,7 @@ extern "C" int rsa_flex_sqrelu(const void* in_hi, const void* in_lo, int64_t in_
   if (!in_hi || !out_hi) return set_error(RSA_E_ARG, "flex_sqrelu: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || hidden < 8 || (hidden & 7) || hidden > 8 * 65535 || !(eps >= 0.f))
     return set_error(RSA_E_ARG, "flex_sqrelu: bad geometry (hidden a multiple of 8, eps >= 0)");
-  if (!fx_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_sqrelu: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_sqrelu: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   const int P = hidden / 8;
   if (in_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "flex_sqrelu: a plane stride is smaller than the map");
@@ -492,18 +451,15 @@ extern "C" int rsa_flex_sqrelu(const void* in_hi, const void* in_lo, int64_t in_
     return set_error(RSA_E_ARG, "flex_sqrelu: a batch stride is smaller than the planes of an image");
   if (out_hi == in_hi && (out_plane_stride != in_plane_stride || out_batch_stride != in_batch_stride))
     return set_error(RSA_E_ARG, "flex_sqrelu: in place needs the same strides");
-  if (fx_misaligned(in_hi) || fx_misaligned(in_lo) || fx_misaligned(out_hi) || fx_misaligned(out_lo))
+  if (misaligned16(in_hi) || misaligned16(in_lo) || misaligned16(out_hi) || misaligned16(out_lo))
     return set_error(RSA_E_ALIGN, "flex_sqrelu: planes must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "flex_sqrelu: map too large");
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)(norm ? 1 : P), (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(flex_sqrelu_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)in_hi, (const char*)in_lo, in_plane_stride,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(flex_sqrelu_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)in_hi, (const char*)in_lo, in_plane_stride,
                        in_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW, P, (int)(norm != 0), eps);
-  else
-    hipLaunchKernelGGL(flex_sqrelu_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)in_hi, (const char*)in_lo, in_plane_stride,
-                       in_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW, P, (int)(norm != 0), eps);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "flex_sqrelu: launch failed") : RSA_OK;
+  });
+  return launch_status("flex_sqrelu: launch failed");
 }
 
 extern "C" int rsa_flex_gate_add(const void* r_hi, const void* r_lo, int64_t r_plane_stride, int64_t r_batch_stride, const void* kv_hi, const void* kv_lo,
@@ -512,7 +468,7 @@ extern "C" int rsa_flex_gate_add(const void* r_hi, const void* r_lo, int64_t r_p
                                  void* stream) {
   if (!r_hi || !kv_hi || !base_f32 || (!out_f32 && !out_hi)) return set_error(RSA_E_ARG, "flex_gate_add: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 8 || (C & 7) || C > 8 * 65535) return set_error(RSA_E_ARG, "flex_gate_add: bad geometry (C a multiple of 8)");
-  if (!fx_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_gate_add: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "flex_gate_add: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   const int P = C / 8;
   if (r_plane_stride < HW || kv_plane_stride < HW || (out_hi && out_plane_stride < HW))
@@ -520,19 +476,15 @@ extern "C" int rsa_flex_gate_add(const void* r_hi, const void* r_lo, int64_t r_p
   if (batch > 1 && (r_batch_stride < (int64_t)P * r_plane_stride || kv_batch_stride < (int64_t)P * kv_plane_stride ||
                     (out_hi && out_batch_stride < (int64_t)P * out_plane_stride)))
     return set_error(RSA_E_ARG, "flex_gate_add: a batch stride is smaller than the planes of an image");
-  if (fx_misaligned(r_hi) || fx_misaligned(r_lo) || fx_misaligned(kv_hi) || fx_misaligned(kv_lo) || fx_misaligned(base_f32) || fx_misaligned(out_f32) ||
-      fx_misaligned(out_hi) || fx_misaligned(out_lo))
+  if (misaligned16(r_hi) || misaligned16(r_lo) || misaligned16(kv_hi) || misaligned16(kv_lo) || misaligned16(base_f32) || misaligned16(out_f32) ||
+      misaligned16(out_hi) || misaligned16(out_lo))
     return set_error(RSA_E_ALIGN, "flex_gate_add: planes and maps must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "flex_gate_add: map too large");
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)P, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(flex_gate_add_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)r_hi, (const char*)r_lo, r_plane_stride,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(flex_gate_add_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)r_hi, (const char*)r_lo, r_plane_stride,
                        r_batch_stride, (const char*)kv_hi, (const char*)kv_lo, kv_plane_stride, kv_batch_stride, (const f32x4*)base_f32, (f32x4*)out_f32,
                        (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW, P);
-  else
-    hipLaunchKernelGGL(flex_gate_add_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)r_hi, (const char*)r_lo, r_plane_stride,
-                       r_batch_stride, (const char*)kv_hi, (const char*)kv_lo, kv_plane_stride, kv_batch_stride, (const f32x4*)base_f32, (f32x4*)out_f32,
-                       (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW, P);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "flex_gate_add: launch failed") : RSA_OK;
+  });
+  return launch_status("flex_gate_add: launch failed");
 }

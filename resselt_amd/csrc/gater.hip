@@ -12,54 +12,11 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ void get_unit(const bf16x8* hi, const bf16x8* lo, int64_t u, float (&v)[8], int fmt) {
-  const bf16x8 h = hi[u];
-  bf16x8 l = {};
-  if (lo != nullptr) l = lo[u];
-  if (fmt == RSA_PF_F16) {
-    const f16x8 hf = __builtin_bit_cast(f16x8, h), lf = __builtin_bit_cast(f16x8, l);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)hf[j] + (lo != nullptr ? (float)lf[j] : 0.f);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (lo != nullptr ? (float)l[j] : 0.f);
-  }
-}
-
-__device__ __forceinline__ void put_unit(bf16x8* hi, bf16x8* lo, int64_t u, const float (&v)[8], int fmt) {
-  if (fmt == RSA_PF_F16) {
-    f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float vj = v[j];
-      asm("" : "+v"(vj));  // opaque: the lo half is the rounding error of THIS hi (conv_common.h, split2)
-      const _Float16 hb = (_Float16)vj;
-      h[j] = hb;
-      l[j] = (_Float16)(vj - (float)hb);
-    }
-    hi[u] = __builtin_bit_cast(bf16x8, h);
-    if (lo != nullptr) lo[u] = __builtin_bit_cast(bf16x8, l);
-    return;
-  }
-  bf16x8 h, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 hb = (__bf16)v[j];
-    h[j] = hb;
-    l[j] = (__bf16)(v[j] - (float)hb);
-  }
-  hi[u] = h;
-  if (lo != nullptr) lo[u] = l;
-}
 
 // thread = pixel; grid (ceil(HW / 256), batch).  Two passes over the pixel's channels (the second one hits the cache)
 __global__ __launch_bounds__(256) void rmsnorm_torch_kernel(const f32x4* __restrict__ x, int64_t HW, int C, float eps, const float* __restrict__ weight,
@@ -357,8 +314,6 @@ __global__ __launch_bounds__(256) void fla_apply_kernel(const FlaParams p, const
   }
 }
 
-bool gt_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
 int64_t fla_chunks(int64_t tokens) { return (tokens + FLA_CHUNK - 1) / FLA_CHUNK; }
 int64_t fla_rec(int d) { return (int64_t)FLA_HEADS * d * d + FLA_HEADS * d; }
 
@@ -370,17 +325,17 @@ int fla_check(const FlaParams* p, const char* what, bool apply) {
   };
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1) return fail(RSA_E_ARG, "bad geometry");
   if (p->head_dim != 24 && p->head_dim != 48) return fail(RSA_E_UNSUPPORTED, "head_dim must be 24 or 48 (eight heads)");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return fail(RSA_E_ARG, "fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt)) return fail(RSA_E_ARG, "fmt must be an rsa_plane_fmt");
   if (!p->qkv_hi || !p->scale || !p->factor || !p->workspace) return fail(RSA_E_ARG, "null operand");
   const int64_t N = (int64_t)p->H * p->W;
   if (N > 0x7fffffff / 4) return fail(RSA_E_UNSUPPORTED, "map too large");
   if (p->qkv_plane_stride < N) return fail(RSA_E_ARG, "the qkv plane stride is smaller than the map");
   if (p->workspace_bytes < rsa_fla_workspace_bytes(p->batch, (int32_t)N, p->head_dim)) return fail(RSA_E_ARG, "workspace too small (rsa_fla_workspace_bytes)");
-  if (gt_misaligned(p->qkv_hi) || gt_misaligned(p->qkv_lo) || gt_misaligned(p->workspace)) return fail(RSA_E_ALIGN, "planes and the workspace must be 16-byte aligned");
+  if (misaligned16(p->qkv_hi) || misaligned16(p->qkv_lo) || misaligned16(p->workspace)) return fail(RSA_E_ALIGN, "planes and the workspace must be 16-byte aligned");
   if (apply) {
     if (!p->out_hi || !p->dwc_weight || !p->dwc_bias) return fail(RSA_E_ARG, "null operand");
     if (p->out_plane_stride < N) return fail(RSA_E_ARG, "the output plane stride is smaller than the map");
-    if (gt_misaligned(p->out_hi) || gt_misaligned(p->out_lo)) return fail(RSA_E_ALIGN, "planes must be 16-byte aligned");
+    if (misaligned16(p->out_hi) || misaligned16(p->out_lo)) return fail(RSA_E_ALIGN, "planes must be 16-byte aligned");
   }
   return RSA_OK;
 }
@@ -393,41 +348,38 @@ using namespace rsa;
 extern "C" int rsa_rmsnorm_torch(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, float eps, const float* weight, void* out_hi, void* out_lo,
                                  int64_t out_plane_stride, int64_t out_batch_stride, int32_t fmt, void* stream) {
   if (!x_f32 || !weight || !out_hi || batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 1 || !(eps >= 0.f)) return set_error(RSA_E_ARG, "rmsnorm_torch: bad argument");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "rmsnorm_torch: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "rmsnorm_torch: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (out_plane_stride < HW) return set_error(RSA_E_ARG, "rmsnorm_torch: the plane stride is smaller than the map");
-  if (gt_misaligned(x_f32) || gt_misaligned(out_hi) || gt_misaligned(out_lo)) return set_error(RSA_E_ALIGN, "rmsnorm_torch: maps must be 16-byte aligned");
+  if (misaligned16(x_f32) || misaligned16(out_hi) || misaligned16(out_lo)) return set_error(RSA_E_ALIGN, "rmsnorm_torch: maps must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "rmsnorm_torch: map too large");
   hipLaunchKernelGGL(rmsnorm_torch_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const f32x4*)x_f32, HW, (int)C, eps,
                      weight, (bf16x8*)out_hi, (bf16x8*)out_lo, out_plane_stride, out_batch_stride, (int)fmt);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "rmsnorm_torch: launch failed") : RSA_OK;
+  return launch_status("rmsnorm_torch: launch failed");
 }
 
 extern "C" int rsa_pixel_unshuffle2(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, float* out_f32, void* stream) {
   if (!x_f32 || !out_f32 || batch < 1 || batch > 65535 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 4 || (C & 3) || C / 4 > 65535)
     return set_error(RSA_E_ARG, "pixel_unshuffle2: bad argument (even H and W, C a multiple of 4)");
   if (x_f32 == out_f32) return set_error(RSA_E_ARG, "pixel_unshuffle2: not in place");
-  if (gt_misaligned(x_f32) || gt_misaligned(out_f32)) return set_error(RSA_E_ALIGN, "pixel_unshuffle2: maps must be 16-byte aligned");
+  if (misaligned16(x_f32) || misaligned16(out_f32)) return set_error(RSA_E_ALIGN, "pixel_unshuffle2: maps must be 16-byte aligned");
   const int64_t hw = (int64_t)(H / 2) * (W / 2);
   if ((hw + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "pixel_unshuffle2: map too large");
   hipLaunchKernelGGL(pixel_unshuffle2_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)(C / 4), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
                      (const f32x4*)x_f32, (int)H, (int)W, (int)(C / 4), (f32x4*)out_f32);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "pixel_unshuffle2: launch failed") : RSA_OK;
+  return launch_status("pixel_unshuffle2: launch failed");
 }
 
 extern "C" int rsa_f32map_concat(const float* a_nchw, int32_t Ca, const float* b_map, int32_t Cb, int32_t batch, int32_t H, int32_t W, float* out_map, void* stream) {
   if (!a_nchw || !b_map || !out_map || batch < 1 || batch > 65535 || H < 1 || W < 1 || Ca < 4 || Cb < 4 || (Ca & 3) || (Cb & 3) || (Ca + Cb) / 4 > 65535)
     return set_error(RSA_E_ARG, "f32map_concat: bad argument (channel counts are multiples of 4)");
   if (out_map == a_nchw || out_map == b_map) return set_error(RSA_E_ARG, "f32map_concat: not in place");
-  if (gt_misaligned(b_map) || gt_misaligned(out_map) || ((uintptr_t)a_nchw & 3)) return set_error(RSA_E_ALIGN, "f32map_concat: maps must be 16-byte aligned");
+  if (misaligned16(b_map) || misaligned16(out_map) || ((uintptr_t)a_nchw & 3)) return set_error(RSA_E_ALIGN, "f32map_concat: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "f32map_concat: map too large");
   hipLaunchKernelGGL(f32map_concat_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)((Ca + Cb) / 4), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, a_nchw,
                      (int)(Ca / 4), (const f32x4*)b_map, (int)(Cb / 4), HW, (f32x4*)out_map);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "f32map_concat: launch failed") : RSA_OK;
+  return launch_status("f32map_concat: launch failed");
 }
 
 // workspace: [batch][REC] finished KV / mean(k), then [batch][chunks][REC] partials (REC = 8 d d + 8 d floats, a multiple of 4)
@@ -482,6 +434,5 @@ extern "C" int rsa_fla_apply(const void* qkv_hi, const void* qkv_lo, int64_t qkv
     hipLaunchKernelGGL(fla_apply_kernel<24>, grid, dim3(256), 0, s, *p, (const float*)p->workspace);
   else
     hipLaunchKernelGGL(fla_apply_kernel<48>, grid, dim3(256), 0, s, *p, (const float*)p->workspace);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "fla_apply: launch failed") : RSA_OK;
+  return launch_status("fla_apply: launch failed");
 }

@@ -244,7 +244,6 @@ __global__ __launch_bounds__(GK_WAVES * 64, GK_MINW(PROD, NQ)) void gemm_k1_kern
               split2<RSA_PF_F16>(v[2], v[3], h[e][1], lo_unused);
             }
             if (has_pl) {  // uniform
-              typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
               const u32x2 h0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
               const u32x2 h1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
               const int pt = pp * 2 + (lg & 1);
@@ -287,7 +286,6 @@ __global__ __launch_bounds__(GK_WAVES * 64, GK_MINW(PROD, NQ)) void gemm_k1_kern
               split2<RSA_PF_F16>(v[0], v[1], h[e][0], lo_unused);
               split2<RSA_PF_F16>(v[2], v[3], h[e][1], lo_unused);
             }
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
             const u32x2 h0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
             const u32x2 h1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
             const int pt = pp * 2 + (lg & 1);  // the pixel tile whose whole unit this lane stores
@@ -364,7 +362,6 @@ __global__ __launch_bounds__(GK_WAVES * 64, GK_MINW(PROD, NQ)) void gemm_k1_kern
                 split2_rt(p.out_fmt == RSA_PF_F16, v[e][0], v[e][1], h[e][0], l[e][0]);
                 split2_rt(p.out_fmt == RSA_PF_F16, v[e][2], v[e][3], h[e][1], l[e][1]);
               }
-              typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
               const u32x2 h0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
               const u32x2 h1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
               const int odd = lg & 1;

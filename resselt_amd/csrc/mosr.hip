@@ -6,61 +6,11 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ void get_unit(const bf16x8* hi, const bf16x8* lo, int64_t u, float (&v)[8], int fmt) {
-  const bf16x8 h = hi[u];
-  bf16x8 l = {};
-  if (lo != nullptr) l = lo[u];
-  if (fmt == RSA_PF_F16) {
-    const f16x8 hf = __builtin_bit_cast(f16x8, h), lf = __builtin_bit_cast(f16x8, l);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)hf[j] + (lo != nullptr ? (float)lf[j] : 0.f);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (lo != nullptr ? (float)l[j] : 0.f);
-  }
-}
-
-__device__ __forceinline__ void put_unit(bf16x8* hi, bf16x8* lo, int64_t u, const float (&v)[8], int fmt) {
-  if (fmt == RSA_PF_F16) {
-    f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float vj = v[j];
-      asm("" : "+v"(vj));  // opaque: the lo half is the rounding error of THIS hi (conv_common.h, split2)
-      const _Float16 hb = (_Float16)vj;
-      h[j] = hb;
-      l[j] = (_Float16)(vj - (float)hb);
-    }
-    hi[u] = __builtin_bit_cast(bf16x8, h);
-    if (lo != nullptr) lo[u] = __builtin_bit_cast(bf16x8, l);
-    return;
-  }
-  bf16x8 h, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 hb = (__bf16)v[j];
-    h[j] = hb;
-    l[j] = (__bf16)(v[j] - (float)hb);
-  }
-  hi[u] = h;
-  if (lo != nullptr) lo[u] = l;
-}
-
-__device__ __forceinline__ float ms_mish(float v) {
-  if (v > 20.f) return v;
-  const float e = expf(v);
-  const float t = e * (e + 2.f);
-  return v * (t / (t + 2.f));
-}
 
 // A workgroup is a TW x TH pixel tile of one output plane (a 2-D tile, not a row: dat.hip dwconv_kernel, round 4 -- the rows a row-shaped
 // workgroup reads were fetched by neighbouring workgroups on other XCDs).  A convolution plane stages its (TH + kh - 1) x (TW + kw - 1) halo
@@ -82,7 +32,7 @@ __device__ __forceinline__ void finish(const Operands& o, int64_t pix, const flo
   float g[8], r[8];
   get_unit(o.g_hi, o.g_lo, pix, g, fmt);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = ms_mish(g[j]) * m[j];
+  for (int j = 0; j < 8; ++j) r[j] = mish_exact(g[j]) * m[j];
   put_unit(o.o_hi, o.o_lo, pix, r, fmt);
 }
 
@@ -239,8 +189,6 @@ __global__ __launch_bounds__(256) void bilinear_add_kernel(const rsa_bilinear_ad
   st_elem(p.out, oi, ld_elem(p.out, oi, p.dtype) + v, p.dtype);
 }
 
-bool ms_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
 }  // namespace
 }  // namespace rsa
 
@@ -249,7 +197,7 @@ using namespace rsa;
 extern "C" int rsa_gated_dwconv(const rsa_gated_dwconv_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "gated_dwconv: null params");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->i_planes < 0 || p->n_segments < 0 || p->n_segments > 4 ||
-      (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16))
+      !plane_fmt_ok(p->fmt))
     return set_error(RSA_E_ARG, "gated_dwconv: bad geometry");
   int64_t planes = p->i_planes;
   for (int s = 0; s < p->n_segments; ++s) {
@@ -262,14 +210,13 @@ extern "C" int rsa_gated_dwconv(const rsa_gated_dwconv_params* p, void* stream) 
   }
   if (planes < 1 || planes > 65535) return set_error(RSA_E_ARG, "gated_dwconv: total planes must be in [1, 65535]");
   if (!p->g_hi || !p->x_hi || !p->out_hi) return set_error(RSA_E_ARG, "gated_dwconv: null pointer");
-  if (ms_misaligned(p->g_hi) || ms_misaligned(p->g_lo) || ms_misaligned(p->x_hi) || ms_misaligned(p->x_lo) || ms_misaligned(p->out_hi) ||
-      ms_misaligned(p->out_lo))
+  if (misaligned16(p->g_hi) || misaligned16(p->g_lo) || misaligned16(p->x_hi) || misaligned16(p->x_lo) || misaligned16(p->out_hi) ||
+      misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "gated_dwconv: planes must be 16-byte aligned");
   const int64_t tiles = (int64_t)((p->W + TW - 1) / TW) * ((p->H + TH - 1) / TH);
   if (tiles > 0x7fffffff) return set_error(RSA_E_ARG, "gated_dwconv: map too large");
   hipLaunchKernelGGL(gated_dwconv_kernel, dim3((unsigned)tiles, (unsigned)planes, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "gated_dwconv: launch failed") : RSA_OK;
+  return launch_status("gated_dwconv: launch failed");
 }
 
 extern "C" int rsa_bilinear_add(const rsa_bilinear_add_params* p, void* stream) {
@@ -283,6 +230,5 @@ extern "C" int rsa_bilinear_add(const rsa_bilinear_add_params* p, void* stream) 
   const float rscale = (float)(1.0 / p->scale);
   hipLaunchKernelGGL(bilinear_add_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)p->C, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p,
                      rscale);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "bilinear_add: launch failed") : RSA_OK;
+  return launch_status("bilinear_add: launch failed");
 }

@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
@@ -20,30 +20,6 @@ namespace {
 constexpr int OM_MAXD = 32;     // channels of a head
 constexpr int OM_MAXTOK = 64;   // tokens of a window (ws <= 8) and of a channel-attention chunk
 constexpr int OM_MAXHEADS = 8;
-
-bool om_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
-template <int FMT>
-__device__ __forceinline__ void om_load(const char* hi, const char* lo, int64_t off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + off);
-  const uint4 l = lo ? *(const uint4*)(lo + off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
-template <int FMT>
-__device__ __forceinline__ void om_store(char* hi, char* lo, int64_t off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-__device__ __forceinline__ float om_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-__device__ __forceinline__ float om_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 
 // byte offset of (image n, plane pl, pixel pix) in a split-plane buffer
 __device__ __forceinline__ int64_t om_off(int64_t n, int64_t batch_stride, int64_t pl, int64_t plane_stride, int64_t pix) {
@@ -59,30 +35,7 @@ __device__ __forceinline__ int64_t om_off(int64_t n, int64_t batch_stride, int64
 // side along x, in grid mode NW windows whose tokens are NEIGHBOURING pixels (token (r, c) of window (wy, wx) sits at pixel
 // (r H/ws + wy, c W/ws + wx)).  The q / k / v units of the NW windows are staged in LDS by the whole workgroup with the window index (grid)
 // or the in-window column (block) fastest, so the global reads come in runs of adjacent pixels.  KS = K steps of 16 head channels.
-typedef __attribute__((ext_vector_type(16))) float om_f32x16;
-typedef __attribute__((ext_vector_type(8))) _Float16 om_f16x8;
 
-template <int FMT>
-__device__ __forceinline__ om_f32x16 om_mfma32(const bf16x8 a, const bf16x8 b, const om_f32x16 c) {
-  if constexpr (FMT == RSA_PF_F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(om_f16x8, a), __builtin_bit_cast(om_f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-template <int FMT>
-__device__ __forceinline__ bf16x8 om_pack16(const float (&v)[8]) {
-  if constexpr (FMT == RSA_PF_F16) {
-    om_f16x8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
-    return __builtin_bit_cast(bf16x8, h);
-  } else {
-    bf16x8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (__bf16)v[j];
-    return r;
-  }
-}
 template <int FMT>
 __device__ __forceinline__ float om_f16v(__bf16 v) {
   if constexpr (FMT == RSA_PF_F16)
@@ -180,11 +133,11 @@ __global__ __launch_bounds__(64 * OmWinCfg<KS>::NW) void omni_window_attn_kernel
       ql[s] = PROD == 3 ? *(const bf16x8*)&s_q[NHL - 1][wave][q * KROW + (2 * s + lh) * 8] : zero8;
     }
     float m = -INFINITY, l = 0.f;
-    om_f32x16 ot;
+    f32x16 ot;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ot[r] = 0.f;
     for (int kt = 0; kt < QT; ++kt) {
-      om_f32x16 a;
+      f32x16 a;
 #pragma unroll
       for (int r = 0; r < 16; ++r) a[r] = 0.f;
 #pragma unroll
@@ -193,10 +146,10 @@ __global__ __launch_bounds__(64 * OmWinCfg<KS>::NW) void omni_window_attn_kernel
         const bf16x8 kh = *(const bf16x8*)&s_k[0][wave][off];
         if (PROD == 3) {
           const bf16x8 kl = *(const bf16x8*)&s_k[NHL - 1][wave][off];
-          a = om_mfma32<FMT>(kl, qh[s], a);
-          a = om_mfma32<FMT>(kh, ql[s], a);
+          a = mfma32<FMT>(kl, qh[s], a);
+          a = mfma32<FMT>(kh, ql[s], a);
         }
-        a = om_mfma32<FMT>(kh, qh[s], a);
+        a = mfma32<FMT>(kh, qh[s], a);
       }
       float tm = -INFINITY;
 #pragma unroll
@@ -245,16 +198,16 @@ __global__ __launch_bounds__(64 * OmWinCfg<KS>::NW) void omni_window_attn_kernel
         float e8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) e8[j] = a[8 * s + j];
-        const bf16x8 ph = om_pack16<FMT>(e8);
+        const bf16x8 ph = pack16<FMT>(e8);
         if (PROD == 3) {
           float r8[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) r8[j] = e8[j] - om_f16v<FMT>(ph[j]);
-          const bf16x8 pl = om_pack16<FMT>(r8);
-          ot = om_mfma32<FMT>(vl, ph, ot);
-          ot = om_mfma32<FMT>(vh, pl, ot);
+          const bf16x8 pl = pack16<FMT>(r8);
+          ot = mfma32<FMT>(vl, ph, ot);
+          ot = mfma32<FMT>(vh, pl, ot);
         }
-        ot = om_mfma32<FMT>(vh, ph, ot);
+        ot = mfma32<FMT>(vh, ph, ot);
       }
     }
     const float lsum = l + __shfl_xor(l, 32);
@@ -329,8 +282,8 @@ __global__ __launch_bounds__(256) void omni_chan_gram_kernel(const rsa_omni_attn
 #pragma unroll
       for (int j = 0; j < 8; ++j) a[j] = b[j] = 0.f;
       if (pl < hp && live) {
-        om_load<FMT>((const char*)p.qkv_hi, (const char*)p.qkv_lo, om_off(n, p.qkv_batch_stride, h * hp + pl, p.qkv_plane_stride, pix), a);
-        om_load<FMT>((const char*)p.qkv_hi, (const char*)p.qkv_lo, om_off(n, p.qkv_batch_stride, (p.heads + h) * hp + pl, p.qkv_plane_stride, pix), b);
+        load_unit<FMT>((const char*)p.qkv_hi, (const char*)p.qkv_lo, om_off(n, p.qkv_batch_stride, h * hp + pl, p.qkv_plane_stride, pix), a);
+        load_unit<FMT>((const char*)p.qkv_hi, (const char*)p.qkv_lo, om_off(n, p.qkv_batch_stride, (p.heads + h) * hp + pl, p.qkv_plane_stride, pix), b);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) sq[t][pl * 8 + j] = a[j], sk[t][pl * 8 + j] = b[j];
@@ -408,7 +361,7 @@ __global__ __launch_bounds__(256) void omni_chan_apply_kernel(const rsa_omni_att
     float a[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) a[j] = 0.f;
-    if (pl < hp) om_load<FMT>((const char*)p.qkv_hi, (const char*)p.qkv_lo, om_off(n, p.qkv_batch_stride, (2 * p.heads + h) * hp + pl, p.qkv_plane_stride, pix), a);
+    if (pl < hp) load_unit<FMT>((const char*)p.qkv_hi, (const char*)p.qkv_lo, om_off(n, p.qkv_batch_stride, (2 * p.heads + h) * hp + pl, p.qkv_plane_stride, pix), a);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[pl * 8 + j] = a[j];
   }
@@ -427,7 +380,7 @@ __global__ __launch_bounds__(256) void omni_chan_apply_kernel(const rsa_omni_att
         }
         o[j] = s;
       }
-      om_store<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, h * hp + pl, p.out_plane_stride, pix), o);
+      store_unit<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, h * hp + pl, p.out_plane_stride, pix), o);
     }
   }
 }
@@ -455,9 +408,9 @@ __global__ __launch_bounds__(256) void omni_chan_window_kernel(const rsa_omni_at
 #pragma unroll
       for (int j = 0; j < 8; ++j) a[j] = b[j] = c[j] = 0.f;
       if (pl < hp && live) {
-        om_load<FMT>(qhi, qlo, om_off(n, p.qkv_batch_stride, h * hp + pl, p.qkv_plane_stride, pix), a);
-        om_load<FMT>(qhi, qlo, om_off(n, p.qkv_batch_stride, (p.heads + h) * hp + pl, p.qkv_plane_stride, pix), b);
-        om_load<FMT>(qhi, qlo, om_off(n, p.qkv_batch_stride, (2 * p.heads + h) * hp + pl, p.qkv_plane_stride, pix), c);
+        load_unit<FMT>(qhi, qlo, om_off(n, p.qkv_batch_stride, h * hp + pl, p.qkv_plane_stride, pix), a);
+        load_unit<FMT>(qhi, qlo, om_off(n, p.qkv_batch_stride, (p.heads + h) * hp + pl, p.qkv_plane_stride, pix), b);
+        load_unit<FMT>(qhi, qlo, om_off(n, p.qkv_batch_stride, (2 * p.heads + h) * hp + pl, p.qkv_plane_stride, pix), c);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) sq[t][pl * 8 + j] = a[j], sk[t][pl * 8 + j] = b[j], sv[t][pl * 8 + j] = c[j];
@@ -510,7 +463,7 @@ __global__ __launch_bounds__(256) void omni_chan_window_kernel(const rsa_omni_at
       for (int c2 = 0; c2 < d; ++c2) s = fmaf(sa[c1][c2], sv[tok][c2], s);
     o[j] = s;
   }
-  om_store<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, h * hp + pl, p.out_plane_stride, om_token_pixel(p, set, tok)), o);
+  store_unit<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, h * hp + pl, p.out_plane_stride, om_token_pixel(p, set, tok)), o);
 }
 
 // ------------------------------------------------------------------------------------------------ gated FFN middle
@@ -533,8 +486,8 @@ __global__ __launch_bounds__(256) void gelu_gate_dwconv_kernel(const rsa_gelu_ga
     if (yy < 0 || yy >= p.H || xx < 0 || xx >= p.W) continue;
     const int64_t q = (int64_t)yy * p.W + xx;
     float u[8], v[8];
-    om_load<FMT>((const char*)p.in_hi, (const char*)p.in_lo, om_off(n, p.in_batch_stride, pl, p.in_plane_stride, q), u);
-    om_load<FMT>((const char*)p.in_hi, (const char*)p.in_lo, om_off(n, p.in_batch_stride, p.planes + pl, p.in_plane_stride, q), v);
+    load_unit<FMT>((const char*)p.in_hi, (const char*)p.in_lo, om_off(n, p.in_batch_stride, pl, p.in_plane_stride, q), u);
+    load_unit<FMT>((const char*)p.in_hi, (const char*)p.in_lo, om_off(n, p.in_batch_stride, p.planes + pl, p.in_plane_stride, q), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       a[j] = fmaf(w1[j * 9 + tap], u[j], a[j]);
@@ -543,8 +496,8 @@ __global__ __launch_bounds__(256) void gelu_gate_dwconv_kernel(const rsa_gelu_ga
   }
   float o[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = om_gelu(a[j]) * b[j];
-  om_store<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, pl, p.out_plane_stride, pix), o);
+  for (int j = 0; j < 8; ++j) o[j] = gelu_erf(a[j]) * b[j];
+  store_unit<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, pl, p.out_plane_stride, pix), o);
 }
 
 // ------------------------------------------------------------------------------------------------ SE apply
@@ -557,10 +510,10 @@ __global__ __launch_bounds__(256) void omni_gate_scale_kernel(const char* ihi, c
   const int64_t off = om_off(n, batch_stride, pl, plane_stride, pix);
   const float* g = gate + ((int64_t)n * planes + pl) * 8;
   float v[8];
-  om_load<FMT>(ihi, ilo, off, v);
+  load_unit<FMT>(ihi, ilo, off, v);
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] *= g[j];
-  om_store<FMT>(ohi, olo, off, v);
+  store_unit<FMT>(ohi, olo, off, v);
 }
 
 // ------------------------------------------------------------------------------------------------ ESA
@@ -656,17 +609,17 @@ __global__ __launch_bounds__(256) void esa_apply_kernel(const rsa_esa_apply_para
 #pragma unroll
         for (int k = 0; k < ESA_MAXF; ++k)
           if (k < f) s = fmaf(s_w4[c * f + k], u[k], s);
-        v = p.x[m4(n, p4, c, HW, pix)] * om_sigmoid(s);
+        v = p.x[m4(n, p4, c, HW, pix)] * sigmoid_exact(s);
       }
       o[j] = v;
       if (c < 4 * p4) p.out[m4(n, p4, c, HW, pix)] = v;
     }
-    if (p.out_hi) om_store<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, pl, p.out_plane_stride, pix), o);
+    if (p.out_hi) store_unit<FMT>((char*)p.out_hi, (char*)p.out_lo, om_off(n, p.out_batch_stride, pl, p.out_plane_stride, pix), o);
   }
 }
 
 int om_planes_ok(const void* hi, const void* lo, int64_t plane_stride, int64_t batch_stride, int64_t HW, int planes) {
-  if (om_misaligned(hi) || om_misaligned(lo)) return RSA_E_ALIGN;
+  if (misaligned16(hi) || misaligned16(lo)) return RSA_E_ALIGN;
   if (plane_stride < HW || batch_stride < (int64_t)planes * plane_stride) return RSA_E_ARG;
   return RSA_OK;
 }
@@ -678,7 +631,7 @@ int om_attn_check(const rsa_omni_attn_params* p, const char* who, bool channel) 
   if (p->heads < 1 || p->heads > OM_MAXHEADS || p->head_dim < 1 || p->head_dim > OM_MAXD)
     return set_error(RSA_E_UNSUPPORTED, "omni attention: heads 1..8 and head_dim 1..32");
   if (!channel && (p->ws < 2 || p->ws * p->ws > OM_MAXTOK)) return set_error(RSA_E_UNSUPPORTED, "omni window attention: ws must be 2..8");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "omni attention: bad plane format");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "omni attention: bad plane format");
   if (!p->qkv_hi || !p->out_hi || (p->out_lo && !p->out_hi)) return set_error(RSA_E_ARG, "omni attention: null operand");
   const bool one_launch = !p->grid && p->ws * p->ws <= OM_MAXTOK;  // window-mode channel attention needs no workspace
   if (channel ? (!p->temperature || (!p->workspace && !one_launch) || p->bias_table) : (p->temperature || p->workspace))
@@ -717,8 +670,7 @@ extern "C" int rsa_omni_window_attention(const rsa_omni_attn_params* p, void* st
     else { if (three) OM_WGO(2, 3, RSA_PF_BF16); else OM_WGO(2, 1, RSA_PF_BF16); }
   }
 #undef OM_WGO
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "omni_window_attention: launch failed") : RSA_OK;
+  return launch_status("omni_window_attention: launch failed");
 }
 
 extern "C" int64_t rsa_omni_channel_attn_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t ws, int32_t heads, int32_t head_dim, int32_t grid) {
@@ -739,35 +691,28 @@ extern "C" int rsa_omni_channel_attention(const rsa_omni_attn_params* p, void* s
   hipStream_t s = (hipStream_t)stream;
   if (!p->grid && p->ws * p->ws <= OM_MAXTOK) {
     const dim3 gw((unsigned)S.nsets, (unsigned)p->heads, (unsigned)p->batch);
-    if (p->fmt == RSA_PF_F16)
-      hipLaunchKernelGGL(omni_chan_window_kernel<RSA_PF_F16>, gw, dim3(256), 0, s, *p);
-    else
-      hipLaunchKernelGGL(omni_chan_window_kernel<RSA_PF_BF16>, gw, dim3(256), 0, s, *p);
-    const hipError_t rc = hipGetLastError();
-    return rc ? set_error(rc, "omni_channel_attention: launch failed") : RSA_OK;
+    with_fmt(p->fmt, [&](auto F) {
+      hipLaunchKernelGGL(omni_chan_window_kernel<decltype(F)::value>, gw, dim3(256), 0, s, *p);
+    });
+    return launch_status("omni_channel_attention: launch failed");
   }
   const int64_t HW = (int64_t)p->H * p->W;
   const dim3 g1((unsigned)S.chunks, (unsigned)(S.nsets * p->heads), (unsigned)p->batch);
   const dim3 g2((unsigned)(S.nsets * p->heads), (unsigned)p->batch);
   const dim3 g3((unsigned)((HW + 255) / 256), (unsigned)p->heads, (unsigned)p->batch);
-  if (p->fmt == RSA_PF_F16) {
-    hipLaunchKernelGGL(omni_chan_gram_kernel<RSA_PF_F16>, g1, dim3(256), 0, s, *p, S);
+  with_fmt(p->fmt, [&](auto F) {
+    hipLaunchKernelGGL(omni_chan_gram_kernel<decltype(F)::value>, g1, dim3(256), 0, s, *p, S);
     hipLaunchKernelGGL(omni_chan_finish_kernel, g2, dim3(256), 0, s, *p, S);
-    hipLaunchKernelGGL(omni_chan_apply_kernel<RSA_PF_F16>, g3, dim3(256), 0, s, *p, S);
-  } else {
-    hipLaunchKernelGGL(omni_chan_gram_kernel<RSA_PF_BF16>, g1, dim3(256), 0, s, *p, S);
-    hipLaunchKernelGGL(omni_chan_finish_kernel, g2, dim3(256), 0, s, *p, S);
-    hipLaunchKernelGGL(omni_chan_apply_kernel<RSA_PF_BF16>, g3, dim3(256), 0, s, *p, S);
-  }
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "omni_channel_attention: launch failed") : RSA_OK;
+    hipLaunchKernelGGL(omni_chan_apply_kernel<decltype(F)::value>, g3, dim3(256), 0, s, *p, S);
+  });
+  return launch_status("omni_channel_attention: launch failed");
 }
 
 extern "C" int rsa_gelu_gate_dwconv(const rsa_gelu_gate_dwconv_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "gelu_gate_dwconv: null params");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->planes < 1 || p->planes > 65535 || p->reserved0 != 0)
     return set_error(RSA_E_ARG, "gelu_gate_dwconv: bad geometry (reserved0 must be 0)");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "gelu_gate_dwconv: bad plane format");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "gelu_gate_dwconv: bad plane format");
   if (!p->in_hi || !p->weight || !p->out_hi) return set_error(RSA_E_ARG, "gelu_gate_dwconv: null operand");
   const int64_t HW = (int64_t)p->H * p->W;
   int rc0 = om_planes_ok(p->in_hi, p->in_lo, p->in_plane_stride, p->in_batch_stride, HW, 2 * p->planes);
@@ -776,18 +721,16 @@ extern "C" int rsa_gelu_gate_dwconv(const rsa_gelu_gate_dwconv_params* p, void* 
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "gelu_gate_dwconv: map too large");
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)p->planes, (unsigned)p->batch);
-  if (p->fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(gelu_gate_dwconv_kernel<RSA_PF_F16>, grid, dim3(256), 0, s, *p);
-  else
-    hipLaunchKernelGGL(gelu_gate_dwconv_kernel<RSA_PF_BF16>, grid, dim3(256), 0, s, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "gelu_gate_dwconv: launch failed") : RSA_OK;
+  with_fmt(p->fmt, [&](auto F) {
+    hipLaunchKernelGGL(gelu_gate_dwconv_kernel<decltype(F)::value>, grid, dim3(256), 0, s, *p);
+  });
+  return launch_status("gelu_gate_dwconv: launch failed");
 }
 
 extern "C" int rsa_omni_gate_scale(const void* in_hi, const void* in_lo, int64_t plane_stride, int64_t batch_stride, int32_t batch, int32_t H, int32_t W,
                                    int32_t planes, const float* gate, int32_t fmt, void* out_hi, void* out_lo, void* stream) {
   if (!in_hi || !gate || !out_hi) return set_error(RSA_E_ARG, "omni_gate_scale: null operand");
-  if (batch < 1 || batch > 65535 || H < 1 || W < 1 || planes < 1 || planes > 65535 || (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) || (in_lo == nullptr) != (out_lo == nullptr))
+  if (batch < 1 || batch > 65535 || H < 1 || W < 1 || planes < 1 || planes > 65535 || !plane_fmt_ok(fmt) || (in_lo == nullptr) != (out_lo == nullptr))
     return set_error(RSA_E_ARG, "omni_gate_scale: bad geometry or plane format (lo planes on both sides or neither)");
   const int64_t HW = (int64_t)H * W;
   int rc0 = om_planes_ok(in_hi, in_lo, plane_stride, batch_stride, HW, planes);
@@ -796,14 +739,11 @@ extern "C" int rsa_omni_gate_scale(const void* in_hi, const void* in_lo, int64_t
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "omni_gate_scale: map too large");
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)planes, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(omni_gate_scale_kernel<RSA_PF_F16>, grid, dim3(256), 0, s, (const char*)in_hi, (const char*)in_lo, plane_stride, batch_stride, HW, planes,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(omni_gate_scale_kernel<decltype(F)::value>, grid, dim3(256), 0, s, (const char*)in_hi, (const char*)in_lo, plane_stride, batch_stride, HW, planes,
                        gate, (char*)out_hi, (char*)out_lo);
-  else
-    hipLaunchKernelGGL(omni_gate_scale_kernel<RSA_PF_BF16>, grid, dim3(256), 0, s, (const char*)in_hi, (const char*)in_lo, plane_stride, batch_stride, HW, planes,
-                       gate, (char*)out_hi, (char*)out_lo);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "omni_gate_scale: launch failed") : RSA_OK;
+  });
+  return launch_status("omni_gate_scale: launch failed");
 }
 
 extern "C" int rsa_esa_conv3x3(const rsa_esa_conv_params* p, void* stream) {
@@ -814,33 +754,31 @@ extern "C" int rsa_esa_conv3x3(const rsa_esa_conv_params* p, void* stream) {
   if (p->H + 2 * p->pad < 3 || p->W + 2 * p->pad < 3 || p->Hout != (p->H + 2 * p->pad - 3) / p->stride + 1 || p->Wout != (p->W + 2 * p->pad - 3) / p->stride + 1)
     return set_error(RSA_E_ARG, "esa_conv3x3: Hout / Wout do not match the geometry");
   if (!p->in || !p->weight || !p->bias || !p->out) return set_error(RSA_E_ARG, "esa_conv3x3: null operand");
-  if (om_misaligned(p->in) || om_misaligned(p->out)) return set_error(RSA_E_ALIGN, "esa_conv3x3: maps must be 16-byte aligned");
+  if (misaligned16(p->in) || misaligned16(p->out)) return set_error(RSA_E_ALIGN, "esa_conv3x3: maps must be 16-byte aligned");
   const int64_t HWo = (int64_t)p->Hout * p->Wout;
   if ((HWo + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "esa_conv3x3: map too large");
   hipLaunchKernelGGL(esa_conv_kernel, dim3((unsigned)((HWo + 255) / 256), (unsigned)p->cout, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "esa_conv3x3: launch failed") : RSA_OK;
+  return launch_status("esa_conv3x3: launch failed");
 }
 
 extern "C" int rsa_esa_maxpool(const float* in, int32_t batch, int32_t C, int32_t H, int32_t W, float* out, void* stream) {
   if (!in || !out) return set_error(RSA_E_ARG, "esa_maxpool: null operand");
   if (batch < 1 || batch > 65535 || C < 1 || C > 65535 || H < 7 || W < 7) return set_error(RSA_E_ARG, "esa_maxpool: bad geometry (H, W >= 7)");
-  if (om_misaligned(in) || om_misaligned(out)) return set_error(RSA_E_ALIGN, "esa_maxpool: maps must be 16-byte aligned");
+  if (misaligned16(in) || misaligned16(out)) return set_error(RSA_E_ALIGN, "esa_maxpool: maps must be 16-byte aligned");
   const int Ho = (H - 7) / 3 + 1, Wo = (W - 7) / 3 + 1;
   const int64_t HWo = (int64_t)Ho * Wo;
   hipLaunchKernelGGL(esa_maxpool_kernel, dim3((unsigned)((HWo + 255) / 256), (unsigned)C, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, in, C, H, W, Ho,
                      Wo, out);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "esa_maxpool: launch failed") : RSA_OK;
+  return launch_status("esa_maxpool: launch failed");
 }
 
 extern "C" int rsa_esa_apply(const rsa_esa_apply_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "esa_apply: null params");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->Hc < 1 || p->Wc < 1 || p->C < 1 || p->C > ESA_MAXC || p->f < 1 || p->f > ESA_MAXF)
     return set_error(RSA_E_ARG, "esa_apply: bad geometry (C 1..128, f 1..32)");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "esa_apply: bad plane format");
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "esa_apply: bad plane format");
   if (!p->x || !p->c1 || !p->c3 || !p->wf || !p->bf || !p->w4 || !p->b4 || !p->out || (p->out_lo && !p->out_hi)) return set_error(RSA_E_ARG, "esa_apply: null operand");
-  if (om_misaligned(p->x) || om_misaligned(p->c1) || om_misaligned(p->c3) || om_misaligned(p->out)) return set_error(RSA_E_ALIGN, "esa_apply: maps must be 16-byte aligned");
+  if (misaligned16(p->x) || misaligned16(p->c1) || misaligned16(p->c3) || misaligned16(p->out)) return set_error(RSA_E_ALIGN, "esa_apply: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   if (p->out_hi) {
     const int rc0 = om_planes_ok(p->out_hi, p->out_lo, p->out_plane_stride, p->out_batch_stride, HW, (p->C + 7) / 8);
@@ -849,10 +787,8 @@ extern "C" int rsa_esa_apply(const rsa_esa_apply_params* p, void* stream) {
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "esa_apply: map too large");
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)p->batch);
-  if (p->fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(esa_apply_kernel<RSA_PF_F16>, grid, dim3(256), 0, s, *p);
-  else
-    hipLaunchKernelGGL(esa_apply_kernel<RSA_PF_BF16>, grid, dim3(256), 0, s, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "esa_apply: launch failed") : RSA_OK;
+  with_fmt(p->fmt, [&](auto F) {
+    hipLaunchKernelGGL(esa_apply_kernel<decltype(F)::value>, grid, dim3(256), 0, s, *p);
+  });
+  return launch_status("esa_apply: launch failed");
 }

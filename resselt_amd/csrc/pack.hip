@@ -19,14 +19,13 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 pk_bf16x8;
-
-// one element -> (hi, lo) halves of plane format fmt, as 16-bit patterns
-__device__ __forceinline__ void split_elem(float v, int fmt, uint16_t& hi, uint16_t& lo) {
+// plane_unit.h's split_elem without its fence: the value here is a loaded weight, not the result of arithmetic, and the fence changes this kernel's code
+__device__ __forceinline__ void pk_split_elem(float v, int fmt, uint16_t& hi, uint16_t& lo) {
   if (fmt == RSA_PF_F16) {
     const _Float16 h = (_Float16)v;
     hi = __builtin_bit_cast(uint16_t, h);
@@ -97,7 +96,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, int cout, int c
       float v = 0.f;
       if (!zero && co < cout && ci < cin && plane < cin_planes) v = w[(((int64_t)co * cin + ci) * ksize + ky) * ksize + kx];
       uint16_t h, l;
-      split_elem(v, fmt, h, l);
+      pk_split_elem(v, fmt, h, l);
       hi[j] = h;
       lo[j] = l;
     }
@@ -119,7 +118,7 @@ __global__ void pack_weights_upphase_kernel(const float* __restrict__ w, int cou
   // taps (of the 3x3 kernel on the upsampled image) that read source row s / source column h of this phase
   const int ky0 = py == 0 ? (s == 0 ? 0 : 1) : (s == 0 ? 0 : 2), ky1 = py == 0 ? (s == 0 ? 0 : 2) : (s == 0 ? 1 : 2);
   const int kx0 = px == 0 ? (h == 0 ? 0 : 1) : (h == 0 ? 0 : 2), kx1 = px == 0 ? (h == 0 ? 0 : 2) : (h == 0 ? 1 : 2);
-  pk_bf16x8 hi, lo;
+  bf16x8 hi, lo;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int ci = 8 * plane + j;
@@ -132,8 +131,8 @@ __global__ void pack_weights_upphase_kernel(const float* __restrict__ w, int cou
     lo[j] = (__bf16)(v - (float)hb);
   }
   const int64_t frag = ((int64_t)t * 4 + ct) * 2;
-  ((pk_bf16x8*)out)[frag * 64 + lane] = hi;
-  ((pk_bf16x8*)out)[(frag + 1) * 64 + lane] = lo;
+  ((bf16x8*)out)[frag * 64 + lane] = hi;
+  ((bf16x8*)out)[(frag + 1) * 64 + lane] = lo;
 }
 
 int64_t packed_weight_bytes(int cout, int cin_planes, int ksize, int products, int layout) {
@@ -154,7 +153,7 @@ extern "C" int64_t rsa_packed_weight_bytes_layout(int32_t cout, int32_t cin_plan
 
 extern "C" int rsa_pack_weights(const float* w_oihw, int32_t cout, int32_t cin, int32_t cin_planes, int32_t ksize, int32_t products, int32_t layout,
                                 int32_t fmt, void* out, void* stream) {
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return rsa::set_error(RSA_E_ARG, "pack_weights: fmt must be an rsa_plane_fmt");
+  if (!rsa::plane_fmt_ok(fmt)) return rsa::set_error(RSA_E_ARG, "pack_weights: fmt must be an rsa_plane_fmt");
   if (w_oihw == nullptr || out == nullptr || cout < 1 || cin < 1 || cin_planes < 1) return rsa::set_error(RSA_E_ARG, "pack_weights: bad argument");
   if ((ksize != 1 && ksize != 3) || (products != 1 && products != 3)) return rsa::set_error(RSA_E_ARG, "pack_weights: ksize must be 1 or 3, products 1 or 3");
   if (cin > 8 * cin_planes) return rsa::set_error(RSA_E_ARG, "pack_weights: cin does not fit in cin_planes");
@@ -162,14 +161,13 @@ extern "C" int rsa_pack_weights(const float* w_oihw, int32_t cout, int32_t cin, 
   if (layout == rsa::RSA_WL_UPPHASE) {
     if (ksize != 3 || products != 3 || cin_planes != 8 || cout != 64 || fmt != RSA_PF_BF16)
       return rsa::set_error(RSA_E_UNSUPPORTED, "pack_weights: the upsampling-phase layout is for 3x3, 3-product, bf16, 64 -> 64 channel layers");
-    if ((uintptr_t)out & 15) return rsa::set_error(RSA_E_ALIGN, "pack_weights: out must be 16-byte aligned");
+    if (rsa::misaligned16(out)) return rsa::set_error(RSA_E_ALIGN, "pack_weights: out must be 16-byte aligned");
     hipLaunchKernelGGL(rsa::pack_weights_upphase_kernel, dim3(32), dim3(256), 0, (hipStream_t)stream, w_oihw, cout, cin, out);
-    const int rcu = (int)hipGetLastError();
-    return rcu ? rsa::set_error(rcu, "pack_weights: launch failed") : RSA_OK;
+    return rsa::launch_status("pack_weights: launch failed");
   }
   if (layout == rsa::RSA_WL_PAIRS && (ksize != 3 || (cin_planes & 3))) return rsa::set_error(RSA_E_UNSUPPORTED, "pack_weights: the tap-pair layout needs a 3x3 layer with whole 32-channel chunks");
   if (layout == rsa::RSA_WL_HALFPAIRS && (ksize != 3 || (cin_planes & 1))) return rsa::set_error(RSA_E_UNSUPPORTED, "pack_weights: the half-chunk tap-pair layout needs a 3x3 layer with an even number of input planes");
-  if ((uintptr_t)out & 15) return rsa::set_error(RSA_E_ALIGN, "pack_weights: out must be 16-byte aligned");
+  if (rsa::misaligned16(out)) return rsa::set_error(RSA_E_ALIGN, "pack_weights: out must be 16-byte aligned");
   const int nhl = products == 3 ? 2 : 1;
   const int64_t total = (layout == rsa::RSA_WL_HALFPAIRS ? (int64_t)(cin_planes / 2) * 5 : (int64_t)((cin_planes + 3) / 4) * ksize * ksize) * ((cout + 15) / 16) * 64;
   int64_t grid = (total + 255) / 256;
@@ -183,6 +181,5 @@ extern "C" int rsa_pack_weights(const float* w_oihw, int32_t cout, int32_t cin, 
   }
   hipLaunchKernelGGL(rsa::pack_weights_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w_oihw, cout, cin, cin_planes, ksize, products,
                      layout, fmt, out);
-  const int rc = (int)hipGetLastError();
-  return rc ? rsa::set_error(rc, "pack_weights: launch failed") : RSA_OK;
+  return rsa::launch_status("pack_weights: launch failed");
 }

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
@@ -144,8 +144,6 @@ static int plk_launch(const rsa_plk_conv_params& p, hipStream_t stream) {
   return p.ksize <= 17 ? plk_launch_k<FMT, PROD, 17>(p, stream) : plk_launch_k<FMT, PROD, 31>(p, stream);
 }
 
-static bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------------------------ GroupNorm
 // Stage 1: one workgroup per (chunk of PIX_PER_CHUNK pixels, image).  Each thread sums v - shift and (v - shift)^2 per group in f32, the
 // shift being the group's first value in the image (so |v - shift| ~ sigma even when |mean| >> sigma); the per-thread (count, mean, M2)
@@ -247,25 +245,6 @@ __global__ __launch_bounds__(256) void gn_stats_final_kernel(const float* ws, in
   }
 }
 
-template <int FMT>
-__device__ __forceinline__ void store_unit(char* hi, char* lo, int64_t byte_off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + byte_off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + byte_off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-template <int FMT>
-__device__ __forceinline__ void load_unit(const char* hi, const char* lo, int64_t byte_off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + byte_off);
-  const uint4 l = lo ? *(const uint4*)(lo + byte_off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
 // thread = (pixel, output plane of 8 channels); grid (ceil(HW/256), C/8, batch)
 template <int FMT>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const rsa_group_norm_apply_params p) {
@@ -336,7 +315,7 @@ extern "C" int rsa_plk_conv(const rsa_plk_conv_params* p, void* stream) {
     return set_error(RSA_E_ARG, "plk_conv: null operand");
   if (p->out_plane_off < 0 || p->in_plane_stride < (int64_t)p->H * p->W || p->out_plane_stride < (int64_t)p->H * p->W)
     return set_error(RSA_E_ARG, "plk_conv: bad strides");
-  if (!aligned16(p->in_hi) || !aligned16(p->in_lo) || !aligned16(p->w_packed) || !aligned16(p->bias) || !aligned16(p->out_hi) || !aligned16(p->out_lo))
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo) || misaligned16(p->w_packed) || misaligned16(p->bias) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "plk_conv: operands must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   if (p->fmt == RSA_PF_BF16 && p->products == 3) return plk_launch<RSA_PF_BF16, 3>(*p, s);
@@ -355,7 +334,7 @@ extern "C" int rsa_group_norm_stats(const float* x_f32, int32_t batch, int32_t H
   if (!x_f32 || !workspace || !stats) return set_error(RSA_E_ARG, "group_norm_stats: null operand");
   if (batch < 1 || H < 1 || W < 1 || C < 4 || C % 4 || groups < 1 || groups > GN_MAXG || C % groups)
     return set_error(RSA_E_ARG, "group_norm_stats: bad geometry (C a multiple of 4 and of groups, groups <= 8)");
-  if (!aligned16(x_f32)) return set_error(RSA_E_ALIGN, "group_norm_stats: x must be 16-byte aligned");
+  if (misaligned16(x_f32)) return set_error(RSA_E_ALIGN, "group_norm_stats: x must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   const int chunks = (int)((HW + GN_PIX_PER_CHUNK - 1) / GN_PIX_PER_CHUNK);
   hipStream_t s = (hipStream_t)stream;
@@ -370,27 +349,21 @@ extern "C" int rsa_group_norm_apply(const rsa_group_norm_apply_params* p, void* 
   if (!p || !p->x_f32 || !p->stats || !p->gamma || !p->beta || (!p->out_hi && !p->out_f32)) return set_error(RSA_E_ARG, "group_norm_apply: null operand");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->C < 8 || p->C % 8 || p->groups < 1 || p->C % p->groups || p->reserved0 != 0)
     return set_error(RSA_E_ARG, "group_norm_apply: bad geometry (C a multiple of 8 and of groups)");
-  if (p->out_fmt != RSA_PF_BF16 && p->out_fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "group_norm_apply: bad out_fmt");
-  if (!aligned16(p->x_f32) || !aligned16(p->skip_f32) || !aligned16(p->out_f32) || !aligned16(p->out_hi) || !aligned16(p->out_lo))
+  if (!plane_fmt_ok(p->out_fmt)) return set_error(RSA_E_ARG, "group_norm_apply: bad out_fmt");
+  if (misaligned16(p->x_f32) || misaligned16(p->skip_f32) || misaligned16(p->out_f32) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "group_norm_apply: operands must be 16-byte aligned");
   const dim3 grid((unsigned)(((int64_t)p->H * p->W + 255) / 256), p->C / 8, p->batch);
-  if (p->out_fmt == RSA_PF_F16)
-    gn_apply_kernel<RSA_PF_F16><<<grid, 256, 0, (hipStream_t)stream>>>(*p);
-  else
-    gn_apply_kernel<RSA_PF_BF16><<<grid, 256, 0, (hipStream_t)stream>>>(*p);
+  with_fmt(p->out_fmt, [&](auto F) { gn_apply_kernel<decltype(F)::value><<<grid, 256, 0, (hipStream_t)stream>>>(*p); });
   return (int)hipGetLastError();
 }
 
 extern "C" int rsa_ea_gate(const rsa_ea_gate_params* p, void* stream) {
   if (!p || !p->g_f32 || !p->x_hi || !p->out_hi) return set_error(RSA_E_ARG, "ea_gate: null operand");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->C < 8 || p->C % 8 || p->reserved0 != 0) return set_error(RSA_E_ARG, "ea_gate: bad geometry (C a multiple of 8)");
-  if (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "ea_gate: bad fmt");
-  if (!aligned16(p->g_f32) || !aligned16(p->x_hi) || !aligned16(p->x_lo) || !aligned16(p->out_hi) || !aligned16(p->out_lo))
+  if (!plane_fmt_ok(p->fmt)) return set_error(RSA_E_ARG, "ea_gate: bad fmt");
+  if (misaligned16(p->g_f32) || misaligned16(p->x_hi) || misaligned16(p->x_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "ea_gate: operands must be 16-byte aligned");
   const dim3 grid((unsigned)(((int64_t)p->H * p->W + 255) / 256), p->C / 8, p->batch);
-  if (p->fmt == RSA_PF_F16)
-    ea_gate_kernel<RSA_PF_F16><<<grid, 256, 0, (hipStream_t)stream>>>(*p);
-  else
-    ea_gate_kernel<RSA_PF_BF16><<<grid, 256, 0, (hipStream_t)stream>>>(*p);
+  with_fmt(p->fmt, [&](auto F) { ea_gate_kernel<decltype(F)::value><<<grid, 256, 0, (hipStream_t)stream>>>(*p); });
   return (int)hipGetLastError();
 }

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
@@ -16,8 +16,6 @@ namespace {
 
 constexpr int RT_GATE_THREADS = 1024;
 constexpr int RT_MAX_C = 512, RT_MAX_HIDDEN = 128;
-
-bool rt_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
 
 // grid (batch), 1024 threads.  Thread t owns four channels (t % C4) of the slots  t / C4, + NSL, + 2 NSL ...: consecutive threads read
 // consecutive 16-byte groups of a slot row (a wave covers 1 KiB), every partial is the f64 sum of its strided slots in ascending order, and
@@ -139,17 +137,17 @@ extern "C" int rsa_rcab_tail(const float* pool_sums, int32_t slots, const float*
                              int64_t out_batch_stride, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t fmt, void* stream) {
   if (!gate || !y_hi || !x_hi || !out_hi) return set_error(RSA_E_ARG, "rcab_tail: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 8 || (C & 7) || C > RT_MAX_C) return set_error(RSA_E_ARG, "rcab_tail: bad geometry (C % 8 == 0, C <= 512)");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "rcab_tail: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "rcab_tail: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (y_plane_stride < HW || x_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "rcab_tail: a plane stride is smaller than the map");
-  if (rt_misaligned(y_hi) || rt_misaligned(y_lo) || rt_misaligned(x_hi) || rt_misaligned(x_lo) || rt_misaligned(out_hi) || rt_misaligned(out_lo) || rt_misaligned(gate))
+  if (misaligned16(y_hi) || misaligned16(y_lo) || misaligned16(x_hi) || misaligned16(x_lo) || misaligned16(out_hi) || misaligned16(out_lo) || misaligned16(gate))
     return set_error(RSA_E_ALIGN, "rcab_tail: planes and the gate must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "rcab_tail: map too large");
   hipStream_t s = (hipStream_t)stream;
   if (pool_sums != nullptr) {
     if (!w1 || !b1 || !w2 || !b2) return set_error(RSA_E_ARG, "rcab_tail: null gate weights");
     if (slots < 1 || hidden < 1 || hidden > RT_MAX_HIDDEN) return set_error(RSA_E_ARG, "rcab_tail: bad slots / hidden (1..128)");
-    if (rt_misaligned(pool_sums)) return set_error(RSA_E_ALIGN, "rcab_tail: pool_sums must be 16-byte aligned");
+    if (misaligned16(pool_sums)) return set_error(RSA_E_ALIGN, "rcab_tail: pool_sums must be 16-byte aligned");
     const int Cp = (C + 15) & ~15;
     hipLaunchKernelGGL(rcab_gate_kernel, dim3((unsigned)batch), dim3(RT_GATE_THREADS), 0, s, pool_sums, (int)slots, (int)C, Cp, (int)hidden, 1.0 / (double)HW, w1, b1,
                        w2, b2, gate);
@@ -157,14 +155,11 @@ extern "C" int rsa_rcab_tail(const float* pool_sums, int32_t slots, const float*
     if (rc) return set_error(rc, "rcab_tail: gate kernel launch failed");
   }
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)(C / 8), (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(rcab_apply_kernel<RSA_PF_F16>, grid, dim3(256), 0, s, (const char*)y_hi, (const char*)y_lo, y_plane_stride, y_batch_stride, (const char*)x_hi,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(rcab_apply_kernel<decltype(F)::value>, grid, dim3(256), 0, s, (const char*)y_hi, (const char*)y_lo, y_plane_stride, y_batch_stride, (const char*)x_hi,
                        (const char*)x_lo, x_plane_stride, x_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW, (int)C, gate);
-  else
-    hipLaunchKernelGGL(rcab_apply_kernel<RSA_PF_BF16>, grid, dim3(256), 0, s, (const char*)y_hi, (const char*)y_lo, y_plane_stride, y_batch_stride, (const char*)x_hi,
-                       (const char*)x_lo, x_plane_stride, x_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW, (int)C, gate);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "rcab_tail: launch failed") : RSA_OK;
+  });
+  return launch_status("rcab_tail: launch failed");
 }
 
 extern "C" int rsa_rcan_input(const void* x, int32_t dtype, int32_t batch, int32_t C, int32_t H, int32_t W, float scale, const float* weight, const float* bias,
@@ -175,6 +170,5 @@ extern "C" int rsa_rcan_input(const void* x, int32_t dtype, int32_t batch, int32
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "rcan_input: map too large");
   hipLaunchKernelGGL(rcan_input_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, (int)dtype, (int)C, HW, scale, weight,
                      bias, out);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "rcan_input: launch failed") : RSA_OK;
+  return launch_status("rcan_input: launch failed");
 }

@@ -13,108 +13,13 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-
-__device__ __forceinline__ void get_unit(const bf16x8* hi, const bf16x8* lo, int64_t u, float (&v)[8], int fmt) {
-  const bf16x8 h = hi[u];
-  bf16x8 l = {};
-  if (lo != nullptr) l = lo[u];
-  if (fmt == RSA_PF_F16) {
-    const f16x8 hf = __builtin_bit_cast(f16x8, h), lf = __builtin_bit_cast(f16x8, l);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)hf[j] + (lo != nullptr ? (float)lf[j] : 0.f);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (lo != nullptr ? (float)l[j] : 0.f);
-  }
-}
-
-__device__ __forceinline__ void put_unit(bf16x8* hi, bf16x8* lo, int64_t u, const float (&v)[8], int fmt) {
-  if (fmt == RSA_PF_F16) {
-    f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float vj = v[j];
-      asm("" : "+v"(vj));  // opaque: the lo half is the rounding error of THIS hi (conv_common.h, split2)
-      const _Float16 hb = (_Float16)vj;
-      h[j] = hb;
-      l[j] = (_Float16)(vj - (float)hb);
-    }
-    hi[u] = __builtin_bit_cast(bf16x8, h);
-    if (lo != nullptr) lo[u] = __builtin_bit_cast(bf16x8, l);
-    return;
-  }
-  bf16x8 h, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 hb = (__bf16)v[j];
-    h[j] = hb;
-    l[j] = (__bf16)(v[j] - (float)hb);
-  }
-  hi[u] = h;
-  if (lo != nullptr) lo[u] = l;
-}
-
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-
 // ------------------------------------------------------------------------------------------------ global-token cross-attention
-template <int FMT>
-__device__ __forceinline__ f32x16 mfma32(const bf16x8 a, const bf16x8 b, const f32x16 c) {
-  if constexpr (FMT == RSA_PF_F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-template <int FMT>
-__device__ __forceinline__ bf16x8 pack16(const float (&v)[8]) {
-  if constexpr (FMT == RSA_PF_F16) {
-    f16x8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
-    return __builtin_bit_cast(bf16x8, h);
-  } else {
-    bf16x8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (__bf16)v[j];
-    return r;
-  }
-}
-
-// four output values -> the 8-byte half of a plane unit (hi, and the rounding residual for a lo plane)
-template <int FMT>
-__device__ __forceinline__ void round4(const float (&v)[4], bf16x4& h, bf16x4& lo4) {
-  if constexpr (FMT == RSA_PF_F16) {
-    f16x4 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float ve = v[e];
-      asm("" : "+v"(ve));
-      hh[e] = (_Float16)ve;
-      ll[e] = (_Float16)(ve - (float)hh[e]);
-    }
-    h = __builtin_bit_cast(bf16x4, hh);
-    lo4 = __builtin_bit_cast(bf16x4, ll);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const __bf16 hb = (__bf16)v[e];
-      h[e] = hb;
-      lo4[e] = (__bf16)(v[e] - (float)hb);
-    }
-  }
-}
-
 constexpr int RG_CHUNK_T = 4;                // key tiles of 32 staged per chunk
 constexpr int RG_QBLOCK = 256;               // queries per workgroup: 4 waves x 2 tiles of 32
 
@@ -442,8 +347,6 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const f32x4* res, const 
   out[i] = o;
 }
 
-bool misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
 }  // namespace
 }  // namespace rsa
 
@@ -462,8 +365,8 @@ extern "C" int rsa_rg_attention(const rsa_rg_attn_params* p, void* stream) {
   if (p->products != 1 && (p->products != 3 || f16)) return set_error(RSA_E_UNSUPPORTED, "rg_attention: products must be 3 (bf16) or 1");
   if (!p->q_hi || !p->k_hi || !p->v_hi || !p->out_hi || (p->products == 3 && (!p->q_lo || !p->k_lo || !p->v_lo)))
     return set_error(RSA_E_ARG, "rg_attention: null pointer");
-  if (misaligned(p->q_hi) || misaligned(p->q_lo) || misaligned(p->k_hi) || misaligned(p->k_lo) || misaligned(p->v_hi) || misaligned(p->v_lo) ||
-      misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->q_hi) || misaligned16(p->q_lo) || misaligned16(p->k_hi) || misaligned16(p->k_lo) || misaligned16(p->v_hi) || misaligned16(p->v_lo) ||
+      misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "rg_attention: pointers must be 16-byte aligned");
   if (p->k_plane_stride < p->nkeys || p->v_plane_stride < p->nkeys || p->q_plane_stride < (int64_t)p->H * p->W ||
       p->out_plane_stride < (int64_t)p->H * p->W)
@@ -478,48 +381,44 @@ extern "C" int rsa_rg_attention(const rsa_rg_attn_params* p, void* stream) {
     hipLaunchKernelGGL((rg_attention_kernel<3, RSA_PF_BF16>), grid, dim3(256), 0, s, *p);
   else
     hipLaunchKernelGGL((rg_attention_kernel<1, RSA_PF_BF16>), grid, dim3(256), 0, s, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "rg_attention: launch failed") : RSA_OK;
+  return launch_status("rg_attention: launch failed");
 }
 
 extern "C" int rsa_rg_reduce(const rsa_rg_reduce_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "rg_reduce: null params");
   if (p->times < 1 || p->times > 6) return set_error(RSA_E_UNSUPPORTED, "rg_reduce: times must be in [1, 6]");
-  if (p->batch < 1 || p->batch > 65535 || p->planes < 1 || p->planes > 65535 || p->H < 1 || p->W < 1 || (p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16))
+  if (p->batch < 1 || p->batch > 65535 || p->planes < 1 || p->planes > 65535 || p->H < 1 || p->W < 1 || !plane_fmt_ok(p->fmt))
     return set_error(RSA_E_ARG, "rg_reduce: bad geometry");
   const int oh = p->H >> (2 * p->times), ow = p->W >> (2 * p->times);
   if (oh < 1 || ow < 1) return set_error(RSA_E_ARG, "rg_reduce: the map reduces to nothing (H or W < 4^times)");
   if (!p->in_hi || !p->out_hi || !p->weight || !p->bias) return set_error(RSA_E_ARG, "rg_reduce: null pointer");
-  if (misaligned(p->in_hi) || misaligned(p->in_lo) || misaligned(p->out_hi) || misaligned(p->out_lo))
+  if (misaligned16(p->in_hi) || misaligned16(p->in_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "rg_reduce: planes must be 16-byte aligned");
   if ((int64_t)oh * ow > 0x7fffffff) return set_error(RSA_E_ARG, "rg_reduce: map too large");
   hipLaunchKernelGGL(rg_reduce_kernel, dim3((unsigned)(oh * ow), (unsigned)p->planes, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p, ow);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "rg_reduce: launch failed") : RSA_OK;
+  return launch_status("rg_reduce: launch failed");
 }
 
 extern "C" int rsa_layernorm_gelu(const rsa_layernorm_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "layernorm_gelu: null params");
-  if (p->batch < 1 || p->H < 1 || p->W < 1 || p->C < 1 || !(p->eps > 0.f) || p->reserved0 != 0 || (p->out_fmt != RSA_PF_BF16 && p->out_fmt != RSA_PF_F16))
+  if (p->batch < 1 || p->H < 1 || p->W < 1 || p->C < 1 || !(p->eps > 0.f) || p->reserved0 != 0 || !plane_fmt_ok(p->out_fmt))
     return set_error(RSA_E_ARG, "layernorm_gelu: bad geometry");
   if (!p->x_f32 || !p->gamma || !p->beta || !p->out_hi || p->out_f32) return set_error(RSA_E_ARG, "layernorm_gelu: needs x, gamma, beta, out_hi (no out_f32)");
-  if (misaligned(p->x_f32) || misaligned(p->out_hi) || misaligned(p->out_lo)) return set_error(RSA_E_ALIGN, "layernorm_gelu: pointers must be 16-byte aligned");
+  if (misaligned16(p->x_f32) || misaligned16(p->out_hi) || misaligned16(p->out_lo)) return set_error(RSA_E_ALIGN, "layernorm_gelu: pointers must be 16-byte aligned");
   const int64_t total = (int64_t)p->batch * p->H * p->W;
   if ((total + 255) / 256 > 0x7fffffff) return set_error(RSA_E_ARG, "layernorm_gelu: map too large");
   hipLaunchKernelGGL(layernorm_gelu_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "layernorm_gelu: launch failed") : RSA_OK;
+  return launch_status("layernorm_gelu: launch failed");
 }
 
 extern "C" int rsa_scale_add(const float* res, const float* gamma, float* out, int32_t batch, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!res || !gamma || !out) return set_error(RSA_E_ARG, "scale_add: null pointer");
   if (batch < 1 || H < 1 || W < 1 || C < 1) return set_error(RSA_E_ARG, "scale_add: bad geometry");
-  if (misaligned(res) || misaligned(gamma) || misaligned(out)) return set_error(RSA_E_ALIGN, "scale_add: pointers must be 16-byte aligned");
+  if (misaligned16(res) || misaligned16(gamma) || misaligned16(out)) return set_error(RSA_E_ALIGN, "scale_add: pointers must be 16-byte aligned");
   const int p4 = (C + 3) >> 2;
   const int64_t HW = (int64_t)H * W, total = (int64_t)batch * p4 * HW;
   if ((total + 255) / 256 > 0x7fffffff) return set_error(RSA_E_ARG, "scale_add: map too large");
   hipLaunchKernelGGL(scale_add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)res, gamma, (f32x4*)out,
                      HW, p4, total);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "scale_add: launch failed") : RSA_OK;
+  return launch_status("scale_add: launch failed");
 }

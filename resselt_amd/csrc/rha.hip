@@ -8,39 +8,11 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "conv_common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 namespace {
-
-bool rh_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
-
-__device__ __forceinline__ float rh_mish(float v) {
-  if (v > 20.f) return v;
-  const float e = expf(v);
-  const float t = e * (e + 2.f);
-  return v * (t / (t + 2.f));
-}
-
-template <int FMT>
-__device__ __forceinline__ void rh_load(const char* hi, const char* lo, int64_t off, float (&v)[8]) {
-  const uint4 h = *(const uint4*)(hi + off);
-  const uint4 l = lo ? *(const uint4*)(lo + off) : make_uint4(0u, 0u, 0u, 0u);
-  const f32x4 a = widen4<FMT>(make_uint2(h.x, h.y), make_uint2(l.x, l.y));
-  const f32x4 b = widen4<FMT>(make_uint2(h.z, h.w), make_uint2(l.z, l.w));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a[j], v[4 + j] = b[j];
-}
-
-template <int FMT>
-__device__ __forceinline__ void rh_store(char* hi, char* lo, int64_t off, const float (&v)[8]) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  *(uint4*)(hi + off) = make_uint4(h[0], h[1], h[2], h[3]);
-  if (lo) *(uint4*)(lo + off) = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // ------------------------------------------------------------------------------------------------ pooled window attention
 // One workgroup of 256 threads per (image, window) of the pooled map.  N = window^2 tokens (16 or 64), C2 channels (8 .. 32), 8 heads of
@@ -130,10 +102,10 @@ __global__ __launch_bounds__(256) void rha_window_attn_kernel(const WinArgs a) {
       const int py = (wy * ws + r + a.shift) % a.Hd, px = (wx * ws + c + a.shift) % a.Wd;
       const int64_t off = (((int64_t)n * a.x_bs + (int64_t)p * a.x_ps) + (int64_t)(py * dn + s) * a.W + (int64_t)px * dn) * 16;
       float m[8];
-      rh_load<FMT>(a.x_hi, a.x_lo, off, m);  // the maximum starts from the first element
+      load_unit<FMT>(a.x_hi, a.x_lo, off, m);  // the maximum starts from the first element
       for (int dx = 1; dx < dn; ++dx) {
         float v[8];
-        rh_load<FMT>(a.x_hi, a.x_lo, off + (int64_t)dx * 16, v);
+        load_unit<FMT>(a.x_hi, a.x_lo, off + (int64_t)dx * 16, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], v[j]);
       }
@@ -287,7 +259,7 @@ __global__ __launch_bounds__(256) void rha_mix_kernel(const MixArgs a) {
       const int hy = idx / MX_HW, hx = idx - hy * MX_HW;
       const int gy = y0 + hy - 2, gx = x0 + hx - 2;
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if ((unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W) rh_load<FMT>(a.x_hi, a.x_lo, base + ((int64_t)gy * a.W + gx) * 16, v);
+      if ((unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W) load_unit<FMT>(a.x_hi, a.x_lo, base + ((int64_t)gy * a.W + gx) * 16, v);
       s_t[0][idx] = (f32x4){v[0], v[1], v[2], v[3]};
       s_t[1][idx] = (f32x4){v[4], v[5], v[6], v[7]};
     }
@@ -328,7 +300,7 @@ __global__ __launch_bounds__(256) void rha_mix_kernel(const MixArgs a) {
       for (int j = 0; j < 4; ++j) o[4 * h + j] = hy * (hx * vAA[j] + lx * vAB[j]) + ly * (hx * vBA[j] + lx * vBB[j]);
     }
   }
-  rh_store<FMT>(a.o_hi, a.o_lo, ((int64_t)n * a.o_bs + (int64_t)pl * a.o_ps + (int64_t)y * a.W + x) * 16, o);
+  store_unit<FMT>(a.o_hi, a.o_lo, ((int64_t)n * a.o_bs + (int64_t)pl * a.o_ps + (int64_t)y * a.W + x) * 16, o);
 }
 
 // ------------------------------------------------------------------------------------------------ gate
@@ -342,17 +314,17 @@ __global__ __launch_bounds__(256) void rha_gate_kernel(const char* fhi, const ch
   const int pl = blockIdx.y, n = blockIdx.z;
   if (pix >= HW) return;
   float g[8], m[8], o[8];
-  rh_load<FMT>(fhi, flo, ((int64_t)n * f_bs + (int64_t)pl * f_ps + pix) * 16, g);
-  rh_load<FMT>(fhi, flo, ((int64_t)n * f_bs + (int64_t)(hp + pl) * f_ps + pix) * 16, m);
+  load_unit<FMT>(fhi, flo, ((int64_t)n * f_bs + (int64_t)pl * f_ps + pix) * 16, g);
+  load_unit<FMT>(fhi, flo, ((int64_t)n * f_bs + (int64_t)(hp + pl) * f_ps + pix) * 16, m);
   if (pl >= ip) {
     float av[8];
-    rh_load<FMT>(ahi, alo, ((int64_t)n * a_bs + (int64_t)(pl - ip) * a_ps + pix) * 16, av);
+    load_unit<FMT>(ahi, alo, ((int64_t)n * a_bs + (int64_t)(pl - ip) * a_ps + pix) * 16, av);
 #pragma unroll
     for (int j = 0; j < 8; ++j) m[j] *= av[j];
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = rh_mish(g[j]) * m[j];
-  rh_store<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pix) * 16, o);
+  for (int j = 0; j < 8; ++j) o[j] = mish_exact(g[j]) * m[j];
+  store_unit<FMT>(ohi, olo, ((int64_t)n * o_bs + (int64_t)pl * o_ps + pix) * 16, o);
 }
 
 bool rha_pow2_le8(int v) { return v == 1 || v == 2 || v == 4 || v == 8; }
@@ -379,12 +351,12 @@ extern "C" int rsa_rha_window_attn(const void* x_hi, const void* x_lo, int64_t x
   if (window != 4 && window != 8) return set_error(RSA_E_ARG, "rha_window_attn: window must be 4 or 8");
   if (shift < 0 || shift >= window) return set_error(RSA_E_ARG, "rha_window_attn: shift must be in [0, window)");
   if (H % (down * window) || W % (down * window)) return set_error(RSA_E_ARG, "rha_window_attn: H and W must be multiples of down * window");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "rha_window_attn: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "rha_window_attn: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   if (x_plane_stride < HW) return set_error(RSA_E_ARG, "rha_window_attn: the plane stride is smaller than the map");
   if (batch > 1 && x_batch_stride < (int64_t)(C2 / 8) * x_plane_stride)
     return set_error(RSA_E_ARG, "rha_window_attn: the batch stride is smaller than the planes of an image");
-  if (rh_misaligned(x_hi) || rh_misaligned(x_lo) || rh_misaligned(wqkv_t) || rh_misaligned(wproj_t) || rh_misaligned(out))
+  if (misaligned16(x_hi) || misaligned16(x_lo) || misaligned16(wqkv_t) || misaligned16(wproj_t) || misaligned16(out))
     return set_error(RSA_E_ALIGN, "rha_window_attn: planes, the two matrices and the output map must be 16-byte aligned");
   const int Hd = H / down, Wd = W / down;
   const int64_t windows = (int64_t)(Hd / window) * (Wd / window);
@@ -395,12 +367,10 @@ extern "C" int rsa_rha_window_attn(const void* x_hi, const void* x_lo, int64_t x
   a.wqkv_t = wqkv_t, a.bqkv = bqkv, a.pos_t = pos_t, a.isc = inv_scale, a.dww = dwc_w, a.dwb = dwc_b, a.wproj_t = wproj_t, a.bproj = bproj, a.out = out;
   const size_t lds = (size_t)rha_lds_floats(C2, window * window) * sizeof(float);
   const dim3 grid((unsigned)windows, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(rha_window_attn_kernel<RSA_PF_F16>, grid, dim3(256), lds, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(rha_window_attn_kernel<RSA_PF_BF16>, grid, dim3(256), lds, (hipStream_t)stream, a);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "rha_window_attn: launch failed") : RSA_OK;
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(rha_window_attn_kernel<decltype(F)::value>, grid, dim3(256), lds, (hipStream_t)stream, a);
+  });
+  return launch_status("rha_window_attn: launch failed");
 }
 
 extern "C" int rsa_rha_mix(const void* x_hi, const void* x_lo, int64_t x_plane_stride, int64_t x_batch_stride, const float* att, void* out_hi, void* out_lo,
@@ -410,14 +380,14 @@ extern "C" int rsa_rha_mix(const void* x_hi, const void* x_lo, int64_t x_plane_s
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || C2 < 8 || (C2 & 7) || C2 > 8 * 16383) return set_error(RSA_E_ARG, "rha_mix: bad geometry");
   if (!rha_pow2_le8(down)) return set_error(RSA_E_ARG, "rha_mix: down must be 1, 2, 4 or 8");
   if (H % down || W % down) return set_error(RSA_E_ARG, "rha_mix: H and W must be multiples of down");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "rha_mix: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "rha_mix: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   const int P = C2 / 8;
   if (x_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "rha_mix: a plane stride is smaller than the map");
   if (batch > 1 && (x_batch_stride < (int64_t)P * x_plane_stride || out_batch_stride < 2 * (int64_t)P * out_plane_stride))
     return set_error(RSA_E_ARG, "rha_mix: a batch stride is smaller than the planes of an image");
   if (x_hi == out_hi) return set_error(RSA_E_ARG, "rha_mix: not in place (a tile reads its neighbours' pixels)");
-  if (rh_misaligned(x_hi) || rh_misaligned(x_lo) || rh_misaligned(out_hi) || rh_misaligned(out_lo) || rh_misaligned(att))
+  if (misaligned16(x_hi) || misaligned16(x_lo) || misaligned16(out_hi) || misaligned16(out_lo) || misaligned16(att))
     return set_error(RSA_E_ALIGN, "rha_mix: planes and the attention map must be 16-byte aligned");
   const int64_t tiles = (int64_t)((W + MX_TW - 1) / MX_TW) * ((H + MX_TH - 1) / MX_TH);
   if (tiles > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "rha_mix: map too large");
@@ -426,12 +396,10 @@ extern "C" int rsa_rha_mix(const void* x_hi, const void* x_lo, int64_t x_plane_s
   a.o_hi = (char*)out_hi, a.o_lo = (char*)out_lo, a.o_ps = out_plane_stride, a.o_bs = out_batch_stride;
   a.H = H, a.W = W, a.C2 = C2, a.down = down, a.Hd = H / down, a.Wd = W / down, a.w = weight, a.b = bias;
   const dim3 grid((unsigned)tiles, (unsigned)(2 * P), (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(rha_mix_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(rha_mix_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "rha_mix: launch failed") : RSA_OK;
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(rha_mix_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  });
+  return launch_status("rha_mix: launch failed");
 }
 
 extern "C" int rsa_rha_gate(const void* f_hi, const void* f_lo, int64_t f_plane_stride, int64_t f_batch_stride, const void* a_hi, const void* a_lo,
@@ -440,25 +408,21 @@ extern "C" int rsa_rha_gate(const void* f_hi, const void* f_lo, int64_t f_plane_
   if (!f_hi || !a_hi || !out_hi) return set_error(RSA_E_ARG, "rha_gate: null operand");
   if (batch < 1 || batch > 65535 || H < 1 || W < 1 || hidden_planes < 1 || hidden_planes > 32767 || i_planes < 0 || i_planes >= hidden_planes)
     return set_error(RSA_E_ARG, "rha_gate: bad geometry (0 <= i_planes < hidden_planes)");
-  if (fmt != RSA_PF_BF16 && fmt != RSA_PF_F16) return set_error(RSA_E_ARG, "rha_gate: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(fmt)) return set_error(RSA_E_ARG, "rha_gate: fmt must be an rsa_plane_fmt");
   const int64_t HW = (int64_t)H * W;
   const int64_t hp = hidden_planes, cp = hidden_planes - i_planes;
   if (f_plane_stride < HW || a_plane_stride < HW || out_plane_stride < HW) return set_error(RSA_E_ARG, "rha_gate: a plane stride is smaller than the map");
   if (batch > 1 && (f_batch_stride < 2 * hp * f_plane_stride || a_batch_stride < cp * a_plane_stride || out_batch_stride < hp * out_plane_stride))
     return set_error(RSA_E_ARG, "rha_gate: a batch stride is smaller than the planes of an image");
   if (out_hi == f_hi || out_hi == a_hi) return set_error(RSA_E_ARG, "rha_gate: not in place");
-  if (rh_misaligned(f_hi) || rh_misaligned(f_lo) || rh_misaligned(a_hi) || rh_misaligned(a_lo) || rh_misaligned(out_hi) || rh_misaligned(out_lo))
+  if (misaligned16(f_hi) || misaligned16(f_lo) || misaligned16(a_hi) || misaligned16(a_lo) || misaligned16(out_hi) || misaligned16(out_lo))
     return set_error(RSA_E_ALIGN, "rha_gate: planes must be 16-byte aligned");
   if ((HW + 255) / 256 > 0x7fffffff) return set_error(RSA_E_UNSUPPORTED, "rha_gate: map too large");
   const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)hidden_planes, (unsigned)batch);
-  if (fmt == RSA_PF_F16)
-    hipLaunchKernelGGL(rha_gate_kernel<RSA_PF_F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)f_hi, (const char*)f_lo, f_plane_stride, f_batch_stride,
+  with_fmt(fmt, [&](auto F) {
+    hipLaunchKernelGGL(rha_gate_kernel<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)f_hi, (const char*)f_lo, f_plane_stride, f_batch_stride,
                        (const char*)a_hi, (const char*)a_lo, a_plane_stride, a_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW,
                        (int)hidden_planes, (int)i_planes);
-  else
-    hipLaunchKernelGGL(rha_gate_kernel<RSA_PF_BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)f_hi, (const char*)f_lo, f_plane_stride, f_batch_stride,
-                       (const char*)a_hi, (const char*)a_lo, a_plane_stride, a_batch_stride, (char*)out_hi, (char*)out_lo, out_plane_stride, out_batch_stride, HW,
-                       (int)hidden_planes, (int)i_planes);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "rha_gate: launch failed") : RSA_OK;
+  });
+  return launch_status("rha_gate: launch failed");
 }

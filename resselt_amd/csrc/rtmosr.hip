@@ -9,13 +9,12 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
+// bf16 planes only.  Not plane_unit.h's get_unit: without a lo plane this form adds nothing (get_unit adds 0.f), and the kernels' code differs
 __device__ __forceinline__ void rt_unit_f32(const bf16x8* hi, const bf16x8* lo, int64_t u, float (&v)[8]) {
   const bf16x8 h = hi[u];
   if (lo != nullptr) {
@@ -26,18 +25,6 @@ __device__ __forceinline__ void rt_unit_f32(const bf16x8* hi, const bf16x8* lo, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
   }
-}
-
-__device__ __forceinline__ void rt_store_unit(bf16x8* hi, bf16x8* lo, int64_t u, const float (&v)[8]) {
-  bf16x8 h, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 hb = (__bf16)v[j];
-    h[j] = hb;
-    l[j] = (__bf16)(v[j] - (float)hb);
-  }
-  hi[u] = h;
-  if (lo != nullptr) lo[u] = l;
 }
 
 // thread = pixel; grid (ceil(HW/256), batch).  x / (||x||_2 * C^-1/2 + eps) * scale + offset
@@ -70,8 +57,8 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const f32x4* x, int64_t HW
         o[half * 4 + r] = c < C ? scale[c] * (v[r] * inv) + offset[c] : 0.f;
       }
     }
-    rt_store_unit(out_hi + (int64_t)n * batch_stride + (int64_t)pl * plane_stride, out_lo ? out_lo + (int64_t)n * batch_stride + (int64_t)pl * plane_stride : nullptr,
-                  pix, o);
+    put_unit(out_hi + (int64_t)n * batch_stride + (int64_t)pl * plane_stride, out_lo ? out_lo + (int64_t)n * batch_stride + (int64_t)pl * plane_stride : nullptr,
+                  pix, o, RSA_PF_BF16);
   }
 }
 
@@ -99,15 +86,8 @@ __global__ __launch_bounds__(256) void unshuffle_pool_kernel(const bf16x8* in_hi
     mx[c] = fmaxf(fmaxf(v[0][c], v[1][c]), fmaxf(v[2][c], v[3][c]));
     pu[((int64_t)n * planes * 8 + pl * 8 + c) * hw + pix] = (f32x4){v[0][c], v[1][c], v[2][c], v[3][c]};
   }
-  rt_store_unit(pool_hi + (int64_t)n * pool_batch_stride + (int64_t)pl * pool_plane_stride,
-                pool_lo ? pool_lo + (int64_t)n * pool_batch_stride + (int64_t)pl * pool_plane_stride : nullptr, pix, mx);
-}
-
-__device__ __forceinline__ float mish_f(float v) {
-  if (v > 20.f) return v;
-  const float e = expf(v);
-  const float t = e * (e + 2.f);
-  return v * (t / (t + 2.f));
+  put_unit(pool_hi + (int64_t)n * pool_batch_stride + (int64_t)pl * pool_plane_stride,
+                pool_lo ? pool_lo + (int64_t)n * pool_batch_stride + (int64_t)pl * pool_plane_stride : nullptr, pix, mx, RSA_PF_BF16);
 }
 
 // thread = (pixel, output plane); grid (ceil(HW/256), planes_out, batch).  out = mish(g) * cat(i, shuffle(c * gate)):
@@ -147,12 +127,10 @@ __global__ __launch_bounds__(256) void gated_shuffle_mul_kernel(const rsa_gated_
   }
   float o[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = mish_f(g[j]) * m[j];
-  rt_store_unit((bf16x8*)p.out_hi + (int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride,
-                p.out_lo ? (bf16x8*)p.out_lo + (int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride : nullptr, pix, o);
+  for (int j = 0; j < 8; ++j) o[j] = mish_exact(g[j]) * m[j];
+  put_unit((bf16x8*)p.out_hi + (int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride,
+                p.out_lo ? (bf16x8*)p.out_lo + (int64_t)n * p.out_batch_stride + (int64_t)pl * p.out_plane_stride : nullptr, pix, o, RSA_PF_BF16);
 }
-
-static bool rt_misaligned(const void* a) { return ((uintptr_t)a & 15) != 0; }
 
 }  // namespace rsa
 
@@ -161,12 +139,11 @@ using namespace rsa;
 extern "C" int rsa_rmsnorm(const float* x_f32, int32_t batch, int32_t H, int32_t W, int32_t C, float eps, const float* scale, const float* offset,
                            void* out_hi, void* out_lo, int64_t out_plane_stride, int64_t out_batch_stride, void* stream) {
   if (!x_f32 || !scale || !offset || !out_hi || batch < 1 || batch > 65535 || H < 1 || W < 1 || C < 1) return set_error(RSA_E_ARG, "rmsnorm: bad argument");
-  if (rt_misaligned(x_f32) || rt_misaligned(out_hi) || rt_misaligned(out_lo)) return set_error(RSA_E_ALIGN, "rmsnorm: maps must be 16-byte aligned");
+  if (misaligned16(x_f32) || misaligned16(out_hi) || misaligned16(out_lo)) return set_error(RSA_E_ALIGN, "rmsnorm: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(rmsnorm_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const f32x4*)x_f32, HW, C, eps,
                      scale, offset, (bf16x8*)out_hi, (bf16x8*)out_lo, out_plane_stride, out_batch_stride);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "rmsnorm: launch failed") : RSA_OK;
+  return launch_status("rmsnorm: launch failed");
 }
 
 extern "C" int rsa_unshuffle_pool(const void* in_hi, const void* in_lo, int64_t in_plane_stride, int64_t in_batch_stride, int32_t batch, int32_t H, int32_t W,
@@ -174,14 +151,13 @@ extern "C" int rsa_unshuffle_pool(const void* in_hi, const void* in_lo, int64_t 
                                   int64_t pool_batch_stride, void* stream) {
   if (!in_hi || !unshuffled_f32 || !pool_hi || batch < 1 || batch > 65535 || H < 2 || W < 2 || (H & 1) || (W & 1) || planes < 1 || planes > 65535)
     return set_error(RSA_E_ARG, "unshuffle_pool: bad argument (H and W must be even)");
-  if (rt_misaligned(in_hi) || rt_misaligned(in_lo) || rt_misaligned(unshuffled_f32) || rt_misaligned(pool_hi) || rt_misaligned(pool_lo))
+  if (misaligned16(in_hi) || misaligned16(in_lo) || misaligned16(unshuffled_f32) || misaligned16(pool_hi) || misaligned16(pool_lo))
     return set_error(RSA_E_ALIGN, "unshuffle_pool: maps must be 16-byte aligned");
   const int64_t hw = (int64_t)(H / 2) * (W / 2);
   hipLaunchKernelGGL(unshuffle_pool_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)planes, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
                      (const bf16x8*)in_hi, (const bf16x8*)in_lo, in_plane_stride, in_batch_stride, H, W, planes, (f32x4*)unshuffled_f32, (bf16x8*)pool_hi,
                      (bf16x8*)pool_lo, pool_plane_stride, pool_batch_stride);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "unshuffle_pool: launch failed") : RSA_OK;
+  return launch_status("unshuffle_pool: launch failed");
 }
 
 extern "C" int rsa_gated_shuffle_mul(const rsa_gated_shuffle_params* p, void* stream) {
@@ -189,11 +165,10 @@ extern "C" int rsa_gated_shuffle_mul(const rsa_gated_shuffle_params* p, void* st
   if (p->batch < 1 || p->batch > 65535 || p->H < 2 || p->W < 2 || (p->H & 1) || (p->W & 1) || p->g_planes < 1 || p->i_planes < 0 || p->i_planes > p->g_planes)
     return set_error(RSA_E_ARG, "gated_shuffle_mul: bad geometry");
   if (!p->f_hi || !p->c_hi || !p->out_hi) return set_error(RSA_E_ARG, "gated_shuffle_mul: null pointer");
-  if (rt_misaligned(p->f_hi) || rt_misaligned(p->f_lo) || rt_misaligned(p->c_hi) || rt_misaligned(p->c_lo) || rt_misaligned(p->out_hi) || rt_misaligned(p->out_lo))
+  if (misaligned16(p->f_hi) || misaligned16(p->f_lo) || misaligned16(p->c_hi) || misaligned16(p->c_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "gated_shuffle_mul: maps must be 16-byte aligned");
   const int64_t HW = (int64_t)p->H * p->W;
   hipLaunchKernelGGL(gated_shuffle_mul_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)p->g_planes, (unsigned)p->batch), dim3(256), 0,
                      (hipStream_t)stream, *p);
-  const hipError_t rc = hipGetLastError();
-  return rc ? set_error(rc, "gated_shuffle_mul: launch failed") : RSA_OK;
+  return launch_status("gated_shuffle_mul: launch failed");
 }

@@ -18,15 +18,10 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "plane_unit.h"
 #include "resselt_amd.h"
 
 namespace rsa {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
 // One workgroup (4 waves) = 64 consecutive tokens; lane = token, wave w owns channel planes w, w+4, w+8, ...  Every load
@@ -155,7 +150,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8
         for (int j = 0; j < 8; ++j) {
           if (p.out_fmt == RSA_PF_F16) {
             float yj = y[j];
-            asm("" : "+v"(yj));  // opaque: see conv_common.h, split2
+            asm("" : "+v"(yj));  // opaque: see plane_unit.h, split2
             const _Float16 hb = (_Float16)yj;
             h[j] = __builtin_bit_cast(uint16_t, hb);
             l[j] = __builtin_bit_cast(uint16_t, (_Float16)(yj - (float)hb));
@@ -187,24 +182,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8
         }
       }
     }
-  }
-}
-
-// two values -> packed hi pair and packed lo pair of a plane format (as conv_common.h::split2; the fp16 form is opaque to the contraction pass)
-template <int FMT>
-__device__ __forceinline__ void ln_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  if constexpr (FMT == RSA_PF_F16) {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-    asm("" : "+v"(a), "+v"(b));
-    const f16x2 h = {(_Float16)a, (_Float16)b};
-    hi = __builtin_bit_cast(uint32_t, h);
-    const f16x2 l = {(_Float16)(a - (float)h[0]), (_Float16)(b - (float)h[1])};
-    lo = __builtin_bit_cast(uint32_t, l);
-  } else {
-    const bf16x2 h = {(__bf16)a, (__bf16)b};
-    hi = __builtin_bit_cast(uint32_t, h);
-    const bf16x2 l = {(__bf16)(a - __builtin_bit_cast(float, hi << 16)), (__bf16)(b - __builtin_bit_cast(float, hi & 0xffff0000u))};
-    lo = __builtin_bit_cast(uint32_t, l);
   }
 }
 
@@ -305,9 +282,9 @@ __global__ __launch_bounds__(256) void layernorm_regs_kernel(const rsa_layernorm
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           if (p.out_fmt == RSA_PF_F16)
-            ln_split2<RSA_PF_F16>(y[2 * j], y[2 * j + 1], h[j], l[j]);
+            split2<RSA_PF_F16>(y[2 * j], y[2 * j + 1], h[j], l[j]);
           else
-            ln_split2<RSA_PF_BF16>(y[2 * j], y[2 * j + 1], h[j], l[j]);
+            split2<RSA_PF_BF16>(y[2 * j], y[2 * j + 1], h[j], l[j]);
         }
         const size_t unit = ((size_t)n * p.out_batch_stride + (size_t)pl * p.out_plane_stride) * 16 + loff;
         *(uint4*)((char*)p.out_hi + unit) = make_uint4(h[0], h[1], h[2], h[3]);
@@ -318,12 +295,6 @@ __global__ __launch_bounds__(256) void layernorm_regs_kernel(const rsa_layernorm
 }
 
 // ------------------------------------------------------------------------------------------------ window attention
-__device__ __forceinline__ bf16x8 pack_hi(const float (&v)[8]) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)v[j];
-  return r;
-}
 
 template <int PROD>
 __global__ __launch_bounds__(256, 2) void window_attention_kernel(const rsa_window_attn_params p) {
@@ -497,11 +468,11 @@ __global__ __launch_bounds__(256, 2) void window_attention_kernel(const rsa_wind
         float e8[8], r8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) e8[j] = st[kt][qt][8 * s + j];
-        const bf16x8 ph = pack_hi(e8);
+        const bf16x8 ph = pack16<RSA_PF_BF16>(e8);
         if (PROD == 3) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) r8[j] = e8[j] - (float)ph[j];
-          const bf16x8 pl = pack_hi(r8);
+          const bf16x8 pl = pack16<RSA_PF_BF16>(r8);
           ot[qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, ot[qt], 0, 0, 0);
           ot[qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, ot[qt], 0, 0, 0);
         }
@@ -541,8 +512,8 @@ extern "C" int rsa_layernorm(const rsa_layernorm_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "layernorm: null params");
   if (p->batch < 1 || p->H < 1 || p->W < 1 || p->C < 1) return set_error(RSA_E_ARG, "layernorm: bad geometry");
   if (!p->x_f32 || !p->gamma || !p->beta || (!p->out_hi && !p->out_f32)) return set_error(RSA_E_ARG, "layernorm: null pointer");
-  if ((p->out_fmt != RSA_PF_BF16 && p->out_fmt != RSA_PF_F16) || p->reserved0 != 0) return set_error(RSA_E_ARG, "layernorm: out_fmt must be an rsa_plane_fmt");
-  if (((uintptr_t)p->x_f32 | (uintptr_t)p->out_hi | (uintptr_t)p->out_lo | (uintptr_t)p->out_f32) & 15)
+  if (!plane_fmt_ok(p->out_fmt) || p->reserved0 != 0) return set_error(RSA_E_ARG, "layernorm: out_fmt must be an rsa_plane_fmt");
+  if (misaligned16(p->x_f32) || misaligned16(p->out_hi) || misaligned16(p->out_lo) || misaligned16(p->out_f32))
     return set_error(RSA_E_ALIGN, "layernorm: maps must be 16-byte aligned");
   const int64_t total = (int64_t)p->batch * p->H * p->W;
   int64_t g = (total + 63) / 64;  // one 256-thread workgroup per 64 tokens
@@ -558,8 +529,7 @@ extern "C" int rsa_layernorm(const rsa_layernorm_params* p, void* stream) {
     hipLaunchKernelGGL(layernorm_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *p);
   else
     hipLaunchKernelGGL(layernorm_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *p);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "layernorm: launch failed") : RSA_OK;
+  return launch_status("layernorm: launch failed");
 }
 
 extern "C" int rsa_window_attention(const rsa_window_attn_params* p, void* stream) {
@@ -571,7 +541,7 @@ extern "C" int rsa_window_attention(const rsa_window_attn_params* p, void* strea
   if (p->shift < 0 || p->shift >= p->window) return set_error(RSA_E_ARG, "window_attention: shift must be in [0, window)");
   if (p->products != 1 && p->products != 3) return set_error(RSA_E_UNSUPPORTED, "window_attention: products must be 1 or 3");
   if (!p->qkv_hi || !p->bias_frag || !p->out_hi || (p->products == 3 && !p->qkv_lo)) return set_error(RSA_E_ARG, "window_attention: null pointer");
-  if (((uintptr_t)p->qkv_hi | (uintptr_t)p->qkv_lo | (uintptr_t)p->out_hi | (uintptr_t)p->out_lo | (uintptr_t)p->bias_frag) & 15)
+  if (misaligned16(p->qkv_hi) || misaligned16(p->qkv_lo) || misaligned16(p->out_hi) || misaligned16(p->out_lo) || misaligned16(p->bias_frag))
     return set_error(RSA_E_ALIGN, "window_attention: pointers must be 16-byte aligned");
   const int64_t items = (int64_t)p->batch * (p->H / p->window) * (p->W / p->window) * p->heads;
   const int64_t blocks = (items + 3) / 4;
@@ -580,6 +550,5 @@ extern "C" int rsa_window_attention(const rsa_window_attn_params* p, void* strea
     hipLaunchKernelGGL(window_attention_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *p);
   else
     hipLaunchKernelGGL(window_attention_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *p);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "window_attention: launch failed") : RSA_OK;
+  return launch_status("window_attention: launch failed");
 }

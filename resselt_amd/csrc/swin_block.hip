@@ -406,8 +406,6 @@ __global__ __launch_bounds__(512) void swin_mlp_block_kernel(const rsa_swin_mlp_
   }
 }
 
-static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
-
 }  // namespace rsa
 
 extern "C" int rsa_swin_attn_block(const rsa_swin_attn_block_params* p, void* stream) {
@@ -422,8 +420,8 @@ extern "C" int rsa_swin_attn_block(const rsa_swin_attn_block_params* p, void* st
   if (p->heads > 8 || p->C % p->heads || p->C / p->heads > 32) return set_error(RSA_E_UNSUPPORTED, "swin_attn_block: at most 8 heads of at most 32 channels");
   if (!p->x || !p->gamma || !p->beta || !p->wqkv || !p->bqkv || !p->bias_frag16 || !p->wproj || !p->bproj || !p->out)
     return set_error(RSA_E_ARG, "swin_attn_block: null pointer");
-  if (!aligned16(p->x) || !aligned16(p->gamma) || !aligned16(p->beta) || !aligned16(p->wqkv) || !aligned16(p->bqkv) || !aligned16(p->bias_frag16) ||
-      !aligned16(p->wproj) || !aligned16(p->bproj) || !aligned16(p->out))
+  if (misaligned16(p->x) || misaligned16(p->gamma) || misaligned16(p->beta) || misaligned16(p->wqkv) || misaligned16(p->bqkv) || misaligned16(p->bias_frag16) ||
+      misaligned16(p->wproj) || misaligned16(p->bproj) || misaligned16(p->out))
     return set_error(RSA_E_ALIGN, "swin_attn_block: pointers must be 16-byte aligned");
   const int64_t windows = (int64_t)p->batch * (p->H / p->window) * (p->W / p->window);
   if (windows > 0x3fffffff) return set_error(RSA_E_UNSUPPORTED, "swin_attn_block: too many windows");
@@ -431,8 +429,7 @@ extern "C" int rsa_swin_attn_block(const rsa_swin_attn_block_params* p, void* st
     hipLaunchKernelGGL(swin_attn_block_kernel<3>, dim3((unsigned)windows), dim3(64 * ((p->heads + 1) / 2)), 0, (hipStream_t)stream, *p);
   else
     hipLaunchKernelGGL(swin_attn_block_kernel<1>, dim3((unsigned)windows), dim3(64 * ((p->heads + 1) / 2)), 0, (hipStream_t)stream, *p);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "swin_attn_block: launch failed") : RSA_OK;
+  return launch_status("swin_attn_block: launch failed");
 }
 
 extern "C" int rsa_swin_mlp_block(const rsa_swin_mlp_block_params* p, void* stream) {
@@ -442,12 +439,12 @@ extern "C" int rsa_swin_mlp_block(const rsa_swin_mlp_block_params* p, void* stre
   if (p->products != 1 && p->products != 3) return set_error(RSA_E_UNSUPPORTED, "swin_mlp_block: products must be 1 or 3");
   if (p->C > 256 || (p->C & 3) || p->hidden > 512) return set_error(RSA_E_UNSUPPORTED, "swin_mlp_block: C must be a multiple of 4, at most 256; hidden at most 512");
   if (!p->x || !p->gamma || !p->beta || !p->w1 || !p->b1 || !p->w2 || !p->b2 || !p->out) return set_error(RSA_E_ARG, "swin_mlp_block: null pointer");
-  if (!aligned16(p->x) || !aligned16(p->gamma) || !aligned16(p->beta) || !aligned16(p->w1) || !aligned16(p->b1) || !aligned16(p->w2) || !aligned16(p->b2) ||
-      !aligned16(p->out) || !aligned16(p->out_hi) || !aligned16(p->out_lo))
+  if (misaligned16(p->x) || misaligned16(p->gamma) || misaligned16(p->beta) || misaligned16(p->w1) || misaligned16(p->b1) || misaligned16(p->w2) || misaligned16(p->b2) ||
+      misaligned16(p->out) || misaligned16(p->out_hi) || misaligned16(p->out_lo))
     return set_error(RSA_E_ALIGN, "swin_mlp_block: pointers must be 16-byte aligned");
   const int64_t tiles = (int64_t)p->batch * (((int64_t)p->H * p->W + SB_TOK - 1) / SB_TOK);
   if (tiles > 0x3fffffff) return set_error(RSA_E_UNSUPPORTED, "swin_mlp_block: too many tokens");
-  if ((p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) || p->reserved0 != 0 || (p->fmt == RSA_PF_F16 && p->products != 1))
+  if (!plane_fmt_ok(p->fmt) || p->reserved0 != 0 || (p->fmt == RSA_PF_F16 && p->products != 1))
     return set_error(RSA_E_ARG, "swin_mlp_block: fmt must be an rsa_plane_fmt (fp16: the one-product form only)");
   if (p->products == 3)
     hipLaunchKernelGGL(swin_mlp_block_kernel<3>, dim3((unsigned)tiles), dim3(512), 0, (hipStream_t)stream, *p);
@@ -455,6 +452,5 @@ extern "C" int rsa_swin_mlp_block(const rsa_swin_mlp_block_params* p, void* stre
     hipLaunchKernelGGL((swin_mlp_block_kernel<1, RSA_PF_F16>), dim3((unsigned)tiles), dim3(512), 0, (hipStream_t)stream, *p);
   else
     hipLaunchKernelGGL(swin_mlp_block_kernel<1>, dim3((unsigned)tiles), dim3(512), 0, (hipStream_t)stream, *p);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "swin_mlp_block: launch failed") : RSA_OK;
+  return launch_status("swin_mlp_block: launch failed");
 }

@@ -464,8 +464,6 @@ __global__ __launch_bounds__(512, PROD == 1 ? 4 : 2) void swin_block_kernel(cons
   }
 }
 
-static bool aligned16f(const void* a) { return ((uintptr_t)a & 15) == 0; }
-
 }  // namespace rsa
 
 extern "C" int rsa_swin_block(const rsa_swin_block_params* p, void* stream) {
@@ -481,12 +479,12 @@ extern "C" int rsa_swin_block(const rsa_swin_block_params* p, void* stream) {
   const void* ptrs[] = {p->x, p->gamma1, p->beta1, p->wqkv, p->bqkv, p->bias_frag16, p->wproj, p->bproj, p->gamma2, p->beta2, p->w1, p->b1, p->w2, p->b2, p->out};
   for (const void* q : ptrs) {
     if (q == nullptr) return set_error(RSA_E_ARG, "swin_block: null pointer");
-    if (!aligned16f(q)) return set_error(RSA_E_ALIGN, "swin_block: pointers must be 16-byte aligned");
+    if (misaligned16(q)) return set_error(RSA_E_ALIGN, "swin_block: pointers must be 16-byte aligned");
   }
-  if (!aligned16f(p->out_hi) || !aligned16f(p->out_lo)) return set_error(RSA_E_ALIGN, "swin_block: pointers must be 16-byte aligned");
+  if (misaligned16(p->out_hi) || misaligned16(p->out_lo)) return set_error(RSA_E_ALIGN, "swin_block: pointers must be 16-byte aligned");
   const int64_t windows = (int64_t)p->batch * (p->H / p->window) * (p->W / p->window);
   if (windows > 0x3fffffff) return set_error(RSA_E_UNSUPPORTED, "swin_block: too many windows");
-  if ((p->fmt != RSA_PF_BF16 && p->fmt != RSA_PF_F16) || p->reserved0 != 0) return set_error(RSA_E_ARG, "swin_block: fmt must be an rsa_plane_fmt");
+  if (!plane_fmt_ok(p->fmt) || p->reserved0 != 0) return set_error(RSA_E_ARG, "swin_block: fmt must be an rsa_plane_fmt");
   if (p->fmt == RSA_PF_F16 && p->products != 1) return set_error(RSA_E_UNSUPPORTED, "swin_block: fp16 operands are compiled for products == 1");
   if (p->products == 3)
     hipLaunchKernelGGL((swin_block_kernel<3, RSA_PF_BF16>), dim3((unsigned)windows), dim3(512), 0, (hipStream_t)stream, *p);
@@ -494,6 +492,5 @@ extern "C" int rsa_swin_block(const rsa_swin_block_params* p, void* stream) {
     hipLaunchKernelGGL((swin_block_kernel<1, RSA_PF_F16>), dim3((unsigned)windows), dim3(512), 0, (hipStream_t)stream, *p);
   else
     hipLaunchKernelGGL((swin_block_kernel<1, RSA_PF_BF16>), dim3((unsigned)windows), dim3(512), 0, (hipStream_t)stream, *p);
-  const int rc = (int)hipGetLastError();
-  return rc ? set_error(rc, "swin_block: launch failed") : RSA_OK;
+  return launch_status("swin_block: launch failed");
 }

@@ -214,9 +214,11 @@ class ATD(EngineModule):
         if c != self.in_chans:
             raise RuntimeError(f'model expects {self.in_chans} input channels, got {c}')
         win = self.window_size
-        if h0 < win or w0 < win:
-            raise RuntimeError(f'a {h0}x{w0} input is below one {win}x{win} window')
         H, Wd = h0 + (win - h0 % win) % win, w0 + (win - w0 % win) % win
+        if 2 * h0 < H or 2 * w0 < Wd:
+            # the flip padding (arch.py:1090-1096) appends ONE mirrored copy: a side below half a window stays short of the window multiple,
+            # and the reference's window partition fails on it; from half a window on (4..7 for a window of 8) the reference runs
+            raise RuntimeError(f'a {h0}x{w0} input is below half a {win}x{win} window: one flip cannot pad it to {H}x{Wd}')
         C_, s, m, rc, hidden = self.embed_dim, self.upscale, self.num_tokens, self.reducted_dim, self.hidden
         ntok = H * Wd
         gs = min(ntok, self.category_size)

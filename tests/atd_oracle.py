@@ -49,8 +49,8 @@ def _resi(sd, name, x):
     return F.conv2d(x, sd[f'{name}.4.weight'], sd[f'{name}.4.bias'], padding=1)
 
 
-def _shift_mask(h, w, ws):
-    img = torch.zeros(h, w)
+def _shift_mask(h, w, ws, like):
+    img = torch.zeros(h, w, dtype=like.dtype, device=like.device)
     cnt = 0
     for a in (slice(0, -ws), slice(-ws, -(ws // 2)), slice(-(ws // 2), None)):
         for b in (slice(0, -ws), slice(-ws, -(ws // 2)), slice(-(ws // 2), None)):
@@ -96,7 +96,7 @@ def _layer(sd, p, x, td, hw, heads, ws, shift, cat_size, rpi, last, force, recor
         record.setdefault('margin', []).append(top2_margin(sim))
         record.setdefault('sim', []).append(sim)
     inv = torch.empty_like(perm)
-    inv.scatter_(1, perm, torch.arange(n).expand(b, n))
+    inv.scatter_(1, perm, torch.arange(n, device=perm.device).expand(b, n))
     sh = torch.gather(qkv, 1, perm[..., None].expand(-1, -1, 3 * c))
     pad_n = ng * gs - n
     padded = torch.cat((sh, torch.flip(sh[:, n - pad_n : n], dims=[1])), dim=1)
@@ -115,7 +115,7 @@ def _layer(sd, p, x, td, hw, heads, ws, shift, cat_size, rpi, last, force, recor
     bias = sd[f'{p}.attn_win.relative_position_bias_table'][rpi.reshape(-1)].view(ws * ws, ws * ws, -1).permute(2, 0, 1)
     a = a + bias.unsqueeze(0)
     if shift:
-        mask = _shift_mask(h, w, ws)
+        mask = _shift_mask(h, w, ws, a)
         a = (a.view(nw // mask.shape[0], mask.shape[0], heads, ws * ws, ws * ws) + mask.unsqueeze(1).unsqueeze(0)).view(nw, heads, ws * ws, ws * ws)
     y = (a.softmax(-1) @ y[2]).transpose(1, 2).reshape(nw, ws * ws, c)
     y = _lin(sd, f'{p}.attn_win.proj', y)
@@ -138,8 +138,7 @@ def _layer(sd, p, x, td, hw, heads, ws, shift, cat_size, rpi, last, force, recor
 
 
 def atd_forward(sd: dict, x: torch.Tensor, hyper: dict, force: list | None = None, record: dict | None = None) -> torch.Tensor:
-    sd = {k: v.detach().to(torch.float32) if v.is_floating_point() else v for k, v in sd.items()}
-    x = x.to(torch.float32)
+    sd = {k: v.detach().to(x.dtype) if v.is_floating_point() else v for k, v in sd.items()}
     ws, s, up = hyper['window_size'], hyper['upscale'], hyper['upsampler']
     rng = hyper.get('img_range', 1.0)
     c_in = sd['conv_first.weight'].shape[1]
@@ -149,7 +148,7 @@ def atd_forward(sd: dict, x: torch.Tensor, hyper: dict, force: list | None = Non
     h, w = (h0 + ws - 1) // ws * ws, (w0 + ws - 1) // ws * ws
     x = torch.cat([x, torch.flip(x, [2])], 2)[:, :, :h]
     x = torch.cat([x, torch.flip(x, [3])], 3)[:, :, :, :w]
-    mean = torch.tensor(RGB_MEAN).view(1, 3, 1, 1) if c_in == 3 else torch.zeros(1, 1, 1, 1)
+    mean = torch.tensor(RGB_MEAN, dtype=x.dtype, device=x.device).view(1, 3, 1, 1) if c_in == 3 else torch.zeros(1, 1, 1, 1, dtype=x.dtype, device=x.device)
     if hyper.get('norm', True):
         x = (x - mean) * rng
     rpi = sd['relative_position_index_SA']

@@ -67,8 +67,8 @@ def _dysample(sd, d, x, scale, groups=4):
     offset = _conv(sd, f'{d}.offset', x) * torch.sigmoid(_conv(sd, f'{d}.scope', x)) * 0.5 + sd[f'{d}.init_pos']
     B, _, H, W = offset.shape
     offset = offset.view(B, 2, -1, H, W)
-    coords = torch.stack(torch.meshgrid([torch.arange(W) + 0.5, torch.arange(H) + 0.5], indexing='ij')).transpose(1, 2).unsqueeze(1).unsqueeze(0)
-    coords = 2 * (coords.to(x.dtype) + offset) / torch.tensor([W, H], dtype=x.dtype).view(1, 2, 1, 1, 1) - 1
+    coords = torch.stack(torch.meshgrid([torch.arange(W, dtype=x.dtype, device=x.device) + 0.5, torch.arange(H, dtype=x.dtype, device=x.device) + 0.5], indexing='ij')).transpose(1, 2).unsqueeze(1).unsqueeze(0)
+    coords = 2 * (coords + offset) / torch.tensor([W, H], dtype=x.dtype, device=x.device).view(1, 2, 1, 1, 1) - 1
     coords = F.pixel_shuffle(coords.reshape(B, -1, H, W), scale).view(B, 2, -1, scale * H, scale * W).permute(0, 2, 3, 4, 1).contiguous().flatten(0, 1)
     out = F.grid_sample(x.reshape(B * groups, -1, H, W), coords, mode='bilinear', align_corners=False, padding_mode='border')
     return _conv(sd, f'{d}.end_conv', out.view(B, -1, scale * H, scale * W))
@@ -91,10 +91,10 @@ def _lda(sd, u, x, scale, groups=2, rng=11.0):
     o = F.conv2d(q.view(B * groups, gc, Ho, Wo), sd[f'{u}.conv_offset.0.weight'], padding=1, groups=gc)
     o = F.silu(_channel_ln(o, sd[f'{u}.conv_offset.1.weight'], sd[f'{u}.conv_offset.1.bias']))
     o = _conv(sd, f'{u}.conv_offset.3', o)
-    base = torch.arange(-1, 2, dtype=torch.float32)
+    base = torch.arange(-1, 2, dtype=x.dtype, device=x.device)
     base_off = torch.stack([base.repeat_interleave(3), base.repeat(3)], 1).flatten().view(1, -1, 1, 1)
     o = (o.tanh() * rng + base_off).view(B * groups, 3, 3, 2, Ho, Wo).permute(0, 1, 4, 2, 5, 3)  # b kh h kw w d
-    rows, cols = torch.meshgrid(torch.arange(Ho), torch.arange(Wo), indexing='ij')
+    rows, cols = torch.meshgrid(torch.arange(Ho, device=x.device), torch.arange(Wo, device=x.device), indexing='ij')
     o = (o + torch.stack((rows, cols), -1).view(1, 1, Ho, 1, Wo, 2)).contiguous().view(B * groups, 3 * Ho, 3 * Wo, 2)
     grid = torch.stack([2 * o[..., 1] / (Wo - 1) - 1, 2 * o[..., 0] / (Ho - 1) - 1], -1)
 
@@ -152,8 +152,8 @@ def _upsampler(sd, x, mode, scale, dim, out, mid):
 
 
 def fdat_forward(sd, x):
-    """The reference FDAT's eval forward for the checkpoint ``sd`` (fp32 CPU tensors) on ``x`` [N, C, h, w]."""
-    sd = {k: v.float() if v.is_floating_point() else v for k, v in sd.items()}
+    """The reference FDAT's eval forward for the checkpoint ``sd`` on ``x`` [N, C, h, w], in the dtype of ``x``."""
+    sd = {k: v.to(x.dtype) if v.is_floating_point() else v for k, v in sd.items()}
     _, mi, scale, dim, out, mid, _ = [int(v) for v in sd['upsampler.MetaUpsample'].tolist()]
     mode = MODS[mi]
     bias = sd['groups.0.blocks.0.attn.bias']

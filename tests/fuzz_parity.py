@@ -32,6 +32,16 @@ def _cugan_accepts(sd, h, w):
     return True
 
 
+def _oracle_accepts(meta, sd, h, w):
+    """The oracles of tests/<arch>_oracle.py raise exactly where the reference does (the plans refuse those sizes too)."""
+    try:
+        with torch.no_grad():
+            oracle_forward(meta, sd, synth.synth_input((1, 3, h, w), seed=0))
+    except Exception:
+        return False
+    return True
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     per_arch = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -61,23 +71,51 @@ def main():
         'realplksr': lambda s: (synth.realplksr_state_dict(dim=rng.choice([32, 64]), n_blocks=2, upscale=rng.choice([1, 2, 3, 4]), kernel_size=rng.choice([9, 17, 31]),
                                                            use_ea=rng.random() < 0.7, dysample=rng.random() < 0.5, seed=s), 1),
         'cugan': lambda s: ((lambda v: synth.cugan_state_dict(v, pro=v != '2x_fast' and rng.random() < 0.5, seed=s))(rng.choice(['2x', '3x', '4x', '2x_fast'])), 16),
+        # the families whose oracles are tests/<arch>_oracle.py: a third element carries what the oracle needs besides the state dict
+        # (helpers.oracle_forward); sizes their oracle refuses are redrawn.  ATD is not here: its category sort makes a free-running
+        # comparison ill-defined (tests/atd_trajectory.py).
+        'mosr': lambda s: ((lambda up, sc: (synth.mosr_state_dict(upscale=sc, n_block=rng.choice([1, 2]), dim=rng.choice([32, 48]), upsampler=up,
+                                                                  kernel_size=rng.choice([3, 5, 7]), seed=s), 1, dict(upsampler=up, upscale=sc)))
+                           (rng.choice(['ps', 'dys', 'gps']), rng.choice([2, 3, 4]))),
+        'mosrv2': lambda s: ((lambda up, sc, un: (synth.mosrv2_state_dict(scale=sc, n_block=rng.choice([1, 2]), dim=32, upsampler=up, unshuffle_mod=un,
+                                                                          rms_norm=rng.random() < 0.5, seed=s), 2, dict(upsampler=up, upscale=sc)))
+                             (rng.choice(['pixelshuffledirect', 'pixelshuffle', 'nearest+conv']), rng.choice([1, 2, 4]), rng.random() < 0.6)),
+        'rgt': lambda s: ((lambda sp, nh: (synth.rgt_state_dict(embed_dim=32, depth=(2,), num_heads=(nh,), split_size=sp, upscale=rng.choice([2, 3, 4]), seed=s), 16,
+                                           dict(split_size=sp, num_heads=(nh,))))(rng.choice([(2, 4), (4, 8), (4, 4)]), rng.choice([2, 4]))),
+        'fdat': lambda s: (synth.fdat_state_dict(scale=rng.choice([2, 4]), embed_dim=rng.choice([32, 48]), num_groups=1, depth_per_group=2, num_heads=4, window_size=rng.choice([4, 8]),
+                                                 upsampler_type=rng.choice(['pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample', 'transpose+conv', 'lda', 'pa_up']),
+                                                 unshuffle_mod=rng.random() < 0.3, seed=s), 1),
+        'omnisr': lambda s: (synth.omnisr_state_dict(num_feat=32, window_size=rng.choice([4, 8]), up_scale=rng.choice([2, 3, 4]), pe=rng.random() < 0.7, seed=s), 9),
+        'rcan': lambda s: (synth.rcan_state_dict(scale=rng.choice([2, 4]), n_resgroups=rng.choice([1, 2]), n_resblocks=2, n_feats=rng.choice([32, 48, 64]), norm=rng.random() < 0.5,
+                                                 unshuffle_mod=rng.random() < 0.4, seed=s), 1),
+        'gater': lambda s: (synth.gater_state_dict(dim=24, num_blocks=(1,) * 7, latent_att=rng.random() < 0.6, seed=s), 5),
+        'eimn': lambda s: (synth.eimn_state_dict(embed_dims=rng.choice([32, 64]), scale=rng.choice([2, 3, 4]), num_stages=rng.choice([1, 2]), seed=s), 1),
+        'rha': lambda s: ((lambda dl: synth.rha_state_dict(dim=32, scale=rng.choice([2, 3, 4]), down_list=dl, window_size=rng.choice([4, 8]), group_blocks=1, res_blocks=2,
+                                                           upsample=rng.choice(['pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample']), seed=s))
+                          (rng.choice([(2, 1), (1,), (2,), (4, 2)])), 5),
+        'flexnet': lambda s: (synth.flexnet_state_dict(seed=s, dim=rng.choice([32, 48]), num_blocks=rng.choice([(1, 1), (2,), (1, 2)]), scale=rng.choice([2, 3, 4]),
+                                                       upsampler=rng.choice(['ps', 'dys', 'n+c']), channel_norm=rng.random() < 0.3), 5),
     }  # fmt: skip
+    own_oracle = ('mosr', 'mosrv2', 'rgt', 'fdat', 'omnisr', 'rcan', 'gater', 'eimn', 'rha', 'flexnet')
     worst = 0.0
     for arch, make in makers.items():
         for k in range(per_arch):
             s = rng.randrange(1 << 20)
-            sd, min_hw = make(s)
+            sd, min_hw, *extra = make(s)
+            meta = dict(extra[0] if extra else {}, arch='esrgan' if arch == 'esrganbig' else arch.split('_')[0])
             n = 1 if arch == 'drct' else rng.choice([1, 1, 2, 3])
             h, w = rng.randint(min_hw, 45), rng.randint(min_hw, 45)
             if arch == 'esrganbig':  # many tiles per workgroup, ragged edges, a row-banded tail
                 h, w = rng.randint(300, 420), rng.randint(500, 700)
             while arch == 'cugan' and not _cugan_accepts(sd, h, w):  # the sizes the reference refuses (the plan refuses them too)
                 h, w = rng.randint(min_hw, 90), rng.randint(min_hw, 90)
+            while arch in own_oracle and not _oracle_accepts(meta, sd, h, w):  # likewise: a reflect pad wider than the image, RG-SA below 16, ...
+                h, w = rng.randint(min_hw, 45), rng.randint(min_hw, 45)
             dt = rng.choice([torch.float32, torch.float32, torch.float16, torch.bfloat16])
             cin = sd['conv_first.weight'].shape[1] if arch == 'swinir_restore' else 3
             x = synth.synth_input((n, cin, h, w), seed=s).to(dt)
             with torch.no_grad():
-                ref = oracle_forward(dict(arch='esrgan' if arch == 'esrganbig' else arch.split('_')[0]), sd, x.float())
+                ref = oracle_forward(meta, sd, x.float())
             model = resselt_amd.load_from_state_dict(dict(sd)).to(dev)
             if arch == 'esrganbig':
                 model.tail_band_rows = rng.choice([64, 100, 4096])

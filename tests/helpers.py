@@ -82,4 +82,26 @@ def oracle_forward(meta, sd, x):
         from oracle.cugan import cugan_forward
 
         return cugan_forward(sd, x)
+    # The families whose oracles live next to the tests (tests/<arch>_oracle.py).  They compute in the dtype of ``x``; what the forward needs
+    # beyond the state dict travels in ``meta``.
+    if meta['arch'] == 'mosr':
+        from mosr_oracle import mosr_forward
+
+        return mosr_forward(sd, x, meta.get('upsampler', 'ps'), meta['upscale'])
+    if meta['arch'] == 'mosrv2':
+        from mosr_oracle import mosrv2_forward
+
+        return mosrv2_forward(sd, x, meta.get('upsampler', 'pixelshuffledirect'), meta['upscale'], meta.get('mid_dim', 32))
+    if meta['arch'] == 'rgt':
+        from rgt_oracle import rgt_forward
+
+        return rgt_forward(sd, x, tuple(meta['split_size']), tuple(meta['num_heads']), meta.get('c_ratio', 0.5))
+    if meta['arch'] == 'atd':
+        from atd_oracle import atd_forward
+
+        return atd_forward(sd, x, meta['hyper'], force=meta.get('force'), record=meta.get('record'))
+    if meta['arch'] in ('fdat', 'omnisr', 'rcan', 'gater', 'eimn', 'rha', 'flexnet'):
+        import importlib
+
+        return getattr(importlib.import_module(f'{meta["arch"]}_oracle'), f'{meta["arch"]}_forward')(sd, x)
     raise KeyError(meta['arch'])

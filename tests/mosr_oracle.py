@@ -1,4 +1,4 @@
-"""Plain-PyTorch fp32 restatements of the MoSR and MoSRv2 forwards from a state dict (CPU), written from the layer descriptions in
+"""Plain-PyTorch restatements (in the dtype of the input: fp32, or fp64 for a high-precision reference) of the MoSR and MoSRv2 forwards from a state dict (CPU), written from the layer descriptions in
 resselt_amd/archs/mosr and resselt_amd/archs/mosrv2.  ``mosrv2_forward`` also takes the x1 ``unshuffle_mod`` checkpoints the reference
 loader reads wrongly."""
 
@@ -58,7 +58,7 @@ def _trunk_tail(sd, t, x):
 
 
 def mosr_forward(sd, x, upsampler, upscale):
-    sd = {k: v.float() for k, v in sd.items()}
+    sd = {k: v.to(x.dtype) for k, v in sd.items()}
     n_block = 0
     while f'gblocks.{n_block + 1}.fc1.weight' in sd:
         n_block += 1
@@ -86,7 +86,7 @@ def mosr_forward(sd, x, upsampler, upscale):
 
 def mosrv2_forward(sd, x, upsampler, scale, mid_dim=32):
     """``scale``: the model's scale (the output is scale x the input); ``unshuffle_mod`` is read from the keys."""
-    sd = {k: v.float() for k, v in sd.items() if not k.endswith('MetaUpsample')}
+    sd = {k: v.to(x.dtype) for k, v in sd.items() if not k.endswith('MetaUpsample')}
     unshuffle = 'gblocks.1.weight' in sd and 'gblocks.0.weight' not in sd
     u, s_int, first = (4 // scale, 4, 2) if unshuffle else (1, scale, 1)
     _, _, h, w = x.shape

@@ -60,7 +60,7 @@ def _attention(sd, p, x, ws, grid):
     sim = (q * (c // HEADS) ** -0.5) @ k.transpose(-1, -2)
     key = f'{p}.fn.rel_pos_bias.weight'
     if key in sd:
-        pos = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing='ij')).reshape(2, -1)
+        pos = torch.stack(torch.meshgrid(torch.arange(ws, device=x.device), torch.arange(ws, device=x.device), indexing='ij')).reshape(2, -1)
         rel = pos[:, :, None] - pos[:, None, :] + ws - 1
         sim = sim + sd[key][rel[0] * (2 * ws - 1) + rel[1]].permute(2, 0, 1)
     o = (sim.softmax(-1) @ v).transpose(1, 2).reshape(t.shape[0], -1, c)
@@ -106,7 +106,7 @@ def _esa(sd, p, x):
 
 
 def omnisr_forward(sd, x):
-    sd = {k: v.float() for k, v in sd.items() if not k.endswith(('total_ops', 'total_params'))}
+    sd = {k: v.to(x.dtype) for k, v in sd.items() if not k.endswith(('total_ops', 'total_params'))}
     c_in = sd['input.weight'].shape[1]
     scale = math.isqrt(sd['up.0.weight'].shape[0] // c_in)
     key = 'residual_layer.0.residual_layer.0.layer.2.fn.rel_pos_bias.weight'
@@ -114,7 +114,7 @@ def omnisr_forward(sd, x):
     res_num = _seq_len(sd, 'residual_layer')
     block_num = _seq_len(sd, 'residual_layer.0.residual_layer') - 1
     h, w = x.shape[2:]
-    x = F.pad(x.float(), (0, (ws - w % ws) % ws, 0, (ws - h % ws) % ws))
+    x = F.pad(x, (0, (ws - w % ws) % ws, 0, (ws - h % ws) % ws))
     residual = _conv(sd, 'input', x)
     out = residual
     for g in range(res_num):

@@ -1,4 +1,4 @@
-"""Plain-torch CPU restatement of RCAN's forward pass (reference archs/rcan/arch.py:320-332) on a state dict, in f32, written from the
+"""Plain-torch CPU restatement of RCAN's forward pass (reference archs/rcan/arch.py:320-332) on a state dict, in the dtype of its input, written from the
 module's structure: it is what the GPU tests compare larger inputs with, and tests/test_rcan_oracle.py pins it to the reference's own
 outputs.  Unlike the reference it leaves its input alone."""
 
@@ -27,9 +27,8 @@ def rcan_hyper(sd) -> dict:
 
 
 def rcan_forward(sd, x: torch.Tensor) -> torch.Tensor:
-    sd = {k: v.float() for k, v in sd.items()}
+    sd = {k: v.to(x.dtype) for k, v in sd.items()}
     hp = rcan_hyper(sd)
-    x = x.float()
     _, _, h, w = x.shape
     d = hp['down']
     x = F.pad(x, (0, (d - w % d) % d, 0, (d - h % d) % d), 'reflect')

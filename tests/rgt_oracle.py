@@ -56,7 +56,7 @@ def _window_attention(q, k, v, bias, hs, ws, shift, heads, scale):
     s = (qw * scale) @ kw.transpose(-1, -2) + bias
     if sh or sw:
         reg = _region_ids(Hp, Wp, hs, ws, sh, sw).reshape(Hp // hs, hs, Wp // ws, ws).permute(0, 2, 1, 3).reshape(Hp // hs, Wp // ws, 1, hs * ws)
-        s = s + torch.where(reg[..., :, None] != reg[..., None, :], -100.0, 0.0)
+        s = s + torch.zeros((), dtype=s.dtype, device=s.device).masked_fill(reg[..., :, None] != reg[..., None, :], -100.0)
     o = torch.softmax(s, -1) @ vw
     o = o.reshape(B, Hp // hs, Wp // ws, heads, hs, ws, c // heads).permute(0, 1, 4, 2, 5, 3, 6).reshape(B, Hp, Wp, c)
     if sh or sw:
@@ -125,9 +125,9 @@ def _resi(x, sd, name):
 
 
 def rgt_forward(sd, x, split_size, num_heads, c_ratio):
-    sd = {k: v.float() for k, v in sd.items()}
+    sd = {k: v.to(x.dtype) for k, v in sd.items()}  # the arithmetic runs in the input's dtype
     B, cin, H, W = x.shape
-    mean = torch.tensor(RGB_MEAN if cin == 3 else [0.0] * cin).view(1, cin, 1, 1)
+    mean = torch.tensor(RGB_MEAN if cin == 3 else [0.0] * cin, dtype=x.dtype, device=x.device).view(1, cin, 1, 1)
     x = x - mean
     first = F.conv2d(x, sd['conv_first.weight'], sd['conv_first.bias'], padding=1)
     C = first.shape[1]

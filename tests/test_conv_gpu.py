@@ -200,6 +200,79 @@ def test_layout_kernel_reflect_pad_and_unshuffle(device):
     assert (got2[:, :12] - ref2).abs().max().item() <= 1e-5 and got2[:, 12:].abs().max().item() == 0.0
 
 
+def _layout_cases(r):
+    """(h, w, ph, pw): every row pad 0..h-1 for h = 2..9 beside a column pad of another amount, then the same transposed; with a
+    PixelUnshuffle(r) only the pads that complete a multiple of r."""
+    out = []
+    for h in range(2, 10):
+        for ph in range(h):
+            w = 2 + (3 * h + ph) % 8
+            pw = (5 * ph + h + 1) % w
+            if pw == ph:
+                pw = (pw + 1) % w
+            out += [(h, w, ph, pw), (w, h, pw, ph)]
+    fit = lambda s, p: next((q for q in range(p, s) if (s + q) % r == 0), None)  # noqa: E731  (the next pad that completes a multiple)
+    out = [(h, w, fit(h, ph), fit(w, pw)) for h, w, ph, pw in out]
+    return sorted({c for c in out if c[2] is not None and c[3] is not None})
+
+
+LAYOUT_OPTIONS = [(c, ms, fmt, lo) for c in (1, 3, 4, 9) for ms in (False, True) for fmt in (tensors.PF_BF16, tensors.PF_F16) for lo in (True, False)]
+
+
+@pytest.mark.parametrize('in_dtype', [torch.float32, torch.float16, torch.bfloat16, torch.uint8], ids=['f32', 'f16', 'bf16', 'u8'])
+@pytest.mark.parametrize('r', [1, 2, 3, 4])
+def test_layout_kernel_every_reflect_pad(device, r, in_dtype):
+    """rsa_nchw_to_planes read back with rsa_planes_to_nchw against F.pad(.., 'reflect') -> F.pixel_unshuffle -> (x - mean) * scale in
+    float64, a batch of two: every pad amount a source of 2..9 rows (columns) allows, the two axes at different amounts, sources that are no
+    multiple of the unshuffle factor, 1 / 3 / 4 / 9 channels (a partly filled last plane: its other channels must be exactly zero), with and
+    without mean / scale, bf16 and fp16 planes with and without lo halves.
+
+    Bars.  With lo halves: 1e-5 * max(1, |ref|max), the bar of test_layout_kernel_reflect_pad_and_unshuffle (hi + lo keep 2^-17 of the
+    value in bf16, less in fp16).  Without: the format's half ulp of the value -- bf16 has an 8-bit significand, so round-to-nearest is off
+    by at most 2^-8 |v|; fp16 has 11 bits, 2^-11 |v|, and below its smallest normal 2^-14 the spacing is 2^-24, half of it 2^-25 -- plus
+    2^-22 * max(1, |ref|max) for the two f32 roundings of (x - mean) * scale (2^-24 each of a value of at most |ref|max), which can also
+    carry a value across a rounding boundary of the plane format."""
+    cases = _layout_cases(r)
+    # the largest pad reflection allows, side - 1, on either axis (2 * side - 1 is odd: with an even r the largest is side - 2)
+    assert any(c[2] == c[0] - 1 - (r + 1) % 2 > 0 for c in cases) and any(c[3] == c[1] - 1 - (r + 1) % 2 > 0 for c in cases)
+    seen = set()
+    for i, (h, w, ph, pw) in enumerate(cases):
+        c, ms, fmt, lo = opt = LAYOUT_OPTIONS[(i + 8 * [torch.float32, torch.float16, torch.bfloat16, torch.uint8].index(in_dtype) + 5 * r) % len(LAYOUT_OPTIONS)]
+        seen.add(opt)
+        x = torch.rand((2, c, h, w), generator=torch.Generator().manual_seed(1000 * r + i))
+        if in_dtype == torch.uint8:
+            xs = (x * 255).round().to(torch.uint8)
+            x64, xin = xs.double() / 255, xs.permute(0, 2, 3, 1).contiguous()
+        else:
+            xin = x.to(in_dtype)
+            x64 = xin.double()
+        mean = torch.linspace(0.1, 0.5, c) if ms else None
+        scale = 255.0 if ms else 1.0
+        ref = F.pad(x64, (0, pw, 0, ph), 'reflect')
+        if ms:
+            ref = (ref - mean.float().double().view(1, c, 1, 1)) * scale
+        ref = F.pixel_unshuffle(ref, r)
+        cp = c * r * r
+        planes = (cp + 7) // 8
+        out = tensors.Planes.empty(2, planes, (h + ph) // r, (w + pw) // r, device, with_lo=lo, fmt=fmt)
+        out.hi.fill_(7.0)  # stale values the kernel must overwrite, in the channels past C too
+        if lo:
+            out.lo.fill_(7.0)
+        ops.nchw_to_planes(xin.to(device), out, None if mean is None else mean.to(device), scale, unshuffle=r)
+        got = ops.planes_to_nchw(out, planes * 8).cpu().double()
+        top = max(1.0, ref.abs().max().item())
+        if lo:
+            bar = torch.full_like(ref, 1e-5 * top)
+        else:
+            bar = ref.abs() * (2.0**-8 if fmt == tensors.PF_BF16 else 2.0**-11) + (2.0**-25 if fmt == tensors.PF_F16 else 0.0) + 2.0**-22 * top
+        what = f'r={r} {in_dtype} {h}x{w} pad {ph},{pw} C={c} mean/scale={ms} fmt={fmt} lo={lo}'
+        assert got.shape[1] == planes * 8 and tuple(got.shape[2:]) == tuple(ref.shape[2:]), what
+        over = (got[:, :cp] - ref).abs() - bar
+        assert over.max().item() <= 0, f'{what}: {over.max().item():.3e} over the bar at {divmod(int(over.argmax()), ref.shape[3])}'
+        assert got[:, cp:].abs().sum().item() == 0.0, f'{what}: the channels past C are not zero'
+    assert len(seen) == len(LAYOUT_OPTIONS) if r == 1 else len(seen) >= 8
+
+
 def test_argument_errors(device):
     wts = ops.ConvWeights.from_oihw(torch.zeros(8, 8, 3, 3), None, 3, device=device)
     xin = tensors.Planes.empty(1, 1, 8, 8, device)

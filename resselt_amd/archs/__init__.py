@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -17,6 +17,7 @@ from .fdat import FDATArch
 from .flexnet import FlexNetArch
 from .gater import GateRArch
 from .hat import HATArch
+from .moesr import MoESRArch
 from .mosr import MoSRArch
 from .mosrv2 import MoSRv2Arch
 from .omnisr import OmniSRArch
@@ -42,3 +43,6 @@ internal_registry.add(RHAArch(), late=True)
 # FlexNet likewise (tests/test_flexnet_loader.py checks the same two properties), one tier further back (``Registry.last``): the contents
 # of ``late`` and what iterating over the registry yields stay what they were.  The reference walks it between ESRGAN and HAT.
 internal_registry.add(FlexNetArch(), last=True)
+# MoESR likewise (tests/test_moesr_loader.py), in ``Registry.after``: the open-ended tier consulted once ``walk()`` has declined, so that
+# ``late``, ``last``, ``walk()`` and what iterating over the registry yields stay what they were.  The reference walks it right behind RTMoSR.
+internal_registry.add(MoESRArch(), after=True)

@@ -148,11 +148,14 @@ class _GatedBase(EngineModule):
         raise NotImplementedError
 
     def _emit_block(self, plan: Plan, blk, n, H, Wd, cur, bufs):
-        """norm -> fc1 -> rsa_gated_dwconv; returns the planes fc2 reads."""
+        """norm -> fc1 -> rsa_gated_dwconv; returns the planes fc2 reads.  ``cur`` None: ``bufs['norm']`` already holds the normalised input
+        (MoESR: the kernel that closed the previous block wrote it)."""
         N_pl, F_pl, M_pl = bufs['norm'], bufs['fc1'], bufs['gate']
         sc, off = blk['norm']
         dim = self.dim
-        if self.rms_norm:
+        if cur is None:
+            pass
+        elif self.rms_norm:
             plan.launch('rsa_rmsnorm', dict(x_f32=cur, batch=n, H=H, W=Wd, C=dim, eps=1e-6, scale=sc, offset=off, out=N_pl))
         else:
             lp = L.LayerNormParams()

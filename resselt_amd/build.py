@@ -27,7 +27,7 @@ def sources() -> list[str]:
 def _hash() -> str:
     h = hashlib.sha256()
     files = sources() + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
-    files.append(os.path.join(ROOT, 'include', 'resselt_amd.h'))
+    files += sorted(os.path.join(ROOT, 'include', f) for f in os.listdir(os.path.join(ROOT, 'include')) if f.endswith('.h'))
     files.append(os.path.abspath(__file__))  # compile flags live here
     for f in files:
         h.update(os.path.relpath(f, ROOT).encode())  # relative: the same tree hashes the same wherever it is checked out

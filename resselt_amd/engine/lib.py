@@ -480,6 +480,29 @@ SIGNATURES = {
 
 EXPORTS = tuple(SIGNATURES)  # every symbol the header declares (tests/test_pack_and_capi.py)
 
+# Entry points of the same library that a header of their own declares beside include/resselt_amd.h (include/resselt_amd_<family>.h), with
+# their mirrors and rows in engine/lib_<family>.py: name -> row, as in SIGNATURES.  ``extend`` adds them; ``load`` demands and types them
+# like the rows above, and ``launch`` / ``invoke`` reach them by name.
+EXTENSIONS: dict = {}
+
+
+def _declare(lib, rows: dict) -> None:
+    for name, (restype, params) in rows.items():
+        if not hasattr(lib, name):
+            raise RuntimeError(f'{lib_path()} does not export {name}; rebuild the library')
+        getattr(lib, name).argtypes = [ctype for _, ctype in params]
+        getattr(lib, name).restype = restype
+
+
+def extend(rows: dict) -> None:
+    """Register the signature rows of an extension header (once, at the import of its engine/lib_<family>.py)."""
+    clash = [name for name in rows if name in SIGNATURES]
+    if clash:
+        raise ValueError(f'{clash} are entry points of include/resselt_amd.h')
+    EXTENSIONS.update(rows)
+    if _lib is not None:
+        _declare(_lib, rows)
+
 
 def lib_path() -> str:
     """The in-tree library; RSA_LIB=path selects an experiment build instead (tools/variant.sh: A/B timing, ablations)."""
@@ -528,6 +551,7 @@ def load() -> C.CDLL:
     for name, (restype, params) in SIGNATURES.items():
         getattr(lib, name).argtypes = [ctype for _, ctype in params]
         getattr(lib, name).restype = restype
+    _declare(lib, EXTENSIONS)
     _lib = lib
     return lib
 

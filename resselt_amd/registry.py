@@ -7,8 +7,8 @@ Behaviour kept from the reference:
     anything else raises ``ValueError`` (registry.py:79-104);
   * the restricted unpickler only admits OrderedDict, ``_rebuild_tensor_v2`` and six storage classes and
     raises ``pickle.UnpicklingError`` for every other global (registry.py:20-46);
-  * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``, then ``Registry.last``), builds the first
-    match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
+  * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``, then ``Registry.last``, then
+    ``Registry.after``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
   * no match raises ``ArchitectureNotFound``.
 
 Documented deviation: the reference hands the *unconverted* dict to ``load_state_dict``, so official
@@ -91,15 +91,18 @@ class Registry:
     has declined: only for an architecture whose detection keys no other one matches and which matches no other one's checkpoints, so
     that its position cannot change who loads what.  ``last`` is a further tier of the same kind, consulted after ``late``; ``walk()`` yields
     all three in the order ``load_from_state_dict`` consults them.  Iterating over the registry and ``len()`` cover ``store`` and ``late``
-    only, as they did before ``last`` existed."""
+    only, as they did before ``last`` existed.  ``after`` is the open-ended tier behind them: any number of architectures, each under the same
+    admission rule, consulted in insertion order once ``walk()`` has declined; ``consulted()`` yields everything, ``after`` included, in
+    consultation order, and ``__iter__``, ``len()`` and ``walk()`` do not see it -- a further architecture needs no further tier."""
 
     def __init__(self):
         self.store: Dict[str, Architecture] = {}
         self.late: Dict[str, Architecture] = {}
         self.last: Dict[str, Architecture] = {}
+        self.after: Dict[str, Architecture] = {}
 
     def __contains__(self, uid: str) -> bool:
-        return uid in self.store or uid in self.late or uid in self.last
+        return uid in self.store or uid in self.late or uid in self.last or uid in self.after
 
     def __iter__(self) -> Iterator[Architecture]:
         return iter(list(self.store.values()) + list(self.late.values()))
@@ -111,8 +114,16 @@ class Registry:
         """Every registered architecture in the order ``load_from_state_dict`` consults them: ``store``, ``late``, ``last``."""
         return iter(list(self.store.values()) + list(self.late.values()) + list(self.last.values()))
 
-    def add(self, arch: Architecture, late: bool = False, last: bool = False) -> None:
+    def consulted(self) -> Iterator[Architecture]:
+        """Every registered architecture in the order ``load_from_state_dict`` consults them: ``walk()``, then ``after``."""
+        return iter(list(self.walk()) + list(self.after.values()))
+
+    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False) -> None:
         """Register an architecture *instance*; re-using an id replaces it in place."""
+        if after and arch.id not in self.store and arch.id not in self.late and arch.id not in self.last:
+            self.after[arch.id] = arch
+            return
+        self.after.pop(arch.id, None)
         if last and arch.id not in self.store and arch.id not in self.late:
             self.last[arch.id] = arch
         elif late and arch.id not in self.store:
@@ -124,7 +135,8 @@ class Registry:
             self.store[arch.id] = arch
 
     def get(self, uid: str) -> Architecture:
-        arch = self.late[uid] if uid in self.late else self.last[uid] if uid in self.last else self.store[uid]  # KeyError for unknown ids, as in the reference
+        tier = next((t for t in (self.late, self.last, self.after) if uid in t), self.store)
+        arch = tier[uid]  # KeyError for unknown ids, as in the reference
         if not arch:
             raise ArchitectureNotFound
         return arch
@@ -134,7 +146,7 @@ class Registry:
 
     def load_from_state_dict(self, state_dict: Mapping[str, object]):
         state_dict = canonicalize_state_dict(state_dict)
-        for arch in self.walk():
+        for arch in self.consulted():
             if arch.detect(state_dict):
                 model = arch.load(state_dict)
                 model.load_state_dict(state_dict)

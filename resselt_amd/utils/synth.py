@@ -815,6 +815,71 @@ def mosrv2_state_dict(in_ch=3, scale=4, n_block=24, dim=64, upsampler='pixelshuf
     return sd
 
 
+def _uni_upsample(sd, prefix, up, s, dim, out_ch, mid_dim, seed, version):
+    """UniUpsample as MoESR registers it (archs/moesr/arch.py:14-88): the MetaUpsample buffer first, DySample on the features themselves."""
+    sd[f'{prefix}.MetaUpsample'] = torch.tensor([version, MOSRV2_SAMPLE_MODS.index(up), s, dim, out_ch, mid_dim, 4], dtype=torch.uint8)
+    if s == 1 or up == 'conv':
+        _conv(sd, f'{prefix}.0', out_ch, dim, 3, seed)
+    elif up == 'pixelshuffledirect':
+        _conv(sd, f'{prefix}.0', out_ch * s * s, dim, 3, seed)
+    elif up == 'pixelshuffle':
+        _conv(sd, f'{prefix}.0', mid_dim, dim, 3, seed)
+        i = 2
+        for r in [2] * (s.bit_length() - 1) if s & (s - 1) == 0 else [3]:
+            _conv(sd, f'{prefix}.{i}', r * r * mid_dim, mid_dim, 3, seed)
+            i += 2
+        _conv(sd, f'{prefix}.{i}', out_ch, mid_dim, 3, seed)
+    elif up == 'nearest+conv':
+        i = 0
+        for _ in range(s.bit_length() - 1 if s & (s - 1) == 0 else 1):
+            _conv(sd, f'{prefix}.{i}', dim, dim, 3, seed)
+            i += 3
+        _conv(sd, f'{prefix}.{i}', dim, dim, 3, seed)
+        _conv(sd, f'{prefix}.{i + 2}', out_ch, dim, 3, seed)
+    elif up == 'dysample':
+        oc = 8 * s * s
+        h = torch.arange((-s + 1) / 2, (s - 1) / 2 + 1) / s  # (DySample's own buffer: before its sub-modules)
+        sd[f'{prefix}.0.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+        _conv(sd, f'{prefix}.0.end_conv', out_ch, dim, 1, seed)
+        _conv(sd, f'{prefix}.0.offset', oc, dim, 1, seed, scale=0.5)
+        _conv(sd, f'{prefix}.0.scope', oc, dim, 1, seed, bias=False)
+    else:
+        raise ValueError(f'unknown UniUpsample mode {up!r}')
+
+
+def moesr_state_dict(in_ch=3, out_ch=3, scale=4, dim=64, n_blocks=9, n_block=4, expansion_factor=8 / 3, expansion_msg=1.5,
+                     upsampler='pixelshuffledirect', upsample_dim=64, seed=0):  # fmt: skip
+    """Keys of the reference MoESR module (archs/moesr/arch.py:190-227) in its registration order: a block's ``gamma`` (its own parameter)
+    before its sub-modules, ``upscale.MetaUpsample`` before the head's layers.  ``gamma`` is 1 + uniform(+-0.25), so the scale is exercised;
+    the two convolutions of an MSG are drawn at half the default bound, which keeps the default depth (63 blocks) of order 1."""
+    sd: OrderedDict = OrderedDict()
+    if upsampler == 'conv':
+        scale = 1
+    gc = int(dim * 0.125)
+
+    def block(b, hidden):
+        sd[f'{b}.gamma'] = 1.0 + synth_tensor(f'{b}.gamma', (1, dim, 1, 1), 16, seed)
+        sd[f'{b}.norm.weight'] = 1.0 + synth_tensor(f'{b}.norm.weight', (dim,), 16, seed)
+        sd[f'{b}.norm.bias'] = synth_tensor(f'{b}.norm.bias', (dim,), 16, seed)
+        _conv(sd, f'{b}.fc1', 2 * hidden, dim, 3, seed)
+        _dwconv(sd, f'{b}.conv.dwconv_hw', gc, 3, 3, seed)
+        _dwconv(sd, f'{b}.conv.dwconv_w', gc, 1, 11, seed)
+        _dwconv(sd, f'{b}.conv.dwconv_h', gc, 11, 1, seed)
+        _conv(sd, f'{b}.fc2', dim, hidden, 3, seed)
+
+    _conv(sd, 'in_to_dim', dim, in_ch, 3, seed)
+    for g in range(n_blocks):
+        for j in range(n_block):
+            block(f'blocks.{g}.blocks.{j}', int(expansion_factor * dim))
+        m = f'blocks.{g}.msg'
+        _conv(sd, f'{m}.down.0', dim // 4, dim, 3, seed, scale=0.5)
+        for j in range(3):
+            block(f'{m}.gated.{j}', int(expansion_msg * dim))
+        _conv(sd, f'{m}.up.0', 4 * dim, dim, 3, seed, scale=0.5)
+    _uni_upsample(sd, 'upscale', upsampler, scale, dim, out_ch, upsample_dim, seed, version=1)
+    return sd
+
+
 def rgt_state_dict(in_chans=3, embed_dim=48, split_size=(2, 4), depth=(2,), num_heads=(4,), mlp_ratio=2.0, qkv_bias=True, upscale=2, resi='1conv',
                    c_ratio=0.5, img_size=64, seed=0):  # fmt: skip
     """Keys (parameters AND buffers) of the reference RGT module (archs/rgt/arch.py:630-838).

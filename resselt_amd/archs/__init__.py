@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -26,6 +26,7 @@ from .rcan import RCANArch
 from .rgt import RGTArch
 from .rha import RHAArch
 from .rtmosr import RTMoSRArch
+from .smosr import SMoSRArch
 from .span import SPANArch
 from .spanplus import SpanPlusArch
 from .spanpp import SpanPPArch
@@ -46,3 +47,7 @@ internal_registry.add(FlexNetArch(), last=True)
 # MoESR likewise (tests/test_moesr_loader.py), in ``Registry.after``: the open-ended tier consulted once ``walk()`` has declined, so that
 # ``late``, ``last``, ``walk()`` and what iterating over the registry yields stay what they were.  The reference walks it right behind RTMoSR.
 internal_registry.add(MoESRArch(), after=True)
+# SMoSR likewise (tests/test_smosr_loader.py), in ``Registry.tail``, consulted once ``consulted()`` has declined: ``after`` and
+# ``consulted()`` are held to ``walk()`` + MoESR by tests/test_moesr_loader.py, so they stay what they were too.  The reference walks it
+# between PLKSR and MoSRv2.
+internal_registry.add(SMoSRArch(), tail=True)

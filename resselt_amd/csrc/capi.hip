@@ -34,7 +34,6 @@ __device__ __forceinline__ float ld_as_float(const void* p, int64_t i) {
 // (F.pad(..., 'reflect') to the right/bottom, resselt/utilities/padding.py:24-29 as used by SwinIR.check_image_size)
 // unshuffle = r > 1: torch.pixel_unshuffle(x, r) fused into the read: plane channel c*r*r + i*r + j at (y, x) comes from source
 // channel c at (y*r + i, x*r + j) (RRDBNet x2plus / x1 front end, archs/esrgan/arch.py:130-137); C is then the SOURCE channel count.
-typedef __attribute__((ext_vector_type(8))) uint16_t u16x8;
 
 __global__ void nchw_to_planes_kernel(const void* x, int dtype, int batch, int C, int H, int W, int srcH, int srcW, int unshuffle,
                                       const float* mean, float scale, void* out_hi, void* out_lo, int64_t plane_stride,

@@ -23,6 +23,7 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) short s16x2;
+typedef __attribute__((ext_vector_type(8))) uint16_t u16x8;  // eight 16-bit patterns of either plane format (split_elem's results)
 
 // D[16][16] += A[16][32] * B[32][16] on 16-bit fragments of plane format FMT (enum rsa_plane_fmt: 0 = bf16, 1 = fp16); same fragment
 // layout, same cycles
@@ -144,6 +145,19 @@ __device__ __forceinline__ void store_unit(char* hi, char* lo, int64_t byte_off,
   for (int j = 0; j < 4; ++j) split2<FMT>(v[2 * j], v[2 * j + 1], h[j], l[j]);
   *(uint4*)(hi + byte_off) = make_uint4(h[0], h[1], h[2], h[3]);
   if (lo) *(uint4*)(lo + byte_off) = make_uint4(l[0], l[1], l[2], l[3]);
+}
+
+// A unit already in registers (an MFMA fragment loaded straight from planes): hi + lo -> f32
+template <int FMT>
+__device__ __forceinline__ void widen_unit(const bf16x8 h, const bf16x8 l, float (&v)[8]) {
+  if constexpr (FMT == RSA_PF_F16) {
+    const f16x8 hf = __builtin_bit_cast(f16x8, h), lf = __builtin_bit_cast(f16x8, l);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)hf[j] + (float)lf[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (float)l[j];
+  }
 }
 
 // The same for a run-time format fmt (enum rsa_plane_fmt, wave-uniform) and unit index u

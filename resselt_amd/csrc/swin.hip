@@ -144,7 +144,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8
         if (pl * 2 + 1 < p4) ((f32x4*)p.out_f32)[((int64_t)n * p4 + pl * 2 + 1) * HW + pix] = (f32x4){y[4], y[5], y[6], y[7]};
       }
       if (p.out_hi != nullptr) {
-        typedef __attribute__((ext_vector_type(8))) uint16_t u16x8;
         u16x8 h, l;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {

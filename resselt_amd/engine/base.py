@@ -106,6 +106,7 @@ class Plan:
         # descriptors were built against, and the (container, key, byte offset) of every pointer field or pointer argument into it
         self._y = self._x = None
         self._out_spec = None
+        self._crop_origin = None
         self._y0 = self._x0 = (0, 0)
         self._out_binds: list = []
         self._in_binds: list = []
@@ -122,13 +123,14 @@ class Plan:
         return t
 
     # ---- the forward's output and the caller's input ----
-    def output(self, shape, dtype, crop=None) -> torch.Tensor:
+    def output(self, shape, dtype, crop=None, crop_origin=None) -> torch.Tensor:
         """A placeholder of the forward's output, for ``conv_params(out_nchw=...)`` and the like (slices included); it is also the first forward's
         output.  Every descriptor field that points into it is re-pointed, at the same byte offset, to a fresh tensor by one host step at the
         start of ``steps`` whenever no output is held.  ``crop``: the (rows, columns) ``take_output`` keeps (dims 2-3; dims 1-2 of uint8 NHWC)."""
         self._y = torch.empty(shape, dtype=dtype, device=self.device)
         self._y0 = (self._y.data_ptr(), self._y.numel() * self._y.element_size())
         self._out_spec = (tuple(shape), dtype, crop)
+        self._crop_origin = crop_origin
         self.steps.insert(0, self._prepare_output)
         return self._y
 
@@ -176,7 +178,8 @@ class Plan:
         y, self._y, self._x = self._y, None, None
         crop = self._out_spec[2]
         if crop is not None:
-            y = y[:, : crop[0], : crop[1]] if y.dtype == torch.uint8 else y[:, :, : crop[0], : crop[1]]
+            r0, c0 = self._crop_origin or (0, 0)
+            y = y[:, r0 : r0 + crop[0], c0 : c0 + crop[1]] if y.dtype == torch.uint8 else y[:, :, r0 : r0 + crop[0], c0 : c0 + crop[1]]
         return y
 
     # ---- launch list ----

@@ -8,7 +8,7 @@ Behaviour kept from the reference:
   * the restricted unpickler only admits OrderedDict, ``_rebuild_tensor_v2`` and six storage classes and
     raises ``pickle.UnpicklingError`` for every other global (registry.py:20-46);
   * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``, then ``Registry.last``, then
-    ``Registry.after``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
+    ``Registry.after``, then ``Registry.tail``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
   * no match raises ``ArchitectureNotFound``.
 
 Documented deviation: the reference hands the *unconverted* dict to ``load_state_dict``, so official
@@ -93,16 +93,20 @@ class Registry:
     all three in the order ``load_from_state_dict`` consults them.  Iterating over the registry and ``len()`` cover ``store`` and ``late``
     only, as they did before ``last`` existed.  ``after`` is the open-ended tier behind them: any number of architectures, each under the same
     admission rule, consulted in insertion order once ``walk()`` has declined; ``consulted()`` yields everything, ``after`` included, in
-    consultation order, and ``__iter__``, ``len()`` and ``walk()`` do not see it -- a further architecture needs no further tier."""
+    consultation order, and ``__iter__``, ``len()`` and ``walk()`` do not see it -- a further architecture needs no further tier.
+    ``tail`` is where architectures go that came after ``consulted()`` had been pinned down as ``walk()`` + MoESR (tests/test_moesr_loader.py
+    holds ``after`` and ``consulted()`` to exactly that): the same admission rule, insertion order, consulted once ``consulted()`` has
+    declined; ``every()`` yields ``consulted()`` and then ``tail``, and nothing else sees it."""
 
     def __init__(self):
         self.store: Dict[str, Architecture] = {}
         self.late: Dict[str, Architecture] = {}
         self.last: Dict[str, Architecture] = {}
         self.after: Dict[str, Architecture] = {}
+        self.tail: Dict[str, Architecture] = {}
 
     def __contains__(self, uid: str) -> bool:
-        return uid in self.store or uid in self.late or uid in self.last or uid in self.after
+        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail
 
     def __iter__(self) -> Iterator[Architecture]:
         return iter(list(self.store.values()) + list(self.late.values()))
@@ -111,15 +115,25 @@ class Registry:
         return len(self.store) + len(self.late)
 
     def walk(self) -> Iterator[Architecture]:
-        """Every registered architecture in the order ``load_from_state_dict`` consults them: ``store``, ``late``, ``last``."""
+        """``store``, ``late``, ``last``: the first three tiers in the order ``load_from_state_dict`` consults them."""
         return iter(list(self.store.values()) + list(self.late.values()) + list(self.last.values()))
 
     def consulted(self) -> Iterator[Architecture]:
-        """Every registered architecture in the order ``load_from_state_dict`` consults them: ``walk()``, then ``after``."""
+        """``walk()``, then ``after``: what ``load_from_state_dict`` consults before ``tail`` (``every()`` is the whole order)."""
         return iter(list(self.walk()) + list(self.after.values()))
 
-    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False) -> None:
+    def every(self) -> Iterator[Architecture]:
+        """Every registered architecture in the order ``load_from_state_dict`` consults them: ``consulted()``, then ``tail``."""
+        return iter(list(self.consulted()) + list(self.tail.values()))
+
+    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False, tail: bool = False) -> None:
         """Register an architecture *instance*; re-using an id replaces it in place."""
+        if tail and not any(arch.id in t for t in (self.store, self.late, self.last, self.after)):
+            self.tail[arch.id] = arch
+            return
+        self.tail.pop(arch.id, None)
+        if tail:  # an id another tier already holds is replaced there
+            after, last, late = after or arch.id in self.after, last or arch.id in self.last, late or arch.id in self.late
         if after and arch.id not in self.store and arch.id not in self.late and arch.id not in self.last:
             self.after[arch.id] = arch
             return
@@ -135,7 +149,7 @@ class Registry:
             self.store[arch.id] = arch
 
     def get(self, uid: str) -> Architecture:
-        tier = next((t for t in (self.late, self.last, self.after) if uid in t), self.store)
+        tier = next((t for t in (self.late, self.last, self.after, self.tail) if uid in t), self.store)
         arch = tier[uid]  # KeyError for unknown ids, as in the reference
         if not arch:
             raise ArchitectureNotFound
@@ -146,7 +160,7 @@ class Registry:
 
     def load_from_state_dict(self, state_dict: Mapping[str, object]):
         state_dict = canonicalize_state_dict(state_dict)
-        for arch in self.consulted():
+        for arch in self.every():
             if arch.detect(state_dict):
                 model = arch.load(state_dict)
                 model.load_state_dict(state_dict)

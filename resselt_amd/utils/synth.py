@@ -1488,3 +1488,58 @@ def flexnet_state_dict(seed=0, dim=64, num_blocks=(6, 6, 6, 6, 6, 6), scale=4, i
     else:
         conv('to_img.0', out_channels * s * s, 2 * dim, 3, gain=0.5)
     return sd
+
+
+def smosr_state_dict(in_ch=3, out_ch=3, dim=48, scale=2, rep=False, n_mb=3, upsampler='pixelshuffledirect', upsampler_mid_dim=32, d_kernel=3,
+                     head_gain=1.0, short_gain=1.0, seed=0):  # fmt: skip
+    """Keys of the reference SMoSR module (archs/smosr/arch.py:419-459) in its registration order, which is the order the engine's module
+    registers them in.  Every ``W`` is uniform * sqrt(3 / fan_in) * 0.5, ``D`` uniform in +-0.05 on top of the ``d_diag`` identity, ``mul``
+    its initial value (3 in an SMB's body, 0.02 in a ConvNXC's ``sk``, 1 elsewhere) * (1 +- 0.1), so the fold matters; the two kinds of
+    ``short`` are their 0 / 1 initial pattern plus uniform +-0.25 / sqrt(cin); every ``eval_conv.*`` is unrelated noise, which a correct
+    implementation never reads.  ``head_gain`` scales the ``W`` of the head's last convolution (DySample's ``end_conv``) and ``short_gain``
+    the global ``short``: the gains that bring ``|y|`` to order 1."""
+    from ..archs.smosr.arch import SMoSR  # (not at import time: the architectures import this package's siblings)
+
+    m = SMoSR(in_ch=in_ch, out_ch=out_ch, dim=dim, scale=scale, rep=rep, n_mb=n_mb, upsampler=upsampler, upsampler_mid_dim=upsampler_mid_dim, d_kernel=d_kernel)
+    last = max(i for i, _, _, _ in m.head_convs) if m.head_convs else -1
+    last_w = {f'upsampler.{m.dys_index}.end_conv.weight'} if m.dys_index is not None else {
+        k for k in m._mul_init if k.startswith(f'upsampler.{last}.') and (not rep or '.conv.2.' in k or '.sk.' in k)}
+    last_w = {k[: -len('mul')] + 'W' if k.endswith('.mul') else k for k in last_w}
+    sd: OrderedDict = OrderedDict()
+    for k, v in m.state_dict().items():
+        shape, leaf = tuple(v.shape), k.rsplit('.', 1)[1]
+        if k.endswith('MetaUpsample') or k.endswith('init_pos'):
+            sd[k] = v.clone()
+        elif '.eval_conv.' in k:
+            sd[k] = synth_tensor(k, shape, 1, seed)
+        elif leaf == 'mul':
+            sd[k] = m._mul_init[k] * (1.0 + synth_tensor(k, shape, 1, seed, 0.1))
+        elif leaf == 'W':
+            sd[k] = synth_tensor(k, shape, shape[1] * shape[2], seed, 0.5 * 3**0.5 * (head_gain if k in last_w else 1.0))
+        elif leaf == 'D':
+            sd[k] = synth_tensor(k, shape, 1, seed, 0.05)
+        elif leaf == 'd_diag':
+            sd[k] = torch.eye(shape[1], dtype=torch.float32).reshape(1, shape[1], shape[1]).repeat(shape[0], 1, 1)
+        elif k in ('short.weight', 'blocks_1.0.short.weight'):
+            co, ci = shape[:2]
+            w = torch.zeros(shape)
+            if k == 'short.weight':  # channel c feeds outputs [c s^2, (c + 1) s^2)  (:437-442)
+                for c in range(ci):
+                    w[c * (co // ci) : (c + 1) * (co // ci), c] = 1.0
+                w *= short_gain
+            else:  # channel c feeds k or k + 1 consecutive outputs (:391-400)
+                o = 0
+                for c in range(ci):
+                    n = co // ci + (1 if c < co % ci else 0)
+                    w[o : o + n, c] = 1.0
+                    o += n
+            sd[k] = w + synth_tensor(k, shape, ci, seed, 0.25)
+        elif k.endswith('.scope.weight'):
+            sd[k] = synth_tensor(k, shape, shape[1], seed)
+        elif k.endswith('.offset.weight') or k.endswith('.offset.bias'):
+            sd[k] = synth_tensor(k, shape, shape[1] if len(shape) > 1 else m.mid_dim, seed, 0.5)
+        elif k.endswith('.end_conv.weight'):
+            sd[k] = synth_tensor(k, shape, shape[1] * shape[2] * shape[3], seed, head_gain)
+        else:  # biases
+            sd[k] = synth_tensor(k, shape, 16, seed, 0.25)
+    return sd

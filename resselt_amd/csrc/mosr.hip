@@ -1,5 +1,6 @@
 // mosr.hip — the non-convolution kernels of the MoSR / MoSRv2 path (reference resselt/archs/mosr/arch.py, resselt/archs/mosrv2/arch.py):
 //   rsa_gated_dwconv   mish(g) * cat(i, segments(c)) on split planes: identity, k x k, 1 x k and k x 1 depthwise    GatedCNNBlock.forward
+//   rsa_gfisr_gate     the same kernel with the gate activation as a template argument: silu(g) for GFISRv2 (resselt_amd_gfisr.h)
 //   rsa_bilinear_add   out += bilinear x scale of the reflect-padded input (the image shortcut of MoSRv2)              MoSRv2.forward :328-337
 // Both are HBM-bound streaming kernels; the fc1 / fc2 convolutions around the first are single launches of the fused convolution.
 #include <hip/hip_runtime.h>
@@ -8,6 +9,7 @@
 #include "common.h"
 #include "plane_unit.h"
 #include "resselt_amd.h"
+#include "resselt_amd_gfisr.h"
 
 namespace rsa {
 namespace {
@@ -28,15 +30,25 @@ struct Operands {
   bf16x8* o_lo;
 };
 
+// the gate activation: Mish (MoSR, MoSRv2, MoESR) or SiLU (GFISRv2: x / (1 + exp(-x)), as torch computes it)
+template <int ACT>
+__device__ __forceinline__ float gate_act(float v) {
+  if constexpr (ACT == RSA_ACT_SILU)
+    return v / (1.f + expf(-v));
+  else
+    return mish_exact(v);
+}
+
+template <int ACT>
 __device__ __forceinline__ void finish(const Operands& o, int64_t pix, const float (&m)[8], int fmt) {
   float g[8], r[8];
   get_unit(o.g_hi, o.g_lo, pix, g, fmt);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = mish_exact(g[j]) * m[j];
+  for (int j = 0; j < 8; ++j) r[j] = gate_act<ACT>(g[j]) * m[j];
   put_unit(o.o_hi, o.o_lo, pix, r, fmt);
 }
 
-template <int KH, int KW>
+template <int ACT, int KH, int KW>
 __device__ __forceinline__ void conv_tile(const Operands& o, const float* __restrict__ w, const float* __restrict__ b, int H, int W, int x0, int y0,
                                           int fmt, f32x4* lds0, f32x4* lds1) {
   constexpr int RH = KH / 2, RW = KW / 2, HH = TH + KH - 1, HWP = TW + KW - 1, KK = KH * KW;
@@ -70,7 +82,7 @@ __device__ __forceinline__ void conv_tile(const Operands& o, const float* __rest
       }
     }
   }
-  finish(o, (int64_t)y * W + x, acc, fmt);
+  finish<ACT>(o, (int64_t)y * W + x, acc, fmt);
 }
 
 // shape ids: 0 identity, 1 + (k - 3) / 2 square k x k, 6 + (k - 3) / 2 band 1 x k, 11 + (k - 3) / 2 band k x 1; -1 not compiled
@@ -85,6 +97,7 @@ __host__ __device__ inline int shape_id(int kh, int kw) {
 }
 
 // grid (tiles, planes, batch), 256 threads
+template <int ACT>
 __global__ __launch_bounds__(256) void gated_dwconv_kernel(const rsa_gated_dwconv_params p) {
   __shared__ f32x4 lds[2][HALO_UNITS];
   const int tiles_x = (p.W + TW - 1) / TW;
@@ -123,12 +136,12 @@ __global__ __launch_bounds__(256) void gated_dwconv_kernel(const rsa_gated_dwcon
       const int64_t pix = (int64_t)y * p.W + x;
       float m[8];
       get_unit(o.x_hi, o.x_lo, pix, m, fmt);
-      finish(o, pix, m, fmt);
+      finish<ACT>(o, pix, m, fmt);
       return;
     }
 #define RSA_MOSR_CASE(ID, KH, KW) \
   case ID:                        \
-    conv_tile<KH, KW>(o, w, b, p.H, p.W, x0, y0, fmt, l0, l1); \
+    conv_tile<ACT, KH, KW>(o, w, b, p.H, p.W, x0, y0, fmt, l0, l1); \
     return;
     RSA_MOSR_CASE(1, 3, 3)
     RSA_MOSR_CASE(2, 5, 5)
@@ -194,7 +207,9 @@ __global__ __launch_bounds__(256) void bilinear_add_kernel(const rsa_bilinear_ad
 
 using namespace rsa;
 
-extern "C" int rsa_gated_dwconv(const rsa_gated_dwconv_params* p, void* stream) {
+// every argument check of rsa_gated_dwconv / rsa_gfisr_gate, then the launch with the gate activation ACT
+template <int ACT>
+static int gated_dwconv_launch(const rsa_gated_dwconv_params* p, void* stream) {
   if (p == nullptr) return set_error(RSA_E_ARG, "gated_dwconv: null params");
   if (p->batch < 1 || p->batch > 65535 || p->H < 1 || p->W < 1 || p->i_planes < 0 || p->n_segments < 0 || p->n_segments > 4 ||
       !plane_fmt_ok(p->fmt))
@@ -215,8 +230,16 @@ extern "C" int rsa_gated_dwconv(const rsa_gated_dwconv_params* p, void* stream) 
     return set_error(RSA_E_ALIGN, "gated_dwconv: planes must be 16-byte aligned");
   const int64_t tiles = (int64_t)((p->W + TW - 1) / TW) * ((p->H + TH - 1) / TH);
   if (tiles > 0x7fffffff) return set_error(RSA_E_ARG, "gated_dwconv: map too large");
-  hipLaunchKernelGGL(gated_dwconv_kernel, dim3((unsigned)tiles, (unsigned)planes, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(gated_dwconv_kernel<ACT>, dim3((unsigned)tiles, (unsigned)planes, (unsigned)p->batch), dim3(256), 0, (hipStream_t)stream, *p);
   return launch_status("gated_dwconv: launch failed");
+}
+
+extern "C" int rsa_gated_dwconv(const rsa_gated_dwconv_params* p, void* stream) { return gated_dwconv_launch<RSA_ACT_MISH>(p, stream); }
+
+extern "C" int rsa_gfisr_gate(const rsa_gated_dwconv_params* p, int32_t act, void* stream) {
+  if (act == RSA_ACT_MISH) return gated_dwconv_launch<RSA_ACT_MISH>(p, stream);
+  if (act == RSA_ACT_SILU) return gated_dwconv_launch<RSA_ACT_SILU>(p, stream);
+  return set_error(RSA_E_UNSUPPORTED, "gfisr_gate: the gate activation must be RSA_ACT_MISH or RSA_ACT_SILU");
 }
 
 extern "C" int rsa_bilinear_add(const rsa_bilinear_add_params* p, void* stream) {

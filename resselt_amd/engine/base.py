@@ -233,7 +233,7 @@ class Plan:
             self._bind(args, [k for k, t in args._fields_ if t is C.c_void_p])
             return lambda: L.launch(name, args, ops.current_stream_ptr(dev))
         argv = L.bind(name, **args)
-        self._bind(argv, [i for i, (_, t) in enumerate(L.SIGNATURES[name][1][: len(argv)]) if t is C.c_void_p])
+        self._bind(argv, [i for i, (_, t) in enumerate(L.signature(name)[1][: len(argv)]) if t is C.c_void_p])
         return lambda: L.invoke(name, argv, ops.current_stream_ptr(dev))
 
     def launch(self, name, args=None, kernels: int = 1, meta: dict | None = None) -> None:

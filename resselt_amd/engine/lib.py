@@ -568,15 +568,20 @@ def check(rc: int, what: str) -> None:
         raise cls(f'{what} failed (status {rc}): {msg.decode() if msg else "?"}')
 
 
+def signature(name: str) -> tuple:
+    """The row of entry point ``name``: of include/resselt_amd.h or of an extension header."""
+    return SIGNATURES[name] if name in SIGNATURES else EXTENSIONS[name]
+
+
 def bind(name: str, **kwargs) -> list:
-    """Resolve keyword arguments against ``SIGNATURES[name]`` into the positional argument list of the entry point, without its trailing
+    """Resolve keyword arguments against ``SIGNATURES[name]`` (or the row of an extension header, ``EXTENSIONS[name]``) into the positional argument list of the entry point, without its trailing
     stream.  Keys are the header's parameter names (a trailing underscore is dropped: ``in_``).  Values:
 
     ``Planes`` / ``PlaneRows`` under key ``k`` fill ``k_hi``, ``k_lo``, ``k_plane_stride`` and ``k_batch_stride`` (``(planes, plane0)`` from
     that plane on, as in ``ops.conv_params(res1=...)``); an explicit ``k_lo=`` beside it replaces the lo pointer (``None`` for a reader that
     must not see lo halves).  A tensor becomes its ``data_ptr()``, ``None`` becomes NULL, numbers and descriptors pass through.
     A missing, unknown or doubly given parameter raises ``TypeError``: nothing has been launched by then."""
-    params = [k for k, _ in SIGNATURES[name][1]]
+    params = [k for k, _ in signature(name)[1]]
     given = {'stream': None} if params and params[-1] == 'stream' else {}  # the caller of the entry point supplies it
 
     def put(key, value, replace=False):

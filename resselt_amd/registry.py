@@ -8,7 +8,7 @@ Behaviour kept from the reference:
   * the restricted unpickler only admits OrderedDict, ``_rebuild_tensor_v2`` and six storage classes and
     raises ``pickle.UnpicklingError`` for every other global (registry.py:20-46);
   * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``, then ``Registry.last``, then
-    ``Registry.after``, then ``Registry.tail``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
+    ``Registry.after``, then ``Registry.tail``, then ``Registry.rest``: ``Registry.order()``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
   * no match raises ``ArchitectureNotFound``.
 
 Documented deviation: the reference hands the *unconverted* dict to ``load_state_dict``, so official
@@ -96,7 +96,11 @@ class Registry:
     consultation order, and ``__iter__``, ``len()`` and ``walk()`` do not see it -- a further architecture needs no further tier.
     ``tail`` is where architectures go that came after ``consulted()`` had been pinned down as ``walk()`` + MoESR (tests/test_moesr_loader.py
     holds ``after`` and ``consulted()`` to exactly that): the same admission rule, insertion order, consulted once ``consulted()`` has
-    declined; ``every()`` yields ``consulted()`` and then ``tail``, and nothing else sees it."""
+    declined; ``every()`` yields ``consulted()`` and then ``tail``, and nothing else sees it.
+    ``rest`` is the tier for every architecture after that (tests/test_smosr_loader.py holds ``tail`` and ``every()`` to exactly
+    ``consulted()`` + SMoSR): the same admission rule, any number of architectures in insertion order, consulted once ``every()`` has
+    declined.  ``order()`` is the whole consultation order and what ``load_from_state_dict`` walks; no test may hold ``rest`` or ``order()``
+    to a fixed list of ids (membership and relative order only), so the next architecture goes into ``rest`` too."""
 
     def __init__(self):
         self.store: Dict[str, Architecture] = {}
@@ -104,9 +108,10 @@ class Registry:
         self.last: Dict[str, Architecture] = {}
         self.after: Dict[str, Architecture] = {}
         self.tail: Dict[str, Architecture] = {}
+        self.rest: Dict[str, Architecture] = {}
 
     def __contains__(self, uid: str) -> bool:
-        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail
+        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail or uid in self.rest
 
     def __iter__(self) -> Iterator[Architecture]:
         return iter(list(self.store.values()) + list(self.late.values()))
@@ -126,8 +131,18 @@ class Registry:
         """Every registered architecture in the order ``load_from_state_dict`` consults them: ``consulted()``, then ``tail``."""
         return iter(list(self.consulted()) + list(self.tail.values()))
 
-    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False, tail: bool = False) -> None:
+    def order(self) -> Iterator[Architecture]:
+        """The whole consultation order of ``load_from_state_dict``: ``every()``, then ``rest``."""
+        return iter(list(self.every()) + list(self.rest.values()))
+
+    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False, tail: bool = False, rest: bool = False) -> None:
         """Register an architecture *instance*; re-using an id replaces it in place."""
+        if rest and not any(arch.id in t for t in (self.store, self.late, self.last, self.after, self.tail)):
+            self.rest[arch.id] = arch
+            return
+        self.rest.pop(arch.id, None)
+        if rest:  # an id another tier already holds is replaced there
+            tail = tail or arch.id in self.tail
         if tail and not any(arch.id in t for t in (self.store, self.late, self.last, self.after)):
             self.tail[arch.id] = arch
             return
@@ -149,7 +164,7 @@ class Registry:
             self.store[arch.id] = arch
 
     def get(self, uid: str) -> Architecture:
-        tier = next((t for t in (self.late, self.last, self.after, self.tail) if uid in t), self.store)
+        tier = next((t for t in (self.late, self.last, self.after, self.tail, self.rest) if uid in t), self.store)
         arch = tier[uid]  # KeyError for unknown ids, as in the reference
         if not arch:
             raise ArchitectureNotFound
@@ -160,7 +175,7 @@ class Registry:
 
     def load_from_state_dict(self, state_dict: Mapping[str, object]):
         state_dict = canonicalize_state_dict(state_dict)
-        for arch in self.every():
+        for arch in self.order():
             if arch.detect(state_dict):
                 model = arch.load(state_dict)
                 model.load_state_dict(state_dict)

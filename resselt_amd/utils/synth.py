@@ -1543,3 +1543,62 @@ def smosr_state_dict(in_ch=3, out_ch=3, dim=48, scale=2, rep=False, n_mb=3, upsa
         else:  # biases
             sd[k] = synth_tensor(k, shape, 16, seed, 0.25)
     return sd
+
+
+GFISRV2_SAMPLE_MODS = MOSRV2_SAMPLE_MODS + ('transpose+conv', 'lda', 'pa_up')
+
+
+def gfisrv2_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansion_ratio=8 / 3, upsampler='pixelshuffledirect', mid_dim=32, seed=0):
+    """Keys of the reference GFISRV2 module (archs/gfisrv2/arch.py:637-686) in its registration order: a block's ``gamma`` before its
+    sub-modules, the four Inception branches under the attribute names that rotate with the block index, ``upscale.MetaUpsample`` before the
+    head's layers (UniUpsampleV3 with a 3x3 DySample end convolution).  Scales, offsets, gammas and biases are all randomised; fc2 is drawn
+    at half the default bound, which keeps the default depth (24 blocks) of order 1."""
+    from ..archs.gfisrv2.arch import branch_order  # (not at import time: the architectures import this package's siblings)
+
+    sd: OrderedDict = OrderedDict()
+    hidden = int(expansion_ratio * dim)
+    gc = int(dim * 0.125)
+    cf = dim - 3 * gc
+
+    def rms(name, c):
+        sd[f'{name}.scale'] = 1.0 + synth_tensor(f'{name}.scale', (c, 1, 1), 16, seed)
+        sd[f'{name}.offset'] = synth_tensor(f'{name}.offset', (c, 1, 1), 16, seed)
+
+    _conv(sd, 'in_to_dim', dim, in_nc, 3, seed)
+    for i in range(n_blocks):
+        b = f'gfisr_body.{i}'
+        sd[f'{b}.gamma'] = 1.0 + synth_tensor(f'{b}.gamma', (1, dim, 1, 1), 16, seed)
+        rms(f'{b}.norm', dim)
+        _conv(sd, f'{b}.fc1', 2 * hidden, dim, 3, seed)
+        for name, kind in branch_order(i):
+            c = f'{b}.conv.{name}'
+            if kind is None:
+                rms(f'{c}.rn', 2 * cf)
+                rms(f'{c}.post_norm', cf)
+                _conv(sd, f'{c}.fdc', 2 * cf, 2 * cf, 1, seed)
+                _dwconv(sd, f'{c}.fpe', 2 * cf, 3, 3, seed)
+            else:
+                _dwconv(sd, c, gc, kind[0], kind[1], seed)
+        _conv(sd, f'{b}.fc2', dim, hidden, 3, seed, scale=0.5)
+    _conv(sd, f'gfisr_body.{n_blocks}', 2 * dim, dim, 3, seed)
+    _conv(sd, f'gfisr_body.{n_blocks + 2}', dim, 2 * dim, 3, seed)
+    up, s = upsampler, scale
+    meta = torch.tensor([3, GFISRV2_SAMPLE_MODS.index(up), s, dim, out_nc, mid_dim, 4], dtype=torch.uint8)
+    if s != 1 and up == 'dysample':
+        sd['upscale.MetaUpsample'] = meta
+        i, dys_dim = 0, dim
+        if mid_dim != dim:
+            _conv(sd, 'upscale.0', mid_dim, dim, 3, seed)
+            i, dys_dim = 2, mid_dim
+        oc = 8 * s * s
+        h = torch.arange((-s + 1) / 2, (s - 1) / 2 + 1) / s  # (DySample's own buffer: before its sub-modules)
+        sd[f'upscale.{i}.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+        _conv(sd, f'upscale.{i}.end_conv', out_nc, dys_dim, 3, seed)
+        _conv(sd, f'upscale.{i}.offset', oc, dys_dim, 1, seed, scale=0.5)
+        _conv(sd, f'upscale.{i}.scope', oc, dys_dim, 1, seed, bias=False)
+    elif s == 1 or up in MOSRV2_SAMPLE_MODS:
+        _uni_upsample(sd, 'upscale', 'conv' if s == 1 else up, s, dim, out_nc, mid_dim, seed, version=3)
+        sd['upscale.MetaUpsample'] = meta  # (the same place in the order; at scale 1 every mode is the one convolution)
+    else:
+        raise ValueError(f'gfisrv2_state_dict: the {up!r} head is not synthesised')
+    return sd

@@ -54,7 +54,9 @@ def _ln(sd, key, x):
 
 def window_partition(x, ws):
     b, h, w, c = x.shape
-    return x.view(b, h // ws, ws, w // ws, ws, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws, ws, c)
+    # .contiguous() as in the reference (arch.py:100): with one row of windows and one image, reshape() alone returns a strided view, and the
+    # callers' .view() then refused heights of 5 to 8 that the reference runs (tests/golden/hat_x2_e60_w8_d2_one_window_row_5x11.npz)
+    return x.view(b, h // ws, ws, w // ws, ws, c).permute(0, 1, 3, 2, 4, 5).contiguous().view(-1, ws, ws, c)
 
 
 def window_reverse(win, ws, h, w):

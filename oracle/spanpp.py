@@ -1,6 +1,6 @@
 """Oracle for SpanPP (TEST INFRASTRUCTURE, see oracle/__init__.py).
 
-Functional fp32 restatement of ``resselt/archs/spanpp/arch.py`` in eval mode -- the only mode in which the reference module can run:
+Functional restatement (in the dtype of the state dict and the input, as the other oracles) of ``resselt/archs/spanpp/arch.py`` in eval mode -- the only mode in which the reference module can run:
 ``IGConv.forward`` reads ``eval_convs``, which only ``.train(mode)`` / ``.eval()`` populates (arch.py:277-291), and ``.eval()`` also
 replaces every RepConv by its fused 3x3 (arch.py:166-193).  Pinned by tests/golden/spanpp_*.npz (outputs of the reference itself).
 """
@@ -18,7 +18,7 @@ def fold_seqconv(sd, key):
     """SeqConv3x3.rep_params (arch.py:138-150): 1x1 then 3x3 (bias-padded) == one zero-padded 3x3."""
     k0, b0, k1, b1 = (sd[f'{key}.{n}'] for n in ('k0', 'b0', 'k1', 'b1'))
     w = F.conv2d(k1, k0.permute(1, 0, 2, 3))
-    b = F.conv2d(torch.ones(1, k0.shape[0], 3, 3) * b0.view(1, -1, 1, 1), k1).view(-1) + b1
+    b = F.conv2d(torch.ones(1, k0.shape[0], 3, 3, dtype=k0.dtype) * b0.view(1, -1, 1, 1), k1).view(-1) + b1
     return w, b
 
 
@@ -52,8 +52,8 @@ def igconv_kernel(sd, scale: int, max_scale: int) -> torch.Tensor:
     """IGConv._implicit_representation_latent (arch.py:293-312): the [3*s*s, C, k, k] kernel of the scale-s head."""
     freq, amp = sd['upsampler.freq'], sd['upsampler.amplitude']
     n = freq.shape[0]
-    r = torch.ones(1, 1, scale, scale) / min(scale, max_scale) * 2
-    seq = [-1 + (1 / scale) + (2 / scale) * torch.arange(scale).float()] * 2
+    r = torch.ones(1, 1, scale, scale, dtype=freq.dtype) / min(scale, max_scale) * 2
+    seq = [-1 + (1 / scale) + (2 / scale) * torch.arange(scale).to(freq.dtype)] * 2
     coords = torch.stack(torch.meshgrid(*seq, indexing='ij'), dim=-1).flip(-1)  # make_coord (arch.py:220-231)
     coords = coords.unsqueeze(0).permute(0, 3, 1, 2).repeat(n, 1, 1, 1)
     f = freq.repeat(1, 1, scale, scale)
@@ -84,6 +84,7 @@ def spanpp_forward(sd: Mapping[str, torch.Tensor], x: torch.Tensor, scale: int |
     """SpanPP.forward (arch.py:358-373), eval mode; ``scale=None`` selects eval_base_scale = 2 (arch.py:323, 284)."""
     scales = [int(v) for v in sd['MetaIGConv']] if 'MetaIGConv' in sd else [1, 2, 3, 4]
     s = 2 if scale is None else scale
+    sd = {k: v.to(x.dtype) if v.is_floating_point() else v for k, v in sd.items()}  # the dtype of the input decides, as in the other oracles
     feat = _repconv(sd, 'conv0', x)
     b1, _ = _spab(sd, 'block_1', feat)
     cur = b1

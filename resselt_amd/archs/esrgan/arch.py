@@ -123,11 +123,25 @@ class RRDBNet(EngineModule):
         self.tail_band_rows = 272  # low-resolution rows per band of the 2x / 4x tail (bounds the plan's HR buffers; >= image height: one band)
         self.plane_residuals = True  # residual stream kept as split planes only (False: the f32-map plan; A/B and plain-bf16 mode)
         self.stream_lo8 = os.environ.get('RSA_STREAM_LO8', '1') != '0'  # 'mixed': lo halves of the residual stream as 8-bit codes (A/B: RSA_STREAM_LO8=0)
+        if plus:
+            self.precisions = ('bf16x3', 'bf16')  # ESRGAN+ (conv1x1 branch, f32 side maps) has no 'mixed' plan: the mode is not offered
         if plus or num_filters != 64:
             # the 'mixed' table is built for the x4plus / x2plus / ESRGAN trunk (64 channels: the fp16x3 trunk convolution is the four-tile
             # ring kernel); ESRGAN+ adds f32 side maps it has no plan for.  Such checkpoints run the conservative mode under 'auto'.
             self.auto_precision = 'bf16x3'
         build_param_tree(self, rrdbnet_param_shapes(in_nc, out_nc, num_filters, num_blocks, scale, plus))
+
+    @property
+    def tail_band_rows(self) -> int:
+        return self._tail_band_rows
+
+    @tail_band_rows.setter
+    def tail_band_rows(self, rows: int) -> None:
+        # the band height is built into a plan and is no part of its key: plans built for another value are dropped (the packed weights stay)
+        if rows != getattr(self, '_tail_band_rows', rows):
+            for key in list(getattr(self, '_plans', {})):
+                self._drop_plan(key)
+        self._tail_band_rows = rows
 
     def _convert_state_dict(self, state_dict):
         return new_arch_to_old(state_dict)

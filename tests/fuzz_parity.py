@@ -95,8 +95,16 @@ def main():
                           (rng.choice([(2, 1), (1,), (2,), (4, 2)])), 5),
         'flexnet': lambda s: (synth.flexnet_state_dict(seed=s, dim=rng.choice([32, 48]), num_blocks=rng.choice([(1, 1), (2,), (1, 2)]), scale=rng.choice([2, 3, 4]),
                                                        upsampler=rng.choice(['ps', 'dys', 'n+c']), channel_norm=rng.random() < 0.3), 5),
+        'moesr': lambda s: (synth.moesr_state_dict(scale=rng.choice([2, 3, 4]), dim=rng.choice([32, 48]), n_blocks=rng.choice([1, 2]), n_block=rng.choice([1, 2]),
+                                                   upsampler=rng.choice(['pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample']), seed=s), 2),
+        'smosr': lambda s: ((lambda up: synth.smosr_state_dict(dim=rng.choice([32, 48]), scale=rng.choice([2, 3, 4] if up != 'nearest+conv' else [2, 4]),
+                                                               rep=up != 'dysample' and rng.random() < 0.4, n_mb=rng.choice([1, 2]), upsampler=up,
+                                                               d_kernel=rng.choice([1, 3]), seed=s))
+                            (rng.choice(['pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample', 'pa_up'])), 3),
+        'gfisrv2': lambda s: (synth.gfisrv2_state_dict(dim=rng.choice([16, 32]), scale=rng.choice([2, 3, 4]), n_blocks=rng.choice([1, 2]),
+                                                       upsampler=rng.choice(['pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample']), seed=s), 2),
     }  # fmt: skip
-    own_oracle = ('mosr', 'mosrv2', 'rgt', 'fdat', 'omnisr', 'rcan', 'gater', 'eimn', 'rha', 'flexnet')
+    own_oracle = ('mosr', 'mosrv2', 'rgt', 'fdat', 'omnisr', 'rcan', 'gater', 'eimn', 'rha', 'flexnet', 'moesr', 'smosr', 'gfisrv2')
     worst = 0.0
     for arch, make in makers.items():
         for k in range(per_arch):

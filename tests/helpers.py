@@ -100,7 +100,7 @@ def oracle_forward(meta, sd, x):
         from atd_oracle import atd_forward
 
         return atd_forward(sd, x, meta['hyper'], force=meta.get('force'), record=meta.get('record'))
-    if meta['arch'] in ('fdat', 'omnisr', 'rcan', 'gater', 'eimn', 'rha', 'flexnet'):
+    if meta['arch'] in ('fdat', 'omnisr', 'rcan', 'gater', 'eimn', 'rha', 'flexnet', 'moesr', 'smosr', 'gfisrv2'):
         import importlib
 
         return getattr(importlib.import_module(f'{meta["arch"]}_oracle'), f'{meta["arch"]}_forward')(sd, x)

@@ -23,6 +23,8 @@ from resselt_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
 
+MODEL_REL = 3e-4  # whole models: max-abs <= MODEL_REL * max(1, |y|max) (the sweep of the original families prints its errors against it)
+
 
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
@@ -243,7 +245,7 @@ def test_dat_matches_reference_vectors(device, name):
     assert y.shape == arr['y'].shape
     err = (y.cpu() - arr['y']).abs().max().item()
     print(f'{name}: max-abs {err:.3e}')
-    assert err <= 3e-4 * max(1.0, arr['y'].abs().max().item()), f'{name}: max-abs {err:.3e}'
+    assert err <= MODEL_REL * max(1.0, arr['y'].abs().max().item()), f'{name}: max-abs {err:.3e}'
 
 
 def test_dat_vs_oracle_dtypes_and_precision(device):
@@ -257,7 +259,7 @@ def test_dat_vs_oracle_dtypes_and_precision(device):
     assert y.shape == ref.shape == (1, 3, 180, 240)
     err = (y.cpu() - ref).abs().max().item()
     print(f'DAT(2x4) bf16x3 max-abs {err:.3e} (|y|max {ref.abs().max():.2f})')
-    assert err <= 3e-4 * max(1.0, ref.abs().max().item())
+    assert err <= MODEL_REL * max(1.0, ref.abs().max().item())
     yh = m(x.to(device).half())
     assert yh.dtype == torch.float16
     with torch.no_grad():

@@ -16,6 +16,8 @@ from helpers import golden_names, load_golden, oracle_forward, synth_state_dict
 
 pytestmark = pytest.mark.gpu
 
+MODEL_REL = 1e-4  # whole models: max-abs <= MODEL_REL * max(1, |y|max) (the sweep of the original families prints its errors against it)
+
 
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
@@ -89,7 +91,7 @@ def test_drct_matches_reference_vectors(device, name):
     assert y.shape == arr['y'].shape
     err = (y.cpu() - arr['y']).abs().max().item()
     print(f'{name}: max-abs {err:.3e}')
-    assert err <= 1e-4 * max(1.0, arr['y'].abs().max().item()), f'{name}: max-abs {err:.3e}'
+    assert err <= MODEL_REL * max(1.0, arr['y'].abs().max().item()), f'{name}: max-abs {err:.3e}'
 
 
 def test_drct_vs_oracle_other_size_and_dtypes(device):
@@ -99,13 +101,13 @@ def test_drct_vs_oracle_other_size_and_dtypes(device):
         ref = oracle_forward(dict(arch='drct'), sd, x)
     m = resselt_amd.load_from_state_dict(dict(sd)).to(device)
     y = m(x.to(device))
-    assert (y.cpu() - ref).abs().max().item() <= 1e-4 * max(1.0, ref.abs().max().item())
+    assert (y.cpu() - ref).abs().max().item() <= MODEL_REL * max(1.0, ref.abs().max().item())
     yh = m(x.half().to(device))
     assert yh.dtype == torch.float16 and (yh.float().cpu() - ref).abs().max().item() <= 4e-3 * max(1.0, ref.abs().max().item())
     m.precision = 'bf16'
     assert (m(x.to(device)).cpu() - ref).abs().max().item() <= 3e-2 * max(1.0, ref.abs().max().item())
     x2 = synth.synth_input((1, 3, 70, 45), seed=10)
-    for precision, bar in (('bf16x3', 1e-4), ('auto', 1e-4)):
+    for precision, bar in (('bf16x3', MODEL_REL), ('auto', MODEL_REL)):
         m.precision = precision
         y1 = m(x.to(device))
         assert (y1.cpu() - ref).abs().max().item() <= bar * max(1.0, ref.abs().max().item()), precision

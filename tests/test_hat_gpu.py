@@ -18,6 +18,8 @@ from resselt_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
 
+MODEL_REL = 3e-4  # whole models: max-abs <= MODEL_REL * max(1, |y|max) (the sweep of the original families prints its errors against it)
+
 
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
@@ -96,7 +98,7 @@ def test_hat_matches_reference_vectors(device, name):
     assert y.shape == arr['y'].shape
     err = (y.cpu() - arr['y']).abs().max().item()
     print(f'{name}: max-abs {err:.3e}')
-    assert err <= 3e-4 * max(1.0, arr['y'].abs().max().item()), f'{name}: max-abs {err:.3e}'
+    assert err <= MODEL_REL * max(1.0, arr['y'].abs().max().item()), f'{name}: max-abs {err:.3e}'
 
 
 def test_hat_vs_oracle_dtypes_and_precision(device):
@@ -110,7 +112,7 @@ def test_hat_vs_oracle_dtypes_and_precision(device):
     assert y.shape == ref.shape == (1, 3, 180, 240)
     err = (y.cpu() - ref).abs().max().item()
     print(f'HAT(2x3) bf16x3 max-abs {err:.3e} (|y|max {ref.abs().max():.2f})')
-    assert err <= 3e-4 * max(1.0, ref.abs().max().item())
+    assert err <= MODEL_REL * max(1.0, ref.abs().max().item())
     yh = m(x.to(device).half())
     assert yh.dtype == torch.float16
     m.precision = 'bf16'

@@ -19,6 +19,8 @@ from resselt_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
 
+MODEL_REL = 3e-4  # whole models: max-abs <= MODEL_REL * max(1, |y|max) (the sweep of the original families prints its errors against it)
+
 
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
@@ -123,7 +125,7 @@ def test_swinir_matches_reference_vectors(device, name, precision):
     assert y.shape == arr['y'].shape
     err = (y.cpu() - arr['y']).abs().max().item()
     print(f'{name} {precision}: max-abs {err:.3e} (|y|max {arr["y"].abs().max():.3f})')
-    assert err <= 3e-4 * max(1.0, arr['y'].abs().max().item()), f'{name} {precision}: max-abs {err:.3e}'
+    assert err <= MODEL_REL * max(1.0, arr['y'].abs().max().item()), f'{name} {precision}: max-abs {err:.3e}'
 
 
 
@@ -140,7 +142,7 @@ def test_swinir_L_vs_oracle_bf16_input(device):
         assert y.shape == ref.shape == (1, 3, 200, 280)
         err = (y.cpu() - ref).abs().max().item()
         print(f'SwinIR-L(3x6) {precision} ({m.resolved_precision()}) max-abs {err:.3e} (|y|max {ref.abs().max():.2f})')
-        assert err <= 3e-4 * max(1.0, ref.abs().max().item())
+        assert err <= MODEL_REL * max(1.0, ref.abs().max().item())
     yb = m(x.to(device).bfloat16())
     assert yb.dtype == torch.bfloat16
     with torch.no_grad():

@@ -221,6 +221,9 @@ def hat_cases():
         ('hat_x4_e180_w16_d2_b2_32x48', dict(embed_dim=180, depths=(2,), num_heads=(6,), window=16, upscale=4), (2, 3, 32, 48), 102),
         ('hat_x3_e96_w8_d3_identity_25x40', dict(embed_dim=96, depths=(3,), num_heads=(6,), upscale=3, mlp_ratio=4.0, resi='identity'), (1, 3, 25, 40), 103),
         ('hat_x2_e180_w16_d2_2_50x70', dict(embed_dim=180, depths=(2, 2), num_heads=(6, 6), window=16, upscale=2), (1, 3, 50, 70), 104),
+        # heights of 5 to 8 pad to ONE row of windows of 8 (one image: the partition of a single window row is a strided view unless made contiguous)
+        ('hat_x2_e60_w8_d2_one_window_row_5x11', dict(depths=(2,), num_heads=(6,)), (1, 3, 5, 11), 105),
+        ('hat_x2_e60_w8_d2_one_window_col_11x5', dict(depths=(2,), num_heads=(6,)), (1, 3, 11, 5), 106),
     ]
     for name, kw, shape, seed in cases:
         sd = synth.hat_state_dict(seed=seed, **kw)

@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR, GFISRv2); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR, GFISRv2, FIGSR); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -14,6 +14,7 @@ from .drct import DRCTArch
 from .eimn import EIMNArch
 from .esrgan import ESRGANArch
 from .fdat import FDATArch
+from .figsr import FIGSRArch
 from .flexnet import FlexNetArch
 from .gater import GateRArch
 from .gfisrv2 import GFISRV2Arch
@@ -55,3 +56,6 @@ internal_registry.add(SMoSRArch(), tail=True)
 # GFISRv2 likewise (tests/test_gfisrv2_loader.py), in ``Registry.rest``: the open-ended tier consulted once ``every()`` has declined, which
 # tests/test_smosr_loader.py holds to ``consulted()`` + SMoSR.  Later architectures of this kind go into ``rest`` too.
 internal_registry.add(GFISRV2Arch(), rest=True)
+# FIGSR, the next of the GFISR family (tests/test_figsr_loader.py checks the same two properties), goes into ``rest`` behind GFISRv2: every
+# older tier and iterator stays what it was.
+internal_registry.add(FIGSRArch(), rest=True)

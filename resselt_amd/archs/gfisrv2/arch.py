@@ -178,6 +178,14 @@ class GFISRV2(_GatedBase):
         W['tail0'] = cw(sd[f'gfisr_body.{t}.weight'], sd[f'gfisr_body.{t}.bias'])
         W['tail1'] = cw(sd[f'gfisr_body.{t + 2}.weight'], sd[f'gfisr_body.{t + 2}.bias'])
         W['zeros'] = torch.zeros(self.dim, dtype=torch.float32, device=device)
+        self._pack_head3(W, sd, products, device)
+        if products.fmt != PF_BF16:
+            check_fp16_range(_conv_weights(W))
+        return W
+
+    def _pack_head3(self, W, sd, products, device) -> None:
+        """UniUpsampleV3 under ``upscale`` into ``W`` (FIGSR's head too: it reads ``head``, ``scale``, ``layers``, ``dys_index``, ``dim``,
+        ``mid_dim`` and ``out_ch`` of the module)."""
         head = sd
         dys3 = self.dys_index is not None and self.scale != 1
         if dys3:
@@ -185,16 +193,13 @@ class GFISRV2(_GatedBase):
             # per launch through a selection matrix, and the convolution reads them as planes (as SMoSR's d_kernel = 3 head)
             d = f'upscale.{self.dys_index}'
             mid = self.mid_dim if self.dys_index else self.dim
-            W['dys.end3'] = cw(sd[f'{d}.end_conv.weight'], sd[f'{d}.end_conv.bias'])
+            W['dys.end3'] = ops.ConvWeights.from_oihw(sd[f'{d}.end_conv.weight'], sd[f'{d}.end_conv.bias'], products, device=device)
             sel = torch.eye(mid, dtype=torch.float32, device=device)
             W['dys.sel'] = [sel[8 * g : 8 * g + 8].contiguous() for g in range(mid // 8)]
             W['dys.zero'] = torch.zeros(8, dtype=torch.float32, device=device)
             head = dict(sd)
             head[f'{d}.end_conv.weight'], head[f'{d}.end_conv.bias'] = torch.zeros((8, mid, 1, 1), device=device), W['dys.zero']
         pack_head(W, head, 'upscale', self.head, self.scale, self.layers, self.dys_index, 8 if dys3 else self.out_ch, products, device)
-        if products.fmt != PF_BF16:
-            check_fp16_range(_conv_weights(W))
-        return W
 
     def macs_per_input_pixel(self) -> int:
         """Convolution and depthwise MACs per pixel; the dense DFT is not a per-pixel cost (O(H + W) per pixel) and is left out."""
@@ -204,9 +209,9 @@ class GFISRV2(_GatedBase):
         return 9 * self.in_ch * d + self.n_block * blk + 9 * d * 2 * d * 2 + head
 
     # ---------------------------------------------------------------- plan
-    def _dft(self, plan: Plan, tabs, inverse: bool, n, H, Wd, spec, scratch, planes: Planes, plane0: int, post=None) -> None:
+    def _dft(self, plan: Plan, tabs, inverse: bool, n, H, Wd, spec, scratch, planes: Planes, plane0: int, post=None, eps: float = EPS) -> None:
         dp = LG.GfisrDftParams()
-        dp.batch, dp.H, dp.W, dp.C, dp.inverse, dp.fmt, dp.eps = n, H, Wd, self.cf, int(inverse), planes.fmt, EPS
+        dp.batch, dp.H, dp.W, dp.C, dp.inverse, dp.fmt, dp.eps = n, H, Wd, self.cf, int(inverse), planes.fmt, eps
         dp.tab_row = tabs['row_inv' if inverse else 'row_fwd'].data_ptr()
         dp.tab_col = tabs['col_inv' if inverse else 'col_fwd'].data_ptr()
         dp.spec, dp.scratch = spec.data_ptr(), scratch.data_ptr()

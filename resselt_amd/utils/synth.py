@@ -1582,7 +1582,12 @@ def gfisrv2_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansio
         _conv(sd, f'{b}.fc2', dim, hidden, 3, seed, scale=0.5)
     _conv(sd, f'gfisr_body.{n_blocks}', 2 * dim, dim, 3, seed)
     _conv(sd, f'gfisr_body.{n_blocks + 2}', dim, 2 * dim, 3, seed)
-    up, s = upsampler, scale
+    _uni_upsample_v3(sd, 'gfisrv2_state_dict', upsampler, scale, dim, out_nc, mid_dim, seed)
+    return sd
+
+
+def _uni_upsample_v3(sd, who, up, s, dim, out_nc, mid_dim, seed):
+    """UniUpsampleV3 with a 3x3 DySample end convolution under ``upscale``, as GFISRv2 and FIGSR register it."""
     meta = torch.tensor([3, GFISRV2_SAMPLE_MODS.index(up), s, dim, out_nc, mid_dim, 4], dtype=torch.uint8)
     if s != 1 and up == 'dysample':
         sd['upscale.MetaUpsample'] = meta
@@ -1600,5 +1605,44 @@ def gfisrv2_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansio
         _uni_upsample(sd, 'upscale', 'conv' if s == 1 else up, s, dim, out_nc, mid_dim, seed, version=3)
         sd['upscale.MetaUpsample'] = meta  # (the same place in the order; at scale 1 every mode is the one convolution)
     else:
-        raise ValueError(f'gfisrv2_state_dict: the {up!r} head is not synthesised')
+        raise ValueError(f'{who}: the {up!r} head is not synthesised')
+
+
+def figsr_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansion_ratio=8 / 3, upsampler='pixelshuffledirect', mid_dim=32, gc=8,
+                     square_kernel_size=13, band_kernel_size=17, shift=(0.5, 0.5, 0.5), scale_norm=(1 / 6, 1 / 6, 1 / 6), halves=None, seed=0):  # fmt: skip
+    """Keys of the reference FIGSR module (archs/figsr/arch.py:624-664) in its registration order: the module's own ``shift`` and
+    ``scale_norm`` first, every RMSNorm with its ``eps`` and ``rms`` parameters (at the reference's values), the two halves (``halves``:
+    their block counts where they shall NOT be the reference's (n // 2, n - n // 2)), the 3x3 convolution behind the second half,
+    ``cat_to_dim``, then ``upscale.MetaUpsample`` before the head's layers.  Scales, offsets and biases are all randomised; fc2 is drawn at
+    half the default bound, which keeps the default depth (24 blocks) of order 1."""
+    sd: OrderedDict = OrderedDict()
+    hidden = int(expansion_ratio * dim) // 8 * 8
+    cf = dim - 3 * gc
+
+    def rms(name, c):
+        sd[f'{name}.scale'] = 1.0 + synth_tensor(f'{name}.scale', (c,), 16, seed)
+        sd[f'{name}.offset'] = synth_tensor(f'{name}.offset', (c,), 16, seed)
+        sd[f'{name}.eps'] = torch.ones(1) * 1e-6
+        sd[f'{name}.rms'] = torch.ones(1) * (c**-0.5)
+
+    sd['shift'] = torch.tensor(shift, dtype=torch.float32).reshape(1, 3, 1, 1)
+    sd['scale_norm'] = torch.tensor(scale_norm, dtype=torch.float32).reshape(1, 3, 1, 1)
+    _conv(sd, 'in_to_dim', dim, in_nc, 3, seed)
+    n1, n2 = (n_blocks // 2, n_blocks - n_blocks // 2) if halves is None else halves
+    for b in [f'gfisr_body_half.{i}' for i in range(n1)] + [f'gfisr_body_half_2.{i}' for i in range(n2)]:
+        rms(f'{b}.norm', dim)
+        _conv(sd, f'{b}.fc1', 2 * hidden, dim, 3, seed)
+        c = f'{b}.conv.fu'
+        rms(f'{c}.rn', 2 * cf)
+        rms(f'{c}.post_norm', cf)
+        _conv(sd, f'{c}.fdc', 2 * cf, 2 * cf, 1, seed)
+        _dwconv(sd, f'{c}.fpe', 2 * cf, 3, 3, seed)
+        _conv(sd, f'{b}.conv.convhw', gc, gc, square_kernel_size, seed)
+        for name, kh, kw in (('convw', 1, band_kernel_size), ('convh', band_kernel_size, 1)):
+            sd[f'{b}.conv.{name}.weight'] = synth_tensor(f'{b}.conv.{name}.weight', (gc, gc, kh, kw), gc * kh * kw, seed)
+            sd[f'{b}.conv.{name}.bias'] = synth_tensor(f'{b}.conv.{name}.bias', (gc,), gc * kh * kw, seed)
+        _conv(sd, f'{b}.fc2', dim, hidden, 3, seed, scale=0.5)
+    _conv(sd, f'gfisr_body_half_2.{n2}', dim, dim, 3, seed)
+    _conv(sd, 'cat_to_dim', dim, 3 * dim, 1, seed)
+    _uni_upsample_v3(sd, 'figsr_state_dict', upsampler, scale, dim, out_nc, mid_dim, seed)
     return sd

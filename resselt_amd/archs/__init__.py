@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR, GFISRv2, FIGSR); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR, GFISRv2, FIGSR, LAWFFT); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -19,6 +19,7 @@ from .flexnet import FlexNetArch
 from .gater import GateRArch
 from .gfisrv2 import GFISRV2Arch
 from .hat import HATArch
+from .lawfft import LAWFFTArch
 from .moesr import MoESRArch
 from .mosr import MoSRArch
 from .mosrv2 import MoSRv2Arch
@@ -59,3 +60,6 @@ internal_registry.add(GFISRV2Arch(), rest=True)
 # FIGSR, the next of the GFISR family (tests/test_figsr_loader.py checks the same two properties), goes into ``rest`` behind GFISRv2: every
 # older tier and iterator stays what it was.
 internal_registry.add(FIGSRArch(), rest=True)
+# LAWFFT likewise (tests/test_lawfft_loader.py checks the same two properties), in ``rest`` behind FIGSR: tests/test_figsr_loader.py holds
+# ``rest[:2]``.
+internal_registry.add(LAWFFTArch(), rest=True)

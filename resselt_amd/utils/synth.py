@@ -1646,3 +1646,69 @@ def figsr_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansion_
     _conv(sd, 'cat_to_dim', dim, 3 * dim, 1, seed)
     _uni_upsample_v3(sd, 'figsr_state_dict', upsampler, scale, dim, out_nc, mid_dim, seed)
     return sd
+
+
+def lawfft_state_dict(in_ch=3, dim=60, local=15, scale=4, n_rblock=4, n_mblock=6, t_mid_factor=1.0, window_size=8, mlp_factor=2.66,
+                      upsampler='pixelshuffledirect', mid_dim=48, unshuffle_mod=False, to_hidden_rows=None, seed=0):  # fmt: skip
+    """Keys and dtypes of the reference LAWFFT module (archs/lawfft/arch.py:380-416) in its registration order: the uint8 ``window_size``
+    buffer first, ``upscale.MetaUpsample`` before the head's layers.  ``local`` is the local width itself (the reference derives it from a
+    float ``split``); the FSAS width is ``int(global * t_mid_factor)`` and ``to_hidden`` has ``int(global * 3 * t_mid_factor)`` rows, as the
+    reference computes them (``to_hidden_rows`` overrides the latter).  The kernel generators' first layer is drawn twice as wide as
+    the default bound, with a bias of the pooled input's order: some of its ReLUs are active and some are not; the second layer's bias is
+    bounded by 1 / k^2, so a generated kernel's taps sum to order 1.  The 1x1 convolutions behind a residual are drawn at half the
+    default bound and the generators' second layers at an eighth of it -- a generated kernel scales with the pooled mean of its own input,
+    so a larger gain squares the stream from group to group on large images --, which keeps the default depth (24 blocks) of order 1 from
+    9 x 11 to 512 x 512."""
+    sd: OrderedDict = OrderedDict()
+    glob = dim - local
+    fsas, rows = int(glob * t_mid_factor), int(glob * 3 * t_mid_factor) if to_hidden_rows is None else to_hidden_rows
+    hid = int(dim * mlp_factor)
+    sd['window_size'] = torch.tensor(window_size, dtype=torch.uint8)
+    s_int = scale
+    if unshuffle_mod and scale < 3:
+        u = 4 // scale
+        _conv(sd, 'in_to_dim.1', dim, in_ch * u * u, 3, seed)
+        s_int = 4
+    else:
+        _conv(sd, 'in_to_dim', dim, in_ch, 3, seed)
+
+    def norm(name, c):
+        sd[f'{name}.weight'] = 1.0 + synth_tensor(f'{name}.weight', (c,), 16, seed)
+        sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), 16, seed)
+
+    def gen(name, c, k):
+        _conv(sd, f'{name}.kernel_gen.1', c, c, 1, seed, scale=2.0)
+        sd[f'{name}.kernel_gen.1.bias'] = synth_tensor(f'{name}.kernel_gen.1.bias', (c,), 4, seed)
+        _conv(sd, f'{name}.kernel_gen.3', c * k * k, c, 1, seed, scale=0.125)
+        sd[f'{name}.kernel_gen.3.bias'] = synth_tensor(f'{name}.kernel_gen.3.bias', (c * k * k,), k**4, seed)
+
+    for r in range(n_rblock):
+        for i in range(n_mblock):
+            b = f'body.{r}.residual.{i}'
+            t, a, c = f'{b}.token_mix', f'{b}.token_mix.1.att', f'{b}.channel_mix1'
+            norm(f'{t}.0', dim)
+            gen(f'{t}.1.local.0', local, 3)
+            gen(f'{t}.1.local.1', local, 5)
+            _conv(sd, f'{a}.to_hidden', rows, glob, 1, seed)
+            _dwconv(sd, f'{a}.to_hidden_dw', rows, 3, 3, seed)
+            _conv(sd, f'{a}.project_out', glob, fsas, 1, seed)
+            norm(f'{a}.norm', fsas)
+            _conv(sd, f'{t}.1.last', dim, dim, 1, seed, scale=0.5)
+            norm(f'{c}.0', dim)
+            _conv(sd, f'{c}.1.project_in', 2 * hid, dim, 1, seed)
+            _dwconv(sd, f'{c}.1.dwconv', 2 * hid, 3, 3, seed)
+            _conv(sd, f'{c}.1.project_out', dim, hid, 1, seed, scale=0.5)
+        gen(f'body.{r}.residual.{n_mblock}', dim, 3)
+    _uni_upsample(sd, 'upscale', 'conv' if s_int == 1 else upsampler, s_int, dim, in_ch, mid_dim, seed, version=2)
+    sd['upscale.MetaUpsample'] = torch.tensor([2, MOSRV2_SAMPLE_MODS.index(upsampler), s_int, dim, in_ch, mid_dim, 4], dtype=torch.uint8)
+    if upsampler == 'dysample' and s_int != 1 and mid_dim != dim:  # UniUpsample (version 2): a mid_dim convolution in front of DySample
+        for k in [k for k in sd if k.startswith('upscale.0.')]:
+            del sd[k]
+        _conv(sd, 'upscale.0', mid_dim, dim, 3, seed)
+        oc = 8 * s_int * s_int
+        h = torch.arange((-s_int + 1) / 2, (s_int - 1) / 2 + 1) / s_int
+        sd['upscale.2.init_pos'] = torch.stack(torch.meshgrid([h, h], indexing='ij')).transpose(1, 2).repeat(1, 4, 1).reshape(1, -1, 1, 1)
+        _conv(sd, 'upscale.2.end_conv', in_ch, mid_dim, 1, seed)
+        _conv(sd, 'upscale.2.offset', oc, mid_dim, 1, seed, scale=0.5)
+        _conv(sd, 'upscale.2.scope', oc, mid_dim, 1, seed, bias=False)
+    return sd

@@ -100,7 +100,10 @@ class Registry:
     ``rest`` is the tier for every architecture after that (tests/test_smosr_loader.py holds ``tail`` and ``every()`` to exactly
     ``consulted()`` + SMoSR): the same admission rule, any number of architectures in insertion order, consulted once ``every()`` has
     declined.  ``order()`` is the whole consultation order and what ``load_from_state_dict`` walks; no test may hold ``rest`` or ``order()``
-    to a fixed list of ids (membership and relative order only), so the next architecture goes into ``rest`` too."""
+    to a fixed list of ids (membership and relative order only), so the next architecture goes into ``rest`` too.
+    ``more`` exists because one did (tests/test_lawfft_loader.py holds ``rest`` and the end of ``order()`` to exactly GFISRv2, FIGSR, LAWFFT):
+    the same admission rule, any number of architectures in insertion order, consulted once ``order()`` has declined; ``full()`` is the
+    whole consultation order and what ``load_from_state_dict`` walks, and no older tier or iterator sees ``more``."""
 
     def __init__(self):
         self.store: Dict[str, Architecture] = {}
@@ -109,9 +112,10 @@ class Registry:
         self.after: Dict[str, Architecture] = {}
         self.tail: Dict[str, Architecture] = {}
         self.rest: Dict[str, Architecture] = {}
+        self.more: Dict[str, Architecture] = {}
 
     def __contains__(self, uid: str) -> bool:
-        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail or uid in self.rest
+        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail or uid in self.rest or uid in self.more
 
     def __iter__(self) -> Iterator[Architecture]:
         return iter(list(self.store.values()) + list(self.late.values()))
@@ -132,11 +136,22 @@ class Registry:
         return iter(list(self.consulted()) + list(self.tail.values()))
 
     def order(self) -> Iterator[Architecture]:
-        """The whole consultation order of ``load_from_state_dict``: ``every()``, then ``rest``."""
+        """``every()``, then ``rest``: what ``load_from_state_dict`` consults before ``more`` (``full()`` is the whole order)."""
         return iter(list(self.every()) + list(self.rest.values()))
 
-    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False, tail: bool = False, rest: bool = False) -> None:
+    def full(self) -> Iterator[Architecture]:
+        """The whole consultation order of ``load_from_state_dict``: ``order()``, then ``more``."""
+        return iter(list(self.order()) + list(self.more.values()))
+
+    def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False, tail: bool = False, rest: bool = False,
+            more: bool = False) -> None:  # fmt: skip
         """Register an architecture *instance*; re-using an id replaces it in place."""
+        if more and not any(arch.id in t for t in (self.store, self.late, self.last, self.after, self.tail, self.rest)):
+            self.more[arch.id] = arch
+            return
+        self.more.pop(arch.id, None)
+        if more:  # an id another tier already holds is replaced there
+            rest = rest or arch.id in self.rest
         if rest and not any(arch.id in t for t in (self.store, self.late, self.last, self.after, self.tail)):
             self.rest[arch.id] = arch
             return
@@ -164,7 +179,7 @@ class Registry:
             self.store[arch.id] = arch
 
     def get(self, uid: str) -> Architecture:
-        tier = next((t for t in (self.late, self.last, self.after, self.tail, self.rest) if uid in t), self.store)
+        tier = next((t for t in (self.late, self.last, self.after, self.tail, self.rest, self.more) if uid in t), self.store)
         arch = tier[uid]  # KeyError for unknown ids, as in the reference
         if not arch:
             raise ArchitectureNotFound
@@ -175,7 +190,7 @@ class Registry:
 
     def load_from_state_dict(self, state_dict: Mapping[str, object]):
         state_dict = canonicalize_state_dict(state_dict)
-        for arch in self.order():
+        for arch in self.full():
             if arch.detect(state_dict):
                 model = arch.load(state_dict)
                 model.load_state_dict(state_dict)

@@ -1712,3 +1712,53 @@ def lawfft_state_dict(in_ch=3, dim=60, local=15, scale=4, n_rblock=4, n_mblock=6
         _conv(sd, 'upscale.2.offset', oc, mid_dim, 1, seed, scale=0.5)
         _conv(sd, 'upscale.2.scope', oc, mid_dim, 1, seed, bias=False)
     return sd
+
+
+GFISR_SLOTS = ('pconv', 'dwconv_hw', 'dwconv_w', 'dwconv_h', 'fsas')  # InceptionDWConv2d's attribute names of GFISR (v1), in channel order
+GFISR_KINDS = ('identity', (3, 3), (1, 11), (11, 1), 'fourier')  # its five modules before rotation
+
+
+def gfisr_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansion_ratio=8 / 3, upsampler='pixelshuffledirect', mid_dim=32,
+                     fft_mode=True, pixel_unshuffle=False, seed=0):  # fmt: skip
+    """Keys of the reference GFISR module (archs/gfisr/arch.py:594-629) in its registration order: a block's ``gamma`` before its
+    sub-modules, the five Inception modules under the attribute names that rotate with the block index (the identity registers nothing; the
+    FourierUnit registers ``ln``, ``fdc``, the 1x1 convolution ``weight.0`` in front of its one-channel softmax, ``fpe``),
+    ``dim_to_out.MetaUpsample`` before the head's layers (UniUpsampleV3 with a 3x3 DySample end convolution).  ``pixel_unshuffle`` with
+    scale 1 or 2 gives ``in_to_dim.1`` over ``in_nc * (4 // scale) ** 2`` channels and a head of scale 4, as the reference module builds
+    them.  Norms, gammas and biases are all randomised; fc2 is drawn at half the default bound, which keeps the default depth (24 blocks)
+    of order 1."""
+    sd: OrderedDict = OrderedDict()
+    hidden = int(expansion_ratio * dim)
+    gc = int(dim / 8)
+    head_scale = scale
+
+    def norm(name, c):
+        sd[f'{name}.weight'] = 1.0 + synth_tensor(f'{name}.weight', (c,), 16, seed)
+        sd[f'{name}.bias'] = synth_tensor(f'{name}.bias', (c,), 16, seed)
+
+    if pixel_unshuffle and scale in (1, 2):
+        down = 4 // scale
+        _conv(sd, 'in_to_dim.1', dim, in_nc * down * down, 3, seed)
+        head_scale = 4
+    else:
+        _conv(sd, 'in_to_dim', dim, in_nc, 3, seed)
+    for i in range(n_blocks):
+        b = f'net.{i}'
+        sd[f'{b}.gamma'] = 1.0 + synth_tensor(f'{b}.gamma', (1, dim, 1, 1), 16, seed)
+        norm(f'{b}.norm', dim)
+        _conv(sd, f'{b}.fc1', 2 * hidden, dim, 3, seed)
+        for t, name in enumerate(GFISR_SLOTS):
+            kind, c = GFISR_KINDS[(i + t) % 5], f'{b}.conv.{name}'
+            if kind == 'fourier' and fft_mode:
+                norm(f'{c}.ln', 2 * gc)
+                _conv(sd, f'{c}.fdc', 2 * gc, 2 * gc, 1, seed)
+                _conv(sd, f'{c}.weight.0', 1, 2 * gc, 1, seed)
+                _dwconv(sd, f'{c}.fpe', 2 * gc, 3, 3, seed)
+            elif isinstance(kind, tuple):
+                _dwconv(sd, c, gc, kind[0], kind[1], seed)
+        _conv(sd, f'{b}.fc2', dim, hidden, 3, seed, scale=0.5)
+    head: OrderedDict = OrderedDict()
+    _uni_upsample_v3(head, 'gfisr_state_dict', upsampler, head_scale, dim, out_nc, mid_dim, seed)
+    for k, v in head.items():
+        sd['dim_to_out.' + k[len('upscale.') :]] = v
+    return sd

@@ -35,10 +35,9 @@ from ...engine.base import EngineModule, Plan
 from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.tensors import PF_BF16, Planes
 from ...engine.transformer import HEAD_PAD, LayerPacker, bias_fragments_qk, layernorm, regroup_proj, regroup_qkv
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes, needs_f32_input, pack_head
+from ...engine.uniupsample import SAMPLE_MODS, SAMPLE_MODS3, Head, OwnMetaUpsample
 from ..dat.arch import pad_rows
 
-SAMPLE_MODS3 = SAMPLE_MODS + ('transpose+conv', 'lda', 'pa_up')
 LDA_RANGE, LDA_EPS = 11.0, 1e-6
 MAX_C = 256  # rsa_fdat_interact
 RECT_MAX_TOKENS = 256  # rsa_rect_attention
@@ -79,7 +78,8 @@ def v3_layers(upsample: str, scale: int, in_dim: int, out_dim: int, mid_dim: int
     raise ValueError(f'An invalid Upsample was selected. Please choose one of {SAMPLE_MODS}')
 
 
-def fdat_param_shapes(in_ch, out_ch, dim, num_groups, depth_per_group, heads, ws, hidden, aim_hidden, unshuffle, s_int, upsampler, mid_dim):
+def fdat_param_shapes(in_ch, dim, num_groups, depth_per_group, heads, ws, hidden, aim_hidden, unshuffle, up: Head, layers):
+    """``up``: the head (its MetaUpsample buffer, and the shapes of the shared modes); ``layers``: ``v3_layers`` of the other three, or None."""
     s = ParamShapes()
     buffers: dict = {}
     if unshuffle > 1:
@@ -106,13 +106,8 @@ def fdat_param_shapes(in_ch, out_ch, dim, num_groups, depth_per_group, heads, ws
             s[f'{b}.ffn.smix.weight'] = (hidden, 1, 3, 3)
         s[f'groups.{g}.conv.weight'] = (dim, dim, 3, 3)
     s['conv_after.weight'] = (dim, dim, 3, 3)
-    buffers['upsampler.MetaUpsample'] = torch.tensor([3, SAMPLE_MODS3.index(upsampler), s_int, dim, out_ch, mid_dim, 4], dtype=torch.uint8)
-    layers = v3_layers(upsampler, s_int, dim, out_ch, mid_dim)
-    if layers is None:
-        hl, dys_index = head_layers(upsampler, s_int, dim, out_ch, mid_dim)
-        head_shapes(s, buffers, 'upsampler', hl, dys_index, s_int, dim, out_ch, mid_dim)
-        return s, buffers
-    for kind, i, co, ci, k in layers:
+    up.shapes(s, buffers)
+    for kind, i, co, ci, k in layers or []:
         u = f'upsampler.{i}'
         if kind == 'conv':
             s.conv(u, co, ci, k)
@@ -133,7 +128,7 @@ def fdat_param_shapes(in_ch, out_ch, dim, num_groups, depth_per_group, heads, ws
     return s, buffers
 
 
-class FDAT(EngineModule):
+class FDAT(OwnMetaUpsample, EngineModule):  # (the reference's load_state_dict override: arch.py:692-699)
     hyperparameters = {}
     precisions = ('bf16x3', 'bf16')
 
@@ -173,16 +168,9 @@ class FDAT(EngineModule):
         self.head, self.mid_dim, self.img_range = upsampler_type, mid_dim, img_range
         self.fused_interact = fused_interact_default()
         self.v3 = v3_layers(upsampler_type, s_int, dim, num_out_ch, mid_dim)
-        self.layers, self.dys_index = head_layers(upsampler_type, s_int, dim, num_out_ch, mid_dim) if self.v3 is None else (None, None)
-        shapes, buffers = fdat_param_shapes(num_in_ch, num_out_ch, dim, num_groups, depth_per_group, heads, ws, self.hidden, aim_hidden, self.unshuffle,
-                                            s_int, upsampler_type, mid_dim)  # fmt: skip
+        self.up = Head('upsampler', upsampler_type, s_int, dim, num_out_ch, mid_dim, version=3)  # (no layers of its own where ``v3`` has them)
+        shapes, buffers = fdat_param_shapes(num_in_ch, dim, num_groups, depth_per_group, heads, ws, self.hidden, aim_hidden, self.unshuffle, self.up, self.v3)
         build_param_tree(self, shapes, buffers)
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        # as the reference (arch.py:692-699): the module's own MetaUpsample wins over the checkpoint's
-        state_dict = dict(state_dict)
-        state_dict['upsampler.MetaUpsample'] = self.get_buffer('upsampler.MetaUpsample')
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     # ---------------------------------------------------------------- weights
     def _pack(self, device, products):
@@ -218,7 +206,7 @@ class FDAT(EngineModule):
             conv(f'groups.{g}.conv')
         conv('conv_after')
         if self.v3 is None:
-            pack_head(W, sd, 'upsampler', self.head, self.s_int, self.layers, self.dys_index, self.out_ch, products, device)
+            self.up.pack(W, sd, products, device)
         else:
             self._pack_v3(W, sd, products, device)
         return W
@@ -268,15 +256,16 @@ class FDAT(EngineModule):
         """MACs of the head per trunk pixel, every layer counted at the resolution it runs at (area relative to the trunk)."""
         s, C_, mid, out = self.s_int, self.dim, self.mid_dim, self.out_ch
         if self.v3 is None:
+            layers = self.up.layers
             if s == 1 or self.head in ('conv', 'pixelshuffledirect'):
-                return sum(co * ci * k * k for _, co, ci, k in self.layers)
+                return self.up.macs()
             if self.head == 'dysample':
-                d = mid if self.dys_index == 2 else C_
-                pre = 9 * C_ * mid if self.dys_index == 2 else 0
+                d = self.up.dys_dim
+                pre = 9 * C_ * mid if self.up.dys_index == 2 else 0
                 return pre + 2 * d * 8 * s * s + d * out * s * s  # offset and scope at LR, the end convolution at HR
             if self.head == 'pixelshuffle':
                 macs, area = 0, 1
-                for _, co, ci, k in self.layers:
+                for _, co, ci, k in layers:
                     macs += co * ci * k * k * area
                     if co == out:
                         break
@@ -284,7 +273,7 @@ class FDAT(EngineModule):
                         area *= co // mid
                 return macs
             # nearest+conv: stage j's convolution runs before its upsampling
-            stages = len(self.layers) - 2
+            stages = len(layers) - 2
             areas = [1] + [4**j for j in range(1, stages)] if s != 3 else [1]
             return sum(9 * C_ * C_ * a for a in areas) + 9 * C_ * C_ * s * s + 9 * C_ * out * s * s
         macs = 0
@@ -456,11 +445,11 @@ class FDAT(EngineModule):
         y = plan.output((n, self.out_ch, H * f, Wd * f), dtype, crop=(h0 * self.scale, w0 * self.scale))
         fe_lo = with_lo or self.head == 'transpose+conv'
         fe = plan.planes(n, cp, H, Wd, fe_lo)
-        want32 = (self.v3 is None and needs_f32_input(self.head, s, self.dys_index, W)) or (self.head == 'lda' and s > 1 and self.mid_dim == C_)
+        want32 = (self.v3 is None and self.up.needs_f32_input(W)) or (self.head == 'lda' and s > 1 and self.mid_dim == C_)
         fe32 = plan.f32map(n, C_, H, Wd) if want32 else None
         plan.conv(ops.conv_params(W['conv_after'], a_pl, H, Wd, cin_planes=cp, res1=first, alpha=1.0, out=fe, out_f32=fe32))
         if self.v3 is None:
-            emit_head(plan, W, self.head, s, self.layers, C_, self.mid_dim, self.dys_index, fe, fe32, y, n, H, Wd, with_lo)
+            self.up.emit(plan, W, fe, fe32, y, with_lo)
         elif self.head == 'transpose+conv':
             self._emit_transpose(plan, W, fe, y, n, H, Wd, with_lo)
         elif self.head == 'pa_up':

@@ -3,7 +3,7 @@
 The gated block is GFISRv2's (``archs/gfisrv2/arch.py``) with dense Inception branches: fc1's output splits into
 [g | i | c | c_hw | c_w | c_h] = [hidden, hidden - dim, dim - 3 gc, gc, gc, gc] channels, every split on a plane boundary by construction
 (``hidden`` and ``gc`` are multiples of 8), the branches do not rotate, and fc1's rows need no re-layout.  ``c`` goes through the
-FourierUnit (GFISRv2's, value for value), ``c_hw`` through a dense gc -> gc square convolution, ``c_w`` / ``c_h`` through dense gc -> gc
+FourierUnit (GFISRv2's, value for value: ``engine/fourier.py``), ``c_hw`` through a dense gc -> gc square convolution, ``c_w`` / ``c_h`` through dense gc -> gc
 1 x K / K x 1 bands.  There is no activation behind fc2 and no gamma: the block is ``fc2(silu(g) * cat(...)) + x``.  Per block, nine
 launches:
 
@@ -29,23 +29,20 @@ import torch
 
 from ...engine import lib as L
 from ...engine import lib_figsr as LF
-from ...engine import lib_gfisr as LG
 from ...engine import ops, plk
 from ...engine.base import Plan, check_fp16_range
+from ...engine.fourier import EPS, dft_workspace, emit_fourier_unit, pack_fourier_unit
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16, Planes
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes
-from ..gfisrv2.arch import GFISRV2
+from ...engine.uniupsample import SAMPLE_MODS, SAMPLE_MODS3, Head, OwnMetaUpsample
 from ..mosr.arch import _check_dims, _conv_weights, _GatedBase
 
-SAMPLE_MODS3 = SAMPLE_MODS + ('transpose+conv', 'lda', 'pa_up')
 MAX_CF = 128  # rsa_gfisr_dft: at most 128 channels per transform
-EPS = 1e-6
 EXTRA = 4  # the reflect pad on every side (arch.py:675)
 HALVES = ('gfisr_body_half', 'gfisr_body_half_2')
 
 
-class FIGSR(_GatedBase):
+class FIGSR(OwnMetaUpsample, _GatedBase):  # (the reference's load_state_dict override: arch.py:666-668)
     rms_norm = True
     global_statistics = True  # the FourierUnit spans the whole tensor it is given: a tile computes what the reference computes on that tile
 
@@ -84,9 +81,7 @@ class FIGSR(_GatedBase):
         self.in_ch, self.out_ch, self.scale, self.dim, self.n_block, self.hidden = in_nc, out_nc, scale, dim, n_blocks, hidden
         self.head, self.mid_dim, self.gc, self.cf, self.halves = upsampler, mid_dim, gc, cf, halves
         self.ksq, self.kband = square_kernel_size, band_kernel_size
-        self.layers, self.dys_index = head_layers(upsampler, scale, dim, out_nc, mid_dim)
-        if any(co % 8 for _, co, _, _ in self.layers[:-1]) or (self.dys_index == 2 and mid_dim % 8):
-            raise NotImplementedError('FIGSR: the head\'s hidden widths must be multiples of 8')
+        self.up = Head('upscale', upsampler, scale, dim, out_nc, mid_dim, end_kernel=3, version=3)
         self.blocks = [f'{HALVES[0]}.{i}' for i in range(halves[0])] + [f'{HALVES[1]}.{i}' for i in range(halves[1])]
         shapes: dict = {'shift': (1, 3, 1, 1), 'scale_norm': (1, 3, 1, 1), 'in_to_dim.weight': (dim, in_nc, 3, 3), 'in_to_dim.bias': (dim,)}
 
@@ -108,12 +103,8 @@ class FIGSR(_GatedBase):
         t = f'{HALVES[1]}.{halves[1]}'
         shapes[f'{t}.weight'], shapes[f'{t}.bias'] = (dim, dim, 3, 3), (dim,)
         shapes['cat_to_dim.weight'], shapes['cat_to_dim.bias'] = (dim, 3 * dim, 1, 1), (dim,)
-        meta = torch.tensor([3, SAMPLE_MODS3.index(upsampler), scale, dim, out_nc, mid_dim, 4], dtype=torch.uint8)
-        buffers = {'upscale.MetaUpsample': meta}
-        head_shapes(shapes, buffers, 'upscale', self.layers, self.dys_index, scale, dim, out_nc, mid_dim)
-        if self.dys_index is not None:  # dysample_end_kernel = 3
-            d = f'upscale.{self.dys_index}.end_conv.weight'
-            shapes[d] = (*shapes[d][:2], 3, 3)
+        buffers: dict = {}
+        self.up.shapes(shapes, buffers, whole_planes='FIGSR')
         build_param_tree(self, shapes, buffers)
         with torch.no_grad():  # the reference's initial values: a module built without a checkpoint normalises as the reference's does
             self.shift.fill_(0.5)
@@ -126,46 +117,25 @@ class FIGSR(_GatedBase):
                 elif name.endswith('.scale'):
                     p.fill_(1.0)
 
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        # as the reference (arch.py:666-668): the module's own MetaUpsample wins over the checkpoint's
-        state_dict = dict(state_dict)
-        state_dict['upscale.MetaUpsample'] = self.get_buffer('upscale.MetaUpsample')
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
-
     # ---------------------------------------------------------------- weights
     @staticmethod
-    def _rms(sd, name, c, rows, device):
-        """(scale / k, offset, eps / k) of the RMSNorm ``name`` over ``c`` channels, padded to ``rows``: the kernels' form of the
-        reference's ``x / (eps + ||x|| rms)`` (k = rms sqrt(c), 1 for the reference's own checkpoints)."""
+    def _rms(sd, name, c):
+        """(scale / k, offset, eps / k) of the RMSNorm ``name`` over ``c`` channels: the kernels' form of the reference's
+        ``x / (eps + ||x|| rms)`` (k = rms sqrt(c), 1 for the reference's own checkpoints)."""
         k = float(sd[f'{name}.rms'].reshape(-1)[0]) * c**0.5
         eps = float(sd[f'{name}.eps'].reshape(-1)[0])
         if not k > 0.0 or not eps > 0.0:
             raise NotImplementedError(f'FIGSR: {name}.rms and {name}.eps must be positive (got {k / c**0.5}, {eps})')
-        scale, offset = (torch.zeros(rows, dtype=torch.float32, device=device) for _ in range(2))
-        scale[:c], offset[:c] = sd[f'{name}.scale'].reshape(-1) / k, sd[f'{name}.offset'].reshape(-1)
-        return scale, offset, eps / k
+        return (sd[f'{name}.scale'].reshape(-1) / k).contiguous(), sd[f'{name}.offset'].reshape(-1).contiguous(), eps / k
 
     def _pack_block(self, W, sd, b, products, device):
-        dim, cf, gc, hidden = self.dim, self.cf, self.gc, self.hidden
-        f32 = torch.float32
-        blk = {'norm': self._rms(sd, f'{b}.norm', dim, dim, device)}
+        dim, cf = self.dim, self.cf
+        blk = {'norm': self._rms(sd, f'{b}.norm', dim)}
         # rsa_rmsnorm writes bf16 planes: in the fp16 mode fc1 reads them in one bf16 product
         blk['fc1'] = ops.ConvWeights.from_oihw(sd[f'{b}.fc1.weight'], sd[f'{b}.fc1.bias'], products if products.fmt == PF_BF16 else 1, fmt=PF_BF16, device=device)
         blk['fc2'] = ops.ConvWeights.from_oihw(sd[f'{b}.fc2.weight'], sd[f'{b}.fc2.bias'], products, device=device)
         fu = f'{b}.conv.fu'
-        sp = 8 * ((2 * cf + 7) // 8)
-
-        def padded(t, rows):
-            out = torch.zeros((rows, *t.shape[1:]), dtype=f32, device=device)
-            out[: t.shape[0]] = t
-            return out.contiguous()
-
-        blk['rn'] = self._rms(sd, f'{fu}.rn', 2 * cf, sp, device)
-        blk['post'] = self._rms(sd, f'{fu}.post_norm', cf, cf, device)
-        blk['fpe'] = (padded(sd[f'{fu}.fpe.weight'].reshape(2 * cf, 9), sp), padded(sd[f'{fu}.fpe.bias'], sp))
-        # fdc's output row 2k is the real part of channel k and 2k + 1 its imaginary part: stored as [real of all | imag of all]
-        rows = torch.cat([torch.arange(0, 2 * cf, 2), torch.arange(1, 2 * cf, 2)]).to(device)
-        blk['fdc'] = ops.ConvWeights.from_oihw(sd[f'{fu}.fdc.weight'][rows], sd[f'{fu}.fdc.bias'][rows], 3, fmt=PF_BF16, device=device)
+        blk.update(pack_fourier_unit(sd, fu, cf, self._rms(sd, f'{fu}.rn', 2 * cf), self._rms(sd, f'{fu}.post_norm', cf), device))
         c = f'{b}.conv'
         blk['hw'] = (plk.pack_plk_weights(sd[f'{c}.convhw.weight'], int(products), products.fmt), plk.plk_bias(sd[f'{c}.convhw.bias']))
         blk['band'] = (LF.pack_band_weights(sd[f'{c}.convw.weight'], sd[f'{c}.convh.weight'], int(products), products.fmt),
@@ -182,7 +152,7 @@ class FIGSR(_GatedBase):
         W['tail'] = cw(sd[f'{t}.weight'], sd[f'{t}.bias'])
         W['cat'] = cw(sd['cat_to_dim.weight'], sd['cat_to_dim.bias'])
         W['shift'], W['scale_norm'] = sd['shift'].reshape(-1).contiguous(), sd['scale_norm'].reshape(-1).contiguous()
-        self._pack_head3(W, sd, products, device)
+        self.up.pack(W, sd, products, device)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -191,28 +161,19 @@ class FIGSR(_GatedBase):
         """Convolution MACs per pixel of the padded map; the dense DFT is not a per-pixel cost (O(H + W) per pixel) and is left out."""
         d, h, cf, gc = self.dim, self.hidden, self.cf, self.gc
         blk = 9 * d * 2 * h + (self.ksq**2 + 2 * self.kband) * gc * gc + 9 * h * d + 2 * cf * 2 * cf + 9 * 2 * cf
-        head = sum(co * ci * k * k for _, co, ci, k in self.layers)
-        return 9 * self.in_ch * d + self.n_block * blk + 9 * d * d + 3 * d * d + head
+        return 9 * self.in_ch * d + self.n_block * blk + 9 * d * d + 3 * d * d + self.up.macs()
 
     # ---------------------------------------------------------------- plan
     def _emit_block(self, plan: Plan, blk, n, H, Wd, cur, bufs):
-        N_pl, F_pl, M_pl, HW_pl, spec, SP, scratch, tabs = (bufs[k] for k in ('norm', 'fc1', 'gate', 'hw', 'spec', 'sp', 'scratch', 'tabs'))
-        cf, gc, Wf = self.cf, self.gc, Wd // 2 + 1
+        N_pl, F_pl, M_pl, HW_pl = (bufs[k] for k in ('norm', 'fc1', 'gate', 'hw'))
+        cf, gc = self.cf, self.gc
         hp, P = self.hidden // 8, gc // 8
         i_pl, f_pl = (self.hidden - self.dim) // 8, cf // 8
         products = 3 if F_pl.lo is not None else 1
         sc, off, eps = blk['norm']
         plan.launch('rsa_rmsnorm', dict(x_f32=cur, batch=n, H=H, W=Wd, C=self.dim, eps=eps, scale=sc, offset=off, out=N_pl))
         plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
-        self._dft(plan, tabs, False, n, H, Wd, spec, scratch, F_pl, hp + i_pl)
-        sp = LG.GfisrSpectralParams()
-        sp.batch, sp.H, sp.W, sp.C, sp.eps = n, H, Wf, 2 * cf, blk['rn'][2]
-        sp.x, sp.scale, sp.offset = spec.data_ptr(), blk['rn'][0].data_ptr(), blk['rn'][1].data_ptr()
-        sp.weight, sp.bias = blk['fpe'][0].data_ptr(), blk['fpe'][1].data_ptr()
-        SP.bind(sp, 'out')
-        plan.launch('rsa_gfisr_spectral', sp, meta=dict(kernel='rsa_gfisr_spectral', flop=0, bytes=n * H * Wf * (2 * cf * 4 + SP.planes * 32)))
-        plan.conv(ops.conv_params(blk['fdc'], SP, H, Wf, act=L.ACT_GELU, out_f32=spec))
-        self._dft(plan, tabs, True, n, H, Wd, spec, scratch, F_pl, hp + i_pl, post=blk['post'][:2], eps=blk['post'][2])
+        emit_fourier_unit(plan, blk, bufs['dft'], n, H, Wd, cf, F_pl, hp + i_pl, bufs['spec'], bufs['sp'])
         # convhw reads the c_hw planes of fc1's output and writes scratch planes: rsa_plk_conv has no in-place form
         c0 = hp + i_pl + f_pl
         src = Planes(F_pl.hi[:, c0 : c0 + P], None if F_pl.lo is None else F_pl.lo[:, c0 : c0 + P])
@@ -258,13 +219,9 @@ class FIGSR(_GatedBase):
         T, S0, S1 = (plan.f32map(n, dim, H, Wd) for _ in range(3))  # in_to_dim's output, and the stream
         cat_pl = plan.planes(n, 3 * pd, H, Wd, with_lo)  # [x1 | x | x0]: what cat_to_dim reads
         feat = plan.planes(n, pd, H, Wd, with_lo)
-        nbytes = int(L.load().rsa_gfisr_dft_scratch_bytes(n, cf, H, Wd))
-        if nbytes <= 0:
-            raise RuntimeError(f'FIGSR: a {H}x{Wd} map is too large for the dense DFT (rsa_gfisr_dft)')
         bufs = dict(norm=plan.planes(n, pd, H, Wd, with_lo, fmt=PF_BF16), fc1=plan.planes(n, 2 * hp, H, Wd, with_lo), gate=plan.planes(n, hp, H, Wd, with_lo),
                     hw=plan.planes(n, gc // 8, H, Wd, with_lo), spec=plan.f32map(n, 2 * cf, H, Wf), sp=plan.planes(n, (2 * cf + 7) // 8, H, Wf, True, fmt=PF_BF16),
-                    scratch=torch.empty(nbytes // 4, dtype=torch.float32, device=dev), tabs=LG.dft_tables(H, Wd, dev))  # fmt: skip
-        plan.keep += [bufs['scratch'], *bufs['tabs'].values()]
+                    dft=dft_workspace(plan, 'FIGSR', n, cf, H, Wd))  # fmt: skip
         plan.conv(ops.conv_params(W['conv0'], x_pl, H, Wd, out=cat_pl, out_plane_off=pd, out_f32=T))
         cur, nxt = T, S0
         for i, b in enumerate(self.blocks):
@@ -278,24 +235,17 @@ class FIGSR(_GatedBase):
             cur, nxt = nxt, (S1 if nxt is S0 else S0)
         plan.conv(ops.conv_params(W['tail'], feat, H, Wd, out=cat_pl))
         fe = plan.planes(n, pd, H, Wd, with_lo)
-        dys3 = self.dys_index is not None and s != 1
-        fe32 = plan.f32map(n, dim, H, Wd) if dys3 and self.dys_index == 0 else None
+        fe32 = plan.f32map(n, dim, H, Wd) if self.up.needs_f32_input(W) else None
         plan.conv(ops.conv_params(W['cat'], cat_pl, H, Wd, out=fe, out_f32=fe32))
         full = torch.empty((n, self.out_ch, H * s, Wd * s), dtype=torch.float32, device=dev)  # the head's result at the padded size
         plan.keep.append(full)
-        if dys3:
-            self._emit_dys3(plan, W, fe, fe32, full, n, H, Wd, with_lo)
-        else:
-            emit_head(plan, W, self.head, s, self.layers, dim, self.mid_dim, self.dys_index, fe, None, full, n, H, Wd, with_lo)
+        self.up.emit(plan, W, fe, fe32, full, with_lo)
         y = plan.output((n, self.out_ch, h0 * s, w0 * s), dtype)
         op = LF.FigsrOutputParams()
         op.batch, op.C, op.H, op.W, op.y0, op.x0, op.out_h, op.out_w, op.dtype = n, self.out_ch, H * s, Wd * s, EXTRA * s, EXTRA * s, h0 * s, w0 * s, ops.rsa_dtype(dtype)
         op.y, op.shift, op.scale_norm, op.out = full.data_ptr(), W['shift'].data_ptr(), W['scale_norm'].data_ptr(), y.data_ptr()
         plan.launch('rsa_figsr_output', op)
         return set_input
-
-    # GFISRv2's Fourier launches and its UniUpsampleV3 head (DySample with the 3x3 end convolution), on this module's attributes
-    _dft, _pack_head3, _emit_dys3 = GFISRV2._dft, GFISRV2._pack_head3, GFISRV2._emit_dys3
 
 
 def p_dim(module, name: str) -> int:

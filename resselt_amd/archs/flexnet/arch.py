@@ -37,7 +37,7 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16
-from ...engine.uniupsample import emit_head, head_layers, pack_head
+from ...engine.uniupsample import Head
 from ..mosr.arch import _conv_weights
 
 RMS_EPS = 2.0**-23  # nn.RMSNorm(eps=None): torch.finfo(torch.float32).eps
@@ -77,11 +77,12 @@ def fold_block(sd, b: str, dim: int, channel_norm: bool) -> dict:
     )  # fmt: skip
 
 
-def nc_layers(scale: int, dim: int, out_ch: int):
-    """InterpolateUpsampler's layers with parameters (arch.py:22-40): [(index in the Sequential, cout, cin, k)]."""
+def nc_head(scale: int, dim: int, out_ch: int) -> Head:
+    """InterpolateUpsampler (arch.py:22-40) as UniUpsample's nearest+conv head; at scale 1 it keeps both of its convolutions."""
+    up = Head('to_img.1', 'nearest+conv', scale, dim, out_ch, dim)
     if scale == 1:
-        return [(0, dim, dim, 3), (2, out_ch, dim, 3)]
-    return head_layers('nearest+conv', scale, dim, out_ch, dim)[0]
+        up.layers = [(0, dim, dim, 3), (2, out_ch, dim, 3)]
+    return up
 
 
 class FlexNet(EngineModule):
@@ -158,7 +159,8 @@ class FlexNet(EngineModule):
         self.layers = []
         if upsampler == 'n+c':
             conv('to_img.0', dim, 2 * dim, 3)
-            self.layers = nc_layers(scale, dim, out_ch)
+            self.up = nc_head(scale, dim, out_ch)
+            self.layers = self.up.layers
             for i, co, ci, k in self.layers:
                 conv(f'to_img.1.{i}', co, ci, k)
         elif upsampler == 'dys':
@@ -213,7 +215,7 @@ class FlexNet(EngineModule):
             W[f'pipeline.att.{li}.conv'] = convblock(f'pipeline.att.{li}.conv')
         if self.upsampler == 'n+c':
             W['to_img.0'] = cw(sd['to_img.0.weight'], sd['to_img.0.bias'])
-            pack_head(W, sd, 'to_img.1', 'nearest+conv', self.scale, self.layers, None, self.out_ch, products, device)
+            self.up.pack(W, sd, products, device)
         elif self.upsampler == 'dys':
             dys.pack(W, sd['to_img.offset.weight'], sd['to_img.offset.bias'], sd['to_img.scope.weight'], sd['to_img.end_conv.weight'].reshape(self.out_ch, -1),
                      sd['to_img.end_conv.bias'], sd['to_img.init_pos'], 4, self.scale, products=products, device=device)  # fmt: skip
@@ -305,5 +307,5 @@ class FlexNet(EngineModule):
                 plan.conv(ops.conv_params(W['head0'], fe, H, Wd, act=L.ACT_LRELU, act_param=0.2, out=o))
                 plan.conv(ops.conv_params(W['head1'], o, H, Wd, out_nchw=y))
             else:
-                emit_head(plan, W, 'nearest+conv', s, self.layers, dim, dim, None, fe, None, y, n, H, Wd, with_lo)
+                self.up.emit(plan, W, fe, None, y, with_lo)
         return set_input

@@ -30,18 +30,16 @@ from __future__ import annotations
 import torch
 
 from ...engine import lib as L
-from ...engine import lib_gfisr as LG
 from ...engine import lib_gfisr1 as LG1
 from ...engine import ops, plk
 from ...engine.base import Plan, check_fp16_range
+from ...engine.fourier import EPS, dft_workspace, emit_dft
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes
-from ..gfisrv2.arch import GFISRV2, SAMPLE_MODS3
+from ...engine.uniupsample import SAMPLE_MODS, SAMPLE_MODS3, Head, OwnMetaUpsample
 from ..mosr.arch import _check_dims, _conv_weights, _GatedBase, pad_dw, relayout_gate
 
 MAX_DIM = 128  # gc = dim / 8 <= 16: rsa_gfisr_ln_spectral takes at most 32 spectral channels
-EPS = 1e-6
 FIXED_MID_DIM = 32  # what the reference's loader always builds (it hands ``upsample_dim=`` to a constructor whose parameter is ``mid_dim``)
 SLOTS = ('pconv', 'dwconv_hw', 'dwconv_w', 'dwconv_h', 'fsas')  # InceptionDWConv2d's attribute names, in channel order
 KINDS = ('identity', (3, 3), (1, 11), (11, 1), 'fourier')  # the five modules before rotation
@@ -82,9 +80,8 @@ def padded_size(H: int, W: int):
     return H + 2 * PAD + H % 2, W + 2 * PAD + W % 2
 
 
-class GFISR(_GatedBase):
+class GFISR(OwnMetaUpsample, _GatedBase):  # (the reference's load_state_dict override: arch.py:620-623)
     global_statistics = True  # the FourierUnit spans the whole tensor it is given: a tile computes what the reference computes on that tile
-    _dft, _pack_head3, _emit_dys3 = GFISRV2._dft, GFISRV2._pack_head3, GFISRV2._emit_dys3
 
     def __init__(self, in_nc: int = 3, dim: int = 48, expansion_ratio: float = 8 / 3, fft_mode: bool = True, scale: int = 4, out_nc: int = 3,
                  upsampler: str = 'pixelshuffledirect', mid_dim: int = 32, pixel_unshuffle: bool = True, n_blocks: int = 24,
@@ -109,12 +106,9 @@ class GFISR(_GatedBase):
         if hidden < dim:
             raise NotImplementedError(f'GFISR: hidden = int(expansion_ratio * dim) must be at least dim (got {hidden})')
         self.in_ch, self.out_ch, self.dim, self.n_block, self.hidden = in_nc, out_nc, dim, n_blocks, hidden
-        self.out_scale, self.scale = scale, s_head  # ``scale``: the head's (what ``_pack_head3`` / ``_emit_dys3`` read); ``out_scale``: the model's
+        self.out_scale, self.scale = scale, s_head  # ``scale``: the head's; ``out_scale``: the model's
         self.head, self.mid_dim, self.gc, self.fft_mode = upsampler, mid_dim, dim // 8, bool(fft_mode)
-        self.cf = self.gc  # the FourierUnit's width, under the name ``_dft`` reads
-        self.layers, self.dys_index = head_layers(upsampler, s_head, dim, out_nc, mid_dim)
-        if any(co % 8 for _, co, _, _ in self.layers[:-1]) or (self.dys_index == 2 and mid_dim % 8):
-            raise NotImplementedError('GFISR: the head\'s hidden widths must be multiples of 8')
+        self.up = Head('dim_to_out', upsampler, s_head, dim, out_nc, mid_dim, end_kernel=3, version=3)
         gc, u = self.gc, self.unshuffle
         first = 'in_to_dim.1' if u > 1 else 'in_to_dim'
         shapes: dict = {f'{first}.weight': (dim, in_nc * u * u, 3, 3), f'{first}.bias': (dim,)}
@@ -133,19 +127,9 @@ class GFISR(_GatedBase):
                 elif isinstance(kind, tuple):
                     shapes[f'{c}.weight'], shapes[f'{c}.bias'] = (gc, 1, *kind), (gc,)
             shapes[f'{b}.fc2.weight'], shapes[f'{b}.fc2.bias'] = (dim, hidden, 3, 3), (dim,)
-        meta = torch.tensor([3, SAMPLE_MODS3.index(upsampler), s_head, dim, out_nc, mid_dim, 4], dtype=torch.uint8)
-        buffers = {'dim_to_out.MetaUpsample': meta}
-        head_shapes(shapes, buffers, 'dim_to_out', self.layers, self.dys_index, s_head, dim, out_nc, mid_dim)
-        if self.dys_index is not None:  # dysample_end_kernel = 3
-            d = f'dim_to_out.{self.dys_index}.end_conv.weight'
-            shapes[d] = (*shapes[d][:2], 3, 3)
+        buffers: dict = {}
+        self.up.shapes(shapes, buffers, whole_planes='GFISR')
         build_param_tree(self, shapes, buffers)
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        # as the reference (arch.py:620-623): the module's own MetaUpsample wins over the checkpoint's
-        state_dict = dict(state_dict)
-        state_dict['dim_to_out.MetaUpsample'] = self.get_buffer('dim_to_out.MetaUpsample')
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     # ---------------------------------------------------------------- weights
     def _pack_block(self, W, sd, b, products, device):
@@ -172,15 +156,14 @@ class GFISR(_GatedBase):
         W[b] = blk
 
     def _pack(self, device, products):
-        sd = {k.replace('dim_to_out.', 'upscale.'): v.detach().to(device=device, dtype=torch.float32)
-              for k, v in self.state_dict().items() if not k.endswith('MetaUpsample')}  # fmt: skip  (the head under the name ``_pack_head3`` reads)
+        sd = {k: v.detach().to(device=device, dtype=torch.float32) for k, v in self.state_dict().items() if not k.endswith('MetaUpsample')}
         first = 'in_to_dim.1' if self.unshuffle > 1 else 'in_to_dim'
         W: dict = {'conv0': ops.ConvWeights.from_oihw(sd[f'{first}.weight'], sd[f'{first}.bias'], products, device=device)}
         for i in range(self.n_block):
             self._pack_block(W, sd, f'net.{i}', products, device)
         W['zeros'] = torch.zeros(self.dim, dtype=torch.float32, device=device)
         W['ones'] = torch.ones(self.dim, dtype=torch.float32, device=device)
-        self._pack_head3(W, sd, products, device)
+        self.up.pack(W, sd, products, device)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -189,8 +172,7 @@ class GFISR(_GatedBase):
         """Convolution and depthwise MACs per input pixel; the dense DFT is not a per-pixel cost (O(H + W) per pixel) and is left out."""
         d, h, gc, u = self.dim, self.hidden, self.gc, self.unshuffle
         blk = 9 * d * 2 * h + (9 + 22) * gc + 9 * h * d + (2 * gc * 2 * gc + 9 * 2 * gc if self.fft_mode else 0)
-        head = sum(co * ci * k * k for _, co, ci, k in self.layers)
-        return (9 * self.in_ch * u * u * d + self.n_block * blk + head) // (u * u)
+        return (9 * self.in_ch * u * u * d + self.n_block * blk + self.up.macs()) // (u * u)
 
     # ---------------------------------------------------------------- plan
     def _window(self, plan: Plan, n, src, src0, H, Wd, dst, dst0, out_H, out_W, top, left, planes) -> None:
@@ -204,14 +186,16 @@ class GFISR(_GatedBase):
         plan.launch('rsa_plane_window', wp, meta=dict(kernel='rsa_plane_window', flop=0, bytes=2 * n * planes * out_H * out_W * unit,
                                                        label='reflect pad' if top > 0 else 'crop'))  # fmt: skip
 
-    def _emit_fourier(self, plan: Plan, blk, n, H, Wd, bufs) -> None:
-        """The FourierUnit on the Fourier branch's planes of fc1's output, in place."""
-        F_pl, P_pl, spec, spec2, scratch, tabs = (bufs[k] for k in ('fc1', 'pad', 'spec', 'spec2', 'scratch', 'tabs'))
+    def _emit_branches(self, plan: Plan, blk, n, H, Wd, bufs) -> None:
+        """The FourierUnit on the Fourier branch's planes of fc1's output, in place (``fft_mode``; otherwise they are an identity's)."""
+        if not self.fft_mode:
+            return
+        F_pl, P_pl, spec, spec2, dft = (bufs[k] for k in ('fc1', 'pad', 'spec', 'spec2', 'dft'))
         Hp, Wp = padded_size(H, Wd)
         Wf = Wp // 2 + 1
         f0, f_pl = blk['planes'] + blk['f0'], blk['f_planes']
         self._window(plan, n, F_pl, f0, H, Wd, P_pl, 0, Hp, Wp, PAD, PAD, f_pl)
-        self._dft(plan, tabs, False, n, Hp, Wp, spec, scratch, P_pl, 0)
+        emit_dft(plan, dft, False, n, self.gc, Hp, Wp, spec, P_pl, 0)
         sp = LG1.GfisrLnSpectralParams()
         sp.batch, sp.H, sp.W, sp.C, sp.eps = n, Hp, Wf, 2 * self.gc, EPS
         sp.x, sp.out = spec.data_ptr(), spec2.data_ptr()
@@ -221,33 +205,8 @@ class GFISR(_GatedBase):
         c2 = 2 * self.gc
         # byte model: the f32 map read once (the halo re-reads stay on chip) and written once
         plan.launch('rsa_gfisr_ln_spectral', sp, meta=dict(kernel='rsa_gfisr_ln_spectral', flop=2 * n * Hp * Wf * (c2 * c2 + 10 * c2), bytes=n * Hp * Wf * 2 * c2 * 4))
-        self._dft(plan, tabs, True, n, Hp, Wp, spec2, scratch, P_pl, 0)
+        emit_dft(plan, dft, True, n, self.gc, Hp, Wp, spec2, P_pl, 0)
         self._window(plan, n, P_pl, 0, Hp, Wp, F_pl, f0, H, Wd, -PAD, -PAD, f_pl)
-
-    def _emit_block(self, plan: Plan, blk, n, H, Wd, cur, bufs):
-        N_pl, F_pl, M_pl = bufs['norm'], bufs['fc1'], bufs['gate']
-        sc, off = blk['norm']
-        lp = L.LayerNormParams()
-        lp.batch, lp.H, lp.W, lp.C, lp.eps = n, H, Wd, self.dim, EPS
-        lp.x_f32, lp.gamma, lp.beta = cur.data_ptr(), sc.data_ptr(), off.data_ptr()
-        N_pl.bind(lp, 'out')
-        lp.out_fmt = N_pl.fmt
-        plan.launch('rsa_layernorm', lp)
-        plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
-        if self.fft_mode:
-            self._emit_fourier(plan, blk, n, H, Wd, bufs)
-        hp = blk['planes']
-        gp = L.GatedDwConvParams()
-        gp.batch, gp.H, gp.W, gp.fmt, gp.i_planes, gp.n_segments = n, H, Wd, F_pl.fmt, blk['i_planes'], len(blk['segs'])
-        for s, (pl, kh, kw, wt, bt) in enumerate(blk['segs']):
-            gp.seg[s].planes, gp.seg[s].kh, gp.seg[s].kw = pl, kh, kw
-            gp.seg[s].weight, gp.seg[s].bias = wt.data_ptr(), bt.data_ptr()
-        F_pl.bind(gp, 'g')
-        F_pl.bind(gp, 'x', hp)
-        M_pl.bind(gp, 'out')
-        unit = 16 * (2 if F_pl.lo is not None else 1)
-        plan.launch('rsa_gated_dwconv', gp, meta=dict(kernel='rsa_gated_dwconv', flop=0, bytes=n * H * Wd * unit * 3 * hp))
-        return M_pl
 
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):  # noqa: C901
         n, c, h0, w0 = x_shape
@@ -275,13 +234,8 @@ class GFISR(_GatedBase):
         bufs = dict(norm=plan.planes(n, pd, H, Wd, with_lo), fc1=plan.planes(n, 2 * hp, H, Wd, with_lo), gate=plan.planes(n, hp, H, Wd, with_lo))
         if self.fft_mode:
             Hp, Wp = padded_size(H, Wd)
-            nbytes = int(L.load().rsa_gfisr_dft_scratch_bytes(n, gc, Hp, Wp))
-            if nbytes <= 0:
-                raise RuntimeError(f'GFISR: a {H}x{Wd} map is too large for the dense DFT (rsa_gfisr_dft)')
             bufs.update(pad=plan.planes(n, (gc + 7) // 8, Hp, Wp, with_lo), spec=plan.f32map(n, 2 * gc, Hp, Wp // 2 + 1),
-                        spec2=plan.f32map(n, 2 * gc, Hp, Wp // 2 + 1), scratch=torch.empty(nbytes // 4, dtype=torch.float32, device=dev),
-                        tabs=LG.dft_tables(Hp, Wp, dev))  # fmt: skip
-            plan.keep += [bufs['scratch'], *bufs['tabs'].values()]
+                        spec2=plan.f32map(n, 2 * gc, Hp, Wp // 2 + 1), dft=dft_workspace(plan, 'GFISR', n, gc, Hp, Wp))  # fmt: skip
         stats = self._unit_stats(n, dev)
         plan.keep.append(stats)
         plan.conv(ops.conv_params(W['conv0'], x_pl, H, Wd, out_f32=trunk))
@@ -294,12 +248,8 @@ class GFISR(_GatedBase):
             cur, nxt = nxt, (S1 if nxt is S0 else S0)
         # net(x) + x: the stream plus in_to_dim's output, as the planes the head reads
         fe = plan.planes(n, pd, H, Wd, with_lo)
-        dys3 = self.dys_index is not None and s != 1
-        fe32 = plan.f32map(n, dim, H, Wd) if dys3 and self.dys_index == 0 else None
+        fe32 = plan.f32map(n, dim, H, Wd) if self.up.needs_f32_input(W) else None
         plan.launch('rsa_group_norm_apply', plk.group_norm_apply_params(cur, dim, 1, stats, W['ones'], W['zeros'], trunk, fe, fe32))
         y = plan.output((n, self.out_ch, H * s, Wd * s), dtype, crop=(h0 * self.out_scale, w0 * self.out_scale))
-        if dys3:
-            self._emit_dys3(plan, W, fe, fe32, y, n, H, Wd, with_lo)
-        else:
-            emit_head(plan, W, self.head, s, self.layers, dim, self.mid_dim, self.dys_index, fe, None, y, n, H, Wd, with_lo)
+        self.up.emit(plan, W, fe, fe32, y, with_lo)
         return set_input

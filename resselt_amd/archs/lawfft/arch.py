@@ -29,13 +29,13 @@ import math
 import torch
 
 from ...engine import lib as L
-from ...engine import lib_gfisr as LG
 from ...engine import lib_lawfft as LW
 from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
+from ...engine.fourier import dft_workspace, emit_dft
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16, Planes
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes, needs_f32_input, pack_head
+from ...engine.uniupsample import SAMPLE_MODS, Head, OwnMetaUpsample
 
 MAX_DIM = 128  # the LAWFFT kernels and rsa_gfisr_dft: at most 128 channels
 EPS = 1e-6
@@ -61,7 +61,7 @@ def _chunked(t: torch.Tensor, chunks: int, width: int) -> torch.Tensor:
     return out
 
 
-class LAWFFT(EngineModule):
+class LAWFFT(OwnMetaUpsample, EngineModule):  # (the reference's load_state_dict override: arch.py:418-420)
     auto_precision = 'bf16x3'
     precisions = ('bf16x3', 'fp16')
     global_statistics = True  # DynamicLocal's pooling and the whole-image correlation span the tensor they are given
@@ -105,8 +105,8 @@ class LAWFFT(EngineModule):
         self.in_ch = self.out_ch = in_ch
         self.scale, self.dim, self.local, self.glob, self.fsas, self.hidden = scale, dim, local, glob, fsas, hidden
         self.n_rblock, self.n_mblock, self.head, self.mid_dim = n_rblock, n_mblock, upsampler, mid_dim
-        self.layers, self.dys_index = head_layers(upsampler, scale, dim, in_ch, mid_dim)
-        if scale != 1 and mid_dim % 8 and (upsampler == 'pixelshuffle' or self.dys_index == 2):
+        self.up = Head('upscale', upsampler, scale, dim, in_ch, mid_dim)
+        if scale != 1 and mid_dim % 8 and (upsampler == 'pixelshuffle' or self.up.dys_index == 2):
             raise NotImplementedError(f'LAWFFT: the {upsampler} head needs mid_dim to be a multiple of 8 (got {mid_dim})')
         shapes: dict = {'in_to_dim.weight': (dim, in_ch, 3, 3), 'in_to_dim.bias': (dim,)}
 
@@ -131,16 +131,9 @@ class LAWFFT(EngineModule):
                 shapes[f'{c}.1.dwconv.weight'], shapes[f'{c}.1.dwconv.bias'] = (2 * hidden, 1, 3, 3), (2 * hidden,)
                 shapes[f'{c}.1.project_out.weight'], shapes[f'{c}.1.project_out.bias'] = (dim, hidden, 1, 1), (dim,)
             gen(f'body.{r}.residual.{n_mblock}', dim, 3)
-        meta = torch.tensor([2, SAMPLE_MODS.index(upsampler), scale, dim, in_ch, mid_dim, 4], dtype=torch.uint8)
-        buffers = {'window_size': torch.tensor(window_size, dtype=torch.uint8), 'upscale.MetaUpsample': meta}
-        head_shapes(shapes, buffers, 'upscale', self.layers, self.dys_index, scale, dim, in_ch, mid_dim)
+        buffers = {'window_size': torch.tensor(window_size, dtype=torch.uint8)}
+        self.up.shapes(shapes, buffers)
         build_param_tree(self, shapes, buffers)
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        # as the reference (arch.py:418-420): the module's own MetaUpsample wins over the checkpoint's
-        state_dict = dict(state_dict)
-        state_dict['upscale.MetaUpsample'] = self.get_buffer('upscale.MetaUpsample')
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     # ---------------------------------------------------------------- weights
     def _pack_block(self, W, sd, b, products, device) -> None:
@@ -180,7 +173,7 @@ class LAWFFT(EngineModule):
                 self._pack_block(W, sd, f'body.{r}.residual.{i}', products, device)
             g = f'body.{r}.residual.{self.n_mblock}.kernel_gen'
             W[f'body.{r}.gen'] = LW.pack_kernel_gen(sd[f'{g}.1.weight'], sd[f'{g}.1.bias'], sd[f'{g}.3.weight'], sd[f'{g}.3.bias'])
-        pack_head(W, sd, 'upscale', self.head, self.scale, self.layers, self.dys_index, self.out_ch, products, device)
+        self.up.pack(W, sd, products, device)
         if products.fmt != PF_BF16:
             convs = [v for v in W.values() if isinstance(v, ops.ConvWeights)]
             convs += [v for blk in W.values() if isinstance(blk, dict) for v in blk.values() if isinstance(v, ops.ConvWeights)]
@@ -193,8 +186,7 @@ class LAWFFT(EngineModule):
         d, lo, cw, hid = self.dim, self.local, self.fsas, self.hidden
         blk = d * 3 * cw + 27 * cw + (9 + 25) * lo + (lo + cw) * d + d * 2 * hid + 18 * hid + hid * d
         win = (self.n_mblock // 2) * 64 * cw
-        head = sum(co * ci * k * k for _, co, ci, k in self.layers)
-        return 9 * self.in_ch * d + self.n_rblock * (self.n_mblock * blk + win + 9 * d) + head
+        return 9 * self.in_ch * d + self.n_rblock * (self.n_mblock * blk + win + 9 * d) + self.up.macs()
 
     # ---------------------------------------------------------------- plan
     def _dynamic_local(self, plan: Plan, gen, k, C, src: Planes, src_plane0, bufs, n, H, Wd, out: Planes | None = None, out_plane0: int = 0, res1=None,
@@ -230,20 +222,6 @@ class LAWFFT(EngineModule):
         lp.out_fmt = out.fmt
         plan.launch('rsa_layernorm', lp)
 
-    def _dft(self, plan: Plan, bufs, inverse: bool, n, H, Wd, spec, planes: Planes, plane0: int) -> None:
-        tabs = bufs['tabs']
-        dp = LG.GfisrDftParams()
-        dp.batch, dp.H, dp.W, dp.C, dp.inverse, dp.fmt, dp.eps = n, H, Wd, self.fsas, int(inverse), planes.fmt, EPS
-        dp.tab_row = tabs['row_inv' if inverse else 'row_fwd'].data_ptr()
-        dp.tab_col = tabs['col_inv' if inverse else 'col_fwd'].data_ptr()
-        dp.spec, dp.scratch = spec.data_ptr(), bufs['scratch'].data_ptr()
-        planes.bind(dp, 'plane', plane0)
-        Wf = Wd // 2 + 1
-        flop = 2 * (H * Wd * 2 * Wf + 4 * H * H * Wf) * self.fsas * n
-        unit = 2 * (2 if planes.lo is not None else 1)
-        nbytes = n * self.fsas * (H * Wd * unit + 2 * H * Wf * 4)
-        plan.launch('rsa_gfisr_dft', dp, kernels=2, meta=dict(kernel='rsa_gfisr_dft', flop=flop, bytes=nbytes, label=f'{"inverse" if inverse else "forward"}, {H}x{Wd}, {self.fsas} channels'))
-
     def _emit_fsas(self, plan: Plan, blk, windowed: bool, bufs, n, H, Wd) -> None:
         """q, k, v = the three plane ranges of D; out = v * LN(corr) into the planes of CAT behind the local ones."""
         D, CAT = bufs['dw'], bufs['cat']
@@ -264,13 +242,13 @@ class LAWFFT(EngineModule):
             return
         A, B, CORR = bufs['spec_a'], bufs['spec_b'], bufs['corr']
         Wf = Wd // 2 + 1
-        self._dft(plan, bufs, False, n, H, Wd, A, D, 0)
-        self._dft(plan, bufs, False, n, H, Wd, B, D, P_w)
+        emit_dft(plan, bufs['dft'], False, n, cw, H, Wd, A, D, 0)
+        emit_dft(plan, bufs['dft'], False, n, cw, H, Wd, B, D, P_w)
         sp = LW.LawfftSpecMulParams()
         sp.batch, sp.H, sp.W, sp.C, sp.scale = n, H, Wf, cw, math.sqrt(H * Wd)
         sp.a, sp.b, sp.out = A.data_ptr(), B.data_ptr(), A.data_ptr()
         plan.launch('rsa_lawfft_spec_mul', sp, meta=dict(kernel='rsa_lawfft_spec_mul', flop=8 * n * H * Wf * cw, bytes=3 * n * H * Wf * 2 * cw * 4))
-        self._dft(plan, bufs, True, n, H, Wd, A, CORR, 0)
+        emit_dft(plan, bufs['dft'], True, n, cw, H, Wd, A, CORR, 0)
         nm = LW.LawfftNormMulParams()
         nm.batch, nm.H, nm.W, nm.C, nm.corr_fmt, nm.fmt, nm.eps = n, H, Wd, cw, CORR.fmt, D.fmt, EPS
         nm.weight, nm.bias = gamma.data_ptr(), beta.data_ptr()
@@ -323,23 +301,19 @@ class LAWFFT(EngineModule):
         def set_input(x):
             ops.nchw_to_planes(x, x_pl)  # the reflect pad on the bottom and right happens in the conversion
 
-        lib = L.load()
-        nbytes = int(lib.rsa_gfisr_dft_scratch_bytes(n, cw, H, Wd))
-        if nbytes <= 0:
-            raise RuntimeError(f'LAWFFT: a {H}x{Wd} map is too large for the dense DFT (rsa_gfisr_dft)')
-        ws_bytes = int(lib.rsa_lawfft_kernel_gen_workspace_bytes(n, dim, H, Wd))
+        dft = dft_workspace(plan, 'LAWFFT', n, cw, H, Wd)
+        ws_bytes = int(L.load().rsa_lawfft_kernel_gen_workspace_bytes(n, dim, H, Wd))
         f32 = torch.float32
         bufs = dict(norm=plan.planes(n, pd, H, Wd, with_lo), hidden=plan.planes(n, 3 * P_w, H, Wd, with_lo), dw=plan.planes(n, 3 * P_w, H, Wd, with_lo),
                     local=plan.planes(n, P_l, H, Wd, with_lo), cat=plan.planes(n, P_l + P_w, H, Wd, with_lo), pin=plan.planes(n, 2 * P_h, H, Wd, with_lo),
                     gate=plan.planes(n, P_h, H, Wd, with_lo), spec_a=plan.f32map(n, 2 * cw, H, Wf), spec_b=plan.f32map(n, 2 * cw, H, Wf),
-                    corr=plan.planes(n, P_w, H, Wd, True, fmt=PF_BF16), scratch=torch.empty(nbytes // 4, dtype=f32, device=dev),
-                    tabs=LG.dft_tables(H, Wd, dev), gen_ws=torch.empty(ws_bytes // 4, dtype=f32, device=dev),
+                    corr=plan.planes(n, P_w, H, Wd, True, fmt=PF_BF16), dft=dft, gen_ws=torch.empty(ws_bytes // 4, dtype=f32, device=dev),
                     kernels=torch.empty(n * 8 * pd * 25, dtype=f32, device=dev))  # fmt: skip
-        plan.keep += [bufs['scratch'], bufs['gen_ws'], bufs['kernels'], *bufs['tabs'].values()]
+        plan.keep += [bufs['gen_ws'], bufs['kernels']]
         trunk, S0, S1, RB0, RB1 = (plan.f32map(n, dim, H, Wd) for _ in range(5))  # in_to_dim's output, the blocks' stream, the groups' inputs
         X = plan.planes(n, pd, H, Wd, with_lo)  # the last block's result as planes: what a group's DynamicLocal reads
         fe = plan.planes(n, pd, H, Wd, with_lo)
-        fe32 = plan.f32map(n, dim, H, Wd) if needs_f32_input(self.head, s, self.dys_index, W) else None
+        fe32 = plan.f32map(n, dim, H, Wd) if self.up.needs_f32_input(W) else None
         plan.conv(ops.conv_params(W['conv0'], x_pl, H, Wd, out_f32=trunk))
         rin = trunk
         for r in range(self.n_rblock):
@@ -356,5 +330,5 @@ class LAWFFT(EngineModule):
                 self._dynamic_local(plan, gen, 3, dim, X, 0, bufs, n, H, Wd, res1=rin, out_f32=rout)
                 rin = rout
         y = plan.output((n, self.out_ch, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
-        emit_head(plan, W, self.head, s, self.layers, dim, self.mid_dim, self.dys_index, fe, fe32, y, n, H, Wd, with_lo)
+        self.up.emit(plan, W, fe, fe32, y, with_lo)
         return set_input

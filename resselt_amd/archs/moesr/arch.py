@@ -28,7 +28,7 @@ from ...engine import ops
 from ...engine.base import Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes, needs_f32_input, pack_head
+from ...engine.uniupsample import SAMPLE_MODS, Head
 from ..mosr.arch import LN_EPS, _check_dims, _conv_weights, _GatedBase
 
 MAX_DIM = 128  # rsa_moesr_stream keeps a pixel's channels in registers
@@ -64,9 +64,7 @@ class MoESR(_GatedBase):
         self._gate_hidden = hidden
         # (UniUpsample of this family gives DySample the features themselves: no mid_dim convolution in front of it)
         self.mid_dim = dim if upsampler == 'dysample' else upsample_dim
-        self.layers, self.dys_index = head_layers(upsampler, scale, dim, out_ch, self.mid_dim)
-        if any(co % 8 for _, co, _, _ in self.layers[:-1]):
-            raise NotImplementedError('MoESR: the head\'s hidden widths must be multiples of 8')
+        self.up = Head('upscale', upsampler, scale, dim, out_ch, self.mid_dim, version=1, meta_mid_dim=upsample_dim)
         shapes: dict = {'in_to_dim.weight': (dim, in_ch, 3, 3), 'in_to_dim.bias': (dim,)}
         for g in range(n_blocks):
             for j in range(n_block):
@@ -76,9 +74,8 @@ class MoESR(_GatedBase):
             for j in range(MSG_BLOCKS):
                 self._block_shapes(shapes, f'{m}.gated.{j}', hidden_msg)
             shapes[f'{m}.up.0.weight'], shapes[f'{m}.up.0.bias'] = (4 * dim, dim, 3, 3), (4 * dim,)
-        meta = torch.tensor([1, SAMPLE_MODS.index(upsampler), scale, dim, out_ch, upsample_dim, 4], dtype=torch.uint8)
-        buffers = {'upscale.MetaUpsample': meta}
-        head_shapes(shapes, buffers, 'upscale', self.layers, self.dys_index, scale, dim, out_ch, self.mid_dim)
+        buffers: dict = {}
+        self.up.shapes(shapes, buffers, whole_planes='MoESR')
         build_param_tree(self, shapes, buffers)
 
     def _block_shapes(self, shapes: dict, b: str, hidden: int) -> None:
@@ -128,7 +125,7 @@ class MoESR(_GatedBase):
                 self._of_width(hidden, self._pack_block, W, sd, b, products, device)
             for name in ('down', 'up'):
                 W[f'blocks.{g}.msg.{name}'] = cw(sd[f'blocks.{g}.msg.{name}.0.weight'], sd[f'blocks.{g}.msg.{name}.0.bias'])
-        pack_head(W, sd, 'upscale', self.head, self.scale, self.layers, self.dys_index, self.out_ch, products, device)
+        self.up.pack(W, sd, products, device)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -137,8 +134,8 @@ class MoESR(_GatedBase):
         d = self.dim
         blk = lambda h: 9 * d * 2 * h + (9 + 22) * self.gc + 9 * h * d  # noqa: E731
         msg = 9 * d * (d // 4) + (MSG_BLOCKS * blk(self.hidden_msg) + 9 * d * 4 * d) // 4  # the stage between the two convolutions runs on a quarter of the pixels
-        head = sum(co * ci * k * k for _, co, ci, k in self.layers)
-        if self.dys_index is not None:
+        head = self.up.macs()
+        if self.up.dys_index is not None:
             head += d * 8 * self.scale * self.scale * 2
         return 9 * self.in_ch * d + self.n_blocks * (self.n_block * blk(self.hidden) + msg) + head
 
@@ -185,7 +182,7 @@ class MoESR(_GatedBase):
         P, Ph = plan.planes(n, pd, H, Wd, with_lo), plan.planes(n, pd, Hh, Wh, with_lo)  # plain planes: what MSG.down / the head and MSG.up read
         bufs = self._of_width(self.hidden, self._block_buffers, plan, n, H, Wd, with_lo)
         bufs_h = self._of_width(self.hidden_msg, self._block_buffers, plan, n, Hh, Wh, with_lo)
-        fe32 = plan.f32map(n, dim, H, Wd) if needs_f32_input(self.head, s, self.dys_index, W) else None
+        fe32 = plan.f32map(n, dim, H, Wd) if self.up.needs_f32_input(W) else None
 
         plan.conv(ops.conv_params(W['conv0'], x_pl, H, Wd, out_f32=trunk))
         for g in range(self.n_blocks):
@@ -212,5 +209,5 @@ class MoESR(_GatedBase):
             else:
                 self._stream(plan, 2, n, H, Wd, U, s_in=S, s_out=S, norm=W[f'blocks.{g + 1}.blocks.0']['norm'], planes=bufs['norm'])
         y = plan.output((n, self.out_ch, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
-        emit_head(plan, W, self.head, s, self.layers, dim, self.mid_dim, self.dys_index, P, fe32, y, n, H, Wd, with_lo)
+        self.up.emit(plan, W, P, fe32, y, with_lo)
         return set_input

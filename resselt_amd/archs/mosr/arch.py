@@ -119,6 +119,7 @@ class _GatedBase(EngineModule):
     precisions = ('bf16x3', 'fp16')
     global_statistics = False
     rms_norm = False
+    gate_entry, gate_act = 'rsa_gated_dwconv', None  # the gate's entry point, and the activation of one that takes it (rsa_gfisr_gate)
 
     def _gate_groups(self):
         raise NotImplementedError
@@ -148,9 +149,14 @@ class _GatedBase(EngineModule):
         raise NotImplementedError
 
     def _emit_block(self, plan: Plan, blk, n, H, Wd, cur, bufs):
-        """norm -> fc1 -> rsa_gated_dwconv; returns the planes fc2 reads.  ``cur`` None: ``bufs['norm']`` already holds the normalised input
-        (MoESR: the kernel that closed the previous block wrote it)."""
-        N_pl, F_pl, M_pl = bufs['norm'], bufs['fc1'], bufs['gate']
+        """norm -> fc1 -> (``_emit_branches``) -> the gate; returns the planes fc2 reads.  ``cur`` None: ``bufs['norm']`` already holds the
+        normalised input (MoESR: the kernel that closed the previous block wrote it)."""
+        self._emit_norm_fc1(plan, blk, n, H, Wd, cur, bufs)
+        self._emit_branches(plan, blk, n, H, Wd, bufs)
+        return self._emit_gate(plan, blk, n, H, Wd, bufs)
+
+    def _emit_norm_fc1(self, plan: Plan, blk, n, H, Wd, cur, bufs) -> None:
+        N_pl, F_pl = bufs['norm'], bufs['fc1']
         sc, off = blk['norm']
         dim = self.dim
         if cur is None:
@@ -165,6 +171,12 @@ class _GatedBase(EngineModule):
             lp.out_fmt = N_pl.fmt
             plan.launch('rsa_layernorm', lp)
         plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
+
+    def _emit_branches(self, plan: Plan, blk, n, H, Wd, bufs) -> None:
+        """What a family runs in place on fc1's output before the gate reads it (the GFISR family's FourierUnit)."""
+
+    def _emit_gate(self, plan: Plan, blk, n, H, Wd, bufs):
+        F_pl, M_pl = bufs['fc1'], bufs['gate']
         hp = blk['planes']
         gp = L.GatedDwConvParams()
         gp.batch, gp.H, gp.W, gp.fmt, gp.i_planes, gp.n_segments = n, H, Wd, F_pl.fmt, blk['i_planes'], len(blk['segs'])
@@ -176,7 +188,8 @@ class _GatedBase(EngineModule):
         M_pl.bind(gp, 'out')
         # byte model: g and cat(i, c) read once, the product written once (the halo re-reads stay on chip)
         unit = 16 * (2 if F_pl.lo is not None else 1)
-        plan.launch('rsa_gated_dwconv', gp, meta=dict(kernel='rsa_gated_dwconv', flop=0, bytes=n * H * Wd * unit * 3 * hp))
+        args = gp if self.gate_act is None else dict(p=gp, act=self.gate_act)
+        plan.launch(self.gate_entry, args, meta=dict(kernel=self.gate_entry, flop=0, bytes=n * H * Wd * unit * 3 * hp))
         return M_pl
 
     def _block_buffers(self, plan: Plan, n, H, Wd, with_lo):

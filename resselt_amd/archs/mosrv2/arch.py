@@ -17,16 +17,16 @@ from __future__ import annotations
 
 import torch
 
-from ...engine import dysample as dys
 from ...engine import lib as L
 from ...engine import ops, plk
 from ...engine.base import Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes, pack_head  # noqa: F401  (SAMPLE_MODS, head_layers: re-exported)
+from ...engine.uniupsample import SAMPLE_MODS, Head, OwnMetaUpsample  # noqa: F401  (SAMPLE_MODS: re-exported)
 from ..mosr.arch import _check_dims, _conv_weights, _GatedBase
 
-class MoSRv2(_GatedBase):
+
+class MoSRv2(OwnMetaUpsample, _GatedBase):  # (the reference's load_state_dict override: arch.py:319-321)
     def __init__(self, in_ch: int = 3, scale: int = 4, n_block: int = 24, dim: int = 64, upsampler: str = 'pixelshuffledirect', expansion_ratio: float = 1.5,
                  mid_dim: int = 32, unshuffle_mod: bool = True, rms_norm: bool = False) -> None:  # fmt: skip
         super().__init__()
@@ -41,9 +41,7 @@ class MoSRv2(_GatedBase):
         self.hidden, self.gc = hidden, int(dim * 0.125)
         if hidden < dim:
             raise NotImplementedError(f'MoSRv2: hidden = int(expansion_ratio * dim) must be at least dim (got {hidden})')
-        self.layers, self.dys_index = head_layers(upsampler, self.s_int, dim, in_ch, mid_dim)
-        if any(co % 8 for _, co, _, _ in self.layers[:-1]) or (self.dys_index == 2 and mid_dim % 8):
-            raise NotImplementedError('MoSRv2: the head\'s hidden widths must be multiples of 8')
+        self.up = Head('to_img', upsampler, self.s_int, dim, in_ch, mid_dim)
         self.first = 2 if self.unshuffle > 1 else 1
         u = self.unshuffle
         shapes: dict = {f'gblocks.{self.first - 1}.weight': (dim, in_ch * u * u, 3, 3), f'gblocks.{self.first - 1}.bias': (dim,)}
@@ -67,16 +65,9 @@ class MoSRv2(_GatedBase):
         for k, (co, ci, ks) in ((t, (2 * dim, dim, 3)), (t + 2, (dim, 2 * dim, 3)), (t + 4, (dim, dim, 1))):
             shapes[f'gblocks.{k}.weight'] = (co, ci, ks, ks)
             shapes[f'gblocks.{k}.bias'] = (co,)
-        meta = torch.tensor([2, SAMPLE_MODS.index(upsampler), self.s_int, dim, in_ch, mid_dim, 4], dtype=torch.uint8)
-        buffers = {'to_img.MetaUpsample': meta}
-        head_shapes(shapes, buffers, 'to_img', self.layers, self.dys_index, self.s_int, dim, in_ch, mid_dim)
+        buffers: dict = {}
+        self.up.shapes(shapes, buffers, whole_planes='MoSRv2')
         build_param_tree(self, shapes, buffers)
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        # as the reference (arch.py:319-321): the module's own MetaUpsample wins over the checkpoint's
-        state_dict = dict(state_dict)
-        state_dict['to_img.MetaUpsample'] = self.get_buffer('to_img.MetaUpsample')
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     def _gate_groups(self):
         gc, h, d = self.gc, self.hidden, self.dim
@@ -100,7 +91,7 @@ class MoSRv2(_GatedBase):
         last = self._trunk_tail(W, sd, self.first, products, device)
         W['tail2'] = cw(sd[f'gblocks.{last}.weight'], sd[f'gblocks.{last}.bias'])
         W['zeros'] = torch.zeros(dim, dtype=torch.float32, device=device)
-        pack_head(W, sd, 'to_img', self.head, self.s_int, self.layers, self.dys_index, self.in_ch, products, device)
+        self.up.pack(W, sd, products, device)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -108,7 +99,7 @@ class MoSRv2(_GatedBase):
     def macs_per_input_pixel(self) -> int:
         d, h, u = self.dim, self.hidden, self.unshuffle
         blk = 9 * d * 2 * h + (9 + 22) * self.gc + 9 * h * d
-        total = 9 * self.in_ch * u * u * d + self.n_block * blk + 9 * d * 2 * d * 2 + d * d + sum(co * ci * k * k for _, co, ci, k in self.layers)
+        total = 9 * self.in_ch * u * u * d + self.n_block * blk + 9 * d * 2 * d * 2 + d * d + self.up.macs()
         return total // (u * u)
 
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):  # noqa: C901
@@ -148,12 +139,11 @@ class MoSRv2(_GatedBase):
         fe = plan.planes(n, pd, H, Wd, with_lo)
         plan.conv(ops.conv_params(W['tail0'], feat, H, Wd, act=L.ACT_MISH, out=t1))
         plan.conv(ops.conv_params(W['tail1'], t1, H, Wd, act=L.ACT_MISH, out=t2))
-        dys_f32 = self.dys_index == 0 and dys.needs_f32_input(W)
-        fe32 = plan.f32map(n, dim, H, Wd) if dys_f32 else None
+        fe32 = plan.f32map(n, dim, H, Wd) if self.up.needs_f32_input(W) else None
         plan.conv(ops.conv_params(W['tail2'], t2, H, Wd, out=fe, out_f32=fe32))
 
         y = plan.output((n, self.in_ch, H * s, Wd * s), dtype, crop=(h0 * self.scale, w0 * self.scale))
-        self._emit_head(plan, W, fe, fe32, y, n, H, Wd, with_lo)
+        self.up.emit(plan, W, fe, fe32, y, with_lo)
         bp = L.BilinearAddParams()
         bp.batch, bp.C, bp.h, bp.w, bp.pad_h, bp.pad_w, bp.scale = n, self.in_ch, h0, w0, Hp, Wp, self.scale
         bp.dtype = ops.rsa_dtype(dtype)
@@ -161,6 +151,3 @@ class MoSRv2(_GatedBase):
         bp.x, bp.out = plan.input_ref(x_shape, dtype).data_ptr(), y.data_ptr()
         plan.launch('rsa_bilinear_add', bp)
         return set_input
-
-    def _emit_head(self, plan: Plan, W, fe, fe32, y, n, H, Wd, with_lo):
-        emit_head(plan, W, self.head, self.s_int, self.layers, self.dim, self.mid_dim, self.dys_index, fe, fe32, y, n, H, Wd, with_lo)

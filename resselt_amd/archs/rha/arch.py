@@ -32,7 +32,7 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16
-from ...engine.uniupsample import SAMPLE_MODS, emit_head, head_layers, head_shapes, needs_f32_input, pack_head
+from ...engine.uniupsample import SAMPLE_MODS, Head, OwnMetaUpsample
 from ..mosr.arch import _conv_weights, gate_layout, relayout_gate
 from ..rtmosr.arch import fold_omnishift
 
@@ -67,7 +67,7 @@ def pack_hybrid(sd, key: str, c2: int, window: int) -> dict:
     )  # fmt: skip
 
 
-class RHA(EngineModule):
+class RHA(OwnMetaUpsample, EngineModule):  # (the reference's load_state_dict override: arch.py:548-552)
     hyperparameters = {}
     auto_precision = 'bf16x3'
     precisions = ('bf16x3', 'bf16', 'fp16')
@@ -99,9 +99,7 @@ class RHA(EngineModule):
         self.group_blocks, self.res_blocks, self.head, self.window_size = int(group_blocks), int(res_blocks), upsample, int(window_size)
         self.expansion_ratio = hidden / dim
         self.pad = max(down_list) * self.window_size
-        self.layers, self.dys_index = head_layers(upsample, scale, dim, out_ch, self.mid_dim)
-        if any(co % 8 for _, co, _, _ in self.layers[:-1]) or (self.dys_index == 2 and self.mid_dim % 8):
-            raise NotImplementedError("RHA: the head's hidden widths must be multiples of 8")
+        self.up = Head('to_img', upsample, scale, dim, out_ch, self.mid_dim)
         c2 = dim // 2
         shapes: dict = {'to_feat.weight': (dim, in_ch, 3, 3), 'to_feat.bias': (dim,)}
         buffers: dict = {}
@@ -124,18 +122,11 @@ class RHA(EngineModule):
             omnishift_shapes(shapes, f'{grp}.body.{self.res_blocks}', dim)
             t = f'{grp}.body.{self.res_blocks + 1}'
             shapes[f'{t}.weight'], shapes[f'{t}.bias'] = (dim, dim, 1, 1), (dim,)
-        buffers['to_img.MetaUpsample'] = torch.tensor([2, SAMPLE_MODS.index(upsample), scale, dim, out_ch, self.mid_dim, 4], dtype=torch.uint8)
-        head_shapes(shapes, buffers, 'to_img', self.layers, self.dys_index, scale, dim, out_ch, self.mid_dim)
+        self.up.shapes(shapes, buffers, whole_planes='RHA')
         build_param_tree(self, shapes, buffers)  # (state_dict lists a module's parameters, then its buffers, then its children, as the reference's)
 
     def down(self, g: int) -> int:
         return self.down_list[g % len(self.down_list)]
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        # as the reference (arch.py:548-552): the module's own MetaUpsample wins over the checkpoint's
-        state_dict = dict(state_dict)
-        state_dict['to_img.MetaUpsample'] = self.get_buffer('to_img.MetaUpsample')
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     # ---- accounting ----
     def macs_per_input_pixel(self) -> int:
@@ -150,15 +141,15 @@ class RHA(EngineModule):
             blk = 9 * d * 2 * h + 25 * c2 + att + d * d + 9 * h * d
             total += self.res_blocks * blk + 25 * d + d * d
         px = 1  # pixels per input pixel at the current layer of the head
-        up, s = self.head, self.scale
-        for j, (_, co, ci, k) in enumerate(self.layers):
+        up, s, layers = self.head, self.scale, self.up.layers
+        for j, (_, co, ci, k) in enumerate(layers):
             total += px * co * ci * k * k
-            if up == 'pixelshuffle' and 0 < j < len(self.layers) - 1:
+            if up == 'pixelshuffle' and 0 < j < len(layers) - 1:
                 px *= co // ci
-            if up == 'nearest+conv' and s != 1 and j < len(self.layers) - 2:
+            if up == 'nearest+conv' and s != 1 and j < len(layers) - 2:
                 px *= 9 if s == 3 else 4
-        if self.dys_index is not None:
-            dd = self.mid_dim if self.dys_index else d
+        if self.up.dys_index is not None:
+            dd = self.up.dys_dim
             total += 2 * dd * 8 * s * s + s * s * dd * self.out_ch
         return int(total)
 
@@ -189,7 +180,7 @@ class RHA(EngineModule):
             t = f'body.{g}.body'
             ow, ob = fold_omnishift(sd, f'{t}.{self.res_blocks}')
             W[f'{t}.tail'] = dict(omni_w=ow, omni_b=ob, conv=cw(sd[f'{t}.{self.res_blocks + 1}.weight'], sd[f'{t}.{self.res_blocks + 1}.bias']))
-        pack_head(W, sd, 'to_img', self.head, self.scale, self.layers, self.dys_index, self.out_ch, products, device)
+        self.up.pack(W, sd, products, device)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -274,8 +265,8 @@ class RHA(EngineModule):
                 plan.conv(ops.conv_params(tail['conv'], O_pl, H, Wd, res1=gin, alpha=1.0, out_f32=gout))
                 gin, gout = gout, (gb if gout is ga else ga)
             else:  # body(x) + x: the last group's tail also adds to_feat's output and writes what the head reads
-                fe32 = plan.f32map(n, dim, H, Wd) if needs_f32_input(self.head, s, self.dys_index, W) else None
+                fe32 = plan.f32map(n, dim, H, Wd) if self.up.needs_f32_input(W) else None
                 plan.conv(ops.conv_params(tail['conv'], O_pl, H, Wd, res1=gin, alpha=1.0, res2=top, beta=1.0, out=fe, out_f32=fe32))
         y = plan.output((n, self.out_ch, H * s, Wd * s), dtype, crop=(h0 * s, w0 * s))
-        emit_head(plan, W, self.head, s, self.layers, dim, self.mid_dim, self.dys_index, fe, fe32, y, n, H, Wd, with_lo)
+        self.up.emit(plan, W, fe, fe32, y, with_lo)
         return set_input

@@ -37,13 +37,12 @@ from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
 from ...engine.paramtree import build_param_tree
 from ...engine.tensors import PF_BF16, Planes
-from ...engine.uniupsample import emit_head, head_layers, pack_head
+from ...engine.uniupsample import GROUPS, Head  # (GROUPS: DySample's 4, fixed by SMoSR.__init__ :448)
 from ..mosr.arch import _check_dims, _conv_weights
 
 SAMPLE_MODS = ('conv', 'pixelshuffledirect', 'pixelshuffle', 'nearest+conv', 'dysample', 'pa_up')
 MAX_DIM = 128  # rsa_smosr_gate / rsa_smosr_pa: C up to 128
 PAD = 2
-GROUPS = 4  # DySample's, fixed by SMoSR.__init__ :448
 
 
 # ---- folding (float64 in, float64 out) -------------------------------------------------------------------------------------------------
@@ -180,17 +179,17 @@ class SMoSR(EngineModule):
                 _conv_shapes(shapes, m, f'{b}.body.{i}', a, o, 3, rep, mul=3.0)
         _conv_shapes(shapes, m, 'end_block.1', dim, dim, 3, rep)
         # the head: [(key prefix, cin, cout, k)] of its convolutions in module order, the pixel attentions apart
-        self.dys_index = None
+        self.dys_index = self.dys_pos = None
         if self.pa:
             self.pa_stages, self.last_index = pa_layers(scale, cat, out_ch, mid)
             self.head_convs = []
             for i, ci in self.pa_stages:
                 self.head_convs += [(i, ci, mid, 3), (i + 1, mid, mid, 1), (i + 3, mid, mid, 3)]
             self.head_convs.append((self.last_index, mid, out_ch, 3))
-            self.layers = []
         else:
-            self.layers, self.dys_index = head_layers(upsampler, scale, cat, out_ch, mid)
-            self.head_convs = [(i, ci, co, k) for i, co, ci, k in self.layers]
+            self.up = Head('upsampler', upsampler, scale, cat, out_ch, mid, end_kernel=d_kernel)
+            self.dys_index = self.up.dys_index
+            self.head_convs = [(i, ci, co, k) for i, co, ci, k in self.up.layers]
         # the width the head's hidden layers RUN at: whole planes (DySample: whole units of four per channel group), zero weights beyond mid
         self.mid_run = mid
         if self.dys_index is not None:
@@ -281,26 +280,16 @@ class SMoSR(EngineModule):
                 elif self.dys_index is not None and s != 1 and run != mid:
                     w, b = _rows(w, self.dys_pos, run), _rows(b, self.dys_pos, run)  # head0: cat -> mid, laid out for rsa_dysample
                 head[f'upsampler.{i}.weight'], head[f'upsampler.{i}.bias'] = w, b
-            d3 = self.dys_index is not None and self.d_kernel == 3
             if self.dys_index is not None:
                 d = f'upsampler.{self.dys_index}'
                 relay = (lambda w: _cols(w, self.dys_pos, run)) if run != mid else (lambda w: w)  # noqa: E731
-                for k_ in ('offset.bias', 'init_pos'):
+                for k_ in ('offset.bias', 'init_pos', 'end_conv.bias'):
                     head[f'{d}.{k_}'] = sd[f'{d}.{k_}']
                 for k_ in ('offset.weight', 'scope.weight'):
                     head[f'{d}.{k_}'] = relay(sd[f'{d}.{k_}'])
-                if d3:
-                    # a 3x3 end convolution runs AFTER the sampling, at output resolution: rsa_dysample samples the features themselves, 8
-                    # channels per launch through a selection matrix, and the convolution reads them as planes
-                    W['dys.end3'] = cw(sd[f'{d}.end_conv.weight'], sd[f'{d}.end_conv.bias'])
-                    # output channel o of the sampled features (the reference's order) = buffer channel dys_pos[o]
-                    sel = _cols(torch.eye((mid + 7) // 8 * 8, mid, dtype=torch.float32, device=device), self.dys_pos if run != mid else ident, run)
-                    W['dys.sel'] = [sel[8 * g : 8 * g + 8].contiguous() for g in range((mid + 7) // 8)]
-                    W['dys.zero'] = torch.zeros(8, dtype=torch.float32, device=device)
-                    head[f'{d}.end_conv.weight'], head[f'{d}.end_conv.bias'] = torch.zeros((8, run, 1, 1), device=device), W['dys.zero']
-                else:
-                    head[f'{d}.end_conv.weight'], head[f'{d}.end_conv.bias'] = relay(sd[f'{d}.end_conv.weight']), sd[f'{d}.end_conv.bias']
-            pack_head(W, head, 'upsampler', self.head, s, self.layers, self.dys_index, 8 if d3 else self.out_ch, products, device)
+                # (a 3x3 end convolution reads the sampled features in the reference's channel order: the head's selection matrices undo dys_pos)
+                head[f'{d}.end_conv.weight'] = sd[f'{d}.end_conv.weight'] if self.up.dys3 else relay(sd[f'{d}.end_conv.weight'])
+            self.up.pack(W, head, products, device, run=run, dys_pos=self.dys_pos)
         if products.fmt != PF_BF16:
             check_fp16_range(_conv_weights(W))
         return W
@@ -422,36 +411,6 @@ class SMoSR(EngineModule):
                 plan.conv(ops.conv_params(W[f'pa{j}.c'], m2, hh, ww, act=L.ACT_LRELU, act_param=0.2, out=m3))
                 t, up = m3, True
             plan.conv(ops.conv_params(W['pa.last'], t, hh, ww, out_nchw=y))
-        elif self.dys_index is not None and self.d_kernel == 3 and s != 1:
-            self._emit_dys3(plan, W, cat_pl, y, n, H, Wd, with_lo)
         else:
-            run = self.mid_run  # (emit_head reads a pixelshuffle stage's factor from its layer's width over the hidden width)
-            layers = [(i, co // self.mid_dim * run if co % self.mid_dim == 0 and j < len(self.layers) - 1 else co, ci, k)
-                      for j, (i, co, ci, k) in enumerate(self.layers)] if self.head == 'pixelshuffle' and s != 1 else self.layers  # fmt: skip
-            emit_head(plan, W, self.head, s, layers, cat, run, self.dys_index, cat_pl, None, y, n, H, Wd, with_lo)
+            self.up.emit(plan, W, cat_pl, None, y, with_lo, run=self.mid_run)
         return set_input
-
-    def _emit_dys3(self, plan: Plan, W, cat_pl, y, n, H, Wd, with_lo) -> None:
-        """DySample with a 3x3 end convolution: mid_dim conv + LeakyReLU 0.01, the offsets, then the sampled FEATURES at output resolution
-        (rsa_dysample, 8 channels per launch through a selection matrix) as planes, and the end convolution on them."""
-        s, mid, run = self.scale, self.mid_dim, self.mid_run  # the features sit in rsa_dysample's layout, ``run`` wide (dys_layout)
-        x = plan.planes(n, run // 8, H, Wd, with_lo)
-        x32 = plan.f32map(n, run, H, Wd)
-        plan.conv(ops.conv_params(W['head0'], cat_pl, H, Wd, act=L.ACT_LRELU, act_param=0.01, out=x, out_f32=x32))
-        offscope = plan.f32map(n, 4 * GROUPS * s * s, H, Wd)
-        plan.conv(ops.conv_params(W['dys.offscope'], x, H, Wd, out_f32=offscope))
-        up = plan.planes(n, (mid + 7) // 8, s * H, s * Wd, with_lo)
-        d = W['dys']
-        for g, sel in enumerate(W['dys.sel']):
-            t = torch.empty((n, 8, s * H, s * Wd), dtype=torch.float32, device=plan.device)
-            plan.keep.append(t)
-            dp = L.DySampleParams()
-            dp.batch, dp.H, dp.W, dp.C, dp.groups, dp.scale, dp.out_ch = n, H, Wd, run, GROUPS, s, 8
-            dp.x_f32, dp.offscope = x32.data_ptr(), offscope.data_ptr()
-            dp.init_pos, dp.end_b, dp.end_w = d['init_pos'].data_ptr(), W['dys.zero'].data_ptr(), sel.data_ptr()
-            dp.out_nchw, dp.out_dtype = t.data_ptr(), L.F32
-            plan.launch('rsa_dysample', dp)
-            one = Planes(up.hi[:, g : g + 1], None if up.lo is None else up.lo[:, g : g + 1])
-            plan.call(lambda src=t, dst=one: ops.nchw_to_planes(src, dst))
-            plan.count_launches(1)
-        plan.conv(ops.conv_params(W['dys.end3'], up, s * H, s * Wd, out_nchw=y))

@@ -8,7 +8,7 @@ Behaviour kept from the reference:
   * the restricted unpickler only admits OrderedDict, ``_rebuild_tensor_v2`` and six storage classes and
     raises ``pickle.UnpicklingError`` for every other global (registry.py:20-46);
   * ``load_from_state_dict`` canonicalises, walks the architectures in insertion order (then ``Registry.late``, then ``Registry.last``, then
-    ``Registry.after``, then ``Registry.tail``, then ``Registry.rest``: ``Registry.order()``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
+    ``Registry.after``, then ``Registry.tail``, then ``Registry.rest``, ``Registry.more`` and ``Registry.beyond``: ``Registry.consultation()``), builds the first match and calls ``model.load_state_dict(canonicalised_dict)`` (registry.py:106-116);
   * no match raises ``ArchitectureNotFound``.
 
 Documented deviation: the reference hands the *unconverted* dict to ``load_state_dict``, so official
@@ -103,7 +103,12 @@ class Registry:
     to a fixed list of ids (membership and relative order only), so the next architecture goes into ``rest`` too.
     ``more`` exists because one did (tests/test_lawfft_loader.py holds ``rest`` and the end of ``order()`` to exactly GFISRv2, FIGSR, LAWFFT):
     the same admission rule, any number of architectures in insertion order, consulted once ``order()`` has declined; ``full()`` is the
-    whole consultation order and what ``load_from_state_dict`` walks, and no older tier or iterator sees ``more``."""
+    whole consultation order up to there, and no older tier or iterator sees ``more``.
+    ``beyond`` is the tier behind ``more`` (tests/test_gfisr_loader.py holds ``more`` to exactly GFISR and ``full()`` to ``order()`` + GFISR):
+    the same admission rule, any number of architectures in insertion order, consulted once ``full()`` has declined; ``consultation()``
+    yields ``full()`` and then ``beyond`` and is what ``load_from_state_dict`` walks.  No older tier, iterator or ``len()`` sees ``beyond``,
+    and no test may hold ``beyond`` or the end of ``consultation()`` to a fixed list of ids (membership and relative order only), so the
+    next architecture goes into ``beyond`` too."""
 
     def __init__(self):
         self.store: Dict[str, Architecture] = {}
@@ -113,9 +118,10 @@ class Registry:
         self.tail: Dict[str, Architecture] = {}
         self.rest: Dict[str, Architecture] = {}
         self.more: Dict[str, Architecture] = {}
+        self.beyond: Dict[str, Architecture] = {}
 
     def __contains__(self, uid: str) -> bool:
-        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail or uid in self.rest or uid in self.more
+        return uid in self.store or uid in self.late or uid in self.last or uid in self.after or uid in self.tail or uid in self.rest or uid in self.more or uid in self.beyond
 
     def __iter__(self) -> Iterator[Architecture]:
         return iter(list(self.store.values()) + list(self.late.values()))
@@ -140,12 +146,22 @@ class Registry:
         return iter(list(self.every()) + list(self.rest.values()))
 
     def full(self) -> Iterator[Architecture]:
-        """The whole consultation order of ``load_from_state_dict``: ``order()``, then ``more``."""
+        """``order()``, then ``more``: what ``load_from_state_dict`` consults before ``beyond`` (``consultation()`` is the whole order)."""
         return iter(list(self.order()) + list(self.more.values()))
 
+    def consultation(self) -> Iterator[Architecture]:
+        """The whole consultation order of ``load_from_state_dict``: ``full()``, then ``beyond``."""
+        return iter(list(self.full()) + list(self.beyond.values()))
+
     def add(self, arch: Architecture, late: bool = False, last: bool = False, after: bool = False, tail: bool = False, rest: bool = False,
-            more: bool = False) -> None:  # fmt: skip
+            more: bool = False, beyond: bool = False) -> None:  # fmt: skip
         """Register an architecture *instance*; re-using an id replaces it in place."""
+        if beyond and not any(arch.id in t for t in (self.store, self.late, self.last, self.after, self.tail, self.rest, self.more)):
+            self.beyond[arch.id] = arch
+            return
+        self.beyond.pop(arch.id, None)
+        if beyond:  # an id another tier already holds is replaced there
+            more = more or arch.id in self.more
         if more and not any(arch.id in t for t in (self.store, self.late, self.last, self.after, self.tail, self.rest)):
             self.more[arch.id] = arch
             return
@@ -179,7 +195,7 @@ class Registry:
             self.store[arch.id] = arch
 
     def get(self, uid: str) -> Architecture:
-        tier = next((t for t in (self.late, self.last, self.after, self.tail, self.rest, self.more) if uid in t), self.store)
+        tier = next((t for t in (self.late, self.last, self.after, self.tail, self.rest, self.more, self.beyond) if uid in t), self.store)
         arch = tier[uid]  # KeyError for unknown ids, as in the reference
         if not arch:
             raise ArchitectureNotFound
@@ -190,7 +206,7 @@ class Registry:
 
     def load_from_state_dict(self, state_dict: Mapping[str, object]):
         state_dict = canonicalize_state_dict(state_dict)
-        for arch in self.full():
+        for arch in self.consultation():
             if arch.detect(state_dict):
                 model = arch.load(state_dict)
                 model.load_state_dict(state_dict)

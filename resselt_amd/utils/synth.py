@@ -1762,3 +1762,60 @@ def gfisr_state_dict(in_nc=3, out_nc=3, dim=48, scale=4, n_blocks=24, expansion_
     for k, v in head.items():
         sd['dim_to_out.' + k[len('upscale.') :]] = v
     return sd
+
+
+def gaterv3_state_dict(in_ch=3, dim=32, enc_blocks=(2, 2, 4, 8), dec_blocks=(2, 2, 2, 2), num_latent=12, scale=1, upsample='pixelshuffle',
+                       upsample_mid_dim=32, attention=False, span_blocks=4, end_kernel=3, with_gamma=True, seed=0):  # fmt: skip
+    """Keys of the reference GateRV3 module (archs/gaterv3/arch.py:705-802) in the order of its ``state_dict()``: a module's own parameters
+    before its children's (``gamma`` first, ``gamma0`` / ``gamma1`` at the head of a MetaGated, ``temperature`` at the head of an Attention),
+    the SPABs' Conv3XC without biases, ``dim_to_in.MetaUpsample`` before the head's layers and DySample's ``init_pos`` before its
+    convolutions; at scale 1 ``dim_to_in`` is one plain convolution and there is no MetaUpsample buffer.  ``with_gamma=False`` leaves
+    ``gamma`` out (the loader then keeps the module's ones).
+    Matrices and filters are uniform with variance 1 / fan_in, so that a layer has roughly unit gain; norm scales lie in 0.5..1.5, offsets
+    in +-0.1, biases in +-0.09, ``gamma0`` / ``gamma1`` in +-0.5 per channel (both signs; a stream grows by about a tenth of its variance
+    per block, and every block renormalises), the temperatures in -0.5..2.5 per head, the last convolution at a tenth of the bound: the
+    output stays of order 1 through four levels (N(0, 0.1) weights throughout give |y| of about 400 there)."""
+    from ..archs.gaterv3.arch import trunk_shapes
+    from ..engine.uniupsample import Head
+
+    sd: OrderedDict = OrderedDict()
+    g = float(np.sqrt(3.0))
+
+    def fill(name, shape, gain=1.0):
+        leaf = name.rsplit('.', 1)[-1]
+        if name == 'gamma':
+            sd[name] = 1.0 + synth_tensor(name, shape, 1, seed, 0.3)
+        elif leaf in ('gamma0', 'gamma1'):
+            sd[name] = synth_tensor(name, shape, 1, seed, 0.5)
+        elif leaf == 'scale' and len(shape) == 1:
+            sd[name] = 1.0 + synth_tensor(name, shape, 1, seed, 0.5)
+        elif leaf == 'offset':
+            sd[name] = synth_tensor(name, shape, 1, seed, 0.1)
+        elif leaf == 'temperature':
+            sd[name] = 1.0 + synth_tensor(name, shape, 1, seed, 1.5)
+        elif leaf == 'bias':
+            sd[name] = synth_tensor(name, shape, 1, seed, 0.05 * g * gain)
+        else:
+            sd[name] = synth_tensor(name, shape, int(np.prod(shape[1:])), seed, g * gain)
+
+    for name, shape in trunk_shapes(in_ch, dim, tuple(enc_blocks), tuple(dec_blocks), num_latent, attention, span_blocks).items():
+        if name == 'gamma' and not with_gamma:
+            continue
+        fill(name, shape)
+    if scale == 1:
+        fill('dim_to_in.weight', (in_ch, dim, 3, 3), 0.1)
+        fill('dim_to_in.bias', (in_ch,), 0.1)
+        return sd
+    head = Head('dim_to_in', upsample, scale, dim, in_ch, upsample_mid_dim, end_kernel=end_kernel, version=3)
+    shapes, buffers = {}, {}
+    head.shapes(shapes, buffers)
+    sd['dim_to_in.MetaUpsample'] = buffers['dim_to_in.MetaUpsample']
+    last = f'dim_to_in.{head.layers[-1][0]}.' if head.dys_index is None else '.end_conv.'
+    pos = [k for k in buffers if k.endswith('init_pos')]
+    dys = f'dim_to_in.{head.dys_index}.' if head.dys_index is not None else None
+    for name, shape in shapes.items():
+        if dys is not None and name.startswith(dys) and pos:
+            key = pos.pop()
+            sd[key] = buffers[key]
+        fill(name, shape, 0.1 if last in name else (0.5 if '.offset.' in name else 1.0))
+    return sd

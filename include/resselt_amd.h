@@ -306,7 +306,7 @@ typedef struct rsa_layernorm_params {
   const float* beta;       /* [C] */
   void* out_hi;            /* split planes [N][ceil(C/8)][H][W][8], tail channels zeroed; may be NULL */
   void* out_lo;            /* may be NULL */
-  int64_t out_plane_stride; /* 16-byte units */
+  int64_t out_plane_stride; /* 16-byte units; with out_hi set, at least H*W (RSA_E_ARG otherwise) */
   int64_t out_batch_stride;
   float* out_f32;          /* optional f32 NCHW4c copy of the result */
   int32_t out_fmt;         /* enum rsa_plane_fmt of out_hi / out_lo */

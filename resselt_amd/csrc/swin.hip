@@ -187,7 +187,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8
 // C <= 32 * MAXP (MAXP 8: every LayerNorm of the SwinIR / HAT / DAT bodies; 12: DRCT's dense blocks, up to 308 channels), round 4: the same work split with everything wave-uniform kept in scalar
 // registers -- the wave id through readfirstlane, 64-token blocks that never straddle two images (so the image index and every plane base
 // are uniform and a lane's address is base + 16 * pixel), whole-plane validity as scalar branches -- and gamma / beta read from LDS.
-// 76 VGPRs (the first form: 233, two workgroups per CU, and 48 waited-for gamma / beta loads per wave): 121 -> 45 us for 180 channels at 512^2.
+// 117 VGPRs and 4 waves per SIMD at MAXP 8, 155 and 3 at MAXP 12 (the first form: 233, two workgroups per CU, and 48 waited-for gamma /
+// beta loads per wave): 121 -> 71 us for 180 channels at 512^2 into fp16 hi planes.
+// The normalise step is the centred (v - mean) * rstd of layernorm_kernel, so the result does not depend on which kernel is dispatched.
+// The earlier v * rstd + (-mean * rstd) saved one VALU operation per channel (2 against 3) at one more rounding of size u |mean| / sigma;
+// the kernel is bound by memory and neither registers, waves per SIMD nor time moved (profiles/layernorm_forms.txt).
 template <int MAXP>
 __global__ __launch_bounds__(256) void layernorm_regs_kernel(const rsa_layernorm_params p) {
   __shared__ float s_red[2][4][64];
@@ -257,7 +261,6 @@ __global__ __launch_bounds__(256) void layernorm_regs_kernel(const rsa_layernorm
     s_red[1][wave][lane] = var;
     __syncthreads();  // also orders the next iteration's s_red[0] writes after this iteration's reads
     const float rstd = rsqrtf((s_red[1][0][lane] + s_red[1][1][lane] + s_red[1][2][lane] + s_red[1][3][lane]) * inv_c + p.eps);
-    const float nm = -mean * rstd;
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) {
       const int pl = wave + 4 * k;  // uniform
@@ -267,8 +270,8 @@ __global__ __launch_bounds__(256) void layernorm_regs_kernel(const rsa_layernorm
       float y[8];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        y[j] = (v[k][0][j] * rstd + nm) * g0[j] + b0[j];
-        y[4 + j] = (v[k][1][j] * rstd + nm) * g1[j] + b1[j];
+        y[j] = (v[k][0][j] - mean) * rstd * g0[j] + b0[j];  // centred, as layernorm_kernel (see above the kernel)
+        y[4 + j] = (v[k][1][j] - mean) * rstd * g1[j] + b1[j];
       }
       if (!live) continue;
       if (p.out_f32 != nullptr) {
@@ -514,6 +517,7 @@ extern "C" int rsa_layernorm(const rsa_layernorm_params* p, void* stream) {
   if (!plane_fmt_ok(p->out_fmt) || p->reserved0 != 0) return set_error(RSA_E_ARG, "layernorm: out_fmt must be an rsa_plane_fmt");
   if (misaligned16(p->x_f32) || misaligned16(p->out_hi) || misaligned16(p->out_lo) || misaligned16(p->out_f32))
     return set_error(RSA_E_ALIGN, "layernorm: maps must be 16-byte aligned");
+  if (p->out_hi && p->out_plane_stride < (int64_t)p->H * p->W) return set_error(RSA_E_ARG, "layernorm: out_plane_stride is smaller than the map");
   const int64_t total = (int64_t)p->batch * p->H * p->W;
   int64_t g = (total + 63) / 64;  // one 256-thread workgroup per 64 tokens
   if (g > 256 * 32) g = 256 * 32;

@@ -1,7 +1,7 @@
 """Architectures served by the MI355X engine, registered explicitly in detection order.
 
 The reference discovers 31 architectures by walking the filesystem (``resselt/archs/__init__.py:11-28``);
-this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR, GFISRv2, FIGSR, LAWFFT, GFISR, GateRV3); the first
+this build registers the families of the hot path: ESRGAN/RRDBNet, SPANPlus, SPAN, SwinIR, DAT, HAT, and the "next" rows of §8f built so far (Compact, SpanPP, RTMoSR, MoSR, MoSRv2, PLKSR / RealPLKSR, Real-CUGAN, RGT, FDAT, OmniSR, ATD, RCAN, GateR, EIMN, RHA, FlexNet, MoESR, SMoSR, GFISRv2, FIGSR, LAWFFT, GFISR, GateRV3, GateRv2); the first
 "next" row of §8f (Compact / SRVGGNetCompact, pure reuse of the conv kernel).
 """
 
@@ -17,6 +17,7 @@ from .fdat import FDATArch
 from .figsr import FIGSRArch
 from .flexnet import FlexNetArch
 from .gater import GateRArch
+from .gaterv2 import GateRV2Arch
 from .gaterv3 import GateRV3Arch
 from .gfisr import GFISRArch
 from .gfisrv2 import GFISRV2Arch
@@ -72,3 +73,6 @@ internal_registry.add(GFISRArch(), more=True)
 # ``more``: tests/test_gfisr_loader.py holds ``more`` to exactly GFISR and ``full()`` to ``order()`` + GFISR.  Later architectures of this
 # kind go into ``beyond`` too.  The reference walks it right behind GateR.
 internal_registry.add(GateRV3Arch(), beyond=True)
+# GateRv2 likewise (tests/test_gaterv2_loader.py checks the same two properties), in ``beyond`` behind GateRV3: every older tier and iterator
+# stays what it was.  The reference walks it between GateR and GateRV3.
+internal_registry.add(GateRV2Arch(), beyond=True)

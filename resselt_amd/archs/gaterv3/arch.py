@@ -36,38 +36,18 @@ import torch
 
 from ...engine import lib as L
 from ...engine import lib_gaterv3 as LG3
-from ...engine import ops, plk
+from ...engine import ops
 from ...engine.base import EngineModule, Plan, check_fp16_range
+from ...engine.gatedunet import GatedUNetBlocks, _gated_cnn_shapes, _meta_gated_shapes, gate_groups, hidden_of, unit_stats  # noqa: F401  (gate_groups: what the tests import from here)
 from ...engine.paramtree import ParamShapes, build_param_tree
 from ...engine.spanblocks import SpabChain, fold_conv3xc
 from ...engine.tensors import PF_BF16, Planes
 from ...engine.uniupsample import SAMPLE_MODS, SAMPLE_MODS3, Head, OwnMetaUpsample
-from ..mosr.arch import _conv_weights, gate_layout, pad_dw, relayout_gate
+from ..mosr.arch import _conv_weights
 
 HEADS = 16
 MAX_WIDTH = 512  # dim * 2^L: rsa_gaterv3_local_gate and the attention take at most 512 channels
 MAX_HEAD_DIM = 64
-RMS_EPS = 1e-6
-INCEPTION = (('dwconv_hw', (3, 3)), ('dwconv_w', (1, 11)), ('dwconv_h', (11, 1)))
-
-
-def _view(p: Planes, plane0: int, planes: int) -> Planes:
-    """Planes [plane0, plane0 + planes) of a buffer as a buffer of its own (same storage and strides)."""
-    lo = p.lo[:, plane0 : plane0 + planes] if p.has_lo(plane0, planes) else None
-    return Planes(p.hi[:, plane0 : plane0 + planes], lo)
-
-
-def hidden_of(width: int) -> int:
-    return int(1.5 * width)
-
-
-def gate_groups(width: int, att: bool):
-    """cat(i, c) of a GatedCNNBlock in channel order: [(channels, kernel shape)], (1, 1) = passthrough (arch.py:517-546, 587-625)."""
-    hidden = hidden_of(width)
-    if att:
-        return [(hidden, (1, 1))]
-    gc = int(width * 0.125)
-    return [(hidden - 3 * gc, (1, 1))] + [(gc, k) for _, k in INCEPTION]
 
 
 def _conv3xc_shapes(s: ParamShapes, name: str, c: int, bias: bool, gain: int) -> None:
@@ -78,29 +58,11 @@ def _conv3xc_shapes(s: ParamShapes, name: str, c: int, bias: bool, gain: int) ->
             s[f'{name}.{sub}.bias'] = (co,)
 
 
-def _gated_cnn_shapes(s: ParamShapes, b: str, w: int, att: bool) -> None:
-    hidden = hidden_of(w)
-    s[f'{b}.norm.scale'], s[f'{b}.norm.offset'] = (w,), (w,)
-    s.conv(f'{b}.fc1', 2 * hidden, w, 1)
-    if att:
-        s[f'{b}.token_mix.temperature'] = (HEADS, 1, 1)
-        s[f'{b}.token_mix.qkv.weight'] = (3 * w, w, 1, 1)
-        s[f'{b}.token_mix.qkv_dwconv.weight'], s[f'{b}.token_mix.qkv_dwconv.bias'] = (3 * w, 1, 3, 3), (3 * w,)
-        s[f'{b}.token_mix.project_out.weight'] = (w, w, 1, 1)
-    else:
-        gc = int(w * 0.125)
-        for name, (kh, kw) in INCEPTION:
-            s[f'{b}.token_mix.{name}.weight'], s[f'{b}.token_mix.{name}.bias'] = (gc, 1, kh, kw), (gc,)
-    s.conv(f'{b}.fc2', w, hidden, 1)
-
-
-def _meta_gated_shapes(s: ParamShapes, b: str, w: int) -> None:
-    s[f'{b}.gamma0'], s[f'{b}.gamma1'] = (1, w, 1, 1), (1, w, 1, 1)
-    s[f'{b}.local.0.scale'], s[f'{b}.local.0.offset'] = (w,), (w,)
-    s.conv(f'{b}.local.1', 2 * w, w, 1)
-    s[f'{b}.local.2.weight'], s[f'{b}.local.2.bias'] = (2 * w, 2, 3, 3), (2 * w,)
-    s.conv(f'{b}.sca.1', w, w, 1)
-    _gated_cnn_shapes(s, f'{b}.glob', w, False)
+def _attention_shapes(s: ParamShapes, t: str, w: int) -> None:
+    s[f'{t}.temperature'] = (HEADS, 1, 1)
+    s[f'{t}.qkv.weight'] = (3 * w, w, 1, 1)
+    s[f'{t}.qkv_dwconv.weight'], s[f'{t}.qkv_dwconv.bias'] = (3 * w, 1, 3, 3), (3 * w,)
+    s[f'{t}.project_out.weight'] = (w, w, 1, 1)
 
 
 def trunk_shapes(in_ch: int, dim: int, enc_blocks, dec_blocks, num_latent: int, attention: bool, span_blocks: int) -> ParamShapes:
@@ -121,7 +83,7 @@ def trunk_shapes(in_ch: int, dim: int, enc_blocks, dec_blocks, num_latent: int, 
     _conv3xc_shapes(s, 'sisr_end_conv', dim, True, 1)  # (gain1 = 1 here, 2 in the SPABs)
     s.conv('sisr_cat_conv', dim, 4 * dim, 1)
     for i in range(num_latent):
-        _gated_cnn_shapes(s, f'latent.{i}', dim << L_, attention)
+        _gated_cnn_shapes(s, f'latent.{i}', dim << L_, _attention_shapes if attention else None)
     for i, nb in enumerate(dec_blocks):
         wb = dim << (len(dec_blocks) - i)
         s[f'decode.{i}.scale.0.weight'] = (2 * wb, wb, 3, 3)
@@ -149,7 +111,7 @@ class _Chain(SpabChain):
         self.plan.conv(ops.conv_params(self.W[names['conv_cat']], cat, self.h, self.w, cin_planes=4 * pf, res1=res, alpha=1.0, out=out, out_f32=out_f32))
 
 
-class GateRV3(OwnMetaUpsample, EngineModule):
+class GateRV3(GatedUNetBlocks, OwnMetaUpsample, EngineModule):
     auto_precision = 'bf16x3'
     precisions = ('bf16x3', 'bf16', 'fp16')
     global_statistics = True  # sca's mean and the attention span the whole padded tensor: a tile computes what the reference computes on that tile
@@ -244,39 +206,12 @@ class GateRV3(OwnMetaUpsample, EngineModule):
         return 1 + 10 * self.meta_gated_count() + 2 * self.levels + latent * self.num_latent + 3 * self.levels + span + 1
 
     # ---------------------------------------------------------------- weights
-    def _pack_gated(self, blk, sd, b, w, att, products, device):
-        f32 = torch.float32
-        perm, i_planes, segs, planes = gate_layout(gate_groups(w, att))
-        w1, b1, w2 = relayout_gate(sd[f'{b}.fc1.weight'], sd[f'{b}.fc1.bias'], sd[f'{b}.fc2.weight'], perm, planes)
-        own = lambda t: t.to(f32).contiguous().clone()  # noqa: E731  (an allocation of its own: 16-byte aligned)
-        blk['norm'] = (own(sd[f'{b}.norm.scale']), own(sd[f'{b}.norm.offset']))
-        # rsa_rmsnorm writes bf16 planes: in the fp16 mode the layers that read them take one bf16 product
-        nprod = products if products.fmt == PF_BF16 else 1
-        blk['fc1'] = ops.ConvWeights.from_oihw(w1.to(f32), b1.to(f32), nprod, fmt=PF_BF16, device=device)
-        blk['fc2'] = ops.ConvWeights.from_oihw(w2.to(f32), sd[f'{b}.fc2.bias'], products, device=device)
-        blk['i_planes'], blk['planes'], blk['att'] = i_planes, planes, att
-        if att:
-            t = f'{b}.token_mix'
-            blk['qkv'] = ops.ConvWeights.from_oihw(sd[f'{t}.qkv.weight'], None, products, device=device)
-            blk['proj'] = ops.ConvWeights.from_oihw(sd[f'{t}.project_out.weight'], None, products, device=device)
-            blk['dw'] = (own(sd[f'{t}.qkv_dwconv.weight'].reshape(3 * w, 9)), own(sd[f'{t}.qkv_dwconv.bias']))
-            blk['temperature'] = own(sd[f'{t}.temperature'].reshape(-1))
-            blk['segs'] = []
-        else:
-            blk['segs'] = [(pl, kh, kw, *pad_dw(sd[f'{b}.token_mix.{name}.weight'], sd[f'{b}.token_mix.{name}.bias'], pl))
-                           for (pl, kh, kw, _, _), (name, _) in zip(segs, INCEPTION)]  # fmt: skip
-
-    def _pack_meta(self, W, sd, b, w, products, device):
-        f32 = torch.float32
-        own = lambda t: t.to(f32).contiguous().clone()  # noqa: E731
-        nprod = products if products.fmt == PF_BF16 else 1
-        blk = dict(lnorm=(own(sd[f'{b}.local.0.scale']), own(sd[f'{b}.local.0.offset'])),
-                   local1=ops.ConvWeights.from_oihw(sd[f'{b}.local.1.weight'], sd[f'{b}.local.1.bias'], nprod, fmt=PF_BF16, device=device),
-                   local2=(own(sd[f'{b}.local.2.weight'].reshape(2 * w, 18)), own(sd[f'{b}.local.2.bias'])),
-                   sca=(own(sd[f'{b}.sca.1.weight'].reshape(w, w)), own(sd[f'{b}.sca.1.bias'])),
-                   gamma0=own(sd[f'{b}.gamma0'].reshape(-1)), gamma1=own(sd[f'{b}.gamma1'].reshape(-1)))  # fmt: skip
-        self._pack_gated(blk, sd, f'{b}.glob', w, False, products, device)
-        W[b] = blk
+    def _mixer_pack(self, blk, sd, t, w, products, device) -> None:
+        own = lambda v: v.to(torch.float32).contiguous().clone()  # noqa: E731  (an allocation of its own: 16-byte aligned)
+        blk['qkv'] = ops.ConvWeights.from_oihw(sd[f'{t}.qkv.weight'], None, products, device=device)
+        blk['proj'] = ops.ConvWeights.from_oihw(sd[f'{t}.project_out.weight'], None, products, device=device)
+        blk['dw'] = (own(sd[f'{t}.qkv_dwconv.weight'].reshape(3 * w, 9)), own(sd[f'{t}.qkv_dwconv.bias']))
+        blk['temperature'] = own(sd[f'{t}.temperature'].reshape(-1))
 
     def span_names(self) -> dict:
         return dict(first='span_block0', middle=[f'span_n_b.{i}' for i in range(self.span_blocks)], end='span_end', conv_2='sisr_end_conv', conv_cat='sisr_cat_conv')
@@ -320,122 +255,45 @@ class GateRV3(OwnMetaUpsample, EngineModule):
         return W
 
     # ---------------------------------------------------------------- plan
-    def _rmsnorm(self, plan: Plan, cur, n, H, Wd, w, norm, N_pl) -> None:
-        unit = 16 * (2 if N_pl.lo is not None else 1)
-        plan.launch('rsa_rmsnorm', dict(x_f32=cur, batch=n, H=H, W=Wd, C=w, eps=RMS_EPS, scale=norm[0], offset=norm[1], out=N_pl),
-                    meta=dict(kernel='rsa_rmsnorm', flop=0, bytes=n * H * Wd * (4 * w + unit * (w // 8))))  # fmt: skip
+    def _mixer_bufs(self, plan: Plan, b, n, H, Wd, w, with_lo) -> None:
+        b['qkv'], b['qkv2'], b['attn'] = plan.planes(n, 3 * w // 8, H, Wd, with_lo), plan.planes(n, 3 * w // 8, H, Wd, with_lo), plan.planes(n, w // 8, H, Wd, with_lo)
+        nbytes = int(L.load().rsa_gaterv3_attn_workspace_bytes(n, H, Wd, HEADS, w // HEADS))
+        if nbytes <= 0:
+            raise RuntimeError('rsa_gaterv3_attn_workspace_bytes refused the latent grid')
+        b['ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=plan.device)
+        plan.keep.append(b['ws'])
 
-    def _gate(self, plan: Plan, blk, n, H, Wd, F_pl, M_pl) -> None:
-        hp = blk['planes']
-        gp = L.GatedDwConvParams()
-        gp.batch, gp.H, gp.W, gp.fmt, gp.i_planes, gp.n_segments = n, H, Wd, F_pl.fmt, blk['i_planes'], len(blk['segs'])
-        for s, (pl, kh, kw, wt, bt) in enumerate(blk['segs']):
-            gp.seg[s].planes, gp.seg[s].kh, gp.seg[s].kw = pl, kh, kw
-            gp.seg[s].weight, gp.seg[s].bias = wt.data_ptr(), bt.data_ptr()
-        F_pl.bind(gp, 'g')
-        F_pl.bind(gp, 'x', hp)
-        M_pl.bind(gp, 'out')
-        unit = 16 * (2 if F_pl.lo is not None else 1)
-        plan.launch('rsa_gated_dwconv', gp, meta=dict(kernel='rsa_gated_dwconv', flop=0, bytes=n * H * Wd * unit * 3 * hp))
-
-    def _bufs(self, plan: Plan, n, H, Wd, w, att, with_lo, cache):
-        key = (w, H, Wd, att)
-        if key in cache:
-            return cache[key]
-        hp = gate_layout(gate_groups(w, att))[3]
-        b = dict(norm=plan.planes(n, w // 8, H, Wd, with_lo, fmt=PF_BF16), fc1=plan.planes(n, 2 * hp, H, Wd, with_lo), gate=plan.planes(n, hp, H, Wd, with_lo))
-        if att:
-            b['qkv'], b['qkv2'], b['attn'] = plan.planes(n, 3 * w // 8, H, Wd, with_lo), plan.planes(n, 3 * w // 8, H, Wd, with_lo), plan.planes(n, w // 8, H, Wd, with_lo)
-            nbytes = int(L.load().rsa_gaterv3_attn_workspace_bytes(n, H, Wd, HEADS, w // HEADS))
-            if nbytes <= 0:
-                raise RuntimeError('rsa_gaterv3_attn_workspace_bytes refused the latent grid')
-            b['ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=plan.device)
-            plan.keep.append(b['ws'])
-        else:
-            b['local'], b['s'] = plan.planes(n, 2 * w // 8, H, Wd, with_lo), plan.planes(n, w // 8, H, Wd, with_lo)
-            nbytes = int(L.load().rsa_gaterv3_local_workspace_bytes(n, H, Wd, w))
-            if nbytes <= 0:
-                raise RuntimeError('rsa_gaterv3_local_workspace_bytes refused the grid')
-            b['ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=plan.device)
-            b['mid'], b['r'] = plan.f32map(n, w, H, Wd), plan.f32map(n, w, H, Wd)
-            plan.keep.append(b['ws'])
-        cache[key] = b
-        return b
-
-    def _gated_cnn(self, plan: Plan, blk, n, H, Wd, w, cur, bufs) -> Planes:
-        """norm -> fc1 -> (attention ->) gate of a GatedCNNBlock on the stream ``cur``; returns the planes fc2 reads."""
-        N_pl, F_pl, M_pl = bufs['norm'], bufs['fc1'], bufs['gate']
-        self._rmsnorm(plan, cur, n, H, Wd, w, blk['norm'], N_pl)
-        plan.conv(ops.conv_params(blk['fc1'], N_pl, H, Wd, out=F_pl))
-        if blk['att']:
-            cp, d = w // 8, w // HEADS
-            c0 = 2 * blk['planes'] - cp  # c's planes in fc1's output: [g | i | c]
-            Q, Q2, A, ws = bufs['qkv'], bufs['qkv2'], bufs['attn'], bufs['ws']
-            unit = 16 * (2 if Q.lo is not None else 1)
-            px = n * H * Wd
-            plan.conv(ops.conv_params(blk['qkv'], F_pl, H, Wd, in_plane0=c0, out=Q))
-            dp = L.DwConvParams()
-            dp.batch, dp.H, dp.W, dp.planes, dp.act, dp.fmt = n, H, Wd, 3 * cp, L.ACT_NONE, Q.fmt
-            Q.bind(dp, 'in')
-            dp.weight, dp.bias = blk['dw'][0].data_ptr(), blk['dw'][1].data_ptr()
-            Q2.bind(dp, 'out')
-            plan.launch('rsa_dwconv3x3', dp, meta=dict(kernel='rsa_dwconv3x3', flop=2 * px * 9 * 3 * w, bytes=px * 6 * cp * unit))
-            ap = LG3.AttnParams()
-            ap.batch, ap.H, ap.W, ap.C, ap.heads, ap.head_dim, ap.fmt = n, H, Wd, w, HEADS, d, Q2.fmt
-            Q2.bind(ap, 'qkv')
-            A.bind(ap, 'out')
-            ap.temperature, ap.workspace, ap.workspace_bytes = blk['temperature'].data_ptr(), ws.data_ptr(), ws.numel() * 4
-            chunks = (H * Wd + LG3.TOKEN_CHUNK - 1) // LG3.TOKEN_CHUNK
-            rec = 4 * HEADS * (d * d + 2 * d)
-            # byte model: q and k read once, a record per chunk written and read, A written and read, v read once, the output planes written
-            plan.launch('rsa_gaterv3_channel_attention', ap, kernels=3,
-                        meta=dict(kernel='rsa_gaterv3_channel_attention', flop=4 * px * w * d, bytes=px * 4 * cp * unit + n * (2 * chunks * rec + 8 * HEADS * d * d)))  # fmt: skip
-            plan.conv(ops.conv_params(blk['proj'], A, H, Wd, out=F_pl, out_plane_off=c0))
-        self._gate(plan, blk, n, H, Wd, F_pl, M_pl)
-        return M_pl
-
-    def _meta_gated(self, plan: Plan, blk, n, H, Wd, w, cur, nxt, bufs, stats, W, out: Planes | None) -> None:
-        N_pl, L_pl, S_pl, ws, mid, R = bufs['norm'], bufs['local'], bufs['s'], bufs['ws'], bufs['mid'], bufs['r']
-        self._rmsnorm(plan, cur, n, H, Wd, w, blk['lnorm'], N_pl)
-        plan.conv(ops.conv_params(blk['local1'], N_pl, H, Wd, out=L_pl))
-        unit = 16 * (2 if L_pl.lo is not None else 1)
-        px, pw = n * H * Wd, w // 8
-        tiles = ((H + LG3.TILE_H - 1) // LG3.TILE_H) * ((Wd + LG3.TILE_W - 1) // LG3.TILE_W)
-        gp = LG3.LocalGateParams()
-        gp.batch, gp.H, gp.W, gp.dim, gp.fmt = n, H, Wd, w, L_pl.fmt
-        L_pl.bind(gp, 'x')
-        S_pl.bind(gp, 'out')
-        gp.weight, gp.bias = blk['local2'][0].data_ptr(), blk['local2'][1].data_ptr()
-        gp.workspace, gp.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        # byte model: the 2 w / 8 input planes read once (the halo re-reads stay on chip), s written once, one record per tile
-        plan.launch('rsa_gaterv3_local_gate', gp, meta=dict(kernel='rsa_gaterv3_local_gate', flop=2 * px * (36 * 2 * w + w), bytes=px * 3 * pw * unit + n * tiles * w * 4))
-        sp = LG3.ScaApplyParams()
-        sp.batch, sp.H, sp.W, sp.dim, sp.fmt = n, H, Wd, w, S_pl.fmt
-        S_pl.bind(sp, 's')
-        sp.sca_w, sp.sca_b, sp.gamma0 = blk['sca'][0].data_ptr(), blk['sca'][1].data_ptr(), blk['gamma0'].data_ptr()
-        sp.short_f32, sp.out_f32 = cur.data_ptr(), mid.data_ptr()
-        sp.workspace, sp.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        plan.launch('rsa_gaterv3_sca_apply', sp, kernels=2,
-                    meta=dict(kernel='rsa_gaterv3_sca_apply', flop=2 * px * w + 2 * n * w * w, bytes=px * (pw * unit + 8 * w) + n * (tiles * w + w * w) * 4))  # fmt: skip
-        m = self._gated_cnn(plan, blk, n, H, Wd, w, mid, bufs)
-        plan.conv(ops.conv_params(blk['fc2'], m, H, Wd, act=L.ACT_MISH, out_f32=R))
-        plan.launch('rsa_group_norm_apply', plk.group_norm_apply_params(R, w, 1, stats, blk['gamma1'], W['zeros'], mid, out, nxt))
-
-    def _stage(self, plan: Plan, W, prefix, nb, n, H, Wd, w, cur, with_lo, cache, stats, out: Planes):
-        """``nb`` MetaGated blocks on the stream ``cur`` (left intact); the last one also writes ``out`` planes.  Returns the final stream."""
-        bufs = self._bufs(plan, n, H, Wd, w, False, with_lo, cache)
-        a, b = plan.f32map(n, w, H, Wd), plan.f32map(n, w, H, Wd)
-        for i in range(nb):
-            nxt = a if cur is not a else b
-            self._meta_gated(plan, W[f'{prefix}.{i}'], n, H, Wd, w, cur, nxt, bufs, stats, W, out if i == nb - 1 else None)
-            cur = nxt
-        return cur
+    def _mixer(self, plan: Plan, blk, n, H, Wd, w, F_pl: Planes, c0: int, bufs) -> None:
+        """The 16-head transposed attention on c's planes of fc1's output: qkv (1x1) -> rsa_dwconv3x3 -> rsa_gaterv3_channel_attention ->
+        project_out (1x1) written over c's planes."""
+        cp, d = w // 8, w // HEADS
+        Q, Q2, A, ws = bufs['qkv'], bufs['qkv2'], bufs['attn'], bufs['ws']
+        unit = 16 * (2 if Q.lo is not None else 1)
+        px = n * H * Wd
+        plan.conv(ops.conv_params(blk['qkv'], F_pl, H, Wd, in_plane0=c0, out=Q))
+        dp = L.DwConvParams()
+        dp.batch, dp.H, dp.W, dp.planes, dp.act, dp.fmt = n, H, Wd, 3 * cp, L.ACT_NONE, Q.fmt
+        Q.bind(dp, 'in')
+        dp.weight, dp.bias = blk['dw'][0].data_ptr(), blk['dw'][1].data_ptr()
+        Q2.bind(dp, 'out')
+        plan.launch('rsa_dwconv3x3', dp, meta=dict(kernel='rsa_dwconv3x3', flop=2 * px * 9 * 3 * w, bytes=px * 6 * cp * unit))
+        ap = LG3.AttnParams()
+        ap.batch, ap.H, ap.W, ap.C, ap.heads, ap.head_dim, ap.fmt = n, H, Wd, w, HEADS, d, Q2.fmt
+        Q2.bind(ap, 'qkv')
+        A.bind(ap, 'out')
+        ap.temperature, ap.workspace, ap.workspace_bytes = blk['temperature'].data_ptr(), ws.data_ptr(), ws.numel() * 4
+        chunks = (H * Wd + LG3.TOKEN_CHUNK - 1) // LG3.TOKEN_CHUNK
+        rec = 4 * HEADS * (d * d + 2 * d)
+        # byte model: q and k read once, a record per chunk written and read, A written and read, v read once, the output planes written
+        plan.launch('rsa_gaterv3_channel_attention', ap, kernels=3,
+                    meta=dict(kernel='rsa_gaterv3_channel_attention', flop=4 * px * w * d, bytes=px * 4 * cp * unit + n * (2 * chunks * rec + 8 * HEADS * d * d)))  # fmt: skip
+        plan.conv(ops.conv_params(blk['proj'], A, H, Wd, out=F_pl, out_plane_off=c0))
 
     def _build_plan(self, plan: Plan, W, x_shape, dtype, products):  # noqa: C901
         n, c, h0, w0 = x_shape
         if c != self.in_ch:
             raise RuntimeError(f'model expects {self.in_ch} input channels, got {c}')
-        P, s, dim, Lv = self.pad, self.scale, self.dim, self.levels
+        P, s, dim = self.pad, self.scale, self.dim
         Hp, Wp = h0 + (P - h0 % P) % P, w0 + (P - w0 % P) % P
         if Hp - h0 >= h0 or Wp - w0 >= w0:
             raise RuntimeError(f'Padding size should be less than the corresponding input dimension (a {h0}x{w0} input cannot be reflect-padded '
@@ -448,55 +306,14 @@ class GateRV3(OwnMetaUpsample, EngineModule):
         def set_input(x):
             ops.nchw_to_planes(x, x_pl)  # check_img_size's bottom / right reflect pad, fused
 
-        stats = torch.zeros((n, 1, 2), dtype=torch.float32, device=plan.device)
-        stats[..., 1] = 1.0
-        plan.keep.append(stats)
+        stats = unit_stats(plan, n)
         chain = _Chain(plan, W, n, Hp, Wp, dim, L.ACT_SILU, with_lo)
         cat_s = chain.new_cat()  # [x | sisr_end_conv | span_block0 | span_end's out1]
         x0 = plan.f32map(n, dim, Hp, Wp)
         plan.conv(ops.conv_params(W['in_to_dim'], x_pl, Hp, Wp, out=cat_s, out_f32=x0))
-        # encoder: level j's last block writes the second half of the decoder's concatenation buffer of that level
-        cats, cur, H, Wd = [], x0, Hp, Wp
-        for j, nb in enumerate(self.enc_blocks):
-            w = dim << j
-            cat = plan.planes(n, 2 * w // 8, H, Wd, with_lo)  # [decode's upsampled output (w) | this level's skip (w)]
-            cats.append(cat)
-            self._stage(plan, W, f'gater_encode.{j}.gated', nb, n, H, Wd, w, cur, with_lo, cache, stats, _view(cat, w // 8, w // 8))
-            t = plan.f32map(n, w // 2, H, Wd)
-            nxt = plan.f32map(n, 2 * w, H // 2, Wd // 2)
-            plan.conv(ops.conv_params(W[f'gater_encode.{j}.scale.0'], cat, H, Wd, in_plane0=w // 8, out_f32=t))
-            plan.launch('rsa_pixel_unshuffle2', dict(x_f32=t, batch=n, H=H, W=Wd, C=w // 2, out_f32=nxt),
-                        meta=dict(kernel='rsa_pixel_unshuffle2', flop=0, bytes=2 * n * H * Wd * 2 * w))  # fmt: skip
-            cur, H, Wd = nxt, H // 2, Wd // 2
-        # latent: GatedCNNBlocks without a residual
-        wl = dim << Lv
-        bufs = self._bufs(plan, n, H, Wd, wl, self.attention, with_lo, cache)
-        la, lb = plan.f32map(n, wl, H, Wd), plan.f32map(n, wl, H, Wd)
-        prev = plan.planes(n, wl // 8, H, Wd, with_lo)
-        for i in range(self.num_latent):
-            blk = W[f'latent.{i}']
-            m = self._gated_cnn(plan, blk, n, H, Wd, wl, cur, bufs)
-            nxt = la if cur is not la else lb
-            last = i == self.num_latent - 1
-            plan.conv(ops.conv_params(blk['fc2'], m, H, Wd, act=L.ACT_MISH, out=prev if last else None, out_f32=None if last else nxt))
-            cur = nxt
-        # decoder
-        for i, nb in enumerate(self.dec_blocks):
-            wb = dim << (Lv - i)
-            w = wb // 2
-            cat = cats[Lv - 1 - i]
-            shuffled = torch.empty((n, w, 2 * H, 2 * Wd), dtype=torch.float32, device=plan.device)
-            plan.keep.append(shuffled)
-            plan.conv(ops.conv_params(W[f'decode.{i}.scale.0'], prev, H, Wd, out_nchw=shuffled, pixel_shuffle=2))
-            H, Wd = 2 * H, 2 * Wd
-            half = _view(cat, 0, w // 8)
-            plan.call(lambda src=shuffled, dst=half: ops.nchw_to_planes(src, dst))
-            plan.count_launches(1)
-            sd_ = plan.f32map(n, w, H, Wd)
-            plan.conv(ops.conv_params(W[f'decode.{i}.shor'], cat, H, Wd, out_f32=sd_))
-            last = i == Lv - 1
-            prev = None if last else plan.planes(n, w // 8, H, Wd, with_lo)
-            cur = self._stage(plan, W, f'decode.{i}.gated', nb, n, H, Wd, w, sd_, with_lo, cache, stats, prev)
+        cats, cur, H, Wd = self._encoder(plan, W, 'gater_encode', n, Hp, Wp, x0, with_lo, cache, stats)
+        prev = self._latent(plan, W, n, H, Wd, cur, self.attention, with_lo, cache)
+        cur = self._decoder(plan, W, n, H, Wd, prev, cats, with_lo, cache, stats)
         # the SPAN branch on in_to_dim's output; its last 1x1 adds the decoder's stream: x + sisr, the planes the head reads
         fe = plan.planes(n, pd, Hp, Wp, with_lo)
         fe32 = plan.f32map(n, dim, Hp, Wp) if self.up is not None and self.up.needs_f32_input(W) else None

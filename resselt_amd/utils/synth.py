@@ -1819,3 +1819,53 @@ def gaterv3_state_dict(in_ch=3, dim=32, enc_blocks=(2, 2, 4, 8), dec_blocks=(2, 
             sd[key] = buffers[key]
         fill(name, shape, 0.1 if last in name else (0.5 if '.offset.' in name else 1.0))
     return sd
+
+
+def gaterv2_state_dict(in_ch=3, dim=48, enc_blocks=(2, 2, 4, 6), dec_blocks=(2, 2, 2, 2), num_latent=10, scale=1, upsample='pixelshuffledirect',
+                       upsample_mid_dim=32, seed=0):  # fmt: skip
+    """Keys of the reference GateRV2 module (archs/gaterv2/arch.py:394-470) in the order of its ``state_dict()``: the trunk, then at scale 1
+    the plain ``dim_to_in`` convolution, above it ``short_to_dim`` (the ConvBlock: block.0, block.2, conv11) and ``upsample`` (UniUpsample
+    v1: the MetaUpsample buffer first, DySample's ``init_pos`` before its convolutions).
+    The value distributions are ``gaterv3_state_dict``'s: matrices and filters uniform with variance 1 / fan_in, norm scales in 0.5..1.5,
+    offsets in +-0.1, biases in +-0.09 (the q / k / v biases included, so that no token's query or key vector is zero), ``gamma0`` /
+    ``gamma1`` in +-0.5 per channel, the last convolution at a tenth of the bound."""
+    from ..archs.gaterv2.arch import trunk_shapes
+    from ..engine.uniupsample import Head
+
+    sd: OrderedDict = OrderedDict()
+    g = float(np.sqrt(3.0))
+
+    def fill(name, shape, gain=1.0):
+        leaf = name.rsplit('.', 1)[-1]
+        if leaf in ('gamma0', 'gamma1'):
+            sd[name] = synth_tensor(name, shape, 1, seed, 0.5)
+        elif leaf == 'scale' and len(shape) == 1:
+            sd[name] = 1.0 + synth_tensor(name, shape, 1, seed, 0.5)
+        elif leaf == 'offset':
+            sd[name] = synth_tensor(name, shape, 1, seed, 0.1)
+        elif leaf == 'bias':
+            sd[name] = synth_tensor(name, shape, 1, seed, 0.05 * g * gain)
+        else:
+            sd[name] = synth_tensor(name, shape, int(np.prod(shape[1:])), seed, g * gain)
+
+    for name, shape in trunk_shapes(in_ch, dim, tuple(enc_blocks), tuple(dec_blocks), num_latent).items():
+        fill(name, shape)
+    if scale == 1:
+        fill('dim_to_in.weight', (in_ch, dim, 3, 3), 0.1)
+        fill('dim_to_in.bias', (in_ch,), 0.1)
+        return sd
+    for name, co, ci, k in (('short_to_dim.block.0', dim, in_ch, 3), ('short_to_dim.block.2', dim, dim, 3), ('short_to_dim.conv11', dim, in_ch, 1)):
+        fill(f'{name}.weight', (co, ci, k, k))
+        fill(f'{name}.bias', (co,))
+    head = Head('upsample', upsample, scale, dim, in_ch, dim if upsample == 'dysample' else upsample_mid_dim, version=1, meta_mid_dim=upsample_mid_dim)
+    shapes, buffers = {}, {}
+    head.shapes(shapes, buffers)
+    sd['upsample.MetaUpsample'] = buffers['upsample.MetaUpsample']
+    last = f'upsample.{head.layers[-1][0]}.' if head.dys_index is None else '.end_conv.'
+    pos = [k for k in buffers if k.endswith('init_pos')]
+    for name, shape in shapes.items():
+        if pos and head.dys_index is not None:
+            key = pos.pop()
+            sd[key] = buffers[key]
+        fill(name, shape, 0.1 if last in name else (0.5 if '.offset.' in name else 1.0))
+    return sd

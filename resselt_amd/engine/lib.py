@@ -47,7 +47,7 @@ def _plane_fields(prefix: str) -> list:
     return _ptr(f'{prefix}_hi', f'{prefix}_lo') + _i64(f'{prefix}_plane_stride', f'{prefix}_batch_stride')
 
 
-# Mirrors of the descriptors in include/resselt_amd.h: field order and types are the ABI (tests/test_pack_and_capi.py compares every one of
+# Mirrors of the descriptors in include/resselt_amd.h: field order and types are the ABI (tests/test_capi_headers.py compares every one of
 # them with the header).
 class ConvParams(C.Structure):
     """Mirror of ``struct rsa_conv_params`` (include/resselt_amd.h); field order is the ABI."""
@@ -368,7 +368,7 @@ def _descriptor(struct) -> tuple:
 
 # Every entry point include/resselt_amd.h declares: name -> (restype, [(parameter name, ctype), ...]), the header's names in the header's
 # order, the trailing ``void* stream`` included.  ``load()`` sets argtypes / restype from it, ``bind`` resolves keyword arguments against
-# it, and tests/test_capi_signatures.py compares every row with its prototype.  A new entry point = its prototype there + its row here.
+# it, and tests/test_capi_headers.py compares every row with its prototype.  A new entry point = its prototype there + its row here.
 SIGNATURES = {
     'rsa_conv2d': _descriptor(ConvParams),
     'rsa_conv2d_list': (C.c_int, _conv('list') + _i32('n') + _ptr('stream')),
@@ -478,12 +478,16 @@ SIGNATURES = {
     'rsa_last_error_string': (C.c_char_p, []),
 }
 
-EXPORTS = tuple(SIGNATURES)  # every symbol the header declares (tests/test_pack_and_capi.py)
+EXPORTS = tuple(SIGNATURES)  # every symbol the header declares
 
 # Entry points of the same library that a header of their own declares beside include/resselt_amd.h (include/resselt_amd_<family>.h), with
-# their mirrors and rows in engine/lib_<family>.py: name -> row, as in SIGNATURES.  ``extend`` adds them; ``load`` demands and types them
+# their mirrors and rows in an engine/lib_<family>.py: name -> row, as in SIGNATURES.  ``extend`` adds them; ``load`` demands and types them
 # like the rows above, and ``launch`` / ``invoke`` reach them by name.
 EXTENSIONS: dict = {}
+
+# Every header under include/ -> the rows table that mirrors it, extensions in registration order (tests/test_capi_headers.py compares
+# each table, and the mirrors of the module that holds it, with its header).
+HEADERS: dict = {'resselt_amd.h': SIGNATURES}
 
 
 def _declare(lib, rows: dict) -> None:
@@ -494,11 +498,14 @@ def _declare(lib, rows: dict) -> None:
         getattr(lib, name).restype = restype
 
 
-def extend(rows: dict) -> None:
-    """Register the signature rows of an extension header (once, at the import of its engine/lib_<family>.py)."""
-    clash = [name for name in rows if name in SIGNATURES]
+def extend(rows: dict, header: str) -> None:
+    """Register the signature rows of extension header ``header`` (its file name under include/; once, at the import of its
+    engine/lib_<family>.py).  A name that another header's table already holds raises ``ValueError``, and nothing is registered."""
+    owner = {name: h for h, table in HEADERS.items() if h != header for name in table}
+    clash = [name for name in rows if name in owner]
     if clash:
-        raise ValueError(f'{clash} are entry points of include/resselt_amd.h')
+        raise ValueError(f'{clash} are entry points of include/{owner[clash[0]]}')
+    HEADERS[header] = rows
     EXTENSIONS.update(rows)
     if _lib is not None:
         _declare(_lib, rows)
@@ -545,13 +552,8 @@ def load() -> C.CDLL:
         )
     _warn_if_stale(path)
     lib = C.CDLL(path)
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise RuntimeError(f'{path} does not export {name}; rebuild the library')
-    for name, (restype, params) in SIGNATURES.items():
-        getattr(lib, name).argtypes = [ctype for _, ctype in params]
-        getattr(lib, name).restype = restype
-    _declare(lib, EXTENSIONS)
+    for rows in HEADERS.values():
+        _declare(lib, rows)
     _lib = lib
     return lib
 

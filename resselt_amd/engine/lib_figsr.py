@@ -2,7 +2,7 @@
 ``rsa_figsr_input``, ``rsa_figsr_output``; csrc/figsr.hip), registered with ``lib.extend``, and the host-side packing of
 ``rsa_figsr_mix``'s band weights (beside ``engine/plk.py``'s ``pack_plk_weights``, whose lane layout it shares).
 
-Field order and types are the ABI; tests/test_figsr_capi.py compares the mirrors and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirrors and the rows with the header.
 """
 
 from __future__ import annotations
@@ -43,7 +43,7 @@ SIGNATURES = {
     'rsa_figsr_output': L._descriptor(FigsrOutputParams),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_figsr.h')
 
 
 def pack_band_weights(w_w: torch.Tensor, w_h: torch.Tensor, products: int, fmt: int) -> torch.Tensor:

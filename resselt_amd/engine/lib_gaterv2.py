@@ -1,7 +1,7 @@
 """ctypes mirror and signature rows of include/resselt_amd_gaterv2.h (``rsa_gaterv2_linear_attention`` and its workspace size;
 csrc/gaterv2.hip), registered with ``lib.extend``.
 
-Field order and types are the ABI; tests/test_gaterv2_capi.py compares the mirror and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirror and the rows with the header.
 """
 
 from __future__ import annotations
@@ -27,7 +27,7 @@ SIGNATURES = {
     'rsa_gaterv2_linear_attention': L._descriptor(AttnParams),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_gaterv2.h')
 
 
 def record_floats(c: int, m: int) -> int:

@@ -1,7 +1,7 @@
 """ctypes mirrors and signature rows of include/resselt_amd_gaterv3.h (``rsa_gaterv3_local_gate``, ``rsa_gaterv3_sca_apply``,
 ``rsa_gaterv3_channel_attention``, ``rsa_gaterv3_shortcut`` and the two workspace sizes; csrc/gaterv3.hip), registered with ``lib.extend``.
 
-Field order and types are the ABI; tests/test_gaterv3_capi.py compares the mirrors and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirrors and the rows with the header.
 """
 
 from __future__ import annotations
@@ -56,4 +56,4 @@ SIGNATURES = {
     'rsa_gaterv3_shortcut': L._descriptor(ShortcutParams),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_gaterv3.h')

@@ -2,7 +2,7 @@
 ``rsa_gfisr_spectral``, ``rsa_gfisr_gate``; csrc/gfisr.hip and csrc/mosr.hip), registered with ``lib.extend``, and the host-side builder of
 the DFT tables ``rsa_gfisr_dft`` multiplies with.
 
-Field order and types are the ABI; tests/test_gfisrv2_capi.py compares the mirrors and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirrors and the rows with the header.
 """
 
 from __future__ import annotations
@@ -37,7 +37,7 @@ SIGNATURES = {
     'rsa_gfisr_gate': (C.c_int, [('p', C.POINTER(L.GatedDwConvParams))] + L._i32('act') + L._ptr('stream')),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_gfisr.h')
 
 
 def _angles(a: np.ndarray, b: np.ndarray, n: int) -> np.ndarray:

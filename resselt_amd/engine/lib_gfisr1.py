@@ -1,7 +1,7 @@
 """ctypes mirrors and signature rows of include/resselt_amd_gfisr1.h (``rsa_gfisr_ln_spectral``, ``rsa_plane_window``; csrc/gfisr1.hip),
 registered with ``lib.extend``.
 
-Field order and types are the ABI; tests/test_gfisr_capi.py compares the mirrors and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirrors and the rows with the header.
 """
 
 from __future__ import annotations
@@ -31,4 +31,4 @@ SIGNATURES = {
     'rsa_plane_window': L._descriptor(PlaneWindowParams),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_gfisr1.h')

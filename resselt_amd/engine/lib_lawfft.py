@@ -2,7 +2,7 @@
 ``rsa_lawfft_norm_mul``, ``rsa_lawfft_kernel_gen``, ``rsa_lawfft_kernel_gen_workspace_bytes``, ``rsa_lawfft_dyn_dwconv``;
 csrc/lawfft.hip), registered with ``lib.extend``, and the host-side layout of the kernel generator's two matrices.
 
-Field order and types are the ABI; tests/test_lawfft_capi.py compares the mirrors and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirrors and the rows with the header.
 """
 
 from __future__ import annotations
@@ -65,7 +65,7 @@ SIGNATURES = {
     'rsa_lawfft_dyn_dwconv': L._descriptor(LawfftDynDwConvParams),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_lawfft.h')
 
 
 def pack_kernel_gen(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor):

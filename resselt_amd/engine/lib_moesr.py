@@ -1,6 +1,6 @@
 """ctypes mirror and signature row of include/resselt_amd_moesr.h (``rsa_moesr_stream``, csrc/moesr.hip), registered with ``lib.extend``.
 
-Field order and types are the ABI; tests/test_moesr_capi.py compares the mirror and the row with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirror and the row with the header.
 """
 
 from __future__ import annotations
@@ -21,4 +21,4 @@ class MoesrStreamParams(C.Structure):
 
 SIGNATURES = {'rsa_moesr_stream': L._descriptor(MoesrStreamParams)}
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_moesr.h')

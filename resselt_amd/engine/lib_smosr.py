@@ -1,7 +1,7 @@
 """ctypes mirrors and signature rows of include/resselt_amd_smosr.h (``rsa_smosr_gate``, ``rsa_smosr_pad``, ``rsa_smosr_pa``;
 csrc/smosr.hip), registered with ``lib.extend``, and the host-side packing of ``rsa_smosr_pa``'s weight fragments.
 
-Field order and types are the ABI; tests/test_smosr_capi.py compares the mirrors and the rows with the header.
+Field order and types are the ABI; tests/test_capi_headers.py compares the mirrors and the rows with the header.
 """
 
 from __future__ import annotations
@@ -42,7 +42,7 @@ SIGNATURES = {
     'rsa_smosr_pa': L._descriptor(SmosrPaParams),
 }
 
-L.extend(SIGNATURES)
+L.extend(SIGNATURES, 'resselt_amd_smosr.h')
 
 
 def pack_pa_weights(w: torch.Tensor, b: torch.Tensor, products: int, fmt: int, device) -> tuple[torch.Tensor, torch.Tensor]:

@@ -1,100 +1,13 @@
-"""``lib.SIGNATURES`` against the prototypes of include/resselt_amd.h, and the keyword binder built on it (reads the header and the table
-only: neither the library nor a GPU)."""
+"""The keyword binder built on ``lib.SIGNATURES`` (reads the table only: neither the library nor a GPU).  tests/test_capi_headers.py compares
+the table with the prototypes of include/resselt_amd.h."""
 
-import copy
 import ctypes
-import os
-import re
 
 import pytest
 
 from resselt_amd.engine import lib as L
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def _header():
-    return open(os.path.join(ROOT, 'include', 'resselt_amd.h')).read()
-
-
-def _header_prototypes():
-    """{entry point: (return class, [(parameter, type class)])} of every prototype in the header.  Type classes: 'i32' (int32_t, int, an
-    enum), 'i64', 'f32', 'cstr' (char*), 'ptr' (any other pointer), or the name of the ``rsa_*_params`` struct a pointer points to."""
-    text = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', _header(), flags=re.S))
-    text = re.sub(r'typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;', '', text, flags=re.S)  # (the struct bodies have their own test)
-
-    def type_class(decl: str) -> str:
-        words = decl.replace('*', ' * ').split()
-        base = [w for w in words if w not in ('const', '*', 'struct', 'enum')]
-        assert len(base) == 1, decl
-        if '*' in words:
-            return 'cstr' if base[0] == 'char' else base[0] if re.fullmatch(r'rsa_\w+_params', base[0]) else 'ptr'
-        return 'i32' if 'enum' in words else {'int': 'i32', 'int32_t': 'i32', 'int64_t': 'i64', 'float': 'f32'}[base[0]]
-
-    out = {}
-    for ret, name, params in re.findall(r'((?:const\s+)?\w+\s*\*?)\s*(rsa_\w+)\s*\(([^)]*)\)\s*;', text):
-        assert name not in out, f'{name} is declared twice'
-        plist = []
-        if params.strip() not in ('', 'void'):
-            for p in params.split(','):
-                m = re.fullmatch(r'(.*?)(\w+)', p.strip(), flags=re.S)
-                assert m, f'{name}: cannot parse {p!r}'
-                plist.append((m.group(2), type_class(m.group(1))))
-        out[name] = (type_class(ret), plist)
-    return out
-
-
-def _struct_names():
-    """ctypes mirror -> the ``struct rsa_*`` its docstring cites."""
-    return {v: re.search(r'struct (rsa_\w+)', v.__doc__).group(1) for v in vars(L).values()
-            if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}  # fmt: skip
-
-
-def _table_prototypes(table):
-    """The same shape for a ``SIGNATURES``-like table."""
-    classes = {ctypes.c_int32: 'i32', ctypes.c_int64: 'i64', ctypes.c_float: 'f32', ctypes.c_void_p: 'ptr', ctypes.c_char_p: 'cstr'}
-    structs = _struct_names()
-
-    def type_class(t):
-        return classes[t] if t in classes else structs[t._type_]
-
-    return {name: (type_class(restype), [(k, type_class(t)) for k, t in params]) for name, (restype, params) in table.items()}
-
-
-def _mismatches(table):
-    header, mirror = _header_prototypes(), _table_prototypes(table)
-    bad = [f'{name}: only in the {"header" if name in header else "table"}' for name in sorted(set(header) ^ set(mirror))]
-    return bad + [f'{name}: header {header[name]} != table {mirror[name]}' for name in sorted(set(header) & set(mirror)) if header[name] != mirror[name]]
-
-
-def test_every_prototype_matches_the_signature_table():
-    header = _header_prototypes()
-    # the looser regex of test_library_exports_every_declared_symbol sees the same names: the parser skipped no multi-line prototype
-    declared = set(re.findall(r'^\s*(?:const\s+)?(?:int|int64_t|char\s*\*|void)\s*\*?\s*(rsa_\w+)\s*\(', _header(), flags=re.M))
-    assert set(header) == declared == set(L.SIGNATURES) == set(L.EXPORTS)
-    assert len(header) == 106
-    assert ctypes.c_int is ctypes.c_int32  # status returns are declared `int`
-    assert _mismatches(L.SIGNATURES) == []
-    print(f'{len(header)} prototypes matched')
-
-
-def test_the_comparison_rejects_a_dropped_argument_and_swapped_names():
-    """One ``i32`` less in one row shifts every later argument; two names swapped in another reorder two equal-typed arguments: neither
-    shows at import, both must show here.  (On a copy: the table itself is not touched.)"""
-    table = copy.deepcopy(L.SIGNATURES)
-    restype, params = table['rsa_rha_gate']
-    i = [k for k, _ in params].index('i_planes')
-    table['rsa_rha_gate'] = (restype, params[:i] + params[i + 1 :])
-    restype, params = table['rsa_scale_add']
-    names = [k for k, _ in params]
-    a, b = names.index('res'), names.index('gamma')
-    params[a], params[b] = params[b], params[a]
-    bad = _mismatches(table)
-    assert len(bad) == 2 and bad[0].startswith('rsa_rha_gate:') and bad[1].startswith('rsa_scale_add:')
-    assert _mismatches(L.SIGNATURES) == []
-
-
-# ---- the binder ----
 class _FakePlanes:
     """What ``bind`` reads of a ``Planes`` buffer: 100 bytes per plane, lo halves 5000 bytes behind the hi halves (or none)."""
 

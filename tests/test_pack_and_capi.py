@@ -1,16 +1,13 @@
-"""Host logic around the C-ABI: weight packing layout, library symbols, descriptor validation (no GPU compute)."""
+"""Host logic around the C-ABI: weight packing layout, kernel choice, descriptor validation (no GPU compute).  The header itself is compared
+with its ctypes description in tests/test_capi_headers.py."""
 
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from resselt_amd.engine import lib as L
 from resselt_amd.engine import pack, tensors
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bf16(x):
@@ -46,72 +43,6 @@ def test_packed_bytes_agree_with_library():
             n *= s
         assert lib.rsa_packed_weight_bytes(cout, planes, k, prod) == 2 * n
     assert lib.rsa_packed_weight_bytes(0, 1, 3, 3) < 0 and lib.rsa_packed_weight_bytes(8, 1, 2, 3) < 0
-
-
-def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, 'include', 'resselt_amd.h')).read()
-    declared = set(re.findall(r'^\s*(?:const\s+)?(?:int|int64_t|char\s*\*|void)\s*\*?\s*(rsa_\w+)\s*\(', header, flags=re.M))
-    assert declared, 'no prototypes parsed from the header'
-    assert declared == set(L.EXPORTS), (declared ^ set(L.EXPORTS))
-    lib = ctypes.CDLL(L.lib_path())
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert L.load().rsa_version() == 400
-
-
-def _header_structs():
-    """{struct name: [(field, type class)]} of every ``typedef struct rsa_* { ... } rsa_*;`` in the header; the type class is 'int32_t',
-    'int64_t', 'float', 'pointer', or ('array', element struct, length)."""
-    header = open(os.path.join(ROOT, 'include', 'resselt_amd.h')).read()
-    header = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', header, flags=re.S))
-    out = {}
-    for name, body, closing in re.findall(r'typedef\s+struct\s+(rsa_\w+)\s*\{(.*?)\}\s*(\w+)\s*;', header, flags=re.S):
-        assert closing == name
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(';'))):
-            m = re.fullmatch(r'(?:const\s+)?(\w+)\b(.*)', decl, flags=re.S)
-            assert m, f'{name}: cannot parse {decl!r}'
-            ctype, rest = m.group(1), m.group(2)
-            for item in rest.split(','):
-                item = item.strip()
-                arr = re.fullmatch(r'(\w+)\s*\[\s*(\d+)\s*\]', item)
-                if arr:
-                    fields.append((arr.group(1), ('array', ctype, int(arr.group(2)))))
-                elif '*' in item:
-                    fields.append((item.replace('*', '').strip(), 'pointer'))
-                else:
-                    assert ctype in ('int32_t', 'int64_t', 'float') and re.fullmatch(r'\w+', item), f'{name}: cannot parse {decl!r}'
-                    fields.append((item, ctype))
-        out[name] = fields
-    return out
-
-
-def _mirror_structs():
-    """The same table for the ctypes mirrors in engine/lib.py, named by the ``struct rsa_*`` their docstrings cite."""
-    classes = {ctypes.c_int32: 'int32_t', ctypes.c_int64: 'int64_t', ctypes.c_float: 'float', ctypes.c_void_p: 'pointer'}
-    mirrors = [v for v in vars(L).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure]
-    c_name = {cls: re.search(r'struct (rsa_\w+)', cls.__doc__).group(1) for cls in mirrors}
-    out = {}
-    for cls in mirrors:
-        fields = []
-        for fname, ftype in cls._fields_:
-            if issubclass(ftype, ctypes.Array):
-                fields.append((fname, ('array', c_name[ftype._type_], ftype._length_)))
-            else:
-                fields.append(('in' if fname == 'in_' else fname, classes[ftype]))  # `in` is a Python keyword
-        assert c_name[cls] not in out, f'two mirrors of {c_name[cls]}'
-        out[c_name[cls]] = fields
-    return out
-
-
-def test_every_struct_matches_header_fields_and_types():
-    """Every descriptor of the C-ABI against its ctypes mirror: the same structs, the same field names in the same order, the same type
-    class.  (Reads the header and the mirrors only: neither the library nor a GPU.)"""
-    header, mirror = _header_structs(), _mirror_structs()
-    assert sorted(header) == sorted(mirror)
-    assert len(header) == 37 and 'rsa_conv_params' in header
-    for name in header:
-        assert mirror[name] == header[name], name
 
 
 def test_cout_tile_choice():

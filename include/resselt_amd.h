@@ -187,7 +187,9 @@ int rsa_conv2d_list(const rsa_conv_params* list, int32_t n, void* stream);
  * (b's last 32 input channels never leave the chip before b has used them; a's output is still written for the later layers); the result
  * is bit-identical to rsa_conv2d(a) followed by rsa_conv2d(b).  rsa_conv2d_list fuses such neighbours by itself unless RSA_CONV_PAIR=0
  * is set in the environment.  rsa_conv_pair_fusable: 1 when the list would fuse (a, b), else 0.  rsa_conv2d_pair on anything else:
- * RSA_E_UNSUPPORTED.  Both descriptors carry their own packed weights (layout 1), exactly as for separate launches. */
+ * RSA_E_UNSUPPORTED.  Both descriptors carry their own packed weights (layout 1), exactly as for separate launches.
+ * A fused launch is ONE sweep over the map: it walks its tiles in the direction of its FIRST descriptor (a.tile_order; b.tile_order is not
+ * looked at).  A caller that alternates tile_order alternates it per launch, giving both halves of a fusable pair the same value. */
 int rsa_conv2d_pair(const rsa_conv_params* a, const rsa_conv_params* b, void* stream);
 int rsa_conv_pair_fusable(const rsa_conv_params* a, const rsa_conv_params* b);
 

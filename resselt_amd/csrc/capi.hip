@@ -177,6 +177,22 @@ static unsigned grid_for(int64_t total, int block) {
 
 }  // namespace rsa
 
+// The launches a descriptor list becomes, in order: visit(i, fused) per launch, i = its first descriptor, fused = descriptors i and i + 1 run
+// as ONE launch (cross-layer fusion: two consecutive growth convolutions of a residual dense block, conv_ring_pair.h).  The walk ends at the
+// first status other than RSA_OK.  rsa_conv2d_list and rsa_conv2d_list_assign_tile_order both walk with it: what one launches together is what
+// the other gives one sweep direction.
+template <class Visit>
+static int for_each_launch(const rsa_conv_params* list, int32_t n, Visit visit) {
+  const bool fuse = rsa::conv_pair_enabled();
+  for (int32_t i = 0; i < n; ++i) {
+    const bool fused = fuse && i + 1 < n && rsa::conv_pair_eligible(list[i], list[i + 1]);
+    const int rc = visit(i, fused);
+    if (rc != RSA_OK) return rc;
+    if (fused) ++i;
+  }
+  return RSA_OK;
+}
+
 extern "C" {
 
 int rsa_version(void) { return RSA_VERSION; }
@@ -197,22 +213,37 @@ static int list_error(int rc, int i) {
 
 int rsa_conv2d_list(const rsa_conv_params* list, int32_t n, void* stream) {
   if (list == nullptr || n < 0) return rsa::set_error(RSA_E_ARG, "rsa_conv2d_list: null list");
-  const bool fuse = rsa::conv_pair_enabled();
-  for (int32_t i = 0; i < n; ++i) {
-    // cross-layer fusion: two consecutive growth convolutions of a residual dense block run as ONE launch (conv_ring_pair.h)
-    if (fuse && i + 1 < n && rsa::conv_pair_eligible(list[i], list[i + 1])) {
+  return for_each_launch(list, n, [&](int32_t i, bool fused) {
+    if (fused) {
       int rc = rsa::conv_validate(list[i]);
       if (rc != RSA_OK) return list_error(rc, i);
       rc = rsa::conv_validate(list[i + 1]);
       if (rc != RSA_OK) return list_error(rc, i + 1);
-      rc = rsa::conv_launch_pair(list[i], list[i + 1], (hipStream_t)stream);
+      rc = rsa::conv_launch_pair(list[i], list[i + 1], (hipStream_t)stream);  // sweeps in the direction of list[i]
       if (rc != 0) return list_error(rsa::set_error(rc, "conv: pair kernel launch failed"), i);
-      ++i;
-      continue;
+      return (int)RSA_OK;
     }
     const int rc = rsa::conv_launch(list[i], (hipStream_t)stream);
-    if (rc != RSA_OK) return list_error(rc, i);
-  }
+    return rc != RSA_OK ? list_error(rc, i) : (int)RSA_OK;
+  });
+}
+
+// Serpentine order per LAUNCH.  rsa_conv_params.tile_order alternates between consecutive layers so that a layer starts on the rows its
+// producer wrote last; a fused pair is one launch and sweeps in the direction of its first descriptor, so only the list launcher knows which
+// neighbours share a direction.  Host only, launches nothing: writes (first_order + k) & 1 into every descriptor of launch k of the list (both
+// halves of a fused pair get the pair's order) and stores the order launch n_launches would get in *next_order (may be NULL), for the caller's
+// next list.  A list without a fusable pair gets strict per-descriptor alternation.  RSA_E_ARG for a NULL list, n < 0, or first_order not 0 / 1.
+int rsa_conv2d_list_assign_tile_order(rsa_conv_params* list, int32_t n, int32_t first_order, int32_t* next_order) {
+  if (list == nullptr || n < 0) return rsa::set_error(RSA_E_ARG, "rsa_conv2d_list_assign_tile_order: null list");
+  if (first_order != 0 && first_order != 1) return rsa::set_error(RSA_E_ARG, "rsa_conv2d_list_assign_tile_order: first_order must be 0 or 1");
+  int32_t order = first_order;
+  for_each_launch(list, n, [&](int32_t i, bool fused) {
+    list[i].tile_order = order;
+    if (fused) list[i + 1].tile_order = order;
+    order ^= 1;
+    return (int)RSA_OK;
+  });
+  if (next_order != nullptr) *next_order = order;
   return RSA_OK;
 }
 

@@ -18,6 +18,7 @@ bool conv_pair_enabled() {
   return (o < 0 ? on : o != 0) && conv_ring_enabled();
 }
 
+// One launch, one sweep: the pair walks its tiles in the direction of its first descriptor (a.tile_order; b's is not looked at).
 int conv_launch_pair(const rsa_conv_params& a, const rsa_conv_params& b, hipStream_t stream) {
   using G = PairGeo;
   PairParams p;

@@ -32,6 +32,7 @@ PRECISIONS = {'bf16x3': (3, PF_BF16), 'bf16': (1, PF_BF16), 'fp16': (1, PF_F16),
 import os as _os
 
 _SERPENTINE = _os.environ.get('RSA_SERPENTINE', '1') != '0'
+_SERPENTINE_PER_LAUNCH = _os.environ.get('RSA_SERPENTINE', '1') != 'desc'  # 'desc': alternate per descriptor, as before the fused pair (A/B runs)
 
 
 class Prec(int):
@@ -97,11 +98,15 @@ class Plan:
         self.kernel_calls: list = []  # (meta, closure) of the non-convolution launches that carry a price tag (see ``call``)
         self.conv_cin: list = []  # per array: the layers' true input channel counts (a descriptor only knows planes of 8)
         self._pending_cin: list = []
-        # Serpentine layer order: every other convolution walks its output tiles bottom-up (``rsa_conv_params.tile_order``), so a layer
-        # starts on the rows its producer wrote last, which are still in the 256 MB Infinity Cache (ring schedule only; RSA_SERPENTINE=0
-        # switches it off for A/B runs).  Measured on RRDBNet-23 at 1080p: 101.0 -> 97.8 ms per frame (profiles/r03_c_*).
+        # Serpentine layer order: every other convolution LAUNCH walks its output tiles bottom-up (``rsa_conv_params.tile_order``), so a
+        # launch starts on the rows its producer wrote last, which are still in the 256 MB Infinity Cache (ring schedule only).  ``conv``
+        # alternates per descriptor; ``flush`` lets the library, which alone knows which neighbours ``rsa_conv2d_list`` fuses into one
+        # launch, re-assign the orders per launch (a list without a fusable pair keeps what ``conv`` set).  RSA_SERPENTINE=0 switches it
+        # off, RSA_SERPENTINE=desc keeps the per-descriptor orders (A/B runs).  Measured on RRDBNet-23 at 1080p, before the fused pair
+        # existed: 101.0 -> 97.8 ms per frame (profiles/r03_c_*); per launch against per descriptor: profiles/launch_order_*.
         self.serpentine = True
         self._n_conv = 0
+        self._launch_order = 0  # tile order of the next convolution launch (``flush``)
         # the forward's output and the caller's input (``output`` / ``input_ref``): the tensor currently held, the address of the placeholder the
         # descriptors were built against, and the (container, key, byte offset) of every pointer field or pointer argument into it
         self._y = self._x = None
@@ -197,6 +202,8 @@ class Plan:
         if not self._pending:
             return None
         arr = (L.ConvParams * len(self._pending))(*self._pending)
+        if self.serpentine and _SERPENTINE and _SERPENTINE_PER_LAUNCH:
+            self._launch_order = L.conv_list_assign_tile_order(arr, self._launch_order)
         for p in arr:
             self._bind(p, _CONV_POINTERS)
         self._n_launches = getattr(self, '_n_launches', 0) + len(self._pending)
@@ -212,6 +219,15 @@ class Plan:
         step._rsa_conv = (arr, self.conv_cin[-1])  # bench.py replays the list launch by launch (in-frame per-kernel timing)
         self.steps.append(step)
         return arr
+
+    def reassign_launch_orders(self) -> None:
+        """Assign the per-launch tile orders of every flushed list again: for tools that change what ``rsa_conv2d_list`` fuses
+        (``lib.set_pair_fusion``) after the plan was built, so that no arm of an A/B runs with the other arm's directions."""
+        if self.serpentine and _SERPENTINE and _SERPENTINE_PER_LAUNCH:
+            order = 0
+            for arr in self.conv_arrays:
+                order = L.conv_list_assign_tile_order(arr, order)
+            self._launch_order = order
 
     def call(self, fn: Callable[[], None], meta: dict | None = None) -> None:
         """A non-convolution launch.  ``meta`` (kernel name, algorithmic flop and bytes of the launch) lets bench.py replay and price it."""

@@ -489,6 +489,12 @@ EXTENSIONS: dict = {}
 # each table, and the mirrors of the module that holds it, with its header).
 HEADERS: dict = {'resselt_amd.h': SIGNATURES}
 
+# Entry points of the library that no header under include/ declares: host-side helpers of the engine's plan builder, documented where
+# csrc/capi.hip defines them.  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
+INTERNAL = {
+    'rsa_conv2d_list_assign_tile_order': (C.c_int, _conv('list') + _i32('n', 'first_order') + [('next_order', C.POINTER(C.c_int32))]),
+}
+
 
 def _declare(lib, rows: dict) -> None:
     for name, (restype, params) in rows.items():
@@ -554,6 +560,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(path)
     for rows in HEADERS.values():
         _declare(lib, rows)
+    _declare(lib, INTERNAL)
     _lib = lib
     return lib
 
@@ -667,6 +674,15 @@ def conv2d_pair(a: ConvParams, b: ConvParams, stream: int) -> None:
 
 def conv_pair_fusable(a: ConvParams, b: ConvParams) -> bool:
     return bool(load().rsa_conv_pair_fusable(C.byref(a), C.byref(b)))
+
+
+def conv_list_assign_tile_order(arr: 'C.Array[ConvParams]', first_order: int) -> int:
+    """Serpentine order per LAUNCH (``rsa_conv2d_list_assign_tile_order``; host only, nothing is launched): launch k of what
+    ``rsa_conv2d_list`` makes of ``arr`` gets ``tile_order = (first_order + k) & 1``, both halves of a fused pair the pair's.  Returns the
+    order the launch behind the list would get (the ``first_order`` of the next list of the same forward)."""
+    nxt = C.c_int32(0)
+    check(load().rsa_conv2d_list_assign_tile_order(arr, len(arr), first_order, C.byref(nxt)), 'rsa_conv2d_list_assign_tile_order')
+    return int(nxt.value)
 
 
 def set_pair_fusion(mode: int) -> None:

@@ -89,6 +89,8 @@ if '--frame' in sys.argv:
     for r in range(4):
         for name, mode in (('separate', 0), ('fused', 1)):
             L.set_pair_fusion(mode)
+            if model.last_plan() is not None:  # the sweep directions follow the launches: neither arm runs with the other's
+                model.last_plan().reassign_launch_orders()
             t = timed(lambda: ys.__setitem__(name, model(x)))
             if r:
                 times[name].append(t)

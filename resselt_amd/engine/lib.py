@@ -489,10 +489,12 @@ EXTENSIONS: dict = {}
 # each table, and the mirrors of the module that holds it, with its header).
 HEADERS: dict = {'resselt_amd.h': SIGNATURES}
 
-# Entry points of the library that no header under include/ declares: host-side helpers of the engine's plan builder, documented where
-# csrc/capi.hip defines them.  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
+# Entry points of the library that no header under include/ declares: helpers of the engine's plan builder and of its tiler, documented
+# where csrc/ defines them (capi.hip, tile_blend.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
 INTERNAL = {
     'rsa_conv2d_list_assign_tile_order': (C.c_int, _conv('list') + _i32('n', 'first_order') + [('next_order', C.POINTER(C.c_int32))]),
+    # the tiler's seam blending (csrc/tile_blend.hip documents the arguments)
+    'rsa_tile_blend_accumulate': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'C', 'win_h', 'win_w', 'src_h', 'src_w', 'src_y', 'src_x') + _ptr('acc') + _i32('acc_h', 'acc_w', 'acc_y', 'acc_x', 'ramp_top', 'ramp_bottom', 'ramp_left', 'ramp_right') + _ptr('stream')),
 }
 
 
@@ -683,6 +685,15 @@ def conv_list_assign_tile_order(arr: 'C.Array[ConvParams]', first_order: int) ->
     nxt = C.c_int32(0)
     check(load().rsa_conv2d_list_assign_tile_order(arr, len(arr), first_order, C.byref(nxt)), 'rsa_conv2d_list_assign_tile_order')
     return int(nxt.value)
+
+
+def tile_blend_accumulate(src: int, src_dtype: int, batch: int, channels: int, window: tuple, src_size: tuple, src_offset: tuple,
+                          acc: int, acc_size: tuple, acc_offset: tuple, ramps: tuple, stream: int) -> None:
+    """Add one tile's weighted window into the full-frame f32 accumulator (``rsa_tile_blend_accumulate``, csrc/tile_blend.hip).  ``src`` /
+    ``acc``: device addresses; ``window``, the sizes and the offsets are ``(rows, columns)`` in output pixels; ``ramps`` = widths of the
+    ``(top, bottom, left, right)`` ramps."""
+    check(load().rsa_tile_blend_accumulate(src, src_dtype, batch, channels, *window, *src_size, *src_offset, acc, *acc_size, *acc_offset, *ramps, stream),
+          'rsa_tile_blend_accumulate')  # fmt: skip
 
 
 def set_pair_fusion(mode: int) -> None:

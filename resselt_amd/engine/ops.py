@@ -330,3 +330,21 @@ def nchw_to_image_u8(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n, h, w, c), dtype=torch.uint8, device=x.device)
     call('rsa_nchw_to_image_u8', x.device, x=x, dtype=rsa_dtype(x.dtype), batch=n, C=c, H=h, W=w, img=out)
     return out
+
+
+def tile_blend_accumulate(acc: torch.Tensor, y: torch.Tensor, window: tuple, src_offset: tuple, acc_offset: tuple, ramps: tuple) -> None:
+    """Add the ``window = (rows, columns)`` of one tile's output ``y`` that starts at ``src_offset``, weighted by its ``ramps =
+    (top, bottom, left, right)``, into the f32 ``[N, C, H, W]`` accumulator at ``acc_offset`` (``rsa_tile_blend_accumulate``: pixels in
+    the top / left ramp are added to, all others stored).  ``y``: float ``[N, C, h, w]``, or a uint8 ``[N, h, w, C]`` image (code / 255)."""
+    require_cuda(acc, 'tile_blend_accumulate')
+    require_cuda(y, 'tile_blend_accumulate')
+    if acc.dtype != torch.float32 or acc.dim() != 4 or not acc.is_contiguous():
+        raise ValueError(f'the accumulator must be a contiguous float32 [N, C, H, W] tensor, got {acc.dtype} {tuple(acc.shape)}')
+    if y.dim() != 4:
+        raise ValueError(f'expected a [N, C, h, w] tensor or a uint8 [N, h, w, C] image, got shape {tuple(y.shape)}')
+    y = y.contiguous()
+    n, c, src_size = (y.shape[0], y.shape[3], (y.shape[1], y.shape[2])) if y.dtype == torch.uint8 else (y.shape[0], y.shape[1], (y.shape[2], y.shape[3]))
+    if (n, c) != (acc.shape[0], acc.shape[1]):
+        raise ValueError(f'tile output with batch {n} and {c} channels does not fit an accumulator of shape {tuple(acc.shape)}')
+    L.tile_blend_accumulate(y.data_ptr(), rsa_dtype(y.dtype), n, c, window, src_size, src_offset, acc.data_ptr(), (acc.shape[2], acc.shape[3]),
+                            acc_offset, ramps, current_stream_ptr(acc.device))  # fmt: skip

@@ -118,18 +118,127 @@ def warn_global_statistics(model, n_tiles: int) -> None:
                       'output differs from the untiled one', RuntimeWarning, stacklevel=3)  # fmt: skip
 
 
-def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], halo: int = 32, align: int = 1, check: bool = True) -> torch.Tensor:
+def blend_window(tile: Tile, height: int, width: int, blend: int, scale: int) -> tuple[int, int, int, int, int, int, int, int]:
+    """What ``tile`` contributes to the blended output of a ``height`` x ``width`` input, in OUTPUT pixels:
+    ``(py0, py1, px0, px1, ramp_top, ramp_bottom, ramp_left, ramp_right)``.
+
+    Per axis a tile that owns input pixels ``[a0, a1)`` contributes ``[a0*s - B, a1*s + B)`` with ``B = blend * scale``, without the
+    ``-B`` at ``a0 = 0`` and the ``+B`` at ``a1 = size`` (an image border has no neighbour).  At an interior edge the first (last) ``2B``
+    pixels of that range are a rising (falling) ramp, ``u = (p - (edge*s - B) + 0.5) / (2B)`` and ``1 - u``, which the neighbour across
+    the edge evaluates on the same pixels, so the two weights sum to one; everywhere else the weight is 1.  A ramp width of 0 means no
+    ramp on that side."""
+    b = blend * scale
+
+    def axis(a0, a1, size):
+        lo, hi = a0 > 0, a1 < size
+        return a0 * scale - (b if lo else 0), a1 * scale + (b if hi else 0), (2 * b if lo else 0), (2 * b if hi else 0)
+
+    py0, py1, top, bottom = axis(tile.y0, tile.y1, height)
+    px0, px1, left, right = axis(tile.x0, tile.x1, width)
+    return py0, py1, px0, px1, top, bottom, left, right
+
+
+def _check_blend(tiles: Sequence[Tile], blend: int, halo: int, align: int) -> None:
+    """The refusals of ``upscale_tiled(blend=)`` for a plan of more than one tile."""
+    if halo % align:
+        halo = (halo // align + 1) * align  # what plan_tiles made of it
+    if blend > halo:
+        raise ValueError(f'blend = {blend} exceeds the halo of {halo} pixels: a tile can only contribute what it has computed')
+    for axis, lo, hi in (('rows', 'y0', 'y1'), ('columns', 'x0', 'x1')):
+        spans = {(getattr(t, lo), getattr(t, hi)) for t in tiles}
+        if len(spans) > 1:
+            a0, a1 = min(spans, key=lambda s: s[1] - s[0])
+            if 2 * blend > a1 - a0:
+                raise ValueError(f'2 * blend = {2 * blend} exceeds the tile extent of {a1 - a0} pixels ({axis} {a0}:{a1}): the bands of adjacent seams would overlap')
+
+
+def _ramp(length: int, rise: int, fall: int, device) -> torch.Tensor:
+    """f32 weights of one axis of a contributed window: rising ramp of ``rise`` pixels, ones, falling ramp of ``fall`` pixels."""
+    wgt = torch.ones(length, dtype=torch.float32, device=device)
+    if rise:
+        wgt[:rise] = (torch.arange(rise, dtype=torch.float32, device=device) + 0.5) / rise
+    if fall:
+        wgt[length - fall :] *= 1 - (torch.arange(fall, dtype=torch.float32, device=device) + 0.5) / fall
+    return wgt
+
+
+def _blend_accumulate(acc: torch.Tensor, y: torch.Tensor, window: tuple[int, int], src_offset: tuple[int, int],
+                      acc_offset: tuple[int, int], ramps: tuple[int, int, int, int]) -> None:  # fmt: skip
+    """``acc[window at acc_offset] (+)= wy * wx * y[window at src_offset]``: pixels in the top or the left ramp have had an earlier
+    contributor (tiles arrive in row-major order) and are added to; every other pixel is stored, so ``acc`` needs no zero fill.
+    GPU tensors: one launch of ``rsa_tile_blend_accumulate``; CPU tensors (the oracle-driven tests): the same formula in torch."""
+    if acc.is_cuda:
+        from .engine import ops
+
+        return ops.tile_blend_accumulate(acc, y, window, src_offset, acc_offset, ramps)
+    (wh, ww), (sy, sx), (py, px), (top, bottom, left, right) = window, src_offset, acc_offset, ramps
+    if _is_image(y):
+        src = y[:, sy : sy + wh, sx : sx + ww].permute(0, 3, 1, 2).to(torch.float32) / 255
+    else:
+        src = y[:, :, sy : sy + wh, sx : sx + ww].to(torch.float32)
+    v = src * (_ramp(wh, top, bottom, y.device)[:, None] * _ramp(ww, left, right, y.device)[None, :])
+    dst = acc[:, :, py : py + wh, px : px + ww]
+    dst[:, :, top:, left:] = v[:, :, top:, left:]
+    dst[:, :, :top] += v[:, :, :top]
+    dst[:, :, top:, :left] += v[:, :, top:, :left]
+
+
+def _blend_tiles(model, x: torch.Tensor, scale: int, tiles: Sequence[Tile], blend: int) -> tuple[torch.Tensor, torch.dtype]:
+    """The blended f32 ``[N, C, H*scale, W*scale]`` frame of ``tiles`` (in ``Tile.index`` order, which the store / accumulate rule needs)
+    and the dtype of the model's outputs."""
+    img = _is_image(x)
+    n = x.shape[0]
+    h, w = (x.shape[1], x.shape[2]) if img else (x.shape[2], x.shape[3])
+    acc = None
+    for t in sorted(tiles, key=lambda t: t.index):
+        crop = (x[:, t.ry0 : t.ry1, t.rx0 : t.rx1] if img else x[:, :, t.ry0 : t.ry1, t.rx0 : t.rx1]).contiguous()
+        y = model(crop)
+        if acc is None:
+            acc = torch.empty((n, y.shape[3] if img else y.shape[1], h * scale, w * scale), dtype=torch.float32, device=y.device)
+        py0, py1, px0, px1, *ramps = blend_window(t, h, w, blend, scale)
+        _blend_accumulate(acc, y, (py1 - py0, px1 - px0), (py0 - t.ry0 * scale, px0 - t.rx0 * scale), (py0, px0), tuple(ramps))
+    return acc, y.dtype
+
+
+def _image_from_acc(acc: torch.Tensor) -> torch.Tensor:
+    """f32 ``[N, C, H, W]`` -> uint8 ``[N, H, W, C]``: clamp to [0, 1], times 255, round half to even."""
+    if acc.is_cuda:
+        from .engine import ops
+
+        return ops.nchw_to_image_u8(acc)
+    return (acc.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], halo: int = 32, align: int = 1, check: bool = True,
+                  blend: int = 0, blend_dtype: torch.dtype | None = None) -> torch.Tensor:  # fmt: skip
     """Single-device tiling of a large image: bounds the engine's activation buffers (e.g. 8K inputs).  ``x``: a float ``[N, C, H, W]``
-    tensor, or a uint8 ``[N, H, W, C]`` image for models with ``supports_u8`` (the layouts ``run_tile`` / ``TileParallel`` take)."""
+    tensor, or a uint8 ``[N, H, W, C]`` image for models with ``supports_u8`` (the layouts ``run_tile`` / ``TileParallel`` take).
+
+    ``blend`` (input pixels, default 0 = crop every halo and paste the tiles side by side): cross-fade neighbouring tiles over a band of
+    ``2 * blend`` input pixels centred on every interior tile edge, with weights that sum to one (``blend_window``).  It hides the step at
+    which two tiles meet when the halo does not cover the model's whole reach (``global_statistics`` models, MoESR); the result still
+    differs from the untiled one.  The band is cut out of the halo that is computed anyway, so ``blend <= halo`` (after ``align`` rounded
+    the halo up), and the context behind the outer edge of a band is ``halo - blend`` pixels.  ``2 * blend`` may not exceed a tile's extent
+    along an axis with several tiles.  The tiles are summed in f32 and the sum is cast to the model's output dtype (``blend_dtype``
+    names another one: ``upscale`` keeps the f32 sum for its 8-bit conversion), or rounded to 8 bits for images.  An image that fits one
+    tile ignores ``blend``."""
     if x.dim() != 4:
         raise ValueError(f'expected a [N, C, H, W] tensor or a uint8 [N, H, W, C] image, got shape {tuple(x.shape)}')
+    if blend < 0:
+        raise ValueError(f'blend = {blend} must be >= 0')
     img = _is_image(x)
     n = x.shape[0]
     h, w = (x.shape[1], x.shape[2]) if img else (x.shape[2], x.shape[3])
     rows, cols = -(-h // tile[0]), -(-w // tile[1])
     warn_global_statistics(model, rows * cols)
+    tiles = plan_tiles(h, w, rows, cols, halo, align)
+    if blend > 0 and len(tiles) > 1:
+        _check_blend(tiles, blend, halo, align)
+        acc, dtype = _blend_tiles(model, x, scale, tiles, blend)
+        out = _image_from_acc(acc) if img else acc.to(dtype if blend_dtype is None else blend_dtype)
+        return _finish(out) if check else out
     out = None
-    for t in plan_tiles(h, w, rows, cols, halo, align):
+    for t in tiles:
         y = run_tile(model, x, t, scale)
         if out is None:
             shape = (n, h * scale, w * scale, y.shape[3]) if img else (n, y.shape[1], h * scale, w * scale)
@@ -142,18 +251,23 @@ def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], hal
 
 
 def upscale(model, image: torch.Tensor, tile: tuple[int, int] | None = None, halo: int = 32, align: int = 1,
-            dtype: torch.dtype = torch.float16, scale: int | None = None) -> torch.Tensor:
+            dtype: torch.dtype = torch.float16, scale: int | None = None, blend: int = 0) -> torch.Tensor:
     """uint8 image in, uint8 image out: ``image`` is [H, W, C] or [N, H, W, C] uint8 on the GPU (what an image decoder delivers).
 
     ``/255`` and the NHWC->NCHW transpose run in one kernel, the model runs on ``dtype`` tensors (whole image, or ``tile``-sized tiles
     with ``halo`` pixels of context when the image is larger than ``tile``), and ``clamp(0, 1) * 255`` + round-half-even + NCHW->NHWC
     run in one kernel.  The reference leaves both conversions and the tiling to its callers.
     ``align``: SwinIR-family models want tile origins on a window multiple.
+    ``blend`` (input pixels, at most ``halo``; 0 = hard crop): cross-fade neighbouring tiles over ``2 * blend`` input pixels around every
+    interior tile edge instead of letting them meet at a step (``upscale_tiled``); the context behind the outer edge of a band is
+    ``halo - blend`` pixels.  The tiles are summed in f32 and rounded to 8 bits once.  An image that fits one tile ignores it.
     """
     from .engine import ops
 
+    if blend < 0:
+        raise ValueError(f'blend = {blend} must be >= 0')
     if getattr(model, 'supports_u8', False) and image.dtype == torch.uint8:
-        return _upscale_u8(model, image, tile, halo, align, scale)
+        return _upscale_u8(model, image, tile, halo, align, scale, blend)
     squeeze = image.dim() == 3
     x = ops.image_u8_to_nchw(image, dtype)
     if scale is None:
@@ -164,13 +278,14 @@ def upscale(model, image: torch.Tensor, tile: tuple[int, int] | None = None, hal
     if tile is None or (h <= tile[0] and w <= tile[1]):
         y = model(x)
     else:
-        y = upscale_tiled(model, x, scale, tile, halo, align, check=False)
+        y = upscale_tiled(model, x, scale, tile, halo, align, check=False, blend=blend, blend_dtype=torch.float32)
     out = _finish(ops.nchw_to_image_u8(y))
     return out[0] if squeeze else out
 
 
-def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale) -> torch.Tensor:
-    """``upscale`` for models that read and write 8-bit images themselves (no separate conversion passes): whole image, or tiles."""
+def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale, blend: int = 0) -> torch.Tensor:
+    """``upscale`` for models that read and write 8-bit images themselves (no separate conversion passes): whole image, or tiles
+    (``blend > 0``: the tiles' 8-bit codes are cross-faded in f32 and rounded once, see ``upscale_tiled``)."""
     squeeze = image.dim() == 3
     img = image.unsqueeze(0) if squeeze else image
     if scale is None:
@@ -179,7 +294,7 @@ def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale) 
     if tile is None or (h <= tile[0] and w <= tile[1]):
         out = model(img)
     else:
-        out = upscale_tiled(model, img, scale, tile, halo, align, check=False)
+        out = upscale_tiled(model, img, scale, tile, halo, align, check=False, blend=blend)
     out = _finish(out)
     return out[0] if squeeze else out
 

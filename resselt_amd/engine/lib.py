@@ -490,11 +490,13 @@ EXTENSIONS: dict = {}
 HEADERS: dict = {'resselt_amd.h': SIGNATURES}
 
 # Entry points of the library that no header under include/ declares: helpers of the engine's plan builder and of its tiler, documented
-# where csrc/ defines them (capi.hip, tile_blend.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
+# where csrc/ defines them (capi.hip, tile_blend.hip, resample.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
 INTERNAL = {
     'rsa_conv2d_list_assign_tile_order': (C.c_int, _conv('list') + _i32('n', 'first_order') + [('next_order', C.POINTER(C.c_int32))]),
     # the tiler's seam blending (csrc/tile_blend.hip documents the arguments)
     'rsa_tile_blend_accumulate': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'C', 'win_h', 'win_w', 'src_h', 'src_w', 'src_y', 'src_x') + _ptr('acc') + _i32('acc_h', 'acc_w', 'acc_y', 'acc_x', 'ramp_top', 'ramp_bottom', 'ramp_left', 'ramp_right') + _ptr('stream')),
+    # upscale(out_size=): the native frame at any size, one launch (csrc/resample.hip documents the arguments)
+    'rsa_resample': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'C', 'src_h', 'src_w') + _ptr('dst') + _i32('dst_dtype', 'dst_h', 'dst_w') + _ptr('start_y', 'weight_y') + _i32('taps_y') + _ptr('start_x', 'weight_x') + _i32('taps_x') + _ptr('stream')),
 }
 
 
@@ -694,6 +696,14 @@ def tile_blend_accumulate(src: int, src_dtype: int, batch: int, channels: int, w
     ``(top, bottom, left, right)`` ramps."""
     check(load().rsa_tile_blend_accumulate(src, src_dtype, batch, channels, *window, *src_size, *src_offset, acc, *acc_size, *acc_offset, *ramps, stream),
           'rsa_tile_blend_accumulate')  # fmt: skip
+
+
+def resample(src: int, src_dtype: int, batch: int, channels: int, src_size: tuple, dst: int, dst_dtype: int, dst_size: tuple,
+             table_y: tuple, table_x: tuple, stream: int) -> None:
+    """Resample a dense frame to ``dst_size`` in one launch (``rsa_resample``, csrc/resample.hip).  ``src`` / ``dst``: device addresses;
+    the sizes are ``(rows, columns)``; ``table_y`` / ``table_x`` = ``(start address, weight address, taps)`` of the device copies of
+    ``tiling.resample_table`` for the rows and the columns."""
+    check(load().rsa_resample(src, src_dtype, batch, channels, *src_size, dst, dst_dtype, *dst_size, *table_y, *table_x, stream), 'rsa_resample')
 
 
 def set_pair_fusion(mode: int) -> None:

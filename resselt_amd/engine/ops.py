@@ -348,3 +348,38 @@ def tile_blend_accumulate(acc: torch.Tensor, y: torch.Tensor, window: tuple, src
         raise ValueError(f'tile output with batch {n} and {c} channels does not fit an accumulator of shape {tuple(acc.shape)}')
     L.tile_blend_accumulate(y.data_ptr(), rsa_dtype(y.dtype), n, c, window, src_size, src_offset, acc.data_ptr(), (acc.shape[2], acc.shape[3]),
                             acc_offset, ramps, current_stream_ptr(acc.device))  # fmt: skip
+
+
+def _resample(x: torch.Tensor, size: tuple, filter: str, out_dtype: torch.dtype, what: str) -> torch.Tensor:
+    """One launch of ``rsa_resample``: ``x`` (float ``[N, C, h, w]`` or a uint8 ``[N, h, w, C]`` image, code / 255) at ``size = (rows,
+    columns)`` as ``out_dtype`` (uint8: an ``[N, rows, columns, C]`` image, ``clamp(0, 1) * 255`` rounded half to even)."""
+    from ..tiling import resample_tables_device
+
+    require_cuda(x, what)
+    if x.dim() != 4:
+        raise ValueError(f'expected a [N, C, h, w] tensor or a uint8 [N, h, w, C] image, got shape {tuple(x.shape)}')
+    x = x.contiguous()
+    n, c, (h, w) = (x.shape[0], x.shape[3], x.shape[1:3]) if x.dtype == torch.uint8 else (x.shape[0], x.shape[1], x.shape[2:4])
+    oh, ow = (int(v) for v in size)
+    (sy, wy), (sx, wx) = resample_tables_device(h, oh, filter, x.device), resample_tables_device(w, ow, filter, x.device)
+    out = torch.empty((n, oh, ow, c) if out_dtype == torch.uint8 else (n, c, oh, ow), dtype=out_dtype, device=x.device)
+    L.resample(x.data_ptr(), rsa_dtype(x.dtype), n, c, (h, w), out.data_ptr(), rsa_dtype(out_dtype), (oh, ow), (sy.data_ptr(), wy.data_ptr(), wy.shape[1]),
+               (sx.data_ptr(), wx.data_ptr(), wx.shape[1]), current_stream_ptr(x.device))  # fmt: skip
+    return out
+
+
+def resample(x: torch.Tensor, size: tuple, filter: str = 'bicubic', dtype: torch.dtype | None = None) -> torch.Tensor:
+    """``x`` (float ``[N, C, h, w]``, or a uint8 ``[N, h, w, C]`` image read as code / 255) resampled to ``size = (rows, columns)`` with
+    torch's antialiased ``filter`` ('bicubic' or 'bilinear'; ``tiling.resample_table``): float ``[N, C, rows, columns]`` of ``dtype``
+    (default: ``x``'s, float32 for an image).  One launch of ``rsa_resample``; at most 8 source pixels per output pixel along an axis."""
+    if dtype is None:
+        dtype = torch.float32 if x.dtype == torch.uint8 else x.dtype
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f'resample returns float32 / float16 / bfloat16 tensors, got dtype = {dtype}')
+    return _resample(x, size, filter, dtype, 'resample')
+
+
+def resample_to_image_u8(x: torch.Tensor, size: tuple, filter: str = 'bicubic') -> torch.Tensor:
+    """As ``resample``, but the result is the uint8 ``[N, rows, columns, C]`` image ``(v.clamp(0, 1) * 255).round()``: resampling and the
+    8-bit conversion of ``nchw_to_image_u8`` in one launch, rounded once."""
+    return _resample(x, size, filter, torch.uint8, 'resample_to_image_u8')

@@ -11,6 +11,8 @@ Host logic only: works with any callable ``model(x) -> y`` (the CPU tests drive 
 
 from __future__ import annotations
 
+import functools
+import math
 from dataclasses import dataclass
 from typing import Callable, Sequence
 
@@ -209,8 +211,137 @@ def _image_from_acc(acc: torch.Tensor) -> torch.Tensor:
     return (acc.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
+RESAMPLE_FILTERS = ('bicubic', 'bilinear')
+RESAMPLE_MAX_RATIO = 8  # source pixels per output pixel along an axis: bounds the taps (33 for bicubic) and the band a workgroup stages
+
+
+def _bicubic(t: float) -> float:
+    """Keys' cubic with a = -0.5."""
+    t = abs(t)
+    if t < 1.0:
+        return ((-0.5 + 2.0) * t - (-0.5 + 3.0)) * t * t + 1.0
+    if t < 2.0:
+        return (((t - 5.0) * t + 8.0) * t - 4.0) * -0.5
+    return 0.0
+
+
+def _triangle(t: float) -> float:
+    t = abs(t)
+    return 1.0 - t if t < 1.0 else 0.0
+
+
+@functools.lru_cache(maxsize=64)
+def resample_table(n_in: int, n_out: int, filter: str = 'bicubic', dtype: torch.dtype = torch.float32) -> tuple[torch.Tensor, torch.Tensor]:
+    """The weights with which an axis of ``n_in`` pixels is resampled to ``n_out``: ``(start int32 [n_out], weight float32 [n_out, taps])``,
+    output ``i`` = sum over ``j`` of ``weight[i, j] * source[start[i] + j]``.  A restatement of what torch's CPU
+    ``F.interpolate(mode=filter, antialias=True, align_corners=False)`` computes, made in f64 and rounded to f32 once.
+    Rows shorter than ``taps`` are padded with zero weights; ``start + taps <= n_in`` holds for every row (a row that would leave the
+    axis is shifted down, its zeros in front).  ``dtype = torch.float64`` returns the weights before that rounding (for checks against
+    torch).  The tensors are shared between callers: do not write to them."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f'resample filter {filter!r} is not one of {RESAMPLE_FILTERS}')
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f'cannot resample {n_in} pixels to {n_out}: both sizes must be >= 1')
+    if n_in > RESAMPLE_MAX_RATIO * n_out:
+        raise ValueError(f'resampling {n_in} pixels to {n_out} shrinks by more than {RESAMPLE_MAX_RATIO}')
+    f, size = (_bicubic, 4) if filter == 'bicubic' else (_triangle, 2)
+    scale = n_in / n_out
+    support = size / 2 * scale if scale >= 1.0 else size / 2
+    inv = 1.0 / scale if scale >= 1.0 else 1.0
+    rows = []
+    for i in range(n_out):
+        c = scale * (i + 0.5)
+        lo = max(int(c - support + 0.5), 0)
+        hi = min(int(c + support + 0.5), n_in)
+        w = [f((j + lo - c + 0.5) * inv) for j in range(hi - lo)]
+        total = sum(w)
+        rows.append((lo, [v / total for v in w]))
+    taps = max(len(w) for _, w in rows)
+    start = torch.empty(n_out, dtype=torch.int32)
+    weight = torch.zeros((n_out, taps), dtype=torch.float64)
+    for i, (lo, w) in enumerate(rows):
+        s = min(lo, n_in - taps)
+        start[i] = s
+        weight[i, lo - s : lo - s + len(w)] = torch.tensor(w, dtype=torch.float64)
+    return start, weight.to(dtype)
+
+
+_RESAMPLE_DEVICE_TABLES: dict = {}
+
+
+def resample_tables_device(n_in: int, n_out: int, filter: str, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """``resample_table`` on ``device``, copied there once per ``(n_in, n_out, filter, device)``."""
+    key = (n_in, n_out, filter, str(device))
+    hit = _RESAMPLE_DEVICE_TABLES.get(key)
+    if hit is None:
+        if len(_RESAMPLE_DEVICE_TABLES) >= 64:
+            _RESAMPLE_DEVICE_TABLES.clear()
+        start, weight = resample_table(n_in, n_out, filter)
+        hit = _RESAMPLE_DEVICE_TABLES[key] = (start.to(device), weight.to(device))
+    return hit
+
+
+def _check_out_args(out_size, out_scale, resample: str) -> None:
+    """The refusals of ``out_size`` / ``out_scale`` / ``resample`` that need neither the image nor the model."""
+    if out_size is not None and out_scale is not None:
+        raise ValueError('give out_size or out_scale, not both')
+    if resample not in RESAMPLE_FILTERS:
+        raise ValueError(f'resample = {resample!r} is not one of {RESAMPLE_FILTERS}')
+    if out_scale is not None and not out_scale > 0:
+        raise ValueError(f'out_scale = {out_scale} must be positive')
+    if out_size is not None and (len(out_size) != 2 or any(int(v) != v or v < 1 for v in out_size)):
+        raise ValueError(f'out_size = {out_size} must be (rows, columns), both >= 1')
+
+
+def _target_size(h: int, w: int, scale: int, out_size, out_scale, resample: str) -> tuple[int, int] | None:
+    """The size to deliver an ``h`` x ``w`` input at, or None when that is the model's native ``h * scale`` x ``w * scale`` (nothing to
+    do).  ``out_scale`` counts from the INPUT size.  Raises before the model runs when an axis would shrink by more than 8."""
+    _check_out_args(out_size, out_scale, resample)
+    if out_size is None and out_scale is None:
+        return None
+    if out_scale is not None:
+        target = max(1, math.floor(h * out_scale + 0.5)), max(1, math.floor(w * out_scale + 0.5))
+    else:
+        target = int(out_size[0]), int(out_size[1])
+    native = h * scale, w * scale
+    if target == native:
+        return None
+    for n_in, n_out in zip(native, target):
+        if n_in > RESAMPLE_MAX_RATIO * n_out:
+            raise ValueError(f'out size {target} shrinks the native {native} frame by more than {RESAMPLE_MAX_RATIO} ({n_in} -> {n_out})')
+    return target
+
+
+def _resample_axis(v: torch.Tensor, table: tuple[torch.Tensor, torch.Tensor], dim: int) -> torch.Tensor:
+    """f32 ``v`` with axis ``dim`` (2 or 3 of ``[N, C, H, W]``) filtered by ``table``: taps in ascending order from zero, as the kernel."""
+    start, weight = table
+    start = start.to(torch.int64)
+    shape = (-1, 1) if dim == 2 else (-1,)
+    acc = torch.zeros(v.shape[:dim] + (start.numel(),) + v.shape[dim + 1 :], dtype=torch.float32)
+    for t in range(weight.shape[1]):
+        acc = torch.addcmul(acc, weight[:, t].reshape(shape), v.index_select(dim, start + t))
+    return acc
+
+
+def _resample_frame(y: torch.Tensor, size: tuple[int, int], filter: str, dtype: torch.dtype) -> torch.Tensor:
+    """The native frame ``y`` (float ``[N, C, H, W]`` or a uint8 ``[N, H, W, C]`` image) at ``size`` as ``dtype``: uint8 means an
+    ``[N, rows, columns, C]`` image (clamp, times 255, round half to even, once), a float dtype an ``[N, C, rows, columns]`` tensor.
+    GPU tensors: one launch of ``rsa_resample``; CPU tensors (the oracle-driven tests): the same tables in torch, rows after columns."""
+    if y.is_cuda:
+        from .engine import ops
+
+        return ops.resample_to_image_u8(y, size, filter) if dtype == torch.uint8 else ops.resample(y, size, filter, dtype)
+    v = y.permute(0, 3, 1, 2).to(torch.float32) / 255 if _is_image(y) else y.to(torch.float32)
+    v = _resample_axis(v, resample_table(v.shape[3], size[1], filter), 3)
+    v = _resample_axis(v, resample_table(v.shape[2], size[0], filter), 2)
+    if dtype == torch.uint8:
+        return (v.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    return v.to(dtype)
+
+
 def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], halo: int = 32, align: int = 1, check: bool = True,
-                  blend: int = 0, blend_dtype: torch.dtype | None = None) -> torch.Tensor:  # fmt: skip
+                  blend: int = 0, blend_dtype: torch.dtype | None = None, out_size: tuple[int, int] | None = None,
+                  out_scale: float | None = None, resample: str = 'bicubic') -> torch.Tensor:  # fmt: skip
     """Single-device tiling of a large image: bounds the engine's activation buffers (e.g. 8K inputs).  ``x``: a float ``[N, C, H, W]``
     tensor, or a uint8 ``[N, H, W, C]`` image for models with ``supports_u8`` (the layouts ``run_tile`` / ``TileParallel`` take).
 
@@ -221,7 +352,13 @@ def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], hal
     the halo up), and the context behind the outer edge of a band is ``halo - blend`` pixels.  ``2 * blend`` may not exceed a tile's extent
     along an axis with several tiles.  The tiles are summed in f32 and the sum is cast to the model's output dtype (``blend_dtype``
     names another one: ``upscale`` keeps the f32 sum for its 8-bit conversion), or rounded to 8 bits for images.  An image that fits one
-    tile ignores ``blend``."""
+    tile ignores ``blend``.
+
+    ``out_size = (rows, columns)`` or ``out_scale`` (a positive factor of the INPUT size, each axis rounded half up, at least 1): deliver
+    the frame at that size instead of ``H * scale`` x ``W * scale``.  The assembled native frame (the pasted tiles, or the f32 sum of a
+    blend) is resampled once with torch's antialiased ``resample`` filter ('bicubic' or 'bilinear': ``resample_table``), by one launch
+    of ``rsa_resample`` that also casts to the model's dtype (``blend_dtype`` as above) or rounds to 8 bits.  An axis may shrink by at
+    most 8 and grow without limit; the native size, or neither argument, changes nothing."""
     if x.dim() != 4:
         raise ValueError(f'expected a [N, C, H, W] tensor or a uint8 [N, H, W, C] image, got shape {tuple(x.shape)}')
     if blend < 0:
@@ -229,13 +366,17 @@ def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], hal
     img = _is_image(x)
     n = x.shape[0]
     h, w = (x.shape[1], x.shape[2]) if img else (x.shape[2], x.shape[3])
+    target = _target_size(h, w, scale, out_size, out_scale, resample)
     rows, cols = -(-h // tile[0]), -(-w // tile[1])
     warn_global_statistics(model, rows * cols)
     tiles = plan_tiles(h, w, rows, cols, halo, align)
     if blend > 0 and len(tiles) > 1:
         _check_blend(tiles, blend, halo, align)
         acc, dtype = _blend_tiles(model, x, scale, tiles, blend)
-        out = _image_from_acc(acc) if img else acc.to(dtype if blend_dtype is None else blend_dtype)
+        if target is not None:
+            out = _resample_frame(acc, target, resample, torch.uint8 if img else (dtype if blend_dtype is None else blend_dtype))
+        else:
+            out = _image_from_acc(acc) if img else acc.to(dtype if blend_dtype is None else blend_dtype)
         return _finish(out) if check else out
     out = None
     for t in tiles:
@@ -247,11 +388,14 @@ def upscale_tiled(model, x: torch.Tensor, scale: int, tile: tuple[int, int], hal
             out[:, t.y0 * scale : t.y1 * scale, t.x0 * scale : t.x1 * scale] = y
         else:
             out[:, :, t.y0 * scale : t.y1 * scale, t.x0 * scale : t.x1 * scale] = y
+    if target is not None:
+        out = _resample_frame(out, target, resample, out.dtype)
     return _finish(out) if check else out
 
 
 def upscale(model, image: torch.Tensor, tile: tuple[int, int] | None = None, halo: int = 32, align: int = 1,
-            dtype: torch.dtype = torch.float16, scale: int | None = None, blend: int = 0) -> torch.Tensor:
+            dtype: torch.dtype = torch.float16, scale: int | None = None, blend: int = 0, out_size: tuple[int, int] | None = None,
+            out_scale: float | None = None, resample: str = 'bicubic') -> torch.Tensor:
     """uint8 image in, uint8 image out: ``image`` is [H, W, C] or [N, H, W, C] uint8 on the GPU (what an image decoder delivers).
 
     ``/255`` and the NHWC->NCHW transpose run in one kernel, the model runs on ``dtype`` tensors (whole image, or ``tile``-sized tiles
@@ -261,13 +405,19 @@ def upscale(model, image: torch.Tensor, tile: tuple[int, int] | None = None, hal
     ``blend`` (input pixels, at most ``halo``; 0 = hard crop): cross-fade neighbouring tiles over ``2 * blend`` input pixels around every
     interior tile edge instead of letting them meet at a step (``upscale_tiled``); the context behind the outer edge of a band is
     ``halo - blend`` pixels.  The tiles are summed in f32 and rounded to 8 bits once.  An image that fits one tile ignores it.
+    ``out_size = (rows, columns)`` or ``out_scale`` (a positive factor of the INPUT size: a x4 model at ``out_scale = 2`` delivers x2; each
+    axis rounded half up, at least 1): deliver the image at that size.  The native frame -- the model's output, the pasted tiles, or the f32
+    sum of a blend -- is read once by one launch of ``rsa_resample``, which applies torch's antialiased ``resample`` filter ('bicubic' or
+    'bilinear') and the 8-bit conversion together: it takes the place of the conversion kernel and the image is rounded once, after the
+    filter.  An axis may shrink by at most 8 and grow without limit.  The native size, or neither argument: nothing changes.
     """
     from .engine import ops
 
     if blend < 0:
         raise ValueError(f'blend = {blend} must be >= 0')
+    _check_out_args(out_size, out_scale, resample)
     if getattr(model, 'supports_u8', False) and image.dtype == torch.uint8:
-        return _upscale_u8(model, image, tile, halo, align, scale, blend)
+        return _upscale_u8(model, image, tile, halo, align, scale, blend, out_size, out_scale, resample)
     squeeze = image.dim() == 3
     x = ops.image_u8_to_nchw(image, dtype)
     if scale is None:
@@ -275,26 +425,32 @@ def upscale(model, image: torch.Tensor, tile: tuple[int, int] | None = None, hal
         if not isinstance(scale, int):
             raise ValueError('this model has several output scales: pass scale=')
     _, _, h, w = x.shape
+    target = _target_size(h, w, scale, out_size, out_scale, resample)
     if tile is None or (h <= tile[0] and w <= tile[1]):
         y = model(x)
     else:
         y = upscale_tiled(model, x, scale, tile, halo, align, check=False, blend=blend, blend_dtype=torch.float32)
-    out = _finish(ops.nchw_to_image_u8(y))
+    out = _finish(ops.nchw_to_image_u8(y) if target is None else ops.resample_to_image_u8(y, target, resample))
     return out[0] if squeeze else out
 
 
-def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale, blend: int = 0) -> torch.Tensor:
+def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale, blend: int = 0, out_size=None, out_scale=None,
+                resample: str = 'bicubic') -> torch.Tensor:  # fmt: skip
     """``upscale`` for models that read and write 8-bit images themselves (no separate conversion passes): whole image, or tiles
-    (``blend > 0``: the tiles' 8-bit codes are cross-faded in f32 and rounded once, see ``upscale_tiled``)."""
+    (``blend > 0``: the tiles' 8-bit codes are cross-faded in f32 and rounded once, see ``upscale_tiled``).  Another output size: the
+    model's 8-bit image, the pasted 8-bit tiles or the f32 sum of the blend is resampled and rounded by one launch."""
     squeeze = image.dim() == 3
     img = image.unsqueeze(0) if squeeze else image
     if scale is None:
         scale = model.parameters_info.upscale
     n, h, w, c = img.shape
     if tile is None or (h <= tile[0] and w <= tile[1]):
+        target = _target_size(h, w, scale, out_size, out_scale, resample)
         out = model(img)
+        if target is not None:
+            out = _resample_frame(out, target, resample, torch.uint8)
     else:
-        out = upscale_tiled(model, img, scale, tile, halo, align, check=False, blend=blend)
+        out = upscale_tiled(model, img, scale, tile, halo, align, check=False, blend=blend, out_size=out_size, out_scale=out_scale, resample=resample)
     out = _finish(out)
     return out[0] if squeeze else out
 
@@ -315,6 +471,9 @@ class TileParallel:
     round are equal full-width row bands of a channel-interleaved image (uint8 ``[1, H, W, C]``: the bands of a round are
     one contiguous slab of the result) the gather writes straight into the result; otherwise tiles are padded to the
     largest tile, gathered into a receive buffer and copied into place.
+
+    The result has the model's native size; a caller who wants another one resamples the gathered result with ``ops.resample`` /
+    ``ops.resample_to_image_u8`` (what ``upscale(out_size=)`` does on one device).
     """
 
     def __init__(self, model: Callable[[torch.Tensor], torch.Tensor], scale: int, halo: int = 32, align: int = 1,

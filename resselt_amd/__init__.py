@@ -43,6 +43,13 @@ def upscale(model, image, **kwargs):
     return _upscale(model, image, **kwargs)
 
 
+def upscale_yuv(model, y, uv, **kwargs):
+    """NV12 / P010 video frame (``y`` and interleaved ``uv`` planes) in, the upscaled planes out (see ``resselt_amd.tiling.upscale_yuv``).  Not part of the reference API."""
+    from .tiling import upscale_yuv as _upscale_yuv
+
+    return _upscale_yuv(model, y, uv, **kwargs)
+
+
 __all__ = [
     'add',
     'get',
@@ -54,4 +61,5 @@ __all__ = [
     'ModelMetadata',
     'Registry',
     'upscale',
+    'upscale_yuv',
 ]

@@ -490,13 +490,16 @@ EXTENSIONS: dict = {}
 HEADERS: dict = {'resselt_amd.h': SIGNATURES}
 
 # Entry points of the library that no header under include/ declares: helpers of the engine's plan builder and of its tiler, documented
-# where csrc/ defines them (capi.hip, tile_blend.hip, resample.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
+# where csrc/ defines them (capi.hip, tile_blend.hip, resample.hip, yuv.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
 INTERNAL = {
     'rsa_conv2d_list_assign_tile_order': (C.c_int, _conv('list') + _i32('n', 'first_order') + [('next_order', C.POINTER(C.c_int32))]),
     # the tiler's seam blending (csrc/tile_blend.hip documents the arguments)
     'rsa_tile_blend_accumulate': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'C', 'win_h', 'win_w', 'src_h', 'src_w', 'src_y', 'src_x') + _ptr('acc') + _i32('acc_h', 'acc_w', 'acc_y', 'acc_x', 'ramp_top', 'ramp_bottom', 'ramp_left', 'ramp_right') + _ptr('stream')),
     # upscale(out_size=): the native frame at any size, one launch (csrc/resample.hip documents the arguments)
     'rsa_resample': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'C', 'src_h', 'src_w') + _ptr('dst') + _i32('dst_dtype', 'dst_h', 'dst_w') + _ptr('start_y', 'weight_y') + _i32('taps_y') + _ptr('start_x', 'weight_x') + _i32('taps_x') + _ptr('stream')),
+    # upscale_yuv(): NV12 / P010 planes <-> float NCHW (csrc/yuv.hip documents the arguments)
+    'rsa_yuv420_to_nchw': (C.c_int, _ptr('y') + _i64('y_pitch', 'y_batch_stride') + _ptr('uv') + _i64('uv_pitch', 'uv_batch_stride') + _i32('bits', 'batch', 'H', 'W', 'matrix', 'full_range', 'chroma_loc') + _ptr('dst') + _i32('dst_dtype') + _ptr('stream')),
+    'rsa_nchw_to_yuv420': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'H', 'W', 'matrix', 'full_range', 'chroma_loc', 'bits') + _ptr('y') + _i64('y_pitch', 'y_batch_stride') + _ptr('uv') + _i64('uv_pitch', 'uv_batch_stride') + _ptr('stream')),
 }
 
 
@@ -704,6 +707,21 @@ def resample(src: int, src_dtype: int, batch: int, channels: int, src_size: tupl
     the sizes are ``(rows, columns)``; ``table_y`` / ``table_x`` = ``(start address, weight address, taps)`` of the device copies of
     ``tiling.resample_table`` for the rows and the columns."""
     check(load().rsa_resample(src, src_dtype, batch, channels, *src_size, dst, dst_dtype, *dst_size, *table_y, *table_x, stream), 'rsa_resample')
+
+
+def yuv420_to_nchw(y: tuple, uv: tuple, bits: int, batch: int, size: tuple, matrix: int, full_range: int, chroma_loc: int, dst: int, dst_dtype: int,
+                   stream: int) -> None:
+    """NV12 (``bits = 8``) / P010 (``bits = 10``) planes -> dense float ``[batch, 3, H, W]`` in one launch (``rsa_yuv420_to_nchw``,
+    csrc/yuv.hip).  ``y`` / ``uv`` = ``(device address, pitch, batch stride)`` in bytes; ``size = (H, W)`` of the luma plane; ``matrix``,
+    ``full_range`` and ``chroma_loc`` are the integers of ``ops.YUV_MATRICES`` / ``YUV_RANGES`` / ``YUV_CHROMA_LOCS``."""
+    check(load().rsa_yuv420_to_nchw(*y, *uv, bits, batch, *size, matrix, full_range, chroma_loc, dst, dst_dtype, stream), 'rsa_yuv420_to_nchw')
+
+
+def nchw_to_yuv420(src: int, src_dtype: int, batch: int, size: tuple, matrix: int, full_range: int, chroma_loc: int, bits: int, y: tuple, uv: tuple,
+                   stream: int) -> None:
+    """Dense float ``[batch, 3, H, W]`` -> NV12 / P010 planes in one launch (``rsa_nchw_to_yuv420``, csrc/yuv.hip); arguments as
+    ``yuv420_to_nchw``."""
+    check(load().rsa_nchw_to_yuv420(src, src_dtype, batch, *size, matrix, full_range, chroma_loc, bits, *y, *uv, stream), 'rsa_nchw_to_yuv420')
 
 
 def set_pair_fusion(mode: int) -> None:

@@ -1,4 +1,5 @@
-"""Python-side builders for the C-ABI launch descriptors (no arithmetic happens here)."""
+"""Python-side builders for the C-ABI launch descriptors (no arithmetic happens here; the two video-format conversions at the end also
+carry the f32 torch form of their definition for CPU tensors, as tiling._resample_frame does)."""
 
 from __future__ import annotations
 
@@ -383,3 +384,172 @@ def resample_to_image_u8(x: torch.Tensor, size: tuple, filter: str = 'bicubic') 
     """As ``resample``, but the result is the uint8 ``[N, rows, columns, C]`` image ``(v.clamp(0, 1) * 255).round()``: resampling and the
     8-bit conversion of ``nchw_to_image_u8`` in one launch, rounded once."""
     return _resample(x, size, filter, torch.uint8, 'resample_to_image_u8')
+
+
+# The pixel formats of video (csrc/yuv.hip, DESIGN.md §31): two-plane Y'CbCr 4:2:0.  The integers are the entry points' enums.
+YUV_FORMATS = {'nv12': (8, torch.uint8), 'p010': (10, torch.uint16)}  # fmt -> (bits, dtype of the samples)
+YUV_MATRICES = {'bt601': 0, 'bt709': 1, 'bt2020': 2}
+YUV_RANGES = {'limited': 0, 'full': 1}
+YUV_CHROMA_LOCS = {'left': 0, 'center': 1}
+_YUV_KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722), 'bt2020': (0.2627, 0.0593)}
+
+
+def _yuv_args(fmt: str, matrix: str, range: str, chroma_loc: str) -> tuple:
+    """``(bits, sample dtype)`` of ``fmt`` after every string has been checked (``ValueError`` names the bad one and the choices)."""
+    for what, value, choices in (('fmt', fmt, YUV_FORMATS), ('matrix', matrix, YUV_MATRICES), ('range', range, YUV_RANGES), ('chroma_loc', chroma_loc, YUV_CHROMA_LOCS)):  # fmt: skip
+        if value not in choices:
+            raise ValueError(f'{what} = {value!r} is not one of {tuple(choices)}')
+    return YUV_FORMATS[fmt]
+
+
+def _yuv_planes(y: torch.Tensor, uv: torch.Tensor, fmt: str) -> tuple:
+    """``y`` ``[H, W]`` / ``[N, H, W]`` and ``uv`` ``[H/2, W/2, 2]`` / ``[N, H/2, W/2, 2]`` as batched planes, checked against ``fmt``."""
+    _, dt = YUV_FORMATS[fmt]
+    if y.dim() not in (2, 3) or uv.dim() != y.dim() + 1:
+        raise ValueError(f'expected y [H, W] or [N, H, W] and uv [H/2, W/2, 2] or [N, H/2, W/2, 2], got {tuple(y.shape)} and {tuple(uv.shape)}')
+    if y.dtype != dt or uv.dtype != dt:
+        raise ValueError(f'{fmt} planes are {dt}, got y {y.dtype} and uv {uv.dtype}')
+    if y.dim() == 2:
+        y, uv = y.unsqueeze(0), uv.unsqueeze(0)
+    n, h, w = y.shape
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 planes need an even, positive luma size, got {h} x {w}')
+    if tuple(uv.shape) != (n, h // 2, w // 2, 2):
+        raise ValueError(f'a y plane of shape {(n, h, w)} goes with a uv plane of shape {(n, h // 2, w // 2, 2)}, got {tuple(uv.shape)}')
+    if y.device != uv.device:
+        raise ValueError(f'y is on {y.device} and uv on {uv.device}')
+    return y, uv
+
+
+def _pitched(t: torch.Tensor, row_dims: int) -> tuple:
+    """``(tensor, pitch, batch stride)`` in bytes of a batched plane whose rows are its last ``row_dims`` dimensions: a view whose rows are
+    dense is passed as it is (its row stride is the pitch), anything else is made contiguous first."""
+    dense = t.stride(-1) == 1 and (row_dims == 1 or t.stride(-2) == 2)
+    row = t.shape[-1] * (t.shape[-2] if row_dims == 2 else 1)
+    rows_dim = -1 - row_dims
+    if not dense or t.stride(rows_dim) < row or (t.shape[0] > 1 and t.stride(0) < t.stride(rows_dim) * t.shape[rows_dim]):
+        t = t.contiguous()
+    return t, t.stride(rows_dim) * t.element_size(), t.stride(0) * t.element_size()
+
+
+def _yuv_coefficients(matrix: str, range: str, bits: int) -> tuple:
+    """``(Kr, Kg, Kb, luma offset, luma range, chroma offset, chroma range)`` in codes, as Python floats."""
+    kr, kb = _YUV_KR_KB[matrix]
+    m, top = 2 ** (bits - 8), 2**bits - 1
+    if range == 'limited':
+        return kr, 1.0 - kr - kb, kb, 16.0 * m, 219.0 * m, 128.0 * m, 224.0 * m
+    return kr, 1.0 - kr - kb, kb, 0.0, float(top), float(2 ** (bits - 1)), float(top)
+
+
+def _codes(t: torch.Tensor, bits: int) -> torch.Tensor:
+    """The samples of a plane as f32 codes (P010: the top 10 bits of the word)."""
+    c = t.to(torch.int32)
+    return (c >> 6 if bits == 10 else c).to(torch.float32)
+
+
+def _chroma_up(c: torch.Tensor, dim: int, n: int, o: float) -> torch.Tensor:
+    """Axis ``dim`` of the chroma codes ``c`` interpolated linearly to ``n`` luma positions for the siting offset ``o`` (exact in f32)."""
+    u = (torch.arange(n, dtype=torch.float64, device=c.device) - o) / 2
+    j = torch.floor(u)
+    f = (u - j).to(torch.float32)
+    last = c.shape[dim] - 1
+    j = j.to(torch.int64)
+    shape = [1] * c.dim()
+    shape[dim] = n
+    f = f.reshape(shape)
+    return (1 - f) * c.index_select(dim, j.clamp(0, last)) + f * c.index_select(dim, (j + 1).clamp(0, last))
+
+
+def _yuv420_to_nchw_torch(y, uv, bits, matrix, range, chroma_loc, dtype):
+    """``yuv420_to_nchw`` for CPU tensors: the definition of csrc/yuv.hip in f32 torch operations (on whatever device the planes are: on the
+    GPU it is the chain of torch operations a caller needed before the kernel existed, which tools/yuv_measure.py times)."""
+    kr, kg, kb, y_off, y_range, c_off, c_range = _yuv_coefficients(matrix, range, bits)
+    n, h, w = y.shape
+    c = _chroma_up(_codes(uv, bits), 1, h, 0.5)
+    c = _chroma_up(c, 2, w, 0.5 if chroma_loc == 'center' else 0.0)
+    yn = (_codes(y, bits) - y_off) * (1.0 / y_range)
+    cb, cr = (c[..., 0] - c_off) * (1.0 / c_range), (c[..., 1] - c_off) * (1.0 / c_range)
+    r = yn + (2 * (1 - kr)) * cr
+    b = yn + (2 * (1 - kb)) * cb
+    g = yn - (kb * 2 * (1 - kb) / kg) * cb - (kr * 2 * (1 - kr) / kg) * cr
+    return torch.stack((r, g, b), 1).clamp(0, 1).to(dtype)
+
+
+def _chroma_down(d: torch.Tensor, dim: int, o: float) -> torch.Tensor:
+    """The SUM (2 terms for ``o = 0.5``, [1 2 1] for ``o = 0``; the caller divides) that makes one chroma sample of every two luma positions."""
+    n = d.shape[dim]
+    even = torch.arange(0, n, 2, device=d.device)
+    if o == 0.5:
+        return d.index_select(dim, even) + d.index_select(dim, even + 1)
+    return (d.index_select(dim, (even - 1).clamp(min=0)) + 2 * d.index_select(dim, even)) + d.index_select(dim, even + 1)
+
+
+def _nchw_to_yuv420_torch(x, bits, dt, matrix, range, chroma_loc):
+    """``nchw_to_yuv420`` for CPU tensors: the definition of csrc/yuv.hip in f32 torch operations."""
+    kr, kg, kb, y_off, y_range, c_off, c_range = _yuv_coefficients(matrix, range, bits)
+    v = x.to(torch.float32)
+    v = torch.where(v.isnan(), torch.zeros_like(v), v).clamp(0, 1)
+    r, g, b = v[:, 0], v[:, 1], v[:, 2]
+    yn = kr * r + (kg * g + kb * b)
+    top = float(2**bits - 1)
+
+    def codes(t):
+        t = t.round().clamp(0, top).to(torch.int32)  # torch rounds half to even
+        return (t << 6 if bits == 10 else t).to(dt)
+
+    y = codes(yn * y_range + y_off)
+    center = chroma_loc == 'center'
+    filt = 0.25 if center else 0.125
+    planes = []
+    for d, k in ((b - yn, kb), (r - yn, kr)):
+        s = _chroma_down(_chroma_down(d, 1, 0.5), 2, 0.5 if center else 0.0)
+        planes.append(codes(s * (c_range * filt / (2 * (1 - k))) + c_off))
+    return y, torch.stack(planes, -1)
+
+
+def yuv420_to_nchw(y: torch.Tensor, uv: torch.Tensor, fmt: str = 'nv12', matrix: str = 'bt709', range: str = 'limited', chroma_loc: str = 'left',
+                   dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """A two-plane Y'CbCr 4:2:0 frame -> float ``[N, 3, H, W]`` R'G'B' in [0, 1] of ``dtype`` (``rsa_yuv420_to_nchw``, one launch).
+
+    ``y``: ``[H, W]`` or ``[N, H, W]``; ``uv``: ``[H/2, W/2, 2]`` or ``[N, H/2, W/2, 2]`` interleaved (Cb, Cr); ``torch.uint8`` for
+    ``fmt = 'nv12'``, ``torch.uint16`` words with the code in their top 10 bits for ``'p010'``.  A row-strided view (a pitched decoder
+    surface: innermost stride 1) is read in place, its row stride is the pitch.  ``matrix``: 'bt601' / 'bt709' / 'bt2020' (non-constant
+    luminance); ``range``: 'limited' / 'full'; ``chroma_loc``: 'left' (H.264 / HEVC default) or 'center'.  Chroma is interpolated
+    linearly, the result is clamped to [0, 1]; the transfer function is untouched.  CPU tensors take the same definition in f32 torch."""
+    bits, _ = _yuv_args(fmt, matrix, range, chroma_loc)
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f'yuv420_to_nchw returns float32 / float16 / bfloat16 tensors, got dtype = {dtype}')
+    y, uv = _yuv_planes(y, uv, fmt)
+    if not y.is_cuda:
+        return _yuv420_to_nchw_torch(y, uv, bits, matrix, range, chroma_loc, dtype)
+    (y, y_pitch, y_stride), (uv, uv_pitch, uv_stride) = _pitched(y, 1), _pitched(uv, 2)
+    n, h, w = y.shape
+    out = torch.empty((n, 3, h, w), dtype=dtype, device=y.device)
+    with torch.cuda.device(y.device):
+        L.yuv420_to_nchw((y.data_ptr(), y_pitch, y_stride), (uv.data_ptr(), uv_pitch, uv_stride), bits, n, (h, w), YUV_MATRICES[matrix],
+                         YUV_RANGES[range], YUV_CHROMA_LOCS[chroma_loc], out.data_ptr(), rsa_dtype(dtype), current_stream_ptr(y.device))  # fmt: skip
+    return out
+
+
+def nchw_to_yuv420(x: torch.Tensor, fmt: str = 'nv12', matrix: str = 'bt709', range: str = 'limited', chroma_loc: str = 'left') -> tuple:
+    """Float ``[N, 3, H, W]`` R'G'B' -> the contiguous planes ``(y [N, H, W], uv [N, H/2, W/2, 2])`` of ``fmt`` (``rsa_nchw_to_yuv420``: both
+    planes from one launch).  The source is clamped to [0, 1] (NaN -> 0), Cb and Cr are filtered to the ``chroma_loc`` siting ([1 2 1] / 4
+    or the mean of two, per axis), codes are rounded half to even.  Arguments as ``yuv420_to_nchw``; CPU tensors take f32 torch."""
+    bits, dt = _yuv_args(fmt, matrix, range, chroma_loc)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f'expected a [N, 3, H, W] tensor, got shape {tuple(x.shape)}')
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f'nchw_to_yuv420 reads float32 / float16 / bfloat16 tensors, got {x.dtype}')
+    n, _, h, w = x.shape
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 planes need an even, positive frame size, got {h} x {w}')
+    if not x.is_cuda:
+        return _nchw_to_yuv420_torch(x, bits, dt, matrix, range, chroma_loc)
+    x = x.contiguous()
+    y = torch.empty((n, h, w), dtype=dt, device=x.device)
+    uv = torch.empty((n, h // 2, w // 2, 2), dtype=dt, device=x.device)
+    e = y.element_size()
+    with torch.cuda.device(x.device):
+        L.nchw_to_yuv420(x.data_ptr(), rsa_dtype(x.dtype), n, (h, w), YUV_MATRICES[matrix], YUV_RANGES[range], YUV_CHROMA_LOCS[chroma_loc], bits,
+                         (y.data_ptr(), w * e, h * w * e), (uv.data_ptr(), w * e, (h // 2) * w * e), current_stream_ptr(x.device))  # fmt: skip
+    return y, uv

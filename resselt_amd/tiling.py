@@ -434,6 +434,58 @@ def upscale(model, image: torch.Tensor, tile: tuple[int, int] | None = None, hal
     return out[0] if squeeze else out
 
 
+def upscale_yuv(model, y: torch.Tensor, uv: torch.Tensor, fmt: str = 'nv12', out_fmt: str | None = None, matrix: str = 'bt709',
+                range: str = 'limited', chroma_loc: str = 'left', tile: tuple[int, int] | None = None, halo: int = 32, align: int = 1,
+                blend: int = 0, dtype: torch.dtype = torch.float16, scale: int | None = None, out_size: tuple[int, int] | None = None,
+                out_scale: float | None = None, resample: str = 'bicubic') -> tuple[torch.Tensor, torch.Tensor]:
+    """Video frame in, video frame out: two-plane Y'CbCr 4:2:0 as a GPU video decoder delivers it and an encoder accepts it.
+
+    ``y`` is ``[H, W]`` or ``[N, H, W]``, ``uv`` ``[H/2, W/2, 2]`` or ``[N, H/2, W/2, 2]`` interleaved (Cb, Cr): ``torch.uint8`` for
+    ``fmt = 'nv12'``, ``torch.uint16`` words with the code in their top 10 bits for ``'p010'``; a pitched surface is passed as a
+    row-strided view.  Returns the contiguous planes ``(y, uv)`` of the upscaled frame in ``out_fmt`` (default: ``fmt``;
+    ``out_fmt='p010'`` with NV12 input delivers an 8-bit source in 10 bits).  ``matrix`` ('bt601' / 'bt709' / 'bt2020'), ``range``
+    ('limited' / 'full') and ``chroma_loc`` ('left': the H.264 / HEVC default; 'center') describe the input and the output alike
+    (``ops.yuv420_to_nchw`` has the definition); the transfer function is untouched.
+
+    One kernel turns the planes into the ``dtype`` R'G'B' tensor the model reads (chroma interpolated linearly), the model runs on the
+    whole frame or on ``tile``-sized tiles exactly as in ``upscale`` (``halo``, ``align``, ``blend``: see there; models with
+    ``supports_u8`` take this float path too), ``out_size`` / ``out_scale`` / ``resample`` resample the native frame once to f32 (rules
+    and errors of ``upscale``; the delivered size must be even), and one kernel writes both planes: the frame is rounded to codes
+    once, at the end.  float16 carries 11 bits: with ``out_fmt='p010'``, ``dtype=torch.float32`` keeps the tenth bit clean."""
+    from .engine import ops
+
+    if out_fmt is None:
+        out_fmt = fmt
+    ops._yuv_args(fmt, matrix, range, chroma_loc)
+    ops._yuv_args(out_fmt, matrix, range, chroma_loc)
+    if blend < 0:
+        raise ValueError(f'blend = {blend} must be >= 0')
+    _check_out_args(out_size, out_scale, resample)
+    info = getattr(model, 'parameters_info', None)
+    if info is not None and (info.in_channels != 3 or info.out_channels != 3):
+        raise ValueError(f'upscale_yuv needs a model with 3 channels in and out, got {info.in_channels} in and {info.out_channels} out')
+    if scale is None:
+        scale = getattr(info, 'upscale', None)
+        if not isinstance(scale, int):
+            raise ValueError('this model does not name one output scale: pass scale=')
+    squeeze = y.dim() == 2
+    y, uv = ops._yuv_planes(y, uv, fmt)  # ValueError for shapes or dtypes that disagree with fmt, and for odd sizes
+    _, h, w = y.shape
+    target = _target_size(h, w, scale, out_size, out_scale, resample)
+    if target is not None and (target[0] % 2 or target[1] % 2):
+        raise ValueError(f'a 4:2:0 frame has an even size: the output size {target} is odd')
+    x = ops.yuv420_to_nchw(y, uv, fmt, matrix, range, chroma_loc, dtype)
+    if tile is None or (h <= tile[0] and w <= tile[1]):
+        out = model(x)
+    else:
+        out = upscale_tiled(model, x, scale, tile, halo, align, check=False, blend=blend, blend_dtype=torch.float32)
+    if target is not None:
+        out = _resample_frame(out, target, resample, torch.float32)
+    oy, ouv = ops.nchw_to_yuv420(out, out_fmt, matrix, range, chroma_loc)
+    _finish(oy)
+    return (oy[0], ouv[0]) if squeeze else (oy, ouv)
+
+
 def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale, blend: int = 0, out_size=None, out_scale=None,
                 resample: str = 'bicubic') -> torch.Tensor:  # fmt: skip
     """``upscale`` for models that read and write 8-bit images themselves (no separate conversion passes): whole image, or tiles

@@ -50,6 +50,13 @@ def upscale_yuv(model, y, uv, **kwargs):
     return _upscale_yuv(model, y, uv, **kwargs)
 
 
+def upscale_rgba(model, image, **kwargs):
+    """Gray / gray + alpha / RGB / RGBA image of 8 or 16 bits in, the upscaled image out (see ``resselt_amd.tiling.upscale_rgba``).  Not part of the reference API."""
+    from .tiling import upscale_rgba as _upscale_rgba
+
+    return _upscale_rgba(model, image, **kwargs)
+
+
 __all__ = [
     'add',
     'get',
@@ -62,4 +69,5 @@ __all__ = [
     'Registry',
     'upscale',
     'upscale_yuv',
+    'upscale_rgba',
 ]

@@ -490,7 +490,7 @@ EXTENSIONS: dict = {}
 HEADERS: dict = {'resselt_amd.h': SIGNATURES}
 
 # Entry points of the library that no header under include/ declares: helpers of the engine's plan builder and of its tiler, documented
-# where csrc/ defines them (capi.hip, tile_blend.hip, resample.hip, yuv.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
+# where csrc/ defines them (capi.hip, tile_blend.hip, resample.hip, yuv.hip, rgba.hip).  Rows as in SIGNATURES; ``load`` demands and types them like the rest.
 INTERNAL = {
     'rsa_conv2d_list_assign_tile_order': (C.c_int, _conv('list') + _i32('n', 'first_order') + [('next_order', C.POINTER(C.c_int32))]),
     # the tiler's seam blending (csrc/tile_blend.hip documents the arguments)
@@ -500,6 +500,9 @@ INTERNAL = {
     # upscale_yuv(): NV12 / P010 planes <-> float NCHW (csrc/yuv.hip documents the arguments)
     'rsa_yuv420_to_nchw': (C.c_int, _ptr('y') + _i64('y_pitch', 'y_batch_stride') + _ptr('uv') + _i64('uv_pitch', 'uv_batch_stride') + _i32('bits', 'batch', 'H', 'W', 'matrix', 'full_range', 'chroma_loc') + _ptr('dst') + _i32('dst_dtype') + _ptr('stream')),
     'rsa_nchw_to_yuv420': (C.c_int, _ptr('src') + _i32('src_dtype', 'batch', 'H', 'W', 'matrix', 'full_range', 'chroma_loc', 'bits') + _ptr('y') + _i64('y_pitch', 'y_batch_stride') + _ptr('uv') + _i64('uv_pitch', 'uv_batch_stride') + _ptr('stream')),
+    # upscale_rgba(): interleaved gray / gray + alpha / RGB / RGBA images of 8 or 16 bits <-> float NCHW (csrc/rgba.hip documents the arguments)
+    'rsa_image_to_nchw_alpha': (C.c_int, _ptr('img') + _i64('pitch', 'batch_stride') + _i32('bits', 'batch', 'H', 'W', 'C', 'Cm', 'bleed') + _ptr('color') + _i32('color_dtype') + _ptr('alpha') + _i32('alpha_mode') + _ptr('flags', 'stream')),
+    'rsa_nchw_to_image_alpha': (C.c_int, _ptr('color') + _i32('color_dtype', 'Cm') + _ptr('alpha') + _i32('alpha_dtype', 'Ca', 'batch', 'H', 'W', 'C', 'bits') + _ptr('img') + _i64('pitch', 'batch_stride') + _ptr('stream')),
 }
 
 
@@ -722,6 +725,24 @@ def nchw_to_yuv420(src: int, src_dtype: int, batch: int, size: tuple, matrix: in
     """Dense float ``[batch, 3, H, W]`` -> NV12 / P010 planes in one launch (``rsa_nchw_to_yuv420``, csrc/yuv.hip); arguments as
     ``yuv420_to_nchw``."""
     check(load().rsa_nchw_to_yuv420(src, src_dtype, batch, *size, matrix, full_range, chroma_loc, bits, *y, *uv, stream), 'rsa_nchw_to_yuv420')
+
+
+def image_to_nchw_alpha(img: tuple, bits: int, batch: int, size: tuple, channels: int, model_channels: int, bleed: int, color: int, color_dtype: int,
+                        alpha: int | None, alpha_mode: int, flags: int | None, stream: int) -> None:
+    """An interleaved 8- / 16-bit image of 1 .. 4 channels -> the dense float ``[batch, model_channels, H, W]`` colour tensor (edge-bled under
+    transparent pixels), the alpha tensor and the per-image "some alpha is below the maximum" flags in one launch
+    (``rsa_image_to_nchw_alpha``, csrc/rgba.hip).  ``img`` = ``(device address, pitch, batch stride)`` in bytes; ``size = (H, W)``;
+    ``alpha_mode``: 0 none, 1 replicated in ``color_dtype``, 2 one f32 channel; ``flags``: zeroed int32 ``[batch]``."""
+    check(load().rsa_image_to_nchw_alpha(*img, bits, batch, *size, channels, model_channels, bleed, color, color_dtype, alpha, alpha_mode, flags, stream),
+          'rsa_image_to_nchw_alpha')  # fmt: skip
+
+
+def nchw_to_image_alpha(color: int, color_dtype: int, model_channels: int, alpha: int | None, alpha_dtype: int, alpha_channels: int, batch: int,
+                        size: tuple, channels: int, bits: int, img: tuple, stream: int) -> None:
+    """Dense float colour ``[batch, model_channels, H, W]`` and an optional alpha source ``[batch, alpha_channels, H, W]`` -> the interleaved
+    8- / 16-bit image of ``channels`` in one launch (``rsa_nchw_to_image_alpha``, csrc/rgba.hip); arguments as ``image_to_nchw_alpha``."""
+    check(load().rsa_nchw_to_image_alpha(color, color_dtype, model_channels, alpha, alpha_dtype, alpha_channels, batch, *size, channels, bits, *img, stream),
+          'rsa_nchw_to_image_alpha')  # fmt: skip
 
 
 def set_pair_fusion(mode: int) -> None:

@@ -1,5 +1,5 @@
-"""Python-side builders for the C-ABI launch descriptors (no arithmetic happens here; the two video-format conversions at the end also
-carry the f32 torch form of their definition for CPU tensors, as tiling._resample_frame does)."""
+"""Python-side builders for the C-ABI launch descriptors (no arithmetic happens here; the video-format and the still-image conversions at
+the end also carry the f32 torch form of their definition for CPU tensors, as tiling._resample_frame does)."""
 
 from __future__ import annotations
 
@@ -553,3 +553,158 @@ def nchw_to_yuv420(x: torch.Tensor, fmt: str = 'nv12', matrix: str = 'bt709', ra
         L.nchw_to_yuv420(x.data_ptr(), rsa_dtype(x.dtype), n, (h, w), YUV_MATRICES[matrix], YUV_RANGES[range], YUV_CHROMA_LOCS[chroma_loc], bits,
                          (y.data_ptr(), w * e, h * w * e), (uv.data_ptr(), w * e, (h // 2) * w * e), current_stream_ptr(x.device))  # fmt: skip
     return y, uv
+
+
+# The still-image formats of upscale_rgba (csrc/rgba.hip): interleaved images of 1 .. 4 channels, 8 or 16 bits.
+IMAGE_DEPTHS = {8: torch.uint8, 16: torch.uint16}
+ALPHA_MODES = {'none': 0, 'model': 1, 'resample': 2}  # the entry point's alpha_mode
+MAX_BLEED = 16
+
+
+def _image_args(img: torch.Tensor, what: str) -> tuple:
+    """``(batched image, bits)`` of an interleaved ``[H, W, C]`` / ``[N, H, W, C]`` image, checked (``ValueError``)."""
+    if img.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f'{what}: an image is torch.uint8 or torch.uint16, got {img.dtype}')
+    if img.dim() not in (3, 4):
+        raise ValueError(f'{what}: expected an [H, W, C] or [N, H, W, C] image, got shape {tuple(img.shape)}')
+    if img.dim() == 3:
+        img = img.unsqueeze(0)
+    n, h, w, c = img.shape
+    if not 1 <= c <= 4 or n < 1 or h < 1 or w < 1:
+        raise ValueError(f'{what}: an image has 1 (gray), 2 (gray + alpha), 3 (RGB) or 4 (RGBA) channels and a positive size, got shape {tuple(img.shape)}')
+    return img, 8 if img.dtype == torch.uint8 else 16
+
+
+def _check_bleed(bleed) -> int:
+    if isinstance(bleed, bool) or int(bleed) != bleed or not 0 <= bleed <= MAX_BLEED:
+        raise ValueError(f'bleed = {bleed} must be an integer in 0 .. {MAX_BLEED}')
+    return int(bleed)
+
+
+def _pitched_image(img: torch.Tensor) -> tuple:
+    """``(image, pitch, batch stride)`` in bytes of an ``[N, H, W, C]`` image: a view whose pixels and rows are dense (innermost strides
+    ``C`` and 1) is passed as it is, its row stride is the pitch; anything else is made contiguous first."""
+    n, h, w, c = img.shape
+    if img.stride(3) != 1 or img.stride(2) != c or img.stride(1) < w * c or (n > 1 and img.stride(0) < img.stride(1) * h):
+        img = img.contiguous()
+    e = img.element_size()
+    return img, img.stride(1) * e, img.stride(0) * e
+
+
+def _bleed_torch(col: torch.Tensor, known: torch.Tensor, passes: int) -> torch.Tensor:
+    """The edge bleed of csrc/rgba.hip on f32 ``col`` ``[N, Cs, H, W]`` with ``known`` bool ``[N, 1, H, W]``: f32 sums in row-major order
+    over the 3 x 3 (a term outside S adds an exact zero)."""
+    import torch.nn.functional as F
+
+    h, w = col.shape[2:]
+    for _ in range(passes):
+        if bool(known.all()) or not bool(known.any()):
+            break
+        cp, kp = F.pad(col * known, (1, 1, 1, 1)), F.pad(known.to(torch.float32), (1, 1, 1, 1))
+        num, den = torch.zeros_like(col), torch.zeros_like(kp[:, :, 1:-1, 1:-1])
+        for dy in range(3):
+            for dx in range(3):
+                if (dy, dx) != (1, 1):
+                    wgt = 2.0 if dy == 1 or dx == 1 else 1.0
+                    num = num + wgt * cp[:, :, dy : dy + h, dx : dx + w]
+                    den = den + wgt * kp[:, :, dy : dy + h, dx : dx + w]
+        fill = ~known & (den > 0)
+        col = torch.where(fill, num / den.clamp(min=1.0), col)
+        known = known | fill
+    return col
+
+
+def image_to_nchw_alpha(img: torch.Tensor, model_channels: int = 3, alpha: str = 'model', bleed: int = 8, dtype: torch.dtype = torch.float16) -> tuple:
+    """An interleaved image -> ``(x, a, flags)`` for a model of ``model_channels`` (``rsa_image_to_nchw_alpha``, one launch).
+
+    ``img``: ``[H, W, C]`` or ``[N, H, W, C]``, ``torch.uint8`` or ``torch.uint16`` (full range), ``C`` = 1 gray, 2 gray + alpha, 3 RGB,
+    4 RGBA; alpha is straight.  A row-strided view whose innermost two strides are dense is read in place.  Values are ``code / M``
+    (``M`` = 255 or 65535); gray is replicated to ``model_channels`` = 3; a colour image needs 3.  The colour under ``alpha = 0`` pixels
+    is bled in from the visible edge in ``bleed`` (0 .. 16) passes (csrc/rgba.hip has the definition); alpha itself never changes.
+    ``x`` is ``[N, Cm, H, W]`` of ``dtype``; with ``alpha = 'model'`` on an image with an alpha channel it is ``[2 N, Cm, H, W]``: the
+    alpha, replicated to ``Cm`` channels, sits behind the colour entries.  ``a`` is the f32 ``[N, 1, H, W]`` alpha for
+    ``alpha = 'resample'``, else None.  ``flags`` is int32 ``[N]``: 1 where an alpha code of the image is below the maximum (None for
+    images without alpha, which ignore ``alpha`` and ``bleed``).  CPU tensors take the same definition in f32 torch."""
+    img, bits = _image_args(img, 'image_to_nchw_alpha')
+    bleed = _check_bleed(bleed)
+    if alpha not in ALPHA_MODES:
+        raise ValueError(f'alpha = {alpha!r} is not one of {tuple(ALPHA_MODES)}')
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f'image_to_nchw_alpha returns float32 / float16 / bfloat16 tensors, got dtype = {dtype}')
+    n, h, w, c = img.shape
+    cm = int(model_channels)
+    if cm not in (1, 3) or (c >= 3 and cm != 3):
+        raise ValueError(f'an image of {c} channels needs a model of 3 channels (gray: 1 or 3), got {model_channels}')
+    has_alpha = c in (2, 4)
+    mode = ALPHA_MODES[alpha] if has_alpha else 0
+    if not img.is_cuda:
+        m = 255.0 if bits == 8 else 65535.0
+        codes = img.to(torch.int32).permute(0, 3, 1, 2)
+        col = codes[:, : c - has_alpha].to(torch.float32) / m
+        a = flags = None
+        if has_alpha:
+            ac = codes[:, c - 1 :]
+            col = _bleed_torch(col, ac > 0, bleed)
+            flags = (ac.reshape(n, -1) < int(m)).any(1).to(torch.int32)
+            av = ac.to(torch.float32) / m
+        x = col.expand(n, cm, h, w).to(dtype) if col.shape[1] == 1 else col.to(dtype)
+        if mode == 1:
+            x = torch.cat((x, av.expand(n, cm, h, w).to(dtype)))
+        elif mode == 2:
+            a = av.contiguous()
+        return x.contiguous(), a, flags
+    img, pitch, stride = _pitched_image(img)
+    x = torch.empty(((2 * n if mode == 1 else n), cm, h, w), dtype=dtype, device=img.device)
+    a = torch.empty((n, 1, h, w), dtype=torch.float32, device=img.device) if mode == 2 else None
+    flags = torch.zeros(n, dtype=torch.int32, device=img.device) if has_alpha else None
+    with torch.cuda.device(img.device):
+        L.image_to_nchw_alpha((img.data_ptr(), pitch, stride), bits, n, (h, w), c, cm, bleed if has_alpha else 0, x.data_ptr(), rsa_dtype(dtype),
+                              x[n:].data_ptr() if mode == 1 else (a.data_ptr() if mode == 2 else None), mode,
+                              flags.data_ptr() if has_alpha else None, current_stream_ptr(img.device))  # fmt: skip
+    return x, a, flags
+
+
+def nchw_to_image_alpha(color: torch.Tensor, alpha: torch.Tensor | None = None, channels: int = 3, bits: int = 8) -> torch.Tensor:
+    """Float colour ``[N, Cm, H, W]`` (and an alpha source ``[N, Ca, H, W]``, ``Ca`` = 1 or ``Cm``, or None) -> the contiguous interleaved
+    ``[N, H, W, channels]`` image of ``bits`` = 8 (uint8) or 16 (uint16) (``rsa_nchw_to_image_alpha``, one launch).  Gray
+    (``channels`` = 1, 2) is the f32 mean of the ``Cm`` colour channels, alpha (``channels`` = 2, 4) the f32 mean of the alpha source's
+    channels, or the maximum code without one; each value is clamped to [0, 1] (NaN -> 0), multiplied by 255 / 65535 and rounded half
+    to even.  CPU tensors take the same definition in f32 torch."""
+    if bits not in IMAGE_DEPTHS:
+        raise ValueError(f'bits = {bits} must be 8 or 16')
+    c = int(channels)
+    if not 1 <= c <= 4:
+        raise ValueError(f'channels = {channels} must be 1 .. 4')
+    if color.dim() != 4 or color.shape[1] not in (1, 3) or (c >= 3 and color.shape[1] != 3):
+        raise ValueError(f'expected a [N, 1 or 3, H, W] colour tensor (3 for a colour image), got shape {tuple(color.shape)}')
+    n, cm, h, w = color.shape
+    if c in (1, 3):
+        alpha = None
+    for t, what in ((color, 'colour'), (alpha, 'alpha')):
+        if t is not None and t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f'nchw_to_image_alpha reads float32 / float16 / bfloat16 tensors, got {t.dtype} ({what})')
+    if alpha is not None and (alpha.dim() != 4 or alpha.shape[1] not in (1, cm) or (alpha.shape[0], *alpha.shape[2:]) != (n, h, w) or alpha.device != color.device):
+        raise ValueError(f'the alpha source of a colour tensor of shape {tuple(color.shape)} is [N, 1 or {cm}, H, W] on the same device, got {tuple(alpha.shape)}')
+    dt = IMAGE_DEPTHS[bits]
+    if not color.is_cuda:
+        m = 255.0 if bits == 8 else 65535.0
+
+        def mean(t):
+            t = t.to(torch.float32)
+            return ((t[:, 0] + t[:, 1]) + t[:, 2]) / 3.0 if t.shape[1] == 3 else t[:, 0]
+
+        planes = [mean(color)] if c <= 2 else [color[:, i].to(torch.float32) for i in range(3)]
+        if c in (2, 4):
+            planes.append(mean(alpha) if alpha is not None else torch.ones((n, h, w), dtype=torch.float32))
+        v = torch.stack(planes, -1)
+        v = torch.where(v.isnan(), torch.zeros_like(v), v).clamp(0, 1)
+        return (v * m).round().to(torch.int32).to(dt).contiguous()  # torch rounds half to even
+    color = color.contiguous()
+    alpha = None if alpha is None else alpha.contiguous()
+    out = torch.empty((n, h, w, c), dtype=dt, device=color.device)
+    e = out.element_size()
+    with torch.cuda.device(color.device):
+        L.nchw_to_image_alpha(color.data_ptr(), rsa_dtype(color.dtype), cm, None if alpha is None else alpha.data_ptr(),
+                              L.F32 if alpha is None else rsa_dtype(alpha.dtype), 1 if alpha is None else alpha.shape[1], n, (h, w), c, bits,
+                              (out.data_ptr(), w * c * e, h * w * c * e), current_stream_ptr(color.device))  # fmt: skip
+    return out

@@ -486,6 +486,81 @@ def upscale_yuv(model, y: torch.Tensor, uv: torch.Tensor, fmt: str = 'nv12', out
     return (oy[0], ouv[0]) if squeeze else (oy, ouv)
 
 
+def upscale_rgba(model, image: torch.Tensor, alpha: str = 'model', bleed: int = 8, out_bits: int | None = None,
+                 tile: tuple[int, int] | None = None, halo: int = 32, align: int = 1, blend: int = 0, dtype: torch.dtype = torch.float16,
+                 scale: int | None = None, out_size: tuple[int, int] | None = None, out_scale: float | None = None,
+                 resample: str = 'bicubic') -> torch.Tensor:
+    """Still image in, still image out, with alpha, gray and 16 bits: ``image`` is ``[H, W, C]`` or ``[N, H, W, C]``, ``torch.uint8`` or
+    ``torch.uint16`` (codes over the full range 0 .. 65535), ``C`` = 1 gray, 2 gray + alpha, 3 RGB, 4 RGBA; alpha is straight, not
+    premultiplied.  A row-strided view whose innermost two strides are dense is read in place.  Returns the contiguous image of the same
+    rank and ``C`` at the size ``upscale`` would deliver, in ``out_bits`` = 8 or 16 (default: the input's depth; 16 bits from an 8-bit
+    source is how a gradient avoids banding).
+
+    The model has ``in_channels == out_channels`` of 1 or 3.  A three-channel model reads a gray image in all three channels and the
+    delivered gray is the mean of its three output channels; a one-channel model takes gray images only.  Models with ``supports_u8``
+    take this float path too.
+
+    ``alpha='model'``: alpha, replicated to the model's channels, goes through the model as ``N`` further batch entries of the same call
+    (one call per tile on a batch of ``2 N``), and the delivered alpha is the mean of the output channels.  ``alpha='resample'``: alpha is
+    resampled to the delivered size with the ``resample`` filter in f32 (``rsa_resample``); the model sees colour only.  When no alpha
+    code of the batch is below the maximum both modes skip the alpha work and deliver the maximum code: an opaque RGBA image costs what
+    the RGB image costs.  The colour stored under fully transparent pixels (usually black) would bleed a dark fringe into the visible
+    edge through the model's receptive field, so the input kernel replaces it by colour bled in from the visible pixels over ``bleed``
+    (0 .. 16) pixels (``ops.image_to_nchw_alpha`` / csrc/rgba.hip have the definition); alpha and the colour of every pixel with
+    ``alpha > 0`` are never changed.  Images without an alpha channel ignore ``alpha`` and ``bleed``.
+
+    ``tile``, ``halo``, ``align``, ``blend``, ``scale``, ``out_size``, ``out_scale`` and ``resample`` keep the rules and the errors of
+    ``upscale``.  Blend sums and resampling stay in f32 and the image is rounded to codes once, at the end.  float16 carries 11 bits:
+    with ``out_bits=16``, ``dtype=torch.float32`` keeps the low bits of the result clean.  For a uint8 RGB image, ``out_bits=8`` and a
+    model without ``supports_u8`` the result equals ``upscale``'s."""
+    from .engine import ops
+
+    if alpha not in ('model', 'resample'):
+        raise ValueError(f"alpha = {alpha!r} is not one of ('model', 'resample')")
+    bleed = ops._check_bleed(bleed)
+    if blend < 0:
+        raise ValueError(f'blend = {blend} must be >= 0')
+    _check_out_args(out_size, out_scale, resample)
+    squeeze = image.dim() == 3
+    img, bits = ops._image_args(image, 'upscale_rgba')
+    if out_bits is None:
+        out_bits = bits
+    if out_bits not in (8, 16):
+        raise ValueError(f'out_bits = {out_bits} must be 8 or 16')
+    n, h, w, c = img.shape
+    info = getattr(model, 'parameters_info', None)
+    cm = 3
+    if info is not None:
+        if info.in_channels != info.out_channels or info.in_channels not in (1, 3):
+            raise ValueError(f'upscale_rgba needs a model with 1 or 3 channels in and as many out, got {info.in_channels} in and {info.out_channels} out')
+        cm = info.in_channels
+    if c >= 3 and cm == 1:
+        raise ValueError(f'a one-channel model takes gray images only, got an image of {c} channels')
+    if scale is None:
+        scale = getattr(info, 'upscale', None)
+        if not isinstance(scale, int):
+            raise ValueError('this model does not name one output scale: pass scale=')
+    target = _target_size(h, w, scale, out_size, out_scale, resample)
+    x, a, flags = ops.image_to_nchw_alpha(img, cm, alpha, bleed, dtype)
+    translucent = flags is not None and bool(flags.any())  # the one host read of the call: it decides the batch the model sees
+    if not translucent:
+        x, a = x[:n], None
+    if tile is None or (h <= tile[0] and w <= tile[1]):
+        out = model(x)
+    else:
+        out = upscale_tiled(model, x, scale, tile, halo, align, check=False, blend=blend, blend_dtype=torch.float32)
+    if target is not None:
+        out = _resample_frame(out, target, resample, torch.float32)
+    src = None
+    if translucent and alpha == 'model':
+        out, src = out[:n], out[n:]
+    elif translucent:
+        size = tuple(out.shape[2:])
+        src = a if size == (h, w) else _resample_frame(a, size, resample, torch.float32)
+    out = _finish(ops.nchw_to_image_alpha(out, src, c, out_bits))
+    return out[0] if squeeze else out
+
+
 def _upscale_u8(model, image: torch.Tensor, tile, halo: int, align: int, scale, blend: int = 0, out_size=None, out_scale=None,
                 resample: str = 'bicubic') -> torch.Tensor:  # fmt: skip
     """``upscale`` for models that read and write 8-bit images themselves (no separate conversion passes): whole image, or tiles
